@@ -12,7 +12,13 @@ encoder patches, 32 collage decoder patches per step).  All inputs are resident 
 unit is the interior patch-step.  With N > 1 every rank runs its own batch of 32 patches (the
 path shards by independent patches: weak scaling, no data-path collective).
 
-Row-sharded tile sweep (`--sweep`, and a short one appended to every default run as the `sweep` object): a fixed ROI of
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps and the result line (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds everything else described below: the hipEvent
+brackets of the timed steps and their `roofline`, the appended `sweep` and `extra` objects and `cpu_baseline`.
+`--dump-outputs DIR` writes what the timed path computed in its last step (rank 0) as float32 DIR/<name>.npy: `state` (the
+image state the step returns) and `eps` (the UNet's noise prediction), or `state` (the ROI canvas) with `--sweep`.
+
+Row-sharded tile sweep (`--sweep`, and with `--full` a short one appended to the default run as the `sweep` object): a fixed ROI of
 `--sweep-hnm x --sweep-wnm` test_brn tiles (256x256 px x 100 channels, 25 z-chunks x 16 interior patches each) in the
 whole-brain configuration (16-bit UNet arithmetic, one float16 state canvas per rank), row-sharded over the N ranks by
 teramind_amd.launch.run_sweep / brain.TileSweep: rank 0's packed weight arena is broadcast once over RCCL and every
@@ -20,12 +26,12 @@ diffusion step ends with the 32-px halo-strip exchange with the neighbouring ran
 scaling: the ROI is the same for every N.  Reported: interior patch-steps/s of the whole job, per-step exchange time
 and bytes, and the world size as RCCL sees it.
 
-The default line also carries `sweep.roofline` (the 16-bit conv kernel's executed TFLOP/s, fraction of the dense peak and
-counter traffic during the sweep's timed steps) and `extra.tile_<dtype>`: the stacked one-tile step (BASELINE config 4's
+The `--full` default line also carries `sweep.roofline` (the 16-bit conv kernel's executed TFLOP/s, fraction of the dense peak
+and counter traffic during the sweep's timed steps) and `extra.tile_<dtype>`: the stacked one-tile step (BASELINE config 4's
 governing shape) on the sweep's packed model, 3 timed steps, with its own `roofline`.
 
-Prints ONE JSON line on rank 0, with `roofline` (dominant kernel, the 3x3x3 implicit-GEMM conv: MFMA FLOPs actually
-issued per launch / average launch duration from hipEvents recorded on the launch stream during the timed region,
+Prints ONE JSON line on rank 0; with `--full` it holds `roofline` (dominant kernel, the 3x3x3 implicit-GEMM conv: MFMA FLOPs
+actually issued per launch / average launch duration from hipEvents recorded on the launch stream during the timed region,
 against the dense MFMA peak of the dtype) and `cpu_baseline` (oracle/teramind_cpu.py on the host cores, bounded sample).
 """
 import argparse
@@ -44,6 +50,7 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0    # same table, "Peak BF16/FP16 MFMA ~2.5 PF den
 T_STEPS = 50
 NEEDED_GFLOP = {1: 320.1, 4: 202.6}   # needed FLOPs per interior patch-step (whole path, 2*MAC)
 Z_AWARE = 0.684                       # share of those FLOPs left when the always-zero z tap is not issued
+DUMP_BYTES = 60_000_000               # --dump-outputs: float32 payload of all arrays together (stays under 64 MB)
 
 
 _T0 = time.perf_counter()
@@ -63,6 +70,23 @@ def kernel_source_sha() -> str:
             h.update(f.encode())
             h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each tensor of `arrays` as float32 d/<name>.npy.  An array larger than its equal share of DUMP_BYTES
+    is written as a fixed sample of its flattened elements instead (indices drawn from a seed-0 generator, sorted): the same
+    elements for every run of the same shape, so that two builds can be compared element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_BYTES // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach()
+        if a.numel() > share:
+            idx = torch.randint(a.numel(), (share,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        np.save(os.path.join(d, name + ".npy"), a.float().cpu().numpy())
+    log(f"outputs written to {d}: {', '.join(arrays)}")
 
 
 def cpu_baseline(cfg, sd, budget_steps=6, b=8, P=1):
@@ -165,16 +189,20 @@ def run_sweep_bench(args, dev, sd, world, rank, steps, warmup):
         if rank == 0:
             log(f"sweep: step {sw.epoch} done in {s:.2f} s")
 
-    # warm-up steps run unprofiled; the hipEvent brackets cover exactly the timed steps
+    # warm-up steps run unprofiled; with --full the hipEvent brackets cover exactly the timed steps
     res = launch.run_sweep(cfg, smp, model, genes, hnm=args.sweep_hnm, wnm=args.sweep_wnm, total_epochs=T, steps=steps,
                            warmup=warmup, device=dev, batch_tiles=args.sweep_batch_tiles, init="device", state="fp16",
-                           on_step=on_step, after_warmup=lambda: model.profile(True), share_halo=share,
+                           on_step=on_step, after_warmup=(lambda: model.profile(True)) if args.full else None, share_halo=share,
                            batch_rows=args.sweep_batch_rows if share else 1, prefetch_genes=not share,
                            cache_level0=bool(args.sweep_cache_level0))
-    prof = model.profile_collect()
-    model.profile(False)
+    prof = None
+    if args.full:
+        prof = model.profile_collect()
+        model.profile(False)
     st = res["sweep"].local_state()
     assert torch.isfinite(st.float()).all(), "non-finite sweep state"
+    if args.sweep and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"state": st})
     # partition-independent digest of the whole ROI state: exact integer sums over the fp16 bit patterns of every rank's rows
     bits = st.contiguous().view(torch.int16).to(torch.int64) & 0xFFFF
     dig = torch.stack([bits.sum(), (bits * bits).sum(), torch.tensor(bits.numel(), device=bits.device)])
@@ -313,6 +341,7 @@ def worker(args):
         tmap = torch.tensor(smp.timestep_map, dtype=torch.int64, device=dev)
 
         pyr = {}
+        last = {}
 
         def one_step(k, state):
             i = T_STEPS - 1 - (k % T_STEPS)
@@ -327,6 +356,8 @@ def worker(args):
                     pyr["p"] = model.precompute_rna(rna, b, imgs=shape_only, patch_size=ps)
                 cond = pyr["p"]
             eps = model(x=xp, t=t, rna=cond, imgs=shape_only, patch_size=ps).pred
+            if args.dump_outputs:
+                last["eps"] = eps
             return sampler_step(smp, i, xp, eps, noise[k % 4] if gen == "ddpm" else None, b, P, P)
 
         state = img
@@ -338,19 +369,23 @@ def worker(args):
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
-        model.profile(True)
+        if args.full:
+            model.profile(True)
         t0 = time.perf_counter()
         for k in range(args.steps):
             state = one_step(args.warmup + k, state)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        prof = model.profile_collect()
-        model.profile(False)
+        if args.full:
+            prof = model.profile_collect()
+            model.profile(False)
         log(f"timed region done: {dt:.3f} s for {args.steps} steps")
         if world > 1:
             dist.barrier()
         dt = launch.reduce_max([dt], dev)[0]
         assert torch.isfinite(state).all(), "non-finite state"
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"state": state, "eps": last["eps"]})
         del model
         if rank == 0:
             units = b * P * P * args.steps * world
@@ -368,15 +403,16 @@ def worker(args):
                                         "(P=4, 625 padded + 400 collage patches), DDIM T=50 schedule, mode B arithmetic, " + args.dtype),
                            "per_gpu_patches_per_step": b * P * P, "parallelism": f"dp{world} (independent patch batches)"},
                 "full_50_step_patches_per_s": round(value / T_STEPS, 4),
-                "roofline": roofline_block(prof, args.dtype, dt, value / world, P, args.tile),
             }
+            if args.full:
+                out["roofline"] = roofline_block(prof, args.dtype, dt, value / world, P, args.tile)
     sweep_steps, sweep_warm = (args.steps, args.warmup) if args.sweep else (args.sweep_steps, 1)
-    if args.sweep or not args.no_sweep:
+    if args.sweep or (args.full and not args.no_sweep):
         torch.cuda.empty_cache()
         sw_out, sw_prof, sw_dt, sw_value, sw_model, sw_cfg = run_sweep_bench(args, dev, sd, world, rank, sweep_steps, sweep_warm)
         # the 16-bit roofline belongs in the driver's line: the sweep's own conv27 figures, and the stacked one-tile step
         # (config 4's governing shape) on the same packed model
-        sw_roof = roofline_block(sw_prof, args.sweep_dtype, sw_dt, sw_value / world, 4, True, sweep=True)
+        sw_roof = roofline_block(sw_prof, args.sweep_dtype, sw_dt, sw_value / world, 4, True, sweep=True) if args.full else None
         extra = None
         if not args.sweep and not args.no_tile_extra:
             torch.cuda.empty_cache()
@@ -390,15 +426,16 @@ def worker(args):
                    "data": "synthetic (hashed weights seed 0, per-tile seeded N(0,1) initial state, sparse integer gene tiles)",
                    "config": {"workload": sw_out["workload"], "parallelism": f"row-sharded tile grid over {world} rank(s), "
                               "32-px halo-strip exchange per step (RCCL send/recv), weight arena broadcast once"},
-                   "roofline": sw_roof,
                    "sweep": sw_out}
+            if args.full:
+                out["roofline"] = sw_roof
         elif rank == 0:
             sw_out["roofline"] = sw_roof
             out["sweep"] = sw_out
             if extra is not None:
                 out["extra"] = {"tile_" + args.sweep_dtype: extra}
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only (the host cores are shared at N>1)
+        if args.full and not args.no_cpu_baseline and world == 1:      # rank 0 at N=1 only (the host cores are shared at N>1)
             out["cpu_baseline"] = cpu_baseline(PathConfig(), sd)
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -411,6 +448,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline (hipEvent brackets of the timed steps), "
+                         "the appended sweep and one-tile extra, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step (rank 0) as float32 DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dtype", choices=["f32", "bf16", "f16"], default="f32",
                     help="f32 = BASELINE configs[1] (the headline); bf16 = config-4 arithmetic (bf16 3x3x3 convs)")
@@ -418,14 +460,14 @@ def main():
                     help="mode-B workload instead: one test_brn tile (25 z-chunks x 5x5 patches, P=4, DDIM) per step")
     ap.add_argument("--sweep", action="store_true",
                     help="measure ONLY the row-sharded tile sweep (strong scaling; --steps / --warmup are diffusion steps of the ROI)")
-    ap.add_argument("--no-sweep", action="store_true", help="default mode: skip the short sweep appended as the `sweep` object")
+    ap.add_argument("--no-sweep", action="store_true", help="--full default mode: skip the short sweep appended as the `sweep` object")
     ap.add_argument("--overlap-streams", type=int, default=1,
                     help="2: the model runs the two halves of a call's images on two HIP streams (bit-identical; faster wall clock, but "
                          "per-kernel durations -- the roofline fields -- then include the other stream's interference). Default 1")
-    ap.add_argument("--no-tile-extra", action="store_true", help="default mode: skip the stacked one-tile 16-bit step appended as `extra`")
+    ap.add_argument("--no-tile-extra", action="store_true", help="--full default mode: skip the stacked one-tile 16-bit step appended as `extra`")
     ap.add_argument("--sweep-hnm", type=int, default=8)
     ap.add_argument("--sweep-wnm", type=int, default=8)
-    ap.add_argument("--sweep-steps", type=int, default=2, help="timed diffusion steps of the appended sweep (1 warm-up step)")
+    ap.add_argument("--sweep-steps", type=int, default=2, help="timed diffusion steps of the appended --full sweep (1 warm-up step)")
     ap.add_argument("--sweep-dtype", choices=["bf16", "f16", "f32"], default="bf16")
     ap.add_argument("--sweep-batch-tiles", type=int, default=8, help="tiles of a tile row per model call")
     ap.add_argument("--sweep-batch-rows", type=int, default=2, help="tile rows per model call (shared-halo windows only)")

@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _bench(extra):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--sweep", "--sweep-hnm", "2", "--sweep-wnm", "2", "--steps", "2", "--warmup", "0",
-           "--no-cpu-baseline"] + extra
+           "--no-cpu-baseline", "--full"] + extra
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -37,10 +37,10 @@ def test_two_rank_sweep_on_one_gpu_equals_single_process():
 
 
 def test_default_bench_line_with_two_ranks_rehearsed():
-    """The driver's form `bench.py --gpus N --steps K --warmup W` at N = 2 (self-spawned ranks): the weak-scaling
-    configs[1] line plus the appended row-sharded sweep object."""
+    """The driver's form `bench.py --gpus N --steps K --warmup W` at N = 2 (self-spawned ranks), with `--full`: the
+    weak-scaling configs[1] line plus the appended row-sharded sweep object."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse", "--steps", "2", "--warmup", "1", "--sweep-hnm", "2",
-           "--sweep-wnm", "1", "--sweep-steps", "1"]
+           "--sweep-wnm", "1", "--sweep-steps", "1", "--full"]
     env = dict(os.environ)
     env.pop("RANK", None); env.pop("WORLD_SIZE", None)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
