@@ -320,6 +320,20 @@ int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host
                    const void* shift_host, const void* mask_cb8, float drop_scale, int per_image, void* dx_cb8,
                    void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream);
 
+/* ResBlock dropout with the keep mask DRAWN on the GPU: element (n, c, z, y, x) of a [N, C, Z, S, S] activation is
+ * dropped iff output word c & 3 of Philox4x32-10(counter (v lo, v hi, site, c >> 2), key (key lo, key hi)) < min(floor(p 2^32),
+ * 2^32 - 1), v = ((n Z + z) S + y) S + x; kept elements are scaled by 1 / (1 - p).  0 <= p < 1; p = 0 is the no-dropout path.
+ * The forward and its backward draw the same mask from (key, site, p): no mask is stored.  Arguments otherwise as above. */
+int tm_op_prep_train_rng(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                         unsigned long long key, unsigned site, float p, int per_image, void* y_cb8, int N, int C, int Z, int S,
+                         void* stream);
+int tm_op_prep_bwd_rng(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                       const void* shift_host, unsigned long long key, unsigned site, float p, int per_image, void* dx_cb8,
+                       void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream);
+/* The keep mask of the two entry points above as an fp32 CB8 tensor [N][ceil(C/8)][Z][S][S][8] of 0 / 1 (pad channels 0): the
+ * supplied-mask ops given this mask compute what the drawing ones compute.  Tests and debugging. */
+int tm_op_dropout_mask(unsigned long long key, unsigned site, float p, void* mask_cb8, int N, int C, int Z, int S, void* stream);
+
 /* dL/dx of Conv3d(k = 3x3x3 pad 1 (ksize 3) | 1x1x1 (ksize 1)): dy CB8 [N, Cout, Z, S, S] -> dx CB8 [N, Cin, Z, S, S];
  * w [Cout][Cin][k^3] HOST as in the reference state_dict.  Runs on the forward MFMA conv kernel with re-packed weights. */
 int tm_op_conv_dgrad(const void* dy_cb8, const void* w_host, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,

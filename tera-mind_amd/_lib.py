@@ -77,6 +77,9 @@ SIGNATURES = {
                        [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "tm_op_prep_train": (c_int, [c_void_p] * 5 + [c_float, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
     "tm_op_prep_bwd": (c_int, [c_void_p] * 6 + [c_float, c_int] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "tm_op_prep_train_rng": (c_int, [c_void_p] * 4 + [C.c_uint64, C.c_uint, c_float, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "tm_op_prep_bwd_rng": (c_int, [c_void_p] * 5 + [C.c_uint64, C.c_uint, c_float, c_int] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
+    "tm_op_dropout_mask": (c_int, [C.c_uint64, C.c_uint, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),
     "tm_op_conv_dgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "tm_op_conv_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "tm_op_ew": (c_int, [c_int] + [c_void_p] * 5 + [C.c_long, c_void_p]),

@@ -61,6 +61,31 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): counter c[4], key (k0, k1) -> c[4] replaced by the output.
+// Registers only: per round two 32x32 -> 64 products (mul_lo / __umulhi), three xors and the key bump.
+__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    c[0] = hi1 ^ c[1] ^ k0; c[1] = lo1; c[2] = hi0 ^ c[3] ^ k1; c[3] = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+// ResBlock dropout keep bits of channel block cb (channels 8 cb .. 8 cb + 7) at voxel index v: bit j set = channel
+// 8 cb + j kept.  Counter (v lo, v hi, site, c >> 2), key (key lo, key hi); channel c takes output word c & 3 and is dropped iff
+// that word < thr.  Two Philox calls per 8 channels.
+__device__ __forceinline__ uint32_t drop_keep8(unsigned long long key, uint32_t site, unsigned long long v, int cb, uint32_t thr) {
+  uint32_t bits = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    uint32_t c[4] = {(uint32_t)v, (uint32_t)(v >> 32), site, (uint32_t)(2 * cb + h)};
+    philox4x32_10(c, (uint32_t)key, (uint32_t)(key >> 32));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bits |= (uint32_t)(c[j] >= thr) << (4 * h + j);
+  }
+  return bits;
+}
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));

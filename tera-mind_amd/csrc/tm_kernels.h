@@ -169,6 +169,14 @@ struct PrepLaunch {
   float drop_scale = 1.f;
 };
 hipError_t launch_prep(const PrepLaunch& L, hipStream_t s);
+// training forward with the keep mask DRAWN in the kernel instead of supplied (drop_keep8: Philox4x32-10; drop_mask
+// null): out = act(...) * keep * L.drop_scale.  One fp32 source, fp32 out, RS_SAME, no collage (prep_kernel<1, *, true>).  The draw
+// parameters travel beside PrepLaunch (PrepDropArgs), so that the inference instantiations keep their arguments and code.
+struct DropRng { unsigned long long key; uint32_t site, thr; };    // drop iff word < thr
+hipError_t launch_prep_drop(const PrepLaunch& L, const DropRng& r, hipStream_t s);
+// the keep mask of drop_keep8 as an fp32 CB8 tensor of 0 / 1 (pad channels 0)
+hipError_t launch_dropout_mask(float* mask, int N, int C, int Z, int S, unsigned long long key, uint32_t site, uint32_t thr,
+                               hipStream_t s);
 // test / measurement knob (tm_op_prep_h16): 0 automatic, 1 prep_kernel, 2 / 3 the two forms of prep_h16_kernel; process-wide,
 // set and reset around the op's own launches only
 void set_prep_variant(int v);
@@ -247,7 +255,8 @@ hipError_t launch_pad_patchify(const float* img, float* patches, int b, int C, i
 hipError_t launch_prep_bwd(const float* x, long x_ns, const float* g, long g_ns, const float* mask, long mask_ns, float drop_scale,
                            const float* w, const float* scale, const float* shift, long mod_stride, int per_image, float* dx,
                            long dx_ns, float* dw, float* dscale, float* dshift, int N, int Cb, int C_real, int Z, int S,
-                           float* scratch, hipStream_t s);           // scratch: prep_bwd_scratch_floats(...) floats (two-stage sums)
+                           float* scratch, hipStream_t s,             // scratch: prep_bwd_scratch_floats(...) floats (two-stage sums)
+                           const DropRng* rng = nullptr);             // non-null: mask drawn in the kernel (mask must be null)
 size_t prep_bwd_scratch_floats(int N, int Cb, int Z, int S, bool with_mod);
 hipError_t launch_conv_wgrad(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, hipStream_t s);
 hipError_t launch_chan_sum(const TV& x, float* out, int C, hipStream_t s);

@@ -516,12 +516,18 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
 // the channel blocks and combine their sums of squares through LDS.
 // ==========================================================================================
 struct PrepArgs { PrepLaunch L; };
+struct PrepDropArgs { PrepLaunch L; DropRng r; };
+__device__ __forceinline__ DropRng rng_of(const PrepArgs&) { return DropRng{0ull, 0u, 0u}; }
+__device__ __forceinline__ DropRng rng_of(const PrepDropArgs& a) { return a.r; }
 
 // CACHED: the voxel's channel blocks owned by this wave (<= 8) stay in registers between the
 // sum-of-squares pass and the apply pass, so every source byte is read from HBM once.
-template <int NSUB, bool CACHED>
-__global__ __launch_bounds__(256) void prep_kernel(PrepArgs pa) {
+// DRAW (NSUB 1, fp32 out; args PrepDropArgs): the training dropout keep mask is drawn here (drop_keep8, one Philox pair per
+// channel block) instead of read from drop_mask.  Its own instantiations: the inference ones compile as without it.
+template <int NSUB, bool CACHED, bool DRAW = false, class Args = PrepArgs>
+__global__ __launch_bounds__(256) void prep_kernel(Args pa) {
   const PrepLaunch& L = pa.L;
+  const DropRng R = rng_of(pa);
   __shared__ float red[4][NSUB][64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int S = L.S, Z = L.Z;
@@ -677,6 +683,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs pa) {
     float o[8], r[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { o[j] = 0.f; r[j] = 0.f; }
+    uint32_t keep = 0;
+    if (DRAW) keep = drop_keep8(R.key, R.site, (unsigned long long)vidx, gb, R.thr);
 #pragma unroll
     for (int sub = 0; sub < NSUB; ++sub) {
       f32x4 a0, a1;
@@ -692,7 +700,8 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs pa) {
         // SiLU on the hardware exp2 / rcp (1 ulp each, ~3e-7 relative on the result) in fp32 too: libm expf + an IEEE division
         // are ~30 VALU instructions per element of an otherwise HBM-bound pass (configs[1] fp32: 55.22 -> 54.63 ms same box)
         if (L.act) v = silu_h16(v);
-        if (L.drop_mask) v *= L.drop_mask[(long)n * L.drop_ns + (long)gb * oplane + oin + j] * L.drop_scale;
+        if (DRAW) v *= (float)((keep >> j) & 1u) * L.drop_scale;
+        else if (L.drop_mask) v *= L.drop_mask[(long)n * L.drop_ns + (long)gb * oplane + oin + j] * L.drop_scale;
         o[j] += v;
       }
     }
@@ -752,6 +761,32 @@ __global__ __launch_bounds__(256) void prep_kernel(PrepArgs pa) {
       if (L.raw_h) *(uint4*)(L.raw_h + (long)n * L.raw_h_nstride + (long)(cbtot + pb) * oplane + oin) = uint4{0u, 0u, 0u, 0u};
     }
   }
+}
+
+// The 0 / 1 keep mask the two drawing kernels use, written as an fp32 CB8 tensor [N][Cb][Z][S][S][8] (pad channels c >= C: 0).
+// One thread per (voxel, channel block).  Tests and debugging only.
+__global__ __launch_bounds__(256) void dropout_mask_kernel(float* mask, long vox, int Cb, int C, long plane_vox,
+                                                           unsigned long long key, uint32_t site, uint32_t thr) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= vox * Cb) return;
+  const long v = t % vox;                           // consecutive threads: consecutive voxels of one channel block
+  const int cb = (int)(t / vox);
+  const long n = v / plane_vox, r = v - n * plane_vox;
+  const uint32_t keep = drop_keep8(key, site, (unsigned long long)v, cb, thr);
+  float o[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = (8 * cb + j < C && ((keep >> j) & 1u)) ? 1.f : 0.f;
+  float* p = mask + ((n * Cb + cb) * plane_vox + r) * 8;
+  *(f32x4*)p = f32x4{o[0], o[1], o[2], o[3]};
+  *(f32x4*)(p + 4) = f32x4{o[4], o[5], o[6], o[7]};
+}
+hipError_t launch_dropout_mask(float* mask, int N, int C, int Z, int S, unsigned long long key, uint32_t site, uint32_t thr,
+                               hipStream_t s) {
+  const int Cb = (C + 7) / 8;
+  const long pv = (long)Z * S * S, vox = (long)N * pv;
+  if (vox * Cb == 0) return hipSuccess;
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)((vox * Cb + 255) / 256)), dim3(256), 0, s, mask, vox, Cb, C, pv, key, site, thr);
+  return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1094,6 +1129,17 @@ static bool launch_prep_h16(const PrepLaunch& L, hipStream_t s, int variant) {
     else hipLaunchKernelGGL((prep_h16_kernel<4, 40, F16>), dim3(grid), dim3(256), 0, s, pa);
   }
   return true;
+}
+
+hipError_t launch_prep_drop(const PrepLaunch& L, const DropRng& r, hipStream_t s) {
+  if (L.nsrc != 1 || L.src_h || L.src[0].collage || L.resample != RS_SAME || !L.out || L.out_h || L.raw || L.raw_h || L.drop_mask ||
+      L.mod == MOD_VOXEL || L.pad_blocks)
+    return hipErrorInvalidValue;
+  PrepDropArgs pa; pa.L = L; pa.r = r;
+  const unsigned grid = (unsigned)(((long)L.N * L.Z * L.S * L.S + 63) / 64);
+  if (L.src[0].Cb <= 32) hipLaunchKernelGGL((prep_kernel<1, true, true, PrepDropArgs>), dim3(grid), dim3(256), 0, s, pa);
+  else hipLaunchKernelGGL((prep_kernel<1, false, true, PrepDropArgs>), dim3(grid), dim3(256), 0, s, pa);
+  return hipGetLastError();
 }
 
 hipError_t launch_prep(const PrepLaunch& L, hipStream_t s) {

@@ -6,6 +6,8 @@
 #include "../../include/teramind_hip.h"
 #include "tm_kernels.h"
 
+#include <algorithm>
+#include <cmath>
 #include <map>
 #include <string>
 #include <vector>
@@ -2062,9 +2064,18 @@ static std::vector<float> pad_rows(const float* v, int rows, int C, int Cp) {
   return o;
 }
 
-extern "C" int tm_op_prep_train(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
-                                const void* mask_cb8, float drop_scale, int per_image, void* y_cb8, int N, int C, int Z, int S,
-                                void* stream) {
+// dropout probability p -> the drawn mask's threshold (drop iff word < thr) and 1 / (1 - p), both as DESIGN §8 fixes them
+static bool drop_rng_of(unsigned long long key, unsigned site, float p, DropRng& r, float& scale) {
+  if (!(p >= 0.f && p < 1.f)) return false;
+  r.key = key; r.site = site;
+  r.thr = (uint32_t)std::min(std::floor((double)p * 4294967296.0), 4294967295.0);
+  scale = 1.0f / (float)(1.0 - (double)p);
+  return true;
+}
+
+static int prep_train_impl(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                           const void* mask_cb8, float drop_scale, const DropRng* rng, int per_image, void* y_cb8, int N, int C, int Z,
+                           int S, void* stream) {
   if (!x_cb8 || !norm_w_host || !y_cb8 || per_image < 1) return fail(TM_ERR_ARG, "bad argument");
   const int Cb = (C + 7) / 8, Cp = Cb * 8, nimg = (N + per_image - 1) / per_image;
   DevTmp tmp;
@@ -2084,16 +2095,33 @@ extern "C" int tm_op_prep_train(const void* x_cb8, const void* norm_w_host, cons
   P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 1; P.per_image = per_image;
   if (dsc) { P.mod = MOD_IMAGE; P.mod_scale = dsc; P.mod_shift = dsh; P.mod_stride = Cp; }
   if (mask_cb8) { P.drop_mask = (const float*)mask_cb8; P.drop_ns = x.nstride; P.drop_scale = drop_scale; }
+  if (rng) P.drop_scale = drop_scale;
   P.out = y.p; P.out_nstride = y.nstride;
-  hipError_t e = launch_prep(P, (hipStream_t)stream);
+  hipError_t e = rng ? launch_prep_drop(P, *rng, (hipStream_t)stream) : launch_prep(P, (hipStream_t)stream);
   hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
   if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "prep (training forward): %s", hipGetErrorString(e != hipSuccess ? e : e2));
   return TM_OK;
 }
 
-extern "C" int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
-                              const void* shift_host, const void* mask_cb8, float drop_scale, int per_image, void* dx_cb8,
-                              void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
+extern "C" int tm_op_prep_train(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                                const void* mask_cb8, float drop_scale, int per_image, void* y_cb8, int N, int C, int Z, int S,
+                                void* stream) {
+  return prep_train_impl(x_cb8, norm_w_host, scale_host, shift_host, mask_cb8, drop_scale, nullptr, per_image, y_cb8, N, C, Z, S, stream);
+}
+
+extern "C" int tm_op_prep_train_rng(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                                    unsigned long long key, unsigned site, float p, int per_image, void* y_cb8, int N, int C, int Z,
+                                    int S, void* stream) {
+  DropRng r;
+  float ds = 1.f;
+  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
+  return prep_train_impl(x_cb8, norm_w_host, scale_host, shift_host, nullptr, p > 0.f ? ds : 1.0f, p > 0.f ? &r : nullptr, per_image,
+                         y_cb8, N, C, Z, S, stream);
+}
+
+static int prep_bwd_impl(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                         const void* shift_host, const void* mask_cb8, float drop_scale, const DropRng* rng, int per_image, void* dx_cb8,
+                         void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
   if (!x_cb8 || !g_cb8 || !norm_w_host || !dx_cb8 || !dw_host || per_image < 1) return fail(TM_ERR_ARG, "bad argument");
   if (scale_host && (!shift_host || !dscale_host || !dshift_host)) return fail(TM_ERR_ARG, "scale without shift / gradient outputs");
   const int Cb = (C + 7) / 8, Cp = Cb * 8, nimg = (N + per_image - 1) / per_image;
@@ -2115,7 +2143,7 @@ extern "C" int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* 
   float* scratch = tmp.up(nullptr, 0, prep_bwd_scratch_floats(N, Cb, Z, S, scale_host != nullptr));
   if (!scratch) return fail(TM_ERR_HIP, "device allocation failed");
   hipError_t e = launch_prep_bwd(x.p, x.nstride, (const float*)g_cb8, x.nstride, (const float*)mask_cb8, x.nstride, drop_scale, dwt,
-                                 dsc, dsh, Cp, per_image, (float*)dx_cb8, x.nstride, ddw, ddsc, ddsh, N, Cb, C, Z, S, scratch, st);
+                                 dsc, dsh, Cp, per_image, (float*)dx_cb8, x.nstride, ddw, ddsc, ddsh, N, Cb, C, Z, S, scratch, st, rng);
   hipError_t e2 = hipStreamSynchronize(st);
   if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "prep backward: %s", hipGetErrorString(e != hipSuccess ? e : e2));
   std::vector<float> h(Cp);
@@ -2130,6 +2158,36 @@ extern "C" int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* 
       memcpy((float*)dshift_host + (size_t)r * C, hh.data() + (size_t)r * Cp, C * sizeof(float));
     }
   }
+  return TM_OK;
+}
+
+extern "C" int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                              const void* shift_host, const void* mask_cb8, float drop_scale, int per_image, void* dx_cb8,
+                              void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
+  return prep_bwd_impl(x_cb8, g_cb8, norm_w_host, scale_host, shift_host, mask_cb8, drop_scale, nullptr, per_image, dx_cb8, dw_host,
+                       dscale_host, dshift_host, N, C, Z, S, stream);
+}
+
+extern "C" int tm_op_prep_bwd_rng(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                                  const void* shift_host, unsigned long long key, unsigned site, float p, int per_image, void* dx_cb8,
+                                  void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
+  DropRng r;
+  float ds = 1.f;
+  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
+  return prep_bwd_impl(x_cb8, g_cb8, norm_w_host, scale_host, shift_host, nullptr, p > 0.f ? ds : 1.0f, p > 0.f ? &r : nullptr, per_image,
+                       dx_cb8, dw_host, dscale_host, dshift_host, N, C, Z, S, stream);
+}
+
+extern "C" int tm_op_dropout_mask(unsigned long long key, unsigned site, float p, void* mask_cb8, int N, int C, int Z, int S,
+                                  void* stream) {
+  DropRng r;
+  float ds = 1.f;
+  if (!mask_cb8 || N < 0 || C < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_dropout_mask((float*)mask_cb8, N, C, Z, S, r.key, r.site, r.thr, st);
+  hipError_t e2 = hipStreamSynchronize(st);
+  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "dropout mask: %s", hipGetErrorString(e != hipSuccess ? e : e2));
   return TM_OK;
 }
 

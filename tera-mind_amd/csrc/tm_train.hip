@@ -16,7 +16,8 @@ namespace tmk {
 //   xh = x * rstd(v),  rstd = rsqrt(mean_c x^2 + eps)          LlamaRMSNorm(dim=1), MBAblocks.py:21-43
 //   n  = xh * w[c]
 //   m  = n * (1 + scale[img][c]) + shift[img][c]               apply_conditions, MBAblocks.py:356-367 (optional)
-//   s  = SiLU(m);  y = s * mask * drop_scale                   nn.SiLU, nn.Dropout(p) with a SUPPLIED keep mask (optional)
+//   s  = SiLU(m);  y = s * mask * drop_scale                   nn.SiLU, nn.Dropout(p) with a SUPPLIED keep mask (optional),
+//                                                              or (DRAW) the mask drawn again as the forward drew it (drop_keep8)
 // Backward, g = dL/dy:
 //   ds = g * mask * drop_scale;  dm = ds * sig(m) * (1 + m * (1 - sig(m)))
 //   dscale[img][c] += dm * n;  dshift[img][c] += dm;  dn = dm * (1 + scale)
@@ -39,8 +40,12 @@ struct PrepBwdArgs {
   float* part_dw;                       // [workgroups][Cb*8] partial sums of this workgroup's 64 voxels
   float* part_ds; float* part_dh;       // [workgroups][2 (image of lane 0 | the next image)][Cb*8] partial dscale / dshift, or null
   int N, Cb, Z, S; float inv_c;
+  unsigned long long drop_key; uint32_t drop_site, drop_thr;    // DRAW only
 };
 
+// DRAW: the keep bits of a channel block are drawn once in pass 1 and kept (8 bits per block) for the wave's first 16 channel
+// blocks (Cb <= 64, every ResBlock of the model); further blocks draw again in pass 2
+template <bool DRAW>
 __global__ __launch_bounds__(256) void prep_bwd_kernel(PrepBwdArgs a) {
   __shared__ float red[4][64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -65,17 +70,18 @@ __global__ __launch_bounds__(256) void prep_bwd_kernel(PrepBwdArgs a) {
   const float rstd = 1.0f / sqrtf((red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) * a.inv_c + TM_EPS);
   __syncthreads();
   // dxh for one channel block (recomputed in both passes: cheaper than keeping Cb * 8 values per lane)
-  auto block = [&](int cb, float (&xh)[8], float (&dxh)[8], float (&dm)[8], float (&nn)[8]) {
+  auto block = [&](int cb, uint32_t keep, float (&xh)[8], float (&dxh)[8], float (&dm)[8], float (&nn)[8]) {
     const float* p = a.x + (long)n * a.x_ns + (long)cb * plane + off;
     const float* gp = a.g + (long)n * a.g_ns + (long)cb * plane + off;
     const f32x4 v0 = *(const f32x4*)p, v1 = *(const f32x4*)(p + 4);
     const f32x4 g0 = *(const f32x4*)gp, g1 = *(const f32x4*)(gp + 4);
     f32x4 k0 = {1.f, 1.f, 1.f, 1.f}, k1 = {1.f, 1.f, 1.f, 1.f};
-    if (a.mask) { const float* mp = a.mask + (long)n * a.mask_ns + (long)cb * plane + off; k0 = *(const f32x4*)mp; k1 = *(const f32x4*)(mp + 4); }
+    if (!DRAW && a.mask) { const float* mp = a.mask + (long)n * a.mask_ns + (long)cb * plane + off; k0 = *(const f32x4*)mp; k1 = *(const f32x4*)(mp + 4); }
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = cb * 8 + j;
-      const float xv = j < 4 ? v0[j] : v1[j - 4], gv = j < 4 ? g0[j] : g1[j - 4], kv = j < 4 ? k0[j] : k1[j - 4];
+      const float xv = j < 4 ? v0[j] : v1[j - 4], gv = j < 4 ? g0[j] : g1[j - 4];
+      const float kv = DRAW ? (float)((keep >> j) & 1u) : (j < 4 ? k0[j] : k1[j - 4]);
       const float wc = a.w[c];
       const float sc = a.scale ? a.scale[(long)img * a.mod_stride + c] : 0.f;
       const float sh = a.shift ? a.shift[(long)img * a.mod_stride + c] : 0.f;
@@ -90,11 +96,18 @@ __global__ __launch_bounds__(256) void prep_bwd_kernel(PrepBwdArgs a) {
   };
   // pass 1: mean_c(dxh * xh) per voxel, and the per-channel sums
   float dot = 0.f;
-  for (int cb = wv; cb < a.Cb; cb += 4) {
+  unsigned long long kb_lo = 0, kb_hi = 0;
+  for (int cb = wv, i = 0; cb < a.Cb; cb += 4, ++i) {
     float xh[8], dxh[8], dm[8], nn[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { xh[j] = 0.f; dxh[j] = 0.f; dm[j] = 0.f; nn[j] = 0.f; }
-    if (valid) block(cb, xh, dxh, dm, nn);
+    uint32_t keep = 0;
+    if (DRAW && valid) {
+      keep = drop_keep8(a.drop_key, a.drop_site, (unsigned long long)vidx, cb, a.drop_thr);
+      if (i < 8) kb_lo |= (unsigned long long)keep << (8 * i);
+      else if (i < 16) kb_hi |= (unsigned long long)keep << (8 * (i - 8));
+    }
+    if (valid) block(cb, keep, xh, dxh, dm, nn);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = cb * 8 + j;
@@ -127,9 +140,13 @@ __global__ __launch_bounds__(256) void prep_bwd_kernel(PrepBwdArgs a) {
   const float mean_dot = (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) * a.inv_c;
   if (!valid) return;
   // pass 2: dx
-  for (int cb = wv; cb < a.Cb; cb += 4) {
+  for (int cb = wv, i = 0; cb < a.Cb; cb += 4, ++i) {
     float xh[8], dxh[8], dm[8], nn[8];
-    block(cb, xh, dxh, dm, nn);
+    uint32_t keep = 0;
+    if (DRAW) keep = i < 8 ? (uint32_t)(kb_lo >> (8 * i)) & 0xFFu
+                           : (i < 16 ? (uint32_t)(kb_hi >> (8 * (i - 8))) & 0xFFu
+                                     : drop_keep8(a.drop_key, a.drop_site, (unsigned long long)vidx, cb, a.drop_thr));
+    block(cb, keep, xh, dxh, dm, nn);
     float* dp = a.dx + (long)n * a.dx_ns + (long)cb * plane + off;
     f32x4 o0, o1;
 #pragma unroll
@@ -180,7 +197,7 @@ size_t prep_bwd_scratch_floats(int N, int Cb, int Z, int S, bool with_mod) {
 hipError_t launch_prep_bwd(const float* x, long x_ns, const float* g, long g_ns, const float* mask, long mask_ns, float drop_scale,
                            const float* w, const float* scale, const float* shift, long mod_stride, int per_image, float* dx,
                            long dx_ns, float* dw, float* dscale, float* dshift, int N, int Cb, int C_real, int Z, int S,
-                           float* scratch, hipStream_t s) {
+                           float* scratch, hipStream_t s, const DropRng* rng) {
   if (per_image < 1 || (long)per_image * Z * S * S < 64 || !scratch) return hipErrorInvalidValue;
   const long vox = (long)N * Z * S * S, nwg = (vox + 63) / 64;
   const int C8 = Cb * 8;
@@ -188,8 +205,14 @@ hipError_t launch_prep_bwd(const float* x, long x_ns, const float* g, long g_ns,
   float* part_ds = scale ? scratch + nwg * C8 : nullptr;
   float* part_dh = scale ? part_ds + nwg * 2 * C8 : nullptr;
   PrepBwdArgs a{x, x_ns, g, g_ns, mask, mask_ns, drop_scale, w, scale, shift, mod_stride, per_image, dx, dx_ns, part_dw, part_ds, part_dh,
-                N, Cb, Z, S, 1.0f / (float)C_real};
-  hipLaunchKernelGGL(prep_bwd_kernel, dim3((unsigned)nwg), dim3(256), 0, s, a);
+                N, Cb, Z, S, 1.0f / (float)C_real, 0ull, 0u, 0u};
+  if (rng) {
+    if (mask) return hipErrorInvalidValue;
+    a.drop_key = rng->key; a.drop_site = rng->site; a.drop_thr = rng->thr;
+    hipLaunchKernelGGL(prep_bwd_kernel<true>, dim3((unsigned)nwg), dim3(256), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(prep_bwd_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, s, a);
+  }
   hipLaunchKernelGGL(prep_bwd_reduce_dw_kernel, dim3((unsigned)((C8 + 63) / 64)), dim3(64), 0, s, part_dw, nwg, C8, dw);
   if (scale) {
     const long nimg = (N + per_image - 1) / per_image;

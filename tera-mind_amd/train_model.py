@@ -16,11 +16,14 @@ model/unet_ours.py).  Here `UNetTrain.forward` records a tape of ops, each with 
 
 Channel concatenation, the half-patch collage (model/unet_ours.py:325-341) and the z slice of down_z are re-indexings of
 device tensors (torch views / cat / pad: no arithmetic); the loss and d(loss)/d(pred) are a handful of elementwise torch
-ops on the two [n, C, ps, ps] predictions (diffusion/base.py:272-288).  The model runs as in `.eval()` with gradients --
-ResBlock dropout (p = 0.1, config_parm.py:46) is the identity here; `training.ResBlockTrain` covers the dropout forward /
-backward with a supplied mask.  Functional, not tuned: every op synchronises, weights are re-packed per call.
+ops on the two [n, C, ps, ps] predictions (diffusion/base.py:272-288).  ResBlock dropout (nn.Dropout(p) between SiLU and the
+second conv, p = 0.1 in the reference, config_parm.py:46) is live when `UNetTrain(..., dropout_p=p)` is given p > 0: the keep
+mask is drawn on the GPU from (per-forward key, block site, p) by the forward prep kernel and drawn again by its backward
+(tm_op_prep_train_rng / tm_op_prep_bwd_rng; the rule is DESIGN.md §8), so no mask is stored.  p = 0 (the default) is the
+model as in `.eval()`.  Functional, not tuned: every op synchronises, weights are re-packed per call.
 """
 import ctypes as C
+import hashlib
 import math
 from typing import Dict, List, Optional, Tuple
 
@@ -72,12 +75,35 @@ def block_plan(cfg: PathConfig):
     return enc, mid, dec
 
 
-class UNetTrain:
-    """forward(x_p, t_map, rna_dense, b) -> (pred, pred2); backward(dpred, dpred2) -> {state_dict key: gradient (host fp32)}.
-    `state` = the reference state_dict (host tensors / arrays)."""
+_OUT_NORM = ".out_layers.0.weight"
 
-    def __init__(self, cfg: PathConfig, state: Dict[str, "object"], device="cuda:0"):
+
+def dropout_sites(keys) -> Dict[str, int]:
+    """ResBlock prefix -> j, its position in the sorted list of state-dict keys ending in `.out_layers.0.weight` (suffix removed).
+    A block's dropout call k (0, or 1 for the plain pass of a decoder block) draws with site 2 j + k."""
+    return {p: j for j, p in enumerate(sorted(k[:-len(_OUT_NORM)] for k in keys if k.endswith(_OUT_NORM)))}
+
+
+def derive_dropout_key(seed: int, step: int, micro: int = 0) -> int:
+    """A 64-bit dropout key for one forward of a training loop: distinct per (base seed, optimizer step, micro-batch), so that no
+    two forwards of a run share masks."""
+    h = hashlib.blake2b(f"teramind-dropout/{int(seed)}/{int(step)}/{int(micro)}".encode(), digest_size=8).digest()
+    return int.from_bytes(h, "little")
+
+
+class UNetTrain:
+    """forward(x_p, t_map, rna_dense, b, dropout_key) -> (pred, pred2); backward(dpred, dpred2) -> {state_dict key: gradient
+    (host fp32)}.  `state` = the reference state_dict (host tensors / arrays); `dropout_p` = the ResBlock dropout probability
+    (0: none, as in `.eval()`)."""
+
+    def __init__(self, cfg: PathConfig, state: Dict[str, "object"], device="cuda:0", dropout_p: float = 0.0):
+        if not 0.0 <= dropout_p < 1.0:
+            raise ValueError(f"dropout_p must lie in [0, 1), got {dropout_p}")
         self.cfg = cfg
+        self.dropout_p = float(dropout_p)
+        self._sites = dropout_sites(state.keys())
+        self._drop_key: Optional[int] = None
+        self._drop_calls: Dict[str, int] = {}
         self.dev = torch.device(device)
         self.W = {k: _host(torch.as_tensor(v)) for k, v in state.items()}
         self._Wd: Dict[str, torch.Tensor] = {}
@@ -150,8 +176,9 @@ class UNetTrain:
         self.tape.append(bwd)
         return out
 
-    def prep(self, x: _V, key: str, ss: Optional[_V] = None, per_image: int = 1) -> _V:
-        """SiLU(RMSNorm_C(x) * w [* (1 + scale[img]) + shift[img]]); ss = plain [nimg, 2 C] value (scale | shift)."""
+    def prep(self, x: _V, key: str, ss: Optional[_V] = None, per_image: int = 1, drop: Optional[Tuple[int, int, float]] = None) -> _V:
+        """[Dropout](SiLU(RMSNorm_C(x) * w [* (1 + scale[img]) + shift[img]])); ss = plain [nimg, 2 C] value (scale | shift);
+        drop = (key, site, p): the keep mask is drawn in the kernel, and drawn again by the backward."""
         nw = self.W[key].reshape(-1)
         N, Z, S = self._geo(x.t)
         sc = sh = None
@@ -159,8 +186,12 @@ class UNetTrain:
             h = ss.t.to("cpu")
             sc, sh = h[:, :x.C].contiguous(), h[:, x.C:].contiguous()
         y = torch.empty_like(x.t)
-        _lib.check(_lib.lib().tm_op_prep_train(_lib.ptr(x.t), _hp(nw), _hp(sc), _hp(sh), None, 1.0, per_image, _lib.ptr(y), N, x.C, Z, S,
-                                               self._st()), "tm_op_prep_train")
+        if drop is None:
+            _lib.check(_lib.lib().tm_op_prep_train(_lib.ptr(x.t), _hp(nw), _hp(sc), _hp(sh), None, 1.0, per_image, _lib.ptr(y), N, x.C, Z, S,
+                                                   self._st()), "tm_op_prep_train")
+        else:
+            _lib.check(_lib.lib().tm_op_prep_train_rng(_lib.ptr(x.t), _hp(nw), _hp(sc), _hp(sh), *drop, per_image, _lib.ptr(y), N, x.C, Z, S,
+                                                       self._st()), "tm_op_prep_train_rng")
         out = _V(y, x.C)
 
         def bwd():
@@ -169,8 +200,13 @@ class UNetTrain:
             dw = torch.empty((x.C,), dtype=torch.float32)
             dsc = torch.empty((nimg, x.C), dtype=torch.float32) if ss is not None else None
             dsh = torch.empty((nimg, x.C), dtype=torch.float32) if ss is not None else None
-            _lib.check(_lib.lib().tm_op_prep_bwd(_lib.ptr(x.t), _lib.ptr(out.g), _hp(nw), _hp(sc), _hp(sh), None, 1.0, per_image, _lib.ptr(dx),
-                                                 _hp(dw), _hp(dsc), _hp(dsh), N, x.C, Z, S, self._st()), "tm_op_prep_bwd")
+            if drop is None:
+                _lib.check(_lib.lib().tm_op_prep_bwd(_lib.ptr(x.t), _lib.ptr(out.g), _hp(nw), _hp(sc), _hp(sh), None, 1.0, per_image,
+                                                     _lib.ptr(dx), _hp(dw), _hp(dsc), _hp(dsh), N, x.C, Z, S, self._st()), "tm_op_prep_bwd")
+            else:
+                _lib.check(_lib.lib().tm_op_prep_bwd_rng(_lib.ptr(x.t), _lib.ptr(out.g), _hp(nw), _hp(sc), _hp(sh), *drop, per_image,
+                                                         _lib.ptr(dx), _hp(dw), _hp(dsc), _hp(dsh), N, x.C, Z, S, self._st()),
+                           "tm_op_prep_bwd_rng")
             self._gacc(key, dw)
             self._acc(x, dx)
             if ss is not None:
@@ -260,7 +296,13 @@ class UNetTrain:
             a, xs = self.resample(a, 2), self.resample(x, 2)
         h1 = self.conv(a, f"{pfx}.in_layers.2")
         ss = self.linear(ste, f"{pfx}.emb_layers.1")
-        d = self.prep(h1, f"{pfx}.out_layers.0.weight", ss, per_image)
+        drop = None
+        if self.dropout_p > 0.0:
+            k = self._drop_calls.get(pfx, 0)           # 0: the block's first call in this forward, 1: its second (decoder, plain pass)
+            assert k < 2, pfx
+            self._drop_calls[pfx] = k + 1
+            drop = (self._drop_key, 2 * self._sites[pfx] + k, self.dropout_p)
+        d = self.prep(h1, f"{pfx}{_OUT_NORM}", ss, per_image, drop)
         h2 = self.conv(d, f"{pfx}.out_layers.3")
         if f"{pfx}.skip_connection.weight" in self.W:
             xs = self.conv(xs, f"{pfx}.skip_connection")
@@ -400,10 +442,18 @@ class UNetTrain:
             out.append(self.resample(x, 1))
         return out
 
-    def forward(self, x_p: torch.Tensor, t_map: torch.Tensor, rna: torch.Tensor, b: int):
+    def forward(self, x_p: torch.Tensor, t_map: torch.Tensor, rna: torch.Tensor, b: int, dropout_key: Optional[int] = None):
         """x_p [b * 4, n_stain * z, ps, ps] (the four patches of each image's 2 x 2 window), t_map [b] model-scale timesteps,
-        rna dense [b * 4, gn, gn, zs * 500]  ->  pred [b, C, ps, ps] (the centre collage patch), pred2 [b * 4, C, ps, ps]."""
+        rna dense [b * 4, gn, gn, zs * 500]  ->  pred [b, C, ps, ps] (the centre collage patch), pred2 [b * 4, C, ps, ps].
+        dropout_key: the 64-bit key of this forward's dropout masks (required when dropout_p > 0; see derive_dropout_key)."""
         cfg = self.cfg
+        if self.dropout_p > 0.0:
+            if dropout_key is None:
+                raise ValueError("UNetTrain.forward: dropout_p > 0 needs a dropout_key")
+            if not 0 <= int(dropout_key) < 1 << 64:
+                raise ValueError("dropout_key must be a 64-bit unsigned integer")
+        self._drop_key = None if dropout_key is None else int(dropout_key)
+        self._drop_calls = {}
         self.tape, self.grads = [], {}
         p1 = p2 = 2
         ne, nd = p1 * p2, (p1 - 1) * (p2 - 1)
@@ -466,10 +516,12 @@ class UNetTrain:
 
 
 def training_loss_and_grads(net: UNetTrain, sampler, x_start, r_start, t, loss_mask, noise, crop_index: Tuple[int, int], patch_size: int = 64,
-                            loss_type: str = "mse"):
+                            loss_type: str = "mse", dropout_p: Optional[float] = None, dropout_key: int = 0):
     """One training objective evaluation with gradients: GaussianDiffusionBeatGans.training_losses (diffusion/base.py:181-289,
     restated forward-only in diffusion.SpacedDiffusionBeatGans.training_losses) + the backward of the whole model.
-    Returns (loss, grads)."""
+    dropout_p: the ResBlock dropout probability (None: keep the net's own, `UNetTrain(dropout_p=...)`, 0 unless set; a value
+    is stored on the net); dropout_key: the 64-bit mask key of this evaluation (derive_dropout_key gives one per step and
+    micro-batch).  Returns (loss, grads)."""
     from .diffusion import sparse_repatch
     from .unet import densify_rna
     dev = net.dev
@@ -496,7 +548,11 @@ def training_loss_and_grads(net: UNetTrain, sampler, x_start, r_start, t, loss_m
     x_p, n_p, m_p = tiles2(x_t[sl]), tiles2(noise[sl]), tiles2(loss_mask[sl])
     b_ = t.shape[0]
     tm = torch.tensor(sampler.timestep_map, dtype=torch.int64, device=dev)[t]
-    pred, pred2 = net.forward(x_p, tm, rna, b_)
+    if dropout_p is not None:
+        if not 0.0 <= dropout_p < 1.0:
+            raise ValueError(f"dropout_p must lie in [0, 1), got {dropout_p}")
+        net.dropout_p = float(dropout_p)
+    pred, pred2 = net.forward(x_p, tm, rna, b_, dropout_key if net.dropout_p > 0.0 else None)
     n_img = n_p.reshape(b_, 2, 2, -1, patch_size, patch_size).permute(0, 3, 1, 4, 2, 5).reshape(b_, -1, 2 * patch_size, 2 * patch_size)
     noise_shift = n_img[:, :, halfp:-halfp, halfp:-halfp]
     d1, d2 = noise_shift - pred, n_p - pred2
