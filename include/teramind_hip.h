@@ -9,9 +9,11 @@
  *   - all tensor pointers are DEVICE pointers owned by the caller (PyTorch-ROCm
  *     allocations); the library borrows them for the duration of the enqueue and never
  *     frees or allocates caller-visible memory.  The only library-owned device memory is
- *     the packed weight arena (freed by tm_model_destroy).
+ *     the packed weight arena (freed by tm_model_destroy); the single-operator entry points
+ *     below keep call-local scratch of their own.
  *   - every call is asynchronous on `stream` (a hipStream_t passed as void*); no hidden
- *     device synchronisation, no internal threads.  One host thread per model.
+ *     device synchronisation, no internal threads.  One host thread per model.  (The
+ *     single-operator entry points below are the exception: see their section.)
  *   - return value: 0 = OK, negative = TM_ERR_*; text via tm_last_error() (thread local).
  *     No C++ exception crosses the ABI.
  *   - image-like tensors are fp32, contiguous, NCHW as in the reference ("b (s z) h w").
@@ -211,7 +213,14 @@ int tm_profile_enable(tm_model* m, int on);
 int tm_profile_collect(tm_model* m, tm_prof_stats* out);
 
 /* ---- single-operator entry points (parity tests of the individual kernels) -------------
- * Layout "CB8": fp32 [N][ceil(C/8)][Z][H][W][8] (channel blocks of 8, zero padded).      */
+ * Layout "CB8": fp32 [N][ceil(C/8)][Z][H][W][8] (channel blocks of 8, zero padded).
+ *
+ * These are test and training entry points (tests/test_gpu_ops.py, teramind_amd.training,
+ * teramind_amd.train_model), not the product path, and they keep the conventions above
+ * only in part: they take HOST weights, biases and gradient outputs where the signature
+ * says so (`*_host`), allocate and free temporary device memory inside the call, and
+ * synchronise `stream` before they return.  tm_op_to_cb8 and tm_op_from_cb8 only enqueue
+ * (no allocation, no synchronisation).                                                   */
 
 /* NCDHW fp32 <-> CB8 */
 int tm_op_to_cb8(const void* x_ncdhw, void* y_cb8, int N, int C, int Z, int H, int W, void* stream);

@@ -95,26 +95,26 @@ static const int BLOSC_MAX_SPLITS = 16, BLOSC_MIN_BUFFERSIZE = 128, BLOSC_HEADER
 int blosc_decompress(const void* src_, size_t src_bytes, void* dst_, size_t dst_cap, size_t* out_bytes) {
   const uint8_t* src = (const uint8_t*)src_;
   uint8_t* dst = (uint8_t*)dst_;
-  if (!src || src_bytes < (size_t)BLOSC_HEADER) return io_fail(TM_ERR_ARG, "blosc: frame shorter than its header");
+  if (!src || src_bytes < (size_t)BLOSC_HEADER) return fail(TM_ERR_ARG, "blosc: frame shorter than its header");
   const unsigned flags = src[2];
   const long typesize = src[3] ? src[3] : 1;
   const long nbytes = le32(src + 4), blocksize = le32(src + 8), cbytes = le32(src + 12);
   if (out_bytes) *out_bytes = (size_t)nbytes;
   if (!dst) return TM_OK;                                        // size query
-  if ((size_t)cbytes > src_bytes) return io_fail(TM_ERR_ARG, "blosc: frame truncated");
-  if ((size_t)nbytes > dst_cap) return io_fail(TM_ERR_ARG, "blosc: destination too small");
+  if ((size_t)cbytes > src_bytes) return fail(TM_ERR_ARG, "blosc: frame truncated");
+  if ((size_t)nbytes > dst_cap) return fail(TM_ERR_ARG, "blosc: destination too small");
   if (nbytes == 0) return TM_OK;
   if (flags & BLOSC_MEMCPYED) {
-    if (cbytes < BLOSC_HEADER + nbytes) return io_fail(TM_ERR_ARG, "blosc: memcpyed frame truncated");
+    if (cbytes < BLOSC_HEADER + nbytes) return fail(TM_ERR_ARG, "blosc: memcpyed frame truncated");
     memcpy(dst, src + BLOSC_HEADER, (size_t)nbytes);
     return TM_OK;
   }
-  if (flags & BLOSC_BITSHUFFLE) return io_fail(TM_ERR_ARG, "blosc: bit-shuffled frames are not supported (zarr default is byte shuffle)");
+  if (flags & BLOSC_BITSHUFFLE) return fail(TM_ERR_ARG, "blosc: bit-shuffled frames are not supported (zarr default is byte shuffle)");
   const int codec = (flags >> 5) & 7;
-  if (codec != 1) return io_fail(TM_ERR_ARG, "blosc: only the lz4 codec is supported (zarr/numcodecs default)");
-  if (blocksize <= 0) return io_fail(TM_ERR_ARG, "blosc: bad block size");
+  if (codec != 1) return fail(TM_ERR_ARG, "blosc: only the lz4 codec is supported (zarr/numcodecs default)");
+  if (blocksize <= 0) return fail(TM_ERR_ARG, "blosc: bad block size");
   const long nblocks = (nbytes + blocksize - 1) / blocksize, leftover = nbytes % blocksize;
-  if (BLOSC_HEADER + 4 * nblocks > cbytes) return io_fail(TM_ERR_ARG, "blosc: block table truncated");
+  if (BLOSC_HEADER + 4 * nblocks > cbytes) return fail(TM_ERR_ARG, "blosc: block table truncated");
   std::vector<uint8_t> tmp((size_t)blocksize);
   const bool shuffled = (flags & BLOSC_SHUFFLE) && typesize > 1;
   for (long j = 0; j < nblocks; ++j) {
@@ -128,19 +128,19 @@ int blosc_decompress(const void* src_, size_t src_bytes, void* dst_, size_t dst_
     uint8_t* o = shuffled ? tmp.data() : dst + j * blocksize;
     long done = 0;
     for (long sp = 0; sp < nsplits; ++sp) {
-      if (ip + 4 > cbytes) return io_fail(TM_ERR_ARG, "blosc: split header out of range");
+      if (ip + 4 > cbytes) return fail(TM_ERR_ARG, "blosc: split header out of range");
       const long cb = le32(src + ip);
       ip += 4;
-      if (cb < 0 || ip + cb > cbytes) return io_fail(TM_ERR_ARG, "blosc: split out of range");
+      if (cb < 0 || ip + cb > cbytes) return fail(TM_ERR_ARG, "blosc: split out of range");
       if (cb == neblock) {
         memcpy(o + done, src + ip, (size_t)neblock);
       } else if (lz4_block_decode(src + ip, cb, o + done, neblock) != neblock) {
-        return io_fail(TM_ERR_ARG, "blosc: lz4 stream does not decode to the split size");
+        return fail(TM_ERR_ARG, "blosc: lz4 stream does not decode to the split size");
       }
       ip += cb;
       done += neblock;
     }
-    if (done != bsize) return io_fail(TM_ERR_ARG, "blosc: block size mismatch");
+    if (done != bsize) return fail(TM_ERR_ARG, "blosc: block size mismatch");
     if (shuffled) {
       uint8_t* d = dst + j * blocksize;
       const long nel = bsize / typesize, rem = bsize - nel * typesize;

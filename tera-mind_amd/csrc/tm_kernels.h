@@ -1,8 +1,10 @@
-// Internal launcher interface between the executor (tm_model.hip) and the kernels
-// (tm_kernels.hip).  Not part of the public ABI (include/teramind_hip.h is).
+// Internal launcher interface between the host side (the executor tm_model.hip, the single-operator
+// hooks tm_ops.hip) and the kernels.  Not part of the public ABI (include/teramind_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/teramind_hip.h"
 
 namespace tmk {
 
@@ -277,9 +279,22 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, flo
                        float gscale, hipStream_t s);
 
 // ---- tile I/O (tm_io.hip) --------------------------------------------------------------
-int io_fail(int code, const char* msg);     // sets the tm_last_error() text, returns code
 hipError_t launch_gene_tile_scatter(const int32_t* crd, const float* dat, long nnz, int gblk, int shift_h, int shift_w,
                                     int gsz, int chan_in, int zpad_ch, float* out, hipStream_t s);
 int blosc_decompress(const void* src, size_t src_bytes, void* dst, size_t dst_cap, size_t* out_bytes);
+
+// ---- host helpers of the C-ABI units (tm_model.hip, tm_ops.hip, tm_io.hip) ---------------
+int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets the tm_last_error() text, returns code
+#define HIP_TRY(expr)                                                                          \
+  do {                                                                                         \
+    hipError_t e_ = (expr);                                                                    \
+    if (e_ != hipSuccess) return fail(TM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+inline bool is_h16(int dtype) { return dtype == TM_DTYPE_BF16 || dtype == TM_DTYPE_F16; }   // 16-bit operand modes
+inline TVH as_h(const TV& t) {      // the same geometry and strides over 16-bit storage
+  TVH v;
+  v.p = (uint16_t*)t.p; v.N = t.N; v.C = t.C; v.Cb = t.Cb; v.Z = t.Z; v.H = t.H; v.W = t.W; v.nstride = t.nstride;
+  return v;
+}
 
 }  // namespace tmk

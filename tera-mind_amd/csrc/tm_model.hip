@@ -3,6 +3,7 @@
 // re-scheduled for inference: time embedding and every ResBlock's emb_layers computed once
 // per image, concat / collage / resample never materialised on their own (they are gather
 // rules of the prep kernel), skip tensors never cloned, `o == 1` decoder pass optional.
+// The single-operator entry points (tm_op_*) live in tm_ops.hip.
 #include "../../include/teramind_hip.h"
 #include "tm_kernels.h"
 
@@ -18,24 +19,17 @@
 
 using namespace tmk;
 
+// the message behind tm_last_error(), shared by every C-ABI unit (tm_ops.hip, tm_io.hip)
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
+int tmk::fail(int code, const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return code;
 }
-// shared with tm_io.hip (same thread-local message buffer behind tm_last_error)
-int tmk::io_fail(int code, const char* msg) { return fail(code, "%s", msg); }
-#define HIP_TRY(expr)                                                                          \
-  do {                                                                                         \
-    hipError_t e_ = (expr);                                                                    \
-    if (e_ != hipSuccess) return fail(TM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
 
 static const int RNA_TAIL[3] = {128, 64, 32};          // model/unet_ours.py:278-279
-static inline bool is_h16(int dtype) { return dtype == TM_DTYPE_BF16 || dtype == TM_DTYPE_F16; }   // 16-bit operand modes
 
 // ------------------------------------------------------------------------------------------
 struct HostParam {
@@ -729,13 +723,6 @@ struct Ctx {
   void check(hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; }
 };
 struct Src { TV t; bool collage; };
-
-// 16-bit view of a stream tensor (16-bit modes only)
-static TVH as_h(const TV& t) {
-  TVH v;
-  v.p = (uint16_t*)t.p; v.N = t.N; v.C = t.C; v.Cb = t.Cb; v.Z = t.Z; v.H = t.H; v.W = t.W; v.nstride = t.nstride;
-  return v;
-}
 
 
 // Debug taps: with TM_DEBUG_DIR set, every block output is written (NCDHW fp32, raw) to
@@ -1612,780 +1599,5 @@ extern "C" int tm_gene_attn(tm_model* m, const void* rna_dense, int B, void* att
                                        ao + (size_t)i * B * G * G, lo, hi, (float*)workspace, s));
   }
   if (rna_mid) HIP_TRY(launch_rna_mid((const float*)rna_dense, B, m->gn, zs, G, (float*)rna_mid, s));
-  return TM_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// single-operator entry points (tests)
-// ------------------------------------------------------------------------------------------
-static TV view_cb8(void* p, int N, int C, int Z, int H, int W) {
-  TV t;
-  t.p = (float*)p; t.N = N; t.C = C; t.Cb = (C + 7) / 8; t.Z = Z; t.H = H; t.W = W;
-  t.nstride = (long)t.Cb * t.plane();
-  return t;
-}
-extern "C" int tm_op_to_cb8(const void* x, void* y, int N, int C, int Z, int H, int W, void* stream) {
-  HIP_TRY(launch_to_cb8((const float*)x, view_cb8(y, N, C, Z, H, W), (hipStream_t)stream));
-  return TM_OK;
-}
-extern "C" int tm_op_from_cb8(const void* x, void* y, int N, int C, int Z, int H, int W, void* stream) {
-  HIP_TRY(launch_from_cb8(view_cb8(const_cast<void*>(x), N, C, Z, H, W), (float*)y, (hipStream_t)stream));
-  return TM_OK;
-}
-extern "C" int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                               int Cout, int Z, int S, int ksize, int zmode, int up2, int tile_variant, void* stream) {
-  if (ksize != 1 && ksize != 3) return fail(TM_ERR_ARG, "ksize must be 1 or 3");
-  if (zmode != ZM_PAD1 && zmode != ZM_INPLANE && zmode != ZM_VALID && zmode != ZM_UPS) return fail(TM_ERR_ARG, "bad zmode");
-  const bool ups = ksize == 3 && zmode == ZM_UPS;       // w [Cout][Cin][27]: conv of the nearest-x2 upsampled x (y at 2S)
-  if (zmode == ZM_UPS && (ksize != 3 || up2)) return fail(TM_ERR_ARG, "ZM_UPS: ksize 3, no fused upsample of the output");
-  const int taps = ksize == 1 ? 1 : (zmode == ZM_INPLANE ? 9 : (ups ? 12 : 27));
-  const int Zout = (ksize == 3 && zmode == ZM_VALID) ? Z - 2 : Z;
-  const int So = (up2 || ups) ? 2 * S : S;
-  ConvW cw;
-  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
-  std::vector<float> pk(ups ? conv_pack_ups_floats(Cout, cw.Cbi) : conv_pack_floats(Cout, cw.Cbi, taps)), bp((size_t)cw.ntile * 64, 0.f);
-  if (ups) conv_pack_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  else conv_pack_host((const float*)w_host, Cout, &Cin, 1, taps, pk.data());
-  memcpy(bp.data(), bias_host, Cout * sizeof(float));
-  float *dw = nullptr, *db = nullptr;
-  HIP_TRY(hipMalloc((void**)&dw, pk.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&db, bp.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(dw, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(db, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  cw.w = dw; cw.bias = db;
-  ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
-  L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Zout, So, So);
-  L.tile_variant = tile_variant;
-  L.zmode = zmode;
-  L.flags = up2 ? EPI_UP2 : 0;
-  hipError_t e = launch_conv_mfma(L, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(dw); (void)hipFree(db);
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "launch_conv_mfma: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "conv_mfma execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-// shared body of the 16-bit 3x3x3 conv test entry points: fp32 CB8 input -> 16-bit CB8 (prep kernel), then the conv
-static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin, int Cout,
-                         int S, int dtype, int waves, const void* norm_w_host, const void* scale_host, const void* shift_host,
-                         int per_image, void* a2_out, void* stream, const void* res_h16 = nullptr, void* y_h16 = nullptr,
-                         int ups = 0, int res_half = 0) {
-  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
-  if (waves != 0 && waves != 4 && waves != 8 && waves != 9) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4, 8 or 9 (lockstep 8-wave form)");
-  const bool f16 = dtype == TM_DTYPE_F16, fused = norm_w_host != nullptr;
-  if (fused && (!scale_host || !shift_host || !a2_out || per_image < 1 || (Cout != 64 && Cout != 128)))
-    return fail(TM_ERR_ARG, "fused epilogue needs Cout in {64, 128}, scale / shift / a2 and per_image >= 1");
-  hipStream_t st = (hipStream_t)stream;
-  const int Cbi = (Cin + 7) / 8, Cbe = (Cbi + 1) / 2 * 2, nt64 = (Cout + 63) / 64;
-  if (ups && (Cout % 128 || res_h16)) return fail(TM_ERR_ARG, "upsampled-input form: Cout a multiple of 128, no residual");
-  const int So = ups ? 2 * S : S;                       // output plane size
-  std::vector<uint16_t> pk(ups ? conv_bf16_pack_ups_elems(Cout, Cbi) : conv_bf16_pack_elems(Cout, Cbi));
-  if (ups) (f16 ? conv_f16_pack_ups_host : conv_bf16_pack_ups_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
-  else (f16 ? conv_f16_pack_host : conv_bf16_pack_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
-  const int nimg = (N + per_image - 1) / per_image;
-  // one device buffer of floats: bias | norm_w | scale [nimg][Cout] | shift [nimg][Cout]
-  std::vector<float> fp((size_t)nt64 * 64 + (fused ? (size_t)Cout * (1 + 2 * nimg) : 0), 0.f);
-  memcpy(fp.data(), bias_host, Cout * sizeof(float));
-  if (fused) {
-    memcpy(fp.data() + nt64 * 64, norm_w_host, Cout * sizeof(float));
-    memcpy(fp.data() + nt64 * 64 + Cout, scale_host, (size_t)nimg * Cout * sizeof(float));
-    memcpy(fp.data() + nt64 * 64 + Cout + (size_t)nimg * Cout, shift_host, (size_t)nimg * Cout * sizeof(float));
-  }
-  uint16_t *dw = nullptr, *dx = nullptr;
-  float* df = nullptr;
-  const long vox = (long)2 * S * S;
-  HIP_TRY(hipMalloc((void**)&dw, pk.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMalloc((void**)&df, fp.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&dx, (size_t)N * Cbe * vox * 8 * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(dw, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(df, fp.data(), fp.size() * sizeof(float), hipMemcpyHostToDevice));
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, 2, S, S);
-  PrepLaunch P;                       // fp32 CB8 -> 16-bit CB8 (no norm / act), pair padding
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-  P.N = N; P.Z = 2; P.S = S; P.h_f16 = f16 ? 1 : 0;
-  P.out_h = dx; P.out_h_nstride = (long)Cbe * vox * 8; P.pad_blocks = Cbe - Cbi;
-  hipError_t e0 = launch_prep(P, st);
-  ConvLaunchH L;
-  L.x.p = dx; L.x.N = N; L.x.Cb = Cbe; L.x.C = Cbe * 8; L.x.Z = 2; L.x.H = S; L.x.W = S; L.x.nstride = P.out_h_nstride;
-  L.w = dw; L.bias = df; L.Cout = Cout; L.force_waves = waves;
-  L.y = view_cb8(y_cb8, N, Cout, 2, So, So);
-  L.ups = ups; L.res_half = res_half;
-  TVH resh = as_h(L.y);
-  if (res_h16) {
-    resh.p = (uint16_t*)const_cast<void*>(res_h16); L.res_h = &resh;
-    if (res_half) { resh.H = So / 2; resh.W = So / 2; resh.nstride = L.y.nstride / 4; }
-  }
-  if (y_h16) { L.y_h = (uint16_t*)y_h16; L.yh_nstride = L.y.nstride; }
-  if (fused) {
-    L.fuse_norm = 1; L.norm_w = df + nt64 * 64; L.mod_scale = L.norm_w + Cout; L.mod_shift = L.mod_scale + (size_t)nimg * Cout;
-    L.mod_stride = Cout; L.per_image = per_image;
-    L.a2.p = (uint16_t*)a2_out; L.a2.N = N; L.a2.Cb = Cout / 8; L.a2.C = Cout; L.a2.Z = 2; L.a2.H = So; L.a2.W = So;
-    L.a2.nstride = (long)(Cout / 8) * 2 * So * So * 8;
-  }
-  hipError_t e = (f16 ? launch_conv27_f16 : launch_conv27_bf16)(L, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  (void)hipFree(dw); (void)hipFree(df); (void)hipFree(dx);
-  if (e0 != hipSuccess) return fail(TM_ERR_HIP, "launch_prep: %s", hipGetErrorString(e0));
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "launch_conv27 (16-bit): %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "conv27 (16-bit) execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-extern "C" int tm_op_conv27_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                                 int Cout, int S, int dtype, int waves, const void* res_h16, void* y_h16, int ups, int res_half,
-                                 void* stream) {
-  if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
-  return op_conv27_h16(x_cb8, w_host, bias_host, y_cb8 ? y_cb8 : y_h16, N, Cin, Cout, S, dtype, waves, nullptr, nullptr, nullptr, 1,
-                       nullptr, stream, res_h16, y_h16, ups, res_half);
-}
-extern "C" int tm_op_conv27_fused(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
-                                  const void* scale_host, const void* shift_host, void* a2_out, int N, int Cin, int Cout,
-                                  int S, int per_image, int dtype, int waves, void* stream) {
-  if (!x_cb8 || !w_host || !bias_host || !norm_w_host || !a2_out) return fail(TM_ERR_ARG, "null argument");
-  // the launcher takes the output geometry from `y`; the fused form never writes it
-  return op_conv27_h16(x_cb8, w_host, bias_host, a2_out, N, Cin, Cout, S, dtype, waves, norm_w_host, scale_host, shift_host,
-                       per_image, a2_out, stream);
-}
-// Timing hook of the 16-bit 3x3x3 conv on random device data (uniform in [-1, 1): the clock the chip holds depends on the
-// operand bits, cdna guide rule 25): the model's launch forms -- 16-bit stream output with an optional 16-bit residual, the
-// fused norm epilogue, the upsampled-input form -- `iters` launches between two events after one warm-up launch.
-__global__ void fill_h16_kernel(uint16_t* p, size_t n, unsigned seed, int f16) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    unsigned hsh = (unsigned)i * 2654435761u ^ (unsigned)(i >> 32) * 40503u ^ seed;
-    hsh ^= hsh >> 15; hsh *= 2246822519u; hsh ^= hsh >> 13; hsh *= 3266489917u; hsh ^= hsh >> 16;
-    const float v = (float)(hsh >> 8) * (1.0f / 8388608.0f) - 1.0f;
-    uint16_t u;
-    if (f16) { const _Float16 hf = (_Float16)v; u = __builtin_bit_cast(uint16_t, hf); }
-    else { const __bf16 bf = (__bf16)v; u = __builtin_bit_cast(uint16_t, bf); }
-    p[i] = u;
-  }
-}
-extern "C" int tm_op_conv27_time(int N, int Cin, int Cout, int S, int dtype, int waves, int ups, int with_res, int fused,
-                                 int iters, float* ms_per_launch, void* stream) {
-  if (!is_h16(dtype) || iters < 1 || !ms_per_launch || N < 1) return fail(TM_ERR_ARG, "bad argument");
-  if (waves != 0 && waves != 4 && waves != 8 && waves != 9) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4, 8 or 9 (lockstep 8-wave form)");
-  if (fused && (Cout != 64 && Cout != 128)) return fail(TM_ERR_ARG, "fused epilogue needs Cout in {64, 128}");
-  if (ups && (Cout % 128 || with_res)) return fail(TM_ERR_ARG, "upsampled-input form: Cout a multiple of 128, no residual");
-  const bool f16 = dtype == TM_DTYPE_F16;
-  hipStream_t st = (hipStream_t)stream;
-  const int Cbi = (Cin + 7) / 8, Cbe = (Cbi + 1) / 2 * 2, nt64 = (Cout + 63) / 64, So = ups ? 2 * S : S;
-  const size_t nw = ups ? conv_bf16_pack_ups_elems(Cout, Cbi) : conv_bf16_pack_elems(Cout, Cbi);
-  const long vox = (long)2 * S * S, voxo = (long)2 * So * So;
-  const size_t nx = (size_t)N * Cbe * vox * 8, ny = (size_t)N * ((Cout + 7) / 8) * voxo * 8;
-  uint16_t *dw = nullptr, *dx = nullptr, *dy = nullptr, *dr = nullptr;
-  float* df = nullptr;
-  const size_t nf = (size_t)nt64 * 64 + (size_t)Cout * 3;
-  HIP_TRY(hipMalloc((void**)&dw, nw * 2));
-  HIP_TRY(hipMalloc((void**)&dx, nx * 2));
-  HIP_TRY(hipMalloc((void**)&dy, ny * 2));
-  if (with_res) HIP_TRY(hipMalloc((void**)&dr, ny * 2));
-  HIP_TRY(hipMalloc((void**)&df, nf * sizeof(float)));
-  hipLaunchKernelGGL(fill_h16_kernel, dim3(2048), dim3(256), 0, st, dw, nw, 11u, f16 ? 1 : 0);
-  hipLaunchKernelGGL(fill_h16_kernel, dim3(2048), dim3(256), 0, st, dx, nx, 23u, f16 ? 1 : 0);
-  if (with_res) hipLaunchKernelGGL(fill_h16_kernel, dim3(2048), dim3(256), 0, st, dr, ny, 37u, f16 ? 1 : 0);
-  std::vector<float> fp(nf, 0.f);
-  for (size_t i = 0; i < nf; ++i) fp[i] = 0.01f * (float)((int)(i * 37 % 101) - 50);
-  for (int i = 0; i < Cout; ++i) fp[(size_t)nt64 * 64 + i] = 1.0f + 0.001f * (float)(i % 17);      // norm_w
-  HIP_TRY(hipMemcpyAsync(df, fp.data(), nf * sizeof(float), hipMemcpyHostToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  ConvLaunchH L;
-  L.x.p = dx; L.x.N = N; L.x.Cb = Cbe; L.x.C = Cbe * 8; L.x.Z = 2; L.x.H = S; L.x.W = S; L.x.nstride = (long)Cbe * vox * 8;
-  L.w = dw; L.bias = df; L.Cout = Cout; L.force_waves = waves;
-  L.y = view_cb8(dy, N, Cout, 2, So, So);
-  L.ups = ups;
-  TVH resh = as_h(L.y);
-  if (with_res) { resh.p = dr; L.res_h = &resh; }
-  L.y_h = dy; L.yh_nstride = L.y.nstride;
-  if (fused) {
-    L.fuse_norm = 1; L.norm_w = df + nt64 * 64; L.mod_scale = L.norm_w + Cout; L.mod_shift = L.mod_scale + Cout;
-    L.mod_stride = 0; L.per_image = N;
-    L.a2.p = dy; L.a2.N = N; L.a2.Cb = Cout / 8; L.a2.C = Cout; L.a2.Z = 2; L.a2.H = So; L.a2.W = So;
-    L.a2.nstride = (long)(Cout / 8) * voxo * 8;
-  }
-  hipEvent_t e0, e1;
-  HIP_TRY(hipEventCreate(&e0));
-  HIP_TRY(hipEventCreate(&e1));
-  hipError_t e = (f16 ? launch_conv27_f16 : launch_conv27_bf16)(L, st);
-  (void)hipEventRecord(e0, st);
-  for (int i = 0; i < iters && e == hipSuccess; ++i) e = (f16 ? launch_conv27_f16 : launch_conv27_bf16)(L, st);
-  (void)hipEventRecord(e1, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  *ms_per_launch = 0.f;
-  if (e == hipSuccess && e2 == hipSuccess) { (void)hipEventElapsedTime(ms_per_launch, e0, e1); *ms_per_launch /= (float)iters; }
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(dw); (void)hipFree(dx); (void)hipFree(dy); (void)hipFree(df);
-  if (dr) (void)hipFree(dr);
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "launch_conv27 (16-bit): %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "conv27 (16-bit) execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-extern "C" int tm_op_conv1_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                                int Cout, int Z, int S, int gelu, int dtype, int waves, const void* res_h16, const void* gate_h16,
-                                void* y_h16, void* stream) {
-  if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
-  if (!y_cb8) y_cb8 = y_h16;                              // geometry carrier only
-  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
-  if (waves != 0 && waves != 4 && waves != 8) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4 or 8");
-  const bool f16 = dtype == TM_DTYPE_F16;
-  hipStream_t st = (hipStream_t)stream;
-  const int Cbi = (Cin + 7) / 8, Cbe = (Cbi + 1) / 2 * 2, nt64 = (Cout + 63) / 64;
-  std::vector<uint16_t> pk(conv1_bf16_pack_elems(Cout, Cbi));
-  (f16 ? conv1_f16_pack_host : conv1_bf16_pack_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
-  std::vector<float> bp((size_t)nt64 * 64, 0.f);
-  memcpy(bp.data(), bias_host, Cout * sizeof(float));
-  uint16_t *dw = nullptr, *dx = nullptr;
-  float* db = nullptr;
-  const long vox = (long)Z * S * S;
-  HIP_TRY(hipMalloc((void**)&dw, pk.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMalloc((void**)&db, bp.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&dx, (size_t)N * Cbe * vox * 8 * sizeof(uint16_t)));
-  HIP_TRY(hipMemcpy(dw, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(db, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
-  PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-  P.N = N; P.Z = Z; P.S = S; P.h_f16 = f16 ? 1 : 0;
-  P.out_h = dx; P.out_h_nstride = (long)Cbe * vox * 8; P.pad_blocks = Cbe - Cbi;
-  hipError_t e0 = launch_prep(P, st);
-  ConvLaunchH L;
-  L.x.p = dx; L.x.N = N; L.x.Cb = Cbe; L.x.C = Cbe * 8; L.x.Z = Z; L.x.H = S; L.x.W = S; L.x.nstride = P.out_h_nstride;
-  L.w = dw; L.bias = db; L.Cout = Cout; L.flags = gelu ? EPI_GELU : 0; L.force_waves = waves;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
-  TVH resh = as_h(L.y), gateh = as_h(L.y);
-  if (res_h16) { resh.p = (uint16_t*)const_cast<void*>(res_h16); L.res_h = &resh; }
-  if (gate_h16) { gateh.p = (uint16_t*)const_cast<void*>(gate_h16); L.gate_h = &gateh; }
-  if (y_h16) { L.y_h = (uint16_t*)y_h16; L.yh_nstride = L.y.nstride; }
-  hipError_t e = (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  (void)hipFree(dw); (void)hipFree(db); (void)hipFree(dx);
-  if (e0 != hipSuccess) return fail(TM_ERR_HIP, "launch_prep: %s", hipGetErrorString(e0));
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "launch_conv1 (16-bit): %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "conv1 (16-bit) execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-extern "C" int tm_op_conv1_concat(const void* const* x_cb8, const int* cin, const int* collage, int nsrc, const void* w_host,
-                                  const void* bias_host, void* y_cb8, int N, int Cout, int Z, int S, int p1, int p2,
-                                  int dtype, int waves, void* stream) {
-  if (!x_cb8 || !cin || !collage || !w_host || !bias_host || !y_cb8 || nsrc < 1 || nsrc > 3) return fail(TM_ERR_ARG, "bad argument");
-  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
-  const bool f16 = dtype == TM_DTYPE_F16;
-  hipStream_t st = (hipStream_t)stream;
-  bool any_col = false;
-  for (int i = 0; i < nsrc; ++i) any_col = any_col || collage[i];
-  const int q = any_col ? (p1 - 1) * (p2 - 1) : 1;
-  if (any_col && (p1 < 2 || p2 < 2 || N % q)) return fail(TM_ERR_ARG, "collage needs N = b * (p1-1) * (p2-1)");
-  const int Nsrc_col = any_col ? N / q * p1 * p2 : N;      // a collaged source lives on the (p1 x p2) grid
-  std::vector<int> seg(cin, cin + nsrc);
-  int Cbi = 0;
-  for (int c : seg) Cbi += (c + 7) / 8;
-  const int Cbe = (Cbi + 1) / 2 * 2, nt64 = (Cout + 63) / 64;
-  std::vector<uint16_t> pk(conv1_bf16_pack_elems(Cout, Cbi));
-  (f16 ? conv1_f16_pack_host : conv1_bf16_pack_host)((const float*)w_host, Cout, seg.data(), nsrc, pk.data());
-  std::vector<float> bp((size_t)nt64 * 64, 0.f);
-  memcpy(bp.data(), bias_host, Cout * sizeof(float));
-  const long vox = (long)Z * S * S;
-  uint16_t *dw = nullptr, *dx[3] = {nullptr, nullptr, nullptr};
-  float* db = nullptr;
-  HIP_TRY(hipMalloc((void**)&dw, pk.size() * sizeof(uint16_t)));
-  HIP_TRY(hipMalloc((void**)&db, bp.size() * sizeof(float)));
-  HIP_TRY(hipMemcpy(dw, pk.data(), pk.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(db, bp.data(), bp.size() * sizeof(float), hipMemcpyHostToDevice));
-  ConvLaunchH L;
-  hipError_t e0 = hipSuccess;
-  for (int i = 0; i < nsrc && e0 == hipSuccess; ++i) {
-    const int Ni = collage[i] ? Nsrc_col : N, cb = (seg[i] + 7) / 8;
-    HIP_TRY(hipMalloc((void**)&dx[i], (size_t)Ni * cb * vox * 8 * sizeof(uint16_t)));
-    TV x = view_cb8(const_cast<void*>(x_cb8[i]), Ni, seg[i], Z, S, S);
-    PrepLaunch P;
-    P.nsrc = 1;
-    P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-    P.N = Ni; P.Z = Z; P.S = S; P.h_f16 = f16 ? 1 : 0;
-    P.out_h = dx[i]; P.out_h_nstride = (long)cb * vox * 8;
-    e0 = launch_prep(P, st);
-    L.xs[i].p = dx[i]; L.xs[i].N = Ni; L.xs[i].Cb = cb; L.xs[i].C = cb * 8; L.xs[i].Z = Z; L.xs[i].H = S; L.xs[i].W = S;
-    L.xs[i].nstride = P.out_h_nstride;
-    L.xs_collage[i] = collage[i] ? 1 : 0;
-  }
-  L.nsrc = nsrc; L.p1 = p1; L.p2 = p2;
-  L.x.p = nullptr; L.x.N = N; L.x.Cb = Cbe; L.x.C = Cbe * 8; L.x.Z = Z; L.x.H = S; L.x.W = S; L.x.nstride = 0;
-  L.w = dw; L.bias = db; L.Cout = Cout; L.force_waves = waves;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
-  hipError_t e = e0 == hipSuccess ? (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st) : e0;
-  hipError_t e2 = hipStreamSynchronize(st);
-  (void)hipFree(dw); (void)hipFree(db);
-  for (int i = 0; i < 3; ++i) if (dx[i]) (void)hipFree(dx[i]);
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "conv1 concat launch: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "conv1 concat execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-extern "C" int tm_op_prep_h16(const void* const* src_h16, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
-                              int p1, int p2, int up2, const void* norm_w_dev, int c_real, int mod, const void* mod_scale,
-                              const void* mod_shift, long mod_stride, int per_image, int act, int dtype, int variant,
-                              void* out_h16, void* raw_h16, int iters, float* elapsed_ms, void* stream) {
-  if (!src_h16 || !src_c || !collage || !out_h16 || nsrc < 1 || nsrc > 3 || iters < 1) return fail(TM_ERR_ARG, "bad argument");
-  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
-  if (mod != MOD_NONE && (!mod_scale || !mod_shift)) return fail(TM_ERR_ARG, "modulation tensors missing");
-  hipStream_t st = (hipStream_t)stream;
-  bool any_col = false;
-  for (int i = 0; i < nsrc; ++i) any_col = any_col || collage[i];
-  const int q = any_col ? (p1 - 1) * (p2 - 1) : 1;
-  if (any_col && (p1 < 2 || p2 < 2 || N % q)) return fail(TM_ERR_ARG, "collage needs N = b * (p1-1) * (p2-1)");
-  if (up2 < 0 || up2 > 2) return fail(TM_ERR_ARG, "up2: 0 same, 1 nearest x2, 2 = 2 x 2 average (Downsample)");
-  if (up2 == 1 && (any_col || (S & 1))) return fail(TM_ERR_ARG, "up2 takes plain sources and an even S");
-  if (up2 == 2 && (any_col || nsrc != 1 || mod != MOD_NONE)) return fail(TM_ERR_ARG, "the downsample form takes one plain source, no modulation");
-  const int Ss = up2 == 1 ? S / 2 : (up2 == 2 ? 2 * S : S);
-  PrepLaunch P;
-  P.nsrc = nsrc;
-  int cbtot = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    const int cb = (src_c[i] + 7) / 8;
-    P.src[i].p = (const float*)src_h16[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
-    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
-    cbtot += cb;
-  }
-  const int cbe = (cbtot + 1) / 2 * 2;
-  P.src_h = 1; P.h_f16 = dtype == TM_DTYPE_F16;
-  P.resample = up2 == 1 ? RS_UP2 : (up2 == 2 ? RS_DOWN2 : RS_SAME); P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
-  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act; P.per_image = per_image > 0 ? per_image : 1;
-  P.mod = mod; P.mod_stride = mod_stride;
-  if (mod == MOD_IMAGE) { P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift; }
-  if (mod == MOD_VOXEL) { P.mod_scale_h = (const uint16_t*)mod_scale; P.mod_shift_h = (const uint16_t*)mod_shift; }
-  P.out_h = (uint16_t*)out_h16; P.out_h_nstride = (long)cbe * Z * S * S * 8; P.pad_blocks = cbe - cbtot;
-  if (raw_h16) { P.raw_h = (uint16_t*)raw_h16; P.raw_h_nstride = P.out_h_nstride; }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (elapsed_ms) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); }
-  set_prep_variant(variant);
-  hipError_t e = launch_prep(P, st);                                   // warm-up / the result
-  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e0, st);
-  for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_prep(P, st);
-  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e1, st);
-  set_prep_variant(0);
-  hipError_t e2 = hipStreamSynchronize(st);
-  if (elapsed_ms) {
-    if (e == hipSuccess && e2 == hipSuccess && iters > 1) { (void)hipEventElapsedTime(elapsed_ms, e0, e1); *elapsed_ms /= (float)(iters - 1); }
-    else *elapsed_ms = 0.f;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  }
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "prep launch: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "prep execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-extern "C" int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_dev,
-                                 const void* kw_dev, void* out, int N, int C, int Z, int S, int dtype, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (C % 64) return fail(TM_ERR_ARG, "C must be a multiple of 64");
-  TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S);
-  TV v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
-  if (dtype == TM_DTYPE_F32) {
-    TV o = view_cb8(out, N, C, Z, S, S);
-    HIP_TRY(launch_window_attn(q, k, v, (const float*)qw_dev, (const float*)kw_dev, o, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return TM_OK;
-  }
-  const int cb = C / 8;
-  const long ns = (long)cb * Z * S * S * 8;
-  uint16_t* buf = nullptr;
-  HIP_TRY(hipMalloc((void**)&buf, (size_t)3 * N * ns * sizeof(uint16_t)));
-  TVH h[3];
-  const TV* src[3] = {&q, &k, &v};
-  hipError_t e = hipSuccess;
-  for (int i = 0; i < 3 && e == hipSuccess; ++i) {
-    h[i].p = buf + (size_t)i * N * ns; h[i].N = N; h[i].C = C; h[i].Cb = cb; h[i].Z = Z; h[i].H = S; h[i].W = S; h[i].nstride = ns;
-    PrepLaunch P;
-    P.nsrc = 1;
-    P.src[0].p = src[i]->p; P.src[0].nstride = src[i]->nstride; P.src[0].Cb = cb;
-    P.N = N; P.Z = Z; P.S = S;
-    P.out_h = h[i].p; P.out_h_nstride = ns;
-    e = launch_prep(P, st);
-  }
-  TVH o = h[0];
-  o.p = (uint16_t*)out;
-  if (e == hipSuccess) e = launch_window_attn_bf16(h[0], h[1], h[2], (const float*)qw_dev, (const float*)kw_dev, o, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  (void)hipFree(buf);
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "window attention launch: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "window attention execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-extern "C" int tm_op_conv_direct(const void* x, const void* w_host, const void* bias_host, void* y, int N, int Cin,
-                                 int Cout, int Zin, int S, int kz, int ky, int kx, int pz, int py, int px, int silu_in,
-                                 int up2_out, void* stream) {
-  const int taps = kz * ky * kx, Cop = (Cout + 7) / 8 * 8;
-  const int Zout = Zin + 2 * pz - kz + 1;
-  if (Zout < 1 || py != ky / 2 || px != kx / 2) return fail(TM_ERR_ARG, "unsupported geometry");
-  std::vector<float> wt((size_t)taps * Cin * Cop, 0.f);
-  const float* w = (const float*)w_host;
-  for (int co = 0; co < Cout; ++co)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int t = 0; t < taps; ++t) wt[((size_t)t * Cin + ci) * Cop + co] = w[((size_t)co * Cin + ci) * taps + t];
-  float *dw = nullptr, *db = nullptr;
-  HIP_TRY(hipMalloc((void**)&dw, wt.size() * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&db, Cout * sizeof(float)));
-  HIP_TRY(hipMemcpy(dw, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(db, bias_host, Cout * sizeof(float), hipMemcpyHostToDevice));
-  DirectLaunch L;
-  L.x = (const float*)x; L.ax = acc_ncdhw(Cin, Zin, S, S);
-  const int So = up2_out ? 2 * S : S;
-  L.y = (float*)y; L.ay = acc_ncdhw(Cout, Zout, So, So);
-  L.w = dw; L.bias = db; L.N = N; L.Cin = Cin; L.Cout = Cout; L.Zin = Zin; L.Zout = Zout; L.S = S;
-  L.kz = kz; L.ky = ky; L.kx = kx; L.pz = pz; L.py = py; L.px = px; L.silu_in = silu_in; L.up2_out = up2_out;
-  hipError_t e = launch_conv_direct(L, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  (void)hipFree(dw); (void)hipFree(db);
-  if (e != hipSuccess) return fail(TM_ERR_HIP, "launch_conv_direct: %s", hipGetErrorString(e));
-  if (e2 != hipSuccess) return fail(TM_ERR_HIP, "conv_direct execution: %s", hipGetErrorString(e2));
-  return TM_OK;
-}
-
-// ------------------------------------------------------------------------------------------
-// training slice: forward with dropout + backward of one ResBlock's pieces
-// ------------------------------------------------------------------------------------------
-// host vector -> device copy living until `free_all`
-struct DevTmp {
-  std::vector<void*> ptrs;
-  float* up(const float* host, size_t n, size_t n_alloc = 0) {
-    float* d = nullptr;
-    if (n_alloc < n) n_alloc = n;
-    if (hipMalloc((void**)&d, n_alloc * sizeof(float)) != hipSuccess) return nullptr;
-    ptrs.push_back(d);
-    if (n_alloc > n && hipMemset(d, 0, n_alloc * sizeof(float)) != hipSuccess) return nullptr;
-    if (n && hipMemcpy(d, host, n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-  }
-  ~DevTmp() { for (void* p : ptrs) (void)hipFree(p); }
-};
-// per-channel vector [rows][C] -> [rows][Cb*8] zero padded (host)
-static std::vector<float> pad_rows(const float* v, int rows, int C, int Cp) {
-  std::vector<float> o((size_t)rows * Cp, 0.f);
-  for (int r = 0; r < rows; ++r) memcpy(o.data() + (size_t)r * Cp, v + (size_t)r * C, C * sizeof(float));
-  return o;
-}
-
-// dropout probability p -> the drawn mask's threshold (drop iff word < thr) and 1 / (1 - p), both as DESIGN §8 fixes them
-static bool drop_rng_of(unsigned long long key, unsigned site, float p, DropRng& r, float& scale) {
-  if (!(p >= 0.f && p < 1.f)) return false;
-  r.key = key; r.site = site;
-  r.thr = (uint32_t)std::min(std::floor((double)p * 4294967296.0), 4294967295.0);
-  scale = 1.0f / (float)(1.0 - (double)p);
-  return true;
-}
-
-static int prep_train_impl(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
-                           const void* mask_cb8, float drop_scale, const DropRng* rng, int per_image, void* y_cb8, int N, int C, int Z,
-                           int S, void* stream) {
-  if (!x_cb8 || !norm_w_host || !y_cb8 || per_image < 1) return fail(TM_ERR_ARG, "bad argument");
-  const int Cb = (C + 7) / 8, Cp = Cb * 8, nimg = (N + per_image - 1) / per_image;
-  DevTmp tmp;
-  const std::vector<float> wp = pad_rows((const float*)norm_w_host, 1, C, Cp);
-  const float* dw = tmp.up(wp.data(), Cp);
-  const float *dsc = nullptr, *dsh = nullptr;
-  if (scale_host) {
-    const std::vector<float> a = pad_rows((const float*)scale_host, nimg, C, Cp), b = pad_rows((const float*)shift_host, nimg, C, Cp);
-    dsc = tmp.up(a.data(), a.size()); dsh = tmp.up(b.data(), b.size());
-    if (!dsc || !dsh) return fail(TM_ERR_HIP, "device allocation failed");
-  }
-  if (!dw) return fail(TM_ERR_HIP, "device allocation failed");
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
-  PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-  P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 1; P.per_image = per_image;
-  if (dsc) { P.mod = MOD_IMAGE; P.mod_scale = dsc; P.mod_shift = dsh; P.mod_stride = Cp; }
-  if (mask_cb8) { P.drop_mask = (const float*)mask_cb8; P.drop_ns = x.nstride; P.drop_scale = drop_scale; }
-  if (rng) P.drop_scale = drop_scale;
-  P.out = y.p; P.out_nstride = y.nstride;
-  hipError_t e = rng ? launch_prep_drop(P, *rng, (hipStream_t)stream) : launch_prep(P, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "prep (training forward): %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_prep_train(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
-                                const void* mask_cb8, float drop_scale, int per_image, void* y_cb8, int N, int C, int Z, int S,
-                                void* stream) {
-  return prep_train_impl(x_cb8, norm_w_host, scale_host, shift_host, mask_cb8, drop_scale, nullptr, per_image, y_cb8, N, C, Z, S, stream);
-}
-
-extern "C" int tm_op_prep_train_rng(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
-                                    unsigned long long key, unsigned site, float p, int per_image, void* y_cb8, int N, int C, int Z,
-                                    int S, void* stream) {
-  DropRng r;
-  float ds = 1.f;
-  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
-  return prep_train_impl(x_cb8, norm_w_host, scale_host, shift_host, nullptr, p > 0.f ? ds : 1.0f, p > 0.f ? &r : nullptr, per_image,
-                         y_cb8, N, C, Z, S, stream);
-}
-
-static int prep_bwd_impl(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
-                         const void* shift_host, const void* mask_cb8, float drop_scale, const DropRng* rng, int per_image, void* dx_cb8,
-                         void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
-  if (!x_cb8 || !g_cb8 || !norm_w_host || !dx_cb8 || !dw_host || per_image < 1) return fail(TM_ERR_ARG, "bad argument");
-  if (scale_host && (!shift_host || !dscale_host || !dshift_host)) return fail(TM_ERR_ARG, "scale without shift / gradient outputs");
-  const int Cb = (C + 7) / 8, Cp = Cb * 8, nimg = (N + per_image - 1) / per_image;
-  DevTmp tmp;
-  const std::vector<float> wp = pad_rows((const float*)norm_w_host, 1, C, Cp);
-  const float* dwt = tmp.up(wp.data(), Cp);
-  float* ddw = tmp.up(nullptr, 0, Cp);
-  const float *dsc = nullptr, *dsh = nullptr;
-  float *ddsc = nullptr, *ddsh = nullptr;
-  if (scale_host) {
-    const std::vector<float> a = pad_rows((const float*)scale_host, nimg, C, Cp), b = pad_rows((const float*)shift_host, nimg, C, Cp);
-    dsc = tmp.up(a.data(), a.size()); dsh = tmp.up(b.data(), b.size());
-    ddsc = tmp.up(nullptr, 0, (size_t)(nimg + 1) * Cp); ddsh = tmp.up(nullptr, 0, (size_t)(nimg + 1) * Cp);
-    if (!dsc || !dsh || !ddsc || !ddsh) return fail(TM_ERR_HIP, "device allocation failed");
-  }
-  if (!dwt || !ddw) return fail(TM_ERR_HIP, "device allocation failed");
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
-  hipStream_t st = (hipStream_t)stream;
-  float* scratch = tmp.up(nullptr, 0, prep_bwd_scratch_floats(N, Cb, Z, S, scale_host != nullptr));
-  if (!scratch) return fail(TM_ERR_HIP, "device allocation failed");
-  hipError_t e = launch_prep_bwd(x.p, x.nstride, (const float*)g_cb8, x.nstride, (const float*)mask_cb8, x.nstride, drop_scale, dwt,
-                                 dsc, dsh, Cp, per_image, (float*)dx_cb8, x.nstride, ddw, ddsc, ddsh, N, Cb, C, Z, S, scratch, st, rng);
-  hipError_t e2 = hipStreamSynchronize(st);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "prep backward: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  std::vector<float> h(Cp);
-  HIP_TRY(hipMemcpy(h.data(), ddw, Cp * sizeof(float), hipMemcpyDeviceToHost));
-  memcpy(dw_host, h.data(), C * sizeof(float));
-  if (scale_host) {
-    std::vector<float> hs((size_t)nimg * Cp), hh((size_t)nimg * Cp);
-    HIP_TRY(hipMemcpy(hs.data(), ddsc, hs.size() * sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(hh.data(), ddsh, hh.size() * sizeof(float), hipMemcpyDeviceToHost));
-    for (int r = 0; r < nimg; ++r) {
-      memcpy((float*)dscale_host + (size_t)r * C, hs.data() + (size_t)r * Cp, C * sizeof(float));
-      memcpy((float*)dshift_host + (size_t)r * C, hh.data() + (size_t)r * Cp, C * sizeof(float));
-    }
-  }
-  return TM_OK;
-}
-
-extern "C" int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
-                              const void* shift_host, const void* mask_cb8, float drop_scale, int per_image, void* dx_cb8,
-                              void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
-  return prep_bwd_impl(x_cb8, g_cb8, norm_w_host, scale_host, shift_host, mask_cb8, drop_scale, nullptr, per_image, dx_cb8, dw_host,
-                       dscale_host, dshift_host, N, C, Z, S, stream);
-}
-
-extern "C" int tm_op_prep_bwd_rng(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
-                                  const void* shift_host, unsigned long long key, unsigned site, float p, int per_image, void* dx_cb8,
-                                  void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
-  DropRng r;
-  float ds = 1.f;
-  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
-  return prep_bwd_impl(x_cb8, g_cb8, norm_w_host, scale_host, shift_host, nullptr, p > 0.f ? ds : 1.0f, p > 0.f ? &r : nullptr, per_image,
-                       dx_cb8, dw_host, dscale_host, dshift_host, N, C, Z, S, stream);
-}
-
-extern "C" int tm_op_dropout_mask(unsigned long long key, unsigned site, float p, void* mask_cb8, int N, int C, int Z, int S,
-                                  void* stream) {
-  DropRng r;
-  float ds = 1.f;
-  if (!mask_cb8 || N < 0 || C < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "bad argument");
-  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_dropout_mask((float*)mask_cb8, N, C, Z, S, r.key, r.site, r.thr, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "dropout mask: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-// dX of Conv3d(k = 3x3x3 pad 1 | 1x1x1), stride 1: the forward MFMA conv of dY with the kernel flipped in z, y, x and
-// cin <-> cout transposed (w_host [Cout][Cin][taps] as in the reference state_dict)
-// ---- AttnBlock training pieces (teramind_amd.training.AttnBlockTrain composes them) ----
-extern "C" int tm_op_ew(int op, const void* a, const void* b, const void* c, void* o1, void* o2, long n, void* stream) {
-  if (op < 0 || op > 8 || !a || !o1 || n < 0) return fail(TM_ERR_ARG, "bad argument");
-  if ((op == 0 || op == 1) && (!b || !c)) return fail(TM_ERR_ARG, "op %d needs b and c", op);
-  if ((op == 3 || op == 5 || op == 6) && !b) return fail(TM_ERR_ARG, "op %d needs b", op);
-  if (op == 1 && !o2) return fail(TM_ERR_ARG, "op 1 needs two outputs");
-  hipError_t e = launch_ew(op, (const float*)a, (const float*)b, (const float*)c, (float*)o1, (float*)o2, n, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "elementwise op: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_modnorm(const void* x_cb8, const void* norm_w_host, const void* scale_cb8, const void* shift_cb8, void* y_cb8, int N,
-                             int C, int Z, int S, void* stream) {
-  if (!x_cb8 || !norm_w_host || !scale_cb8 || !shift_cb8 || !y_cb8) return fail(TM_ERR_ARG, "bad argument");
-  const int Cb = (C + 7) / 8, Cp = Cb * 8;
-  DevTmp tmp;
-  const std::vector<float> wp = pad_rows((const float*)norm_w_host, 1, C, Cp);
-  const float* dw = tmp.up(wp.data(), Cp);
-  if (!dw) return fail(TM_ERR_HIP, "device allocation failed");
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
-  PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-  P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 0;
-  P.mod = MOD_VOXEL; P.mod_scale = (const float*)scale_cb8; P.mod_shift = (const float*)shift_cb8; P.mod_stride = x.nstride;
-  P.out = y.p; P.out_nstride = y.nstride;
-  hipError_t e = launch_prep(P, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "modulate(norm): %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_modnorm_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_cb8, void* dx_cb8,
-                                 void* dscale_cb8, void* dshift_cb8, void* dw_host, int N, int C, int Z, int S, void* stream) {
-  if (!x_cb8 || !g_cb8 || !norm_w_host || !scale_cb8 || !dx_cb8 || !dscale_cb8 || !dshift_cb8 || !dw_host)
-    return fail(TM_ERR_ARG, "bad argument");
-  const int Cb = (C + 7) / 8, Cp = Cb * 8;
-  DevTmp tmp;
-  const std::vector<float> wp = pad_rows((const float*)norm_w_host, 1, C, Cp);
-  const float* dwt = tmp.up(wp.data(), Cp);
-  float* ddw = tmp.up(nullptr, 0, Cp);
-  const long vox = (long)N * Z * S * S;
-  float* scratch = tmp.up(nullptr, 0, (size_t)((vox + 63) / 64) * Cp);
-  if (!dwt || !ddw || !scratch) return fail(TM_ERR_HIP, "device allocation failed");
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_modnorm_bwd(x, (const float*)g_cb8, dwt, (const float*)scale_cb8, (float*)dx_cb8, (float*)dscale_cb8,
-                                    (float*)dshift_cb8, ddw, C, scratch, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "modulate(norm) backward: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  std::vector<float> h(Cp);
-  HIP_TRY(hipMemcpy(h.data(), ddw, Cp * sizeof(float), hipMemcpyDeviceToHost));
-  memcpy(dw_host, h.data(), C * sizeof(float));
-  return TM_OK;
-}
-
-extern "C" int tm_op_window_attn_train(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_host, const void* kw_host,
-                                       const void* dout_cb8, void* o_cb8, void* dq_cb8, void* dk_cb8, void* dv_cb8, void* dqw_host,
-                                       void* dkw_host, int N, int C, int Z, int S, void* stream) {
-  const bool bwd = dout_cb8 != nullptr;
-  if (!q_cb8 || !k_cb8 || !v_cb8 || !qw_host || !kw_host) return fail(TM_ERR_ARG, "bad argument");
-  if (bwd ? (!dq_cb8 || !dk_cb8 || !dv_cb8 || !dqw_host || !dkw_host) : !o_cb8) return fail(TM_ERR_ARG, "missing output");
-  const int T = Z * (S / 2) * (S / 2);
-  if ((S & 1) || (T != 32 && T != 64 && T != 128) || C > 512 || C < 1)
-    return fail(TM_ERR_ARG, "window of %d tokens / C = %d: the training attention core takes 32, 64 or 128 tokens and C <= 512", T, C);
-  const int Cb = (C + 7) / 8, Cp = Cb * 8;
-  DevTmp tmp;
-  const std::vector<float> qp = pad_rows((const float*)qw_host, 1, C, Cp), kp = pad_rows((const float*)kw_host, 1, C, Cp);
-  const float *dqw_in = tmp.up(qp.data(), Cp), *dkw_in = tmp.up(kp.data(), Cp);
-  float *gq = nullptr, *gk = nullptr, *scratch = nullptr;
-  if (bwd) {
-    gq = tmp.up(nullptr, 0, Cp); gk = tmp.up(nullptr, 0, Cp);
-    scratch = tmp.up(nullptr, 0, (size_t)2 * N * 4 * Cp);
-    if (!gq || !gk || !scratch) return fail(TM_ERR_HIP, "device allocation failed");
-  }
-  if (!dqw_in || !dkw_in) return fail(TM_ERR_HIP, "device allocation failed");
-  TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S),
-     v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_attn_train(q, k, v, dqw_in, dkw_in, (const float*)dout_cb8, (float*)o_cb8, (float*)dq_cb8, (float*)dk_cb8,
-                                   (float*)dv_cb8, gq, gk, scratch, bwd, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "window attention (training): %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  if (bwd) {
-    std::vector<float> h(Cp);
-    HIP_TRY(hipMemcpy(h.data(), gq, Cp * sizeof(float), hipMemcpyDeviceToHost));
-    memcpy(dqw_host, h.data(), C * sizeof(float));
-    HIP_TRY(hipMemcpy(h.data(), gk, Cp * sizeof(float), hipMemcpyDeviceToHost));
-    memcpy(dkw_host, h.data(), C * sizeof(float));
-  }
-  return TM_OK;
-}
-
-extern "C" int tm_op_gemm_f32(const void* A_dev, const void* B_dev, const void* bias_dev, void* C_dev, int M, int N, int K,
-                              const long* strides9_host, int batch, int bias_mode, int accumulate, float alpha, void* stream) {
-  if (!A_dev || !B_dev || !C_dev || !strides9_host || M < 1 || N < 1 || K < 1 || batch < 1 || bias_mode < 0 || bias_mode > 2 ||
-      (bias_mode && !bias_dev))
-    return fail(TM_ERR_ARG, "bad argument");
-  hipError_t e = launch_gemm_f32((const float*)A_dev, (const float*)B_dev, (const float*)bias_dev, (float*)C_dev, M, N, K, strides9_host,
-                                 batch, bias_mode, accumulate, alpha, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "gemm: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_rows(int op, const void* x_dev, const void* w_dev, const void* g_dev, void* y_dev, void* dw_dev, long rows, int D,
-                          void* stream) {
-  if (op < 0 || op > 3 || !x_dev || !y_dev || rows < 1 || D < 1 || D > 8192) return fail(TM_ERR_ARG, "bad argument");
-  if ((op <= 1 && !w_dev) || ((op == 1 || op == 3) && !g_dev) || (op == 1 && !dw_dev)) return fail(TM_ERR_ARG, "op %d: missing operand", op);
-  DevTmp tmp;
-  float* scratch = nullptr;
-  if (op == 1) {
-    scratch = tmp.up(nullptr, 0, (size_t)((rows + 3) / 4) * D);
-    if (!scratch) return fail(TM_ERR_HIP, "device allocation failed");
-  }
-  hipError_t e = launch_rows(op, (const float*)x_dev, (const float*)w_dev, (const float*)g_dev, (float*)y_dev, (float*)dw_dev, scratch, rows, D,
-                             (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "row op: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_resample(const void* x_cb8, void* y_cb8, int N, int C, int Z, int S_out, int mode, void* stream) {
-  if (!x_cb8 || !y_cb8 || (mode != 1 && mode != 2) || (mode == 1 && (S_out & 1))) return fail(TM_ERR_ARG, "bad argument");
-  const int S_in = mode == 1 ? S_out / 2 : S_out * 2;
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S_in, S_in), y = view_cb8(y_cb8, N, C, Z, S_out, S_out);
-  PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-  P.resample = mode == 1 ? RS_UP2 : RS_DOWN2;
-  P.N = N; P.Z = Z; P.S = S_out; P.inv_c = 1.0f / (float)C;
-  P.out = y.p; P.out_nstride = y.nstride;
-  hipError_t e = launch_prep(P, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "resample: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_sumsq(const void* x_dev, long n, float* out_host, void* stream) {
-  if (!x_dev || n < 1 || !out_host) return fail(TM_ERR_ARG, "bad argument");
-  const int nwg = (int)std::min<long>(1024, (n + 255) / 256);
-  DevTmp tmp;
-  float* scratch = tmp.up(nullptr, 0, (size_t)nwg + 8);
-  if (!scratch) return fail(TM_ERR_HIP, "device allocation failed");
-  hipError_t e = launch_sumsq((const float*)x_dev, n, scratch + nwg, scratch, nwg, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "sum of squares: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  HIP_TRY(hipMemcpy(out_host, scratch + nwg, sizeof(float), hipMemcpyDeviceToHost));
-  return TM_OK;
-}
-
-extern "C" int tm_op_adam(void* p_dev, const void* g_dev, void* m_dev, void* v_dev, long n, float lr, float beta1, float beta2, float eps,
-                          float weight_decay, int step, float grad_scale, void* stream) {
-  if (!p_dev || !g_dev || !m_dev || !v_dev || n < 1 || step < 1) return fail(TM_ERR_ARG, "bad argument");
-  hipError_t e = launch_adam((float*)p_dev, (const float*)g_dev, (float*)m_dev, (float*)v_dev, n, lr, beta1, beta2, eps, weight_decay, step,
-                             grad_scale, (hipStream_t)stream);
-  hipError_t e2 = hipStreamSynchronize((hipStream_t)stream);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "adam: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  return TM_OK;
-}
-
-extern "C" int tm_op_conv_dgrad(const void* dy_cb8, const void* w_host, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,
-                                int ksize, void* stream) {
-  if (!dy_cb8 || !w_host || !dx_cb8 || (ksize != 1 && ksize != 3)) return fail(TM_ERR_ARG, "bad argument");
-  const int taps = ksize == 1 ? 1 : 27;
-  const float* w = (const float*)w_host;
-  std::vector<float> wt((size_t)Cin * Cout * taps);
-  for (int co = 0; co < Cout; ++co)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int t = 0; t < taps; ++t) wt[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = w[((size_t)co * Cin + ci) * taps + t];
-  std::vector<float> zb(Cin, 0.f);
-  return tm_op_conv_mfma(dy_cb8, wt.data(), zb.data(), dx_cb8, N, Cout, Cin, Z, S, ksize, ZM_PAD1, 0, 0, stream);
-}
-
-// dW [Cout][Cin][taps] and db [Cout] (HOST outputs) of the same convs from the forward input x and dY
-extern "C" int tm_op_conv_wgrad(const void* x_cb8, const void* dy_cb8, void* dw_host, void* db_host_or_null, int N, int Cin,
-                                int Cout, int Z, int S, int ksize, void* stream) {
-  if (!x_cb8 || !dy_cb8 || !dw_host || (ksize != 1 && ksize != 3)) return fail(TM_ERR_ARG, "bad argument");
-  if (Z < 1 || Z > 4) return fail(TM_ERR_ARG, "weight gradient: Z must be 1 .. 4 (the kernel stages up to four z planes)");
-  const int taps = ksize == 1 ? 1 : 27;
-  hipStream_t st = (hipStream_t)stream;
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = view_cb8(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
-  DevTmp tmp;
-  const size_t nw = (size_t)Cout * Cin * taps;
-  float* ddw = tmp.up(nullptr, 0, nw);
-  float* ddb = tmp.up(nullptr, 0, (size_t)dy.Cb * 8);
-  if (!ddw || !ddb) return fail(TM_ERR_HIP, "device allocation failed");
-  hipError_t e = launch_conv_wgrad(x, dy, ddw, Cin, Cout, taps, st);
-  if (e == hipSuccess && db_host_or_null) e = launch_chan_sum(dy, ddb, Cout, st);
-  hipError_t e2 = hipStreamSynchronize(st);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(TM_ERR_HIP, "conv wgrad: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-  HIP_TRY(hipMemcpy(dw_host, ddw, nw * sizeof(float), hipMemcpyDeviceToHost));
-  if (db_host_or_null) HIP_TRY(hipMemcpy(db_host_or_null, ddb, Cout * sizeof(float), hipMemcpyDeviceToHost));
   return TM_OK;
 }

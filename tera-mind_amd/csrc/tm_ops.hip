@@ -1,0 +1,690 @@
+// Single-operator entry points of the C-ABI (include/teramind_hip.h): one kernel form per call, for the parity tests
+// (tests/test_gpu_ops.py) and the training step (teramind_amd.training / train_model).  Unlike the executor (tm_model.hip)
+// these hooks take HOST weights where the signature says so, own their device scratch for the duration of the call
+// (DevTmp) and synchronise `stream` before returning (finish); tm_op_to_cb8 / tm_op_from_cb8 only enqueue.
+#include "../../include/teramind_hip.h"
+#include "tm_kernels.h"
+
+#include <algorithm>
+#include <cmath>
+#include <tuple>
+#include <utility>
+#include <vector>
+#include <string.h>
+
+using namespace tmk;
+
+// Device scratch of one call: buffers and events, released on every return path.  After a failed HIP call every further
+// request returns nullptr; the hook checks `err` once after allocating and returns report().
+struct DevTmp {
+  std::vector<void*> ptrs;
+  std::vector<hipEvent_t> events;
+  hipError_t err = hipSuccess;
+  const char* what = "";
+  DevTmp() = default;
+  DevTmp(const DevTmp&) = delete;
+  DevTmp& operator=(const DevTmp&) = delete;
+  ~DevTmp() {
+    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
+    for (void* p : ptrs) (void)hipFree(p);
+  }
+  bool ok(hipError_t e, const char* call) {
+    if (e != hipSuccess) { err = e; what = call; }
+    return e == hipSuccess;
+  }
+  // n elements of T, copied from `host` if given
+  template <class T> T* alloc(size_t n, const T* host = nullptr) {
+    void* p = nullptr;
+    if (err != hipSuccess || !ok(hipMalloc(&p, n * sizeof(T)), "hipMalloc")) return nullptr;
+    ptrs.push_back(p);
+    if (host && !ok(hipMemcpy(p, host, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy")) return nullptr;
+    return (T*)p;
+  }
+  float* zeros(size_t n) {
+    float* p = alloc<float>(n);
+    return p && ok(hipMemset(p, 0, n * sizeof(float)), "hipMemset") ? p : nullptr;
+  }
+  hipEvent_t event() {
+    hipEvent_t ev = nullptr;
+    if (err != hipSuccess || !ok(hipEventCreate(&ev), "hipEventCreate")) return nullptr;
+    events.push_back(ev);
+    return ev;
+  }
+  int report() const { return fail(TM_ERR_HIP, "%s failed: %s", what, hipGetErrorString(err)); }
+};
+
+// the tail of every synchronising hook: wait for `stream`, report the first error as "<what>: <HIP error>"
+static int finish(hipStream_t st, hipError_t e, const char* what) {
+  const hipError_t e2 = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = e2;
+  return e == hipSuccess ? TM_OK : fail(TM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+static TV view_cb8(void* p, int N, int C, int Z, int H, int W) {
+  TV t;
+  t.p = (float*)p; t.N = N; t.C = C; t.Cb = (C + 7) / 8; t.Z = Z; t.H = H; t.W = W;
+  t.nstride = (long)t.Cb * t.plane();
+  return t;
+}
+static TVH view_h16(void* p, int N, int C, int Z, int H, int W) { return as_h(view_cb8(p, N, C, Z, H, W)); }
+
+// fp32 CB8 x -> a 16-bit CB8 copy in `tmp` (prep kernel, no norm / act); `pair`: even block count (zero pad blocks), the
+// operand form of the 16-bit conv kernels.  Launches nothing once `e` holds an error.
+static TVH to_h16(DevTmp& tmp, const TV& x, bool f16, bool pair, hipStream_t st, hipError_t& e) {
+  if (e != hipSuccess) return TVH();
+  const int Cb = pair ? (x.Cb + 1) / 2 * 2 : x.Cb;
+  const TVH h = view_h16(tmp.alloc<uint16_t>((size_t)x.N * Cb * x.plane()), x.N, Cb * 8, x.Z, x.H, x.W);
+  if (tmp.err) { e = tmp.err; return h; }
+  PrepLaunch P;
+  P.nsrc = 1;
+  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  P.N = x.N; P.Z = x.Z; P.S = x.H; P.h_f16 = f16 ? 1 : 0;
+  P.out_h = h.p; P.out_h_nstride = h.nstride; P.pad_blocks = Cb - x.Cb;
+  e = launch_prep(P, st);
+  return h;
+}
+
+// packed conv weights and the bias zero padded to ceil(Cout / 64) * 64 floats (what the MFMA epilogues read), in `tmp`
+template <class T>
+static std::pair<const T*, const float*> upload_conv(DevTmp& tmp, const std::vector<T>& w, const void* bias_host, int Cout) {
+  std::vector<float> b((size_t)(Cout + 63) / 64 * 64, 0.f);
+  memcpy(b.data(), bias_host, Cout * sizeof(float));
+  return {tmp.alloc(w.size(), w.data()), tmp.alloc(b.size(), b.data())};
+}
+
+// per-channel vectors: [rows][C] host <-> [rows][Cp] zero padded device rows
+static const float* upload_rows(DevTmp& tmp, const void* host, int rows, int C, int Cp) {
+  std::vector<float> o((size_t)rows * Cp, 0.f);
+  for (int r = 0; r < rows; ++r) memcpy(o.data() + (size_t)r * Cp, (const float*)host + (size_t)r * C, C * sizeof(float));
+  return tmp.alloc(o.size(), o.data());
+}
+static hipError_t download_rows(void* host, const float* dev, int rows, int C, int Cp) {
+  std::vector<float> h((size_t)rows * Cp);
+  const hipError_t e = hipMemcpy(h.data(), dev, h.size() * sizeof(float), hipMemcpyDeviceToHost);
+  for (int r = 0; r < rows && e == hipSuccess; ++r) memcpy((float*)host + (size_t)r * C, h.data() + (size_t)r * Cp, C * sizeof(float));
+  return e;
+}
+
+// ------------------------------------------------------------------------------------------
+// single-operator entry points (tests)
+// ------------------------------------------------------------------------------------------
+extern "C" int tm_op_to_cb8(const void* x, void* y, int N, int C, int Z, int H, int W, void* stream) {
+  HIP_TRY(launch_to_cb8((const float*)x, view_cb8(y, N, C, Z, H, W), (hipStream_t)stream));
+  return TM_OK;
+}
+extern "C" int tm_op_from_cb8(const void* x, void* y, int N, int C, int Z, int H, int W, void* stream) {
+  HIP_TRY(launch_from_cb8(view_cb8(const_cast<void*>(x), N, C, Z, H, W), (float*)y, (hipStream_t)stream));
+  return TM_OK;
+}
+extern "C" int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                               int Cout, int Z, int S, int ksize, int zmode, int up2, int tile_variant, void* stream) {
+  if (ksize != 1 && ksize != 3) return fail(TM_ERR_ARG, "ksize must be 1 or 3");
+  if (zmode != ZM_PAD1 && zmode != ZM_INPLANE && zmode != ZM_VALID && zmode != ZM_UPS) return fail(TM_ERR_ARG, "bad zmode");
+  const bool ups = ksize == 3 && zmode == ZM_UPS;       // w [Cout][Cin][27]: conv of the nearest-x2 upsampled x (y at 2S)
+  if (zmode == ZM_UPS && (ksize != 3 || up2)) return fail(TM_ERR_ARG, "ZM_UPS: ksize 3, no fused upsample of the output");
+  const int taps = ksize == 1 ? 1 : (zmode == ZM_INPLANE ? 9 : (ups ? 12 : 27));
+  const int Zout = (ksize == 3 && zmode == ZM_VALID) ? Z - 2 : Z;
+  const int So = (up2 || ups) ? 2 * S : S;
+  ConvW cw;
+  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
+  std::vector<float> pk(ups ? conv_pack_ups_floats(Cout, cw.Cbi) : conv_pack_floats(Cout, cw.Cbi, taps));
+  if (ups) conv_pack_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
+  else conv_pack_host((const float*)w_host, Cout, &Cin, 1, taps, pk.data());
+  DevTmp tmp;
+  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, Zout, So, So);
+  L.tile_variant = tile_variant;
+  L.zmode = zmode;
+  L.flags = up2 ? EPI_UP2 : 0;
+  return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_mfma");
+}
+
+// The ConvLaunchH of the 16-bit 3x3x3 conv hooks (Z == 2): x N x Cin channels (blocks paired) at S x S, y Cout channels at
+// So = S, or 2S in the upsampled-input form; fused: the norm epilogue writes the 16-bit a2 at y's geometry.  Rejects the
+// forms the kernels do not take, before any device call; the caller sets the pointers.
+static int conv27_launch(ConvLaunchH& L, int N, int Cin, int Cout, int S, int waves, int ups, bool res, bool fused) {
+  if (waves != 0 && waves != 4 && waves != 8 && waves != 9) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4, 8 or 9 (lockstep 8-wave form)");
+  if (fused && Cout != 64 && Cout != 128) return fail(TM_ERR_ARG, "fused epilogue needs Cout in {64, 128}");
+  if (ups && (Cout % 128 || res)) return fail(TM_ERR_ARG, "upsampled-input form: Cout a multiple of 128, no residual");
+  const int So = ups ? 2 * S : S;
+  L.x = view_h16(nullptr, N, ((Cin + 7) / 8 + 1) / 2 * 16, 2, S, S);
+  L.Cout = Cout; L.force_waves = waves; L.ups = ups;
+  L.y = view_cb8(nullptr, N, Cout, 2, So, So);
+  if (fused) { L.fuse_norm = 1; L.a2 = view_h16(nullptr, N, Cout, 2, So, So); }
+  return TM_OK;
+}
+// shared body of the 16-bit 3x3x3 conv test entry points: fp32 CB8 input -> 16-bit CB8 (prep kernel), then the conv
+static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin, int Cout,
+                         int S, int dtype, int waves, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                         int per_image, void* a2_out, void* stream, const void* res_h16 = nullptr, void* y_h16 = nullptr,
+                         int ups = 0, int res_half = 0) {
+  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
+  const bool f16 = dtype == TM_DTYPE_F16, fused = norm_w_host != nullptr;
+  if (fused && (!scale_host || !shift_host || !a2_out || per_image < 1))
+    return fail(TM_ERR_ARG, "fused epilogue needs scale / shift / a2 and per_image >= 1");
+  ConvLaunchH L;
+  if (int rc = conv27_launch(L, N, Cin, Cout, S, waves, ups, res_h16 != nullptr, fused)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int Cbi = (Cin + 7) / 8, nimg = (N + per_image - 1) / per_image;
+  std::vector<uint16_t> pk(ups ? conv_bf16_pack_ups_elems(Cout, Cbi) : conv_bf16_pack_elems(Cout, Cbi));
+  if (ups) (f16 ? conv_f16_pack_ups_host : conv_bf16_pack_ups_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
+  else (f16 ? conv_f16_pack_host : conv_bf16_pack_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
+  DevTmp tmp;
+  std::tie(L.w, L.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (fused) {                                          // norm_w [Cout], scale / shift [nimg][Cout]
+    L.norm_w = tmp.alloc(Cout, (const float*)norm_w_host);
+    L.mod_scale = tmp.alloc((size_t)nimg * Cout, (const float*)scale_host);
+    L.mod_shift = tmp.alloc((size_t)nimg * Cout, (const float*)shift_host);
+    L.mod_stride = Cout; L.per_image = per_image; L.a2.p = (uint16_t*)a2_out;
+  }
+  if (tmp.err) return tmp.report();
+  hipError_t e = hipSuccess;
+  L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, 2, S, S), f16, true, st, e);
+  L.y.p = (float*)y_cb8;
+  L.res_half = res_half;
+  TVH resh = as_h(L.y);
+  if (res_h16) {
+    resh.p = (uint16_t*)const_cast<void*>(res_h16); L.res_h = &resh;
+    if (res_half) { resh.H = L.y.H / 2; resh.W = L.y.W / 2; resh.nstride = L.y.nstride / 4; }
+  }
+  if (y_h16) { L.y_h = (uint16_t*)y_h16; L.yh_nstride = L.y.nstride; }
+  if (e == hipSuccess) e = (f16 ? launch_conv27_f16 : launch_conv27_bf16)(L, st);
+  return finish(st, e, "conv27 (16-bit)");
+}
+extern "C" int tm_op_conv27_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                 int Cout, int S, int dtype, int waves, const void* res_h16, void* y_h16, int ups, int res_half,
+                                 void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
+  return op_conv27_h16(x_cb8, w_host, bias_host, y_cb8 ? y_cb8 : y_h16, N, Cin, Cout, S, dtype, waves, nullptr, nullptr, nullptr, 1,
+                       nullptr, stream, res_h16, y_h16, ups, res_half);
+}
+extern "C" int tm_op_conv27_fused(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
+                                  const void* scale_host, const void* shift_host, void* a2_out, int N, int Cin, int Cout,
+                                  int S, int per_image, int dtype, int waves, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || !norm_w_host || !a2_out) return fail(TM_ERR_ARG, "null argument");
+  // the launcher takes the output geometry from `y`; the fused form never writes it
+  return op_conv27_h16(x_cb8, w_host, bias_host, a2_out, N, Cin, Cout, S, dtype, waves, norm_w_host, scale_host, shift_host,
+                       per_image, a2_out, stream);
+}
+// Timing hook of the 16-bit 3x3x3 conv on random device data (uniform in [-1, 1): the clock the chip holds depends on the
+// operand bits, cdna guide rule 25): the model's launch forms -- 16-bit stream output with an optional 16-bit residual, the
+// fused norm epilogue, the upsampled-input form -- `iters` launches between two events after one warm-up launch.
+__global__ void fill_h16_kernel(uint16_t* p, size_t n, unsigned seed, int f16) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned hsh = (unsigned)i * 2654435761u ^ (unsigned)(i >> 32) * 40503u ^ seed;
+    hsh ^= hsh >> 15; hsh *= 2246822519u; hsh ^= hsh >> 13; hsh *= 3266489917u; hsh ^= hsh >> 16;
+    const float v = (float)(hsh >> 8) * (1.0f / 8388608.0f) - 1.0f;
+    uint16_t u;
+    if (f16) { const _Float16 hf = (_Float16)v; u = __builtin_bit_cast(uint16_t, hf); }
+    else { const __bf16 bf = (__bf16)v; u = __builtin_bit_cast(uint16_t, bf); }
+    p[i] = u;
+  }
+}
+extern "C" int tm_op_conv27_time(int N, int Cin, int Cout, int S, int dtype, int waves, int ups, int with_res, int fused,
+                                 int iters, float* ms_per_launch, void* stream) {
+  if (!is_h16(dtype) || iters < 1 || !ms_per_launch || N < 1) return fail(TM_ERR_ARG, "bad argument");
+  ConvLaunchH L;
+  if (int rc = conv27_launch(L, N, Cin, Cout, S, waves, ups, with_res, fused)) return rc;
+  const bool f16 = dtype == TM_DTYPE_F16;
+  hipStream_t st = (hipStream_t)stream;
+  const int Cbi = (Cin + 7) / 8, nt64 = (Cout + 63) / 64;
+  const size_t nw = ups ? conv_bf16_pack_ups_elems(Cout, Cbi) : conv_bf16_pack_elems(Cout, Cbi);
+  const size_t nx = (size_t)N * L.x.nstride, ny = (size_t)N * L.y.nstride;
+  const size_t nf = (size_t)nt64 * 64 + (size_t)Cout * 3;                  // bias | norm_w | scale | shift
+  std::vector<float> fp(nf);
+  for (size_t i = 0; i < nf; ++i) fp[i] = 0.01f * (float)((int)(i * 37 % 101) - 50);
+  for (int i = 0; i < Cout; ++i) fp[(size_t)nt64 * 64 + i] = 1.0f + 0.001f * (float)(i % 17);      // norm_w
+  DevTmp tmp;
+  uint16_t *dw = tmp.alloc<uint16_t>(nw), *dx = tmp.alloc<uint16_t>(nx), *dy = tmp.alloc<uint16_t>(ny);
+  uint16_t* dr = with_res ? tmp.alloc<uint16_t>(ny) : nullptr;
+  const float* df = tmp.alloc(nf, fp.data());
+  hipEvent_t e0 = tmp.event(), e1 = tmp.event();
+  if (tmp.err) return tmp.report();
+  hipLaunchKernelGGL(fill_h16_kernel, dim3(2048), dim3(256), 0, st, dw, nw, 11u, f16 ? 1 : 0);
+  hipLaunchKernelGGL(fill_h16_kernel, dim3(2048), dim3(256), 0, st, dx, nx, 23u, f16 ? 1 : 0);
+  if (with_res) hipLaunchKernelGGL(fill_h16_kernel, dim3(2048), dim3(256), 0, st, dr, ny, 37u, f16 ? 1 : 0);
+  HIP_TRY(hipStreamSynchronize(st));
+  L.x.p = dx; L.w = dw; L.bias = df;
+  L.y.p = (float*)dy; L.y_h = dy; L.yh_nstride = L.y.nstride;
+  TVH resh = as_h(L.y);
+  if (with_res) { resh.p = dr; L.res_h = &resh; }
+  if (fused) {
+    L.norm_w = df + nt64 * 64; L.mod_scale = L.norm_w + Cout; L.mod_shift = L.mod_scale + Cout;
+    L.mod_stride = 0; L.per_image = N; L.a2.p = dy;
+  }
+  const auto conv = f16 ? launch_conv27_f16 : launch_conv27_bf16;
+  hipError_t e = conv(L, st);                                             // warm-up
+  if (e == hipSuccess) e = hipEventRecord(e0, st);
+  for (int i = 0; i < iters && e == hipSuccess; ++i) e = conv(L, st);
+  if (e == hipSuccess) e = hipEventRecord(e1, st);
+  *ms_per_launch = 0.f;
+  const int rc = finish(st, e, "conv27 (16-bit)");
+  if (rc == TM_OK) { (void)hipEventElapsedTime(ms_per_launch, e0, e1); *ms_per_launch /= (float)iters; }
+  return rc;
+}
+extern "C" int tm_op_conv1_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                int Cout, int Z, int S, int gelu, int dtype, int waves, const void* res_h16, const void* gate_h16,
+                                void* y_h16, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
+  if (!y_cb8) y_cb8 = y_h16;                              // geometry carrier only
+  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
+  if (waves != 0 && waves != 4 && waves != 8) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4 or 8");
+  const bool f16 = dtype == TM_DTYPE_F16;
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<uint16_t> pk(conv1_bf16_pack_elems(Cout, (Cin + 7) / 8));
+  (f16 ? conv1_f16_pack_host : conv1_bf16_pack_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
+  DevTmp tmp;
+  ConvLaunchH L;
+  std::tie(L.w, L.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  hipError_t e = hipSuccess;
+  L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
+  L.Cout = Cout; L.flags = gelu ? EPI_GELU : 0; L.force_waves = waves;
+  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  TVH resh = as_h(L.y), gateh = as_h(L.y);
+  if (res_h16) { resh.p = (uint16_t*)const_cast<void*>(res_h16); L.res_h = &resh; }
+  if (gate_h16) { gateh.p = (uint16_t*)const_cast<void*>(gate_h16); L.gate_h = &gateh; }
+  if (y_h16) { L.y_h = (uint16_t*)y_h16; L.yh_nstride = L.y.nstride; }
+  if (e == hipSuccess) e = (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st);
+  return finish(st, e, "conv1 (16-bit)");
+}
+extern "C" int tm_op_conv1_concat(const void* const* x_cb8, const int* cin, const int* collage, int nsrc, const void* w_host,
+                                  const void* bias_host, void* y_cb8, int N, int Cout, int Z, int S, int p1, int p2,
+                                  int dtype, int waves, void* stream) {
+  if (!x_cb8 || !cin || !collage || !w_host || !bias_host || !y_cb8 || nsrc < 1 || nsrc > 3) return fail(TM_ERR_ARG, "bad argument");
+  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
+  const bool f16 = dtype == TM_DTYPE_F16;
+  hipStream_t st = (hipStream_t)stream;
+  bool any_col = false;
+  for (int i = 0; i < nsrc; ++i) any_col = any_col || collage[i];
+  const int q = any_col ? (p1 - 1) * (p2 - 1) : 1;
+  if (any_col && (p1 < 2 || p2 < 2 || N % q)) return fail(TM_ERR_ARG, "collage needs N = b * (p1-1) * (p2-1)");
+  const int Nsrc_col = any_col ? N / q * p1 * p2 : N;      // a collaged source lives on the (p1 x p2) grid
+  int Cbi = 0;
+  for (int i = 0; i < nsrc; ++i) Cbi += (cin[i] + 7) / 8;
+  std::vector<uint16_t> pk(conv1_bf16_pack_elems(Cout, Cbi));
+  (f16 ? conv1_f16_pack_host : conv1_bf16_pack_host)((const float*)w_host, Cout, cin, nsrc, pk.data());
+  DevTmp tmp;
+  ConvLaunchH L;
+  std::tie(L.w, L.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < nsrc; ++i) {
+    L.xs[i] = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8[i]), collage[i] ? Nsrc_col : N, cin[i], Z, S, S), f16, false, st, e);
+    L.xs_collage[i] = collage[i] ? 1 : 0;
+  }
+  L.nsrc = nsrc; L.p1 = p1; L.p2 = p2;
+  L.x = view_h16(nullptr, N, (Cbi + 1) / 2 * 16, Z, S, S);
+  L.x.nstride = 0;
+  L.Cout = Cout; L.force_waves = waves;
+  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  if (e == hipSuccess) e = (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st);
+  return finish(st, e, "conv1 concat");
+}
+extern "C" int tm_op_prep_h16(const void* const* src_h16, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
+                              int p1, int p2, int up2, const void* norm_w_dev, int c_real, int mod, const void* mod_scale,
+                              const void* mod_shift, long mod_stride, int per_image, int act, int dtype, int variant,
+                              void* out_h16, void* raw_h16, int iters, float* elapsed_ms, void* stream) {
+  if (!src_h16 || !src_c || !collage || !out_h16 || nsrc < 1 || nsrc > 3 || iters < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
+  if (mod != MOD_NONE && (!mod_scale || !mod_shift)) return fail(TM_ERR_ARG, "modulation tensors missing");
+  hipStream_t st = (hipStream_t)stream;
+  bool any_col = false;
+  for (int i = 0; i < nsrc; ++i) any_col = any_col || collage[i];
+  const int q = any_col ? (p1 - 1) * (p2 - 1) : 1;
+  if (any_col && (p1 < 2 || p2 < 2 || N % q)) return fail(TM_ERR_ARG, "collage needs N = b * (p1-1) * (p2-1)");
+  if (up2 < 0 || up2 > 2) return fail(TM_ERR_ARG, "up2: 0 same, 1 nearest x2, 2 = 2 x 2 average (Downsample)");
+  if (up2 == 1 && (any_col || (S & 1))) return fail(TM_ERR_ARG, "up2 takes plain sources and an even S");
+  if (up2 == 2 && (any_col || nsrc != 1 || mod != MOD_NONE)) return fail(TM_ERR_ARG, "the downsample form takes one plain source, no modulation");
+  const int Ss = up2 == 1 ? S / 2 : (up2 == 2 ? 2 * S : S);
+  PrepLaunch P;
+  P.nsrc = nsrc;
+  int cbtot = 0;
+  for (int i = 0; i < nsrc; ++i) {
+    const int cb = (src_c[i] + 7) / 8;
+    P.src[i].p = (const float*)src_h16[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
+    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
+    cbtot += cb;
+  }
+  const int cbe = (cbtot + 1) / 2 * 2;
+  P.src_h = 1; P.h_f16 = dtype == TM_DTYPE_F16;
+  P.resample = up2 == 1 ? RS_UP2 : (up2 == 2 ? RS_DOWN2 : RS_SAME); P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
+  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act; P.per_image = per_image > 0 ? per_image : 1;
+  P.mod = mod; P.mod_stride = mod_stride;
+  if (mod == MOD_IMAGE) { P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift; }
+  if (mod == MOD_VOXEL) { P.mod_scale_h = (const uint16_t*)mod_scale; P.mod_shift_h = (const uint16_t*)mod_shift; }
+  P.out_h = (uint16_t*)out_h16; P.out_h_nstride = (long)cbe * Z * S * S * 8; P.pad_blocks = cbe - cbtot;
+  if (raw_h16) { P.raw_h = (uint16_t*)raw_h16; P.raw_h_nstride = P.out_h_nstride; }
+  DevTmp tmp;
+  hipEvent_t e0 = elapsed_ms ? tmp.event() : nullptr, e1 = elapsed_ms ? tmp.event() : nullptr;
+  if (tmp.err) return tmp.report();
+  set_prep_variant(variant);
+  hipError_t e = launch_prep(P, st);                                   // warm-up / the result
+  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e0, st);
+  for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_prep(P, st);
+  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e1, st);
+  set_prep_variant(0);
+  const int rc = finish(st, e, "prep");
+  if (elapsed_ms) {
+    *elapsed_ms = 0.f;
+    if (rc == TM_OK && iters > 1) { (void)hipEventElapsedTime(elapsed_ms, e0, e1); *elapsed_ms /= (float)(iters - 1); }
+  }
+  return rc;
+}
+extern "C" int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_dev,
+                                 const void* kw_dev, void* out, int N, int C, int Z, int S, int dtype, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (C % 64) return fail(TM_ERR_ARG, "C must be a multiple of 64");
+  const TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S);
+  const TV v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
+  const float *qw = (const float*)qw_dev, *kw = (const float*)kw_dev;
+  if (dtype == TM_DTYPE_F32) return finish(st, launch_window_attn(q, k, v, qw, kw, view_cb8(out, N, C, Z, S, S), st), "window attention");
+  DevTmp tmp;
+  hipError_t e = hipSuccess;
+  const TVH hq = to_h16(tmp, q, false, false, st, e), hk = to_h16(tmp, k, false, false, st, e), hv = to_h16(tmp, v, false, false, st, e);
+  TVH o = hq;
+  o.p = (uint16_t*)out;
+  if (e == hipSuccess) e = launch_window_attn_bf16(hq, hk, hv, qw, kw, o, st);
+  return finish(st, e, "window attention");
+}
+extern "C" int tm_op_conv_direct(const void* x, const void* w_host, const void* bias_host, void* y, int N, int Cin,
+                                 int Cout, int Zin, int S, int kz, int ky, int kx, int pz, int py, int px, int silu_in,
+                                 int up2_out, void* stream) {
+  const int taps = kz * ky * kx, Cop = (Cout + 7) / 8 * 8;
+  const int Zout = Zin + 2 * pz - kz + 1;
+  if (Zout < 1 || py != ky / 2 || px != kx / 2) return fail(TM_ERR_ARG, "unsupported geometry");
+  std::vector<float> wt((size_t)taps * Cin * Cop, 0.f);
+  const float* w = (const float*)w_host;
+  for (int co = 0; co < Cout; ++co)
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int t = 0; t < taps; ++t) wt[((size_t)t * Cin + ci) * Cop + co] = w[((size_t)co * Cin + ci) * taps + t];
+  DevTmp tmp;
+  DirectLaunch L;
+  std::tie(L.w, L.bias) = upload_conv(tmp, wt, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  L.x = (const float*)x; L.ax = acc_ncdhw(Cin, Zin, S, S);
+  const int So = up2_out ? 2 * S : S;
+  L.y = (float*)y; L.ay = acc_ncdhw(Cout, Zout, So, So);
+  L.N = N; L.Cin = Cin; L.Cout = Cout; L.Zin = Zin; L.Zout = Zout; L.S = S;
+  L.kz = kz; L.ky = ky; L.kx = kx; L.pz = pz; L.py = py; L.px = px; L.silu_in = silu_in; L.up2_out = up2_out;
+  return finish((hipStream_t)stream, launch_conv_direct(L, (hipStream_t)stream), "conv_direct");
+}
+
+// ------------------------------------------------------------------------------------------
+// training slice: forward with dropout + backward of one ResBlock's pieces
+// ------------------------------------------------------------------------------------------
+// dropout probability p -> the drawn mask's threshold (drop iff word < thr) and 1 / (1 - p), both as DESIGN §8 fixes them
+static bool drop_rng_of(unsigned long long key, unsigned site, float p, DropRng& r, float& scale) {
+  if (!(p >= 0.f && p < 1.f)) return false;
+  r.key = key; r.site = site;
+  r.thr = (uint32_t)std::min(std::floor((double)p * 4294967296.0), 4294967295.0);
+  scale = 1.0f / (float)(1.0 - (double)p);
+  return true;
+}
+
+static int prep_train_impl(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                           const void* mask_cb8, float drop_scale, const DropRng* rng, int per_image, void* y_cb8, int N, int C, int Z,
+                           int S, void* stream) {
+  if (!x_cb8 || !norm_w_host || !y_cb8 || per_image < 1) return fail(TM_ERR_ARG, "bad argument");
+  const int Cb = (C + 7) / 8, Cp = Cb * 8, nimg = (N + per_image - 1) / per_image;
+  DevTmp tmp;
+  const float* dw = upload_rows(tmp, norm_w_host, 1, C, Cp);
+  const float *dsc = nullptr, *dsh = nullptr;
+  if (scale_host) { dsc = upload_rows(tmp, scale_host, nimg, C, Cp); dsh = upload_rows(tmp, shift_host, nimg, C, Cp); }
+  if (tmp.err) return tmp.report();
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
+  PrepLaunch P;
+  P.nsrc = 1;
+  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 1; P.per_image = per_image;
+  if (dsc) { P.mod = MOD_IMAGE; P.mod_scale = dsc; P.mod_shift = dsh; P.mod_stride = Cp; }
+  if (mask_cb8) { P.drop_mask = (const float*)mask_cb8; P.drop_ns = x.nstride; P.drop_scale = drop_scale; }
+  if (rng) P.drop_scale = drop_scale;
+  P.out = y.p; P.out_nstride = y.nstride;
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, rng ? launch_prep_drop(P, *rng, st) : launch_prep(P, st), "prep (training forward)");
+}
+
+extern "C" int tm_op_prep_train(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                                const void* mask_cb8, float drop_scale, int per_image, void* y_cb8, int N, int C, int Z, int S,
+                                void* stream) {
+  return prep_train_impl(x_cb8, norm_w_host, scale_host, shift_host, mask_cb8, drop_scale, nullptr, per_image, y_cb8, N, C, Z, S, stream);
+}
+
+extern "C" int tm_op_prep_train_rng(const void* x_cb8, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                                    unsigned long long key, unsigned site, float p, int per_image, void* y_cb8, int N, int C, int Z,
+                                    int S, void* stream) {
+  DropRng r;
+  float ds = 1.f;
+  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
+  return prep_train_impl(x_cb8, norm_w_host, scale_host, shift_host, nullptr, p > 0.f ? ds : 1.0f, p > 0.f ? &r : nullptr, per_image,
+                         y_cb8, N, C, Z, S, stream);
+}
+
+static int prep_bwd_impl(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                         const void* shift_host, const void* mask_cb8, float drop_scale, const DropRng* rng, int per_image, void* dx_cb8,
+                         void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
+  if (!x_cb8 || !g_cb8 || !norm_w_host || !dx_cb8 || !dw_host || per_image < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (scale_host && (!shift_host || !dscale_host || !dshift_host)) return fail(TM_ERR_ARG, "scale without shift / gradient outputs");
+  const int Cb = (C + 7) / 8, Cp = Cb * 8, nimg = (N + per_image - 1) / per_image;
+  DevTmp tmp;
+  const float* dwt = upload_rows(tmp, norm_w_host, 1, C, Cp);
+  float* ddw = tmp.zeros(Cp);
+  const float *dsc = nullptr, *dsh = nullptr;
+  float *ddsc = nullptr, *ddsh = nullptr;
+  if (scale_host) {
+    dsc = upload_rows(tmp, scale_host, nimg, C, Cp); dsh = upload_rows(tmp, shift_host, nimg, C, Cp);
+    ddsc = tmp.zeros((size_t)(nimg + 1) * Cp); ddsh = tmp.zeros((size_t)(nimg + 1) * Cp);
+  }
+  float* scratch = tmp.zeros(prep_bwd_scratch_floats(N, Cb, Z, S, scale_host != nullptr));
+  if (tmp.err) return tmp.report();
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_prep_bwd(x.p, x.nstride, (const float*)g_cb8, x.nstride, (const float*)mask_cb8, x.nstride, drop_scale, dwt,
+                                 dsc, dsh, Cp, per_image, (float*)dx_cb8, x.nstride, ddw, ddsc, ddsh, N, Cb, C, Z, S, scratch, st, rng);
+  if (int rc = finish(st, e, "prep backward")) return rc;
+  HIP_TRY(download_rows(dw_host, ddw, 1, C, Cp));
+  if (scale_host) {
+    HIP_TRY(download_rows(dscale_host, ddsc, nimg, C, Cp));
+    HIP_TRY(download_rows(dshift_host, ddsh, nimg, C, Cp));
+  }
+  return TM_OK;
+}
+
+extern "C" int tm_op_prep_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                              const void* shift_host, const void* mask_cb8, float drop_scale, int per_image, void* dx_cb8,
+                              void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
+  return prep_bwd_impl(x_cb8, g_cb8, norm_w_host, scale_host, shift_host, mask_cb8, drop_scale, nullptr, per_image, dx_cb8, dw_host,
+                       dscale_host, dshift_host, N, C, Z, S, stream);
+}
+
+extern "C" int tm_op_prep_bwd_rng(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_host,
+                                  const void* shift_host, unsigned long long key, unsigned site, float p, int per_image, void* dx_cb8,
+                                  void* dw_host, void* dscale_host, void* dshift_host, int N, int C, int Z, int S, void* stream) {
+  DropRng r;
+  float ds = 1.f;
+  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
+  return prep_bwd_impl(x_cb8, g_cb8, norm_w_host, scale_host, shift_host, nullptr, p > 0.f ? ds : 1.0f, p > 0.f ? &r : nullptr, per_image,
+                       dx_cb8, dw_host, dscale_host, dshift_host, N, C, Z, S, stream);
+}
+
+extern "C" int tm_op_dropout_mask(unsigned long long key, unsigned site, float p, void* mask_cb8, int N, int C, int Z, int S,
+                                  void* stream) {
+  DropRng r;
+  float ds = 1.f;
+  if (!mask_cb8 || N < 0 || C < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (!drop_rng_of(key, site, p, r, ds)) return fail(TM_ERR_ARG, "dropout p must lie in [0, 1)");
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_dropout_mask((float*)mask_cb8, N, C, Z, S, r.key, r.site, r.thr, st), "dropout mask");
+}
+
+// ---- AttnBlock training pieces (teramind_amd.training.AttnBlockTrain composes them) ----
+extern "C" int tm_op_ew(int op, const void* a, const void* b, const void* c, void* o1, void* o2, long n, void* stream) {
+  if (op < 0 || op > 8 || !a || !o1 || n < 0) return fail(TM_ERR_ARG, "bad argument");
+  if ((op == 0 || op == 1) && (!b || !c)) return fail(TM_ERR_ARG, "op %d needs b and c", op);
+  if ((op == 3 || op == 5 || op == 6) && !b) return fail(TM_ERR_ARG, "op %d needs b", op);
+  if (op == 1 && !o2) return fail(TM_ERR_ARG, "op 1 needs two outputs");
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_ew(op, (const float*)a, (const float*)b, (const float*)c, (float*)o1, (float*)o2, n, st), "elementwise op");
+}
+
+extern "C" int tm_op_modnorm(const void* x_cb8, const void* norm_w_host, const void* scale_cb8, const void* shift_cb8, void* y_cb8, int N,
+                             int C, int Z, int S, void* stream) {
+  if (!x_cb8 || !norm_w_host || !scale_cb8 || !shift_cb8 || !y_cb8) return fail(TM_ERR_ARG, "bad argument");
+  const int Cb = (C + 7) / 8, Cp = Cb * 8;
+  DevTmp tmp;
+  const float* dw = upload_rows(tmp, norm_w_host, 1, C, Cp);
+  if (tmp.err) return tmp.report();
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
+  PrepLaunch P;
+  P.nsrc = 1;
+  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 0;
+  P.mod = MOD_VOXEL; P.mod_scale = (const float*)scale_cb8; P.mod_shift = (const float*)shift_cb8; P.mod_stride = x.nstride;
+  P.out = y.p; P.out_nstride = y.nstride;
+  return finish((hipStream_t)stream, launch_prep(P, (hipStream_t)stream), "modulate(norm)");
+}
+
+extern "C" int tm_op_modnorm_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_host, const void* scale_cb8, void* dx_cb8,
+                                 void* dscale_cb8, void* dshift_cb8, void* dw_host, int N, int C, int Z, int S, void* stream) {
+  if (!x_cb8 || !g_cb8 || !norm_w_host || !scale_cb8 || !dx_cb8 || !dscale_cb8 || !dshift_cb8 || !dw_host)
+    return fail(TM_ERR_ARG, "bad argument");
+  const int Cb = (C + 7) / 8, Cp = Cb * 8;
+  DevTmp tmp;
+  const float* dwt = upload_rows(tmp, norm_w_host, 1, C, Cp);
+  float* ddw = tmp.zeros(Cp);
+  const long vox = (long)N * Z * S * S;
+  float* scratch = tmp.zeros((size_t)((vox + 63) / 64) * Cp);
+  if (tmp.err) return tmp.report();
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_modnorm_bwd(x, (const float*)g_cb8, dwt, (const float*)scale_cb8, (float*)dx_cb8, (float*)dscale_cb8,
+                                    (float*)dshift_cb8, ddw, C, scratch, st);
+  if (int rc = finish(st, e, "modulate(norm) backward")) return rc;
+  HIP_TRY(download_rows(dw_host, ddw, 1, C, Cp));
+  return TM_OK;
+}
+
+extern "C" int tm_op_window_attn_train(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_host, const void* kw_host,
+                                       const void* dout_cb8, void* o_cb8, void* dq_cb8, void* dk_cb8, void* dv_cb8, void* dqw_host,
+                                       void* dkw_host, int N, int C, int Z, int S, void* stream) {
+  const bool bwd = dout_cb8 != nullptr;
+  if (!q_cb8 || !k_cb8 || !v_cb8 || !qw_host || !kw_host) return fail(TM_ERR_ARG, "bad argument");
+  if (bwd ? (!dq_cb8 || !dk_cb8 || !dv_cb8 || !dqw_host || !dkw_host) : !o_cb8) return fail(TM_ERR_ARG, "missing output");
+  const int T = Z * (S / 2) * (S / 2);
+  if ((S & 1) || (T != 32 && T != 64 && T != 128) || C > 512 || C < 1)
+    return fail(TM_ERR_ARG, "window of %d tokens / C = %d: the training attention core takes 32, 64 or 128 tokens and C <= 512", T, C);
+  const int Cb = (C + 7) / 8, Cp = Cb * 8;
+  DevTmp tmp;
+  const float *dqw_in = upload_rows(tmp, qw_host, 1, C, Cp), *dkw_in = upload_rows(tmp, kw_host, 1, C, Cp);
+  float *gq = bwd ? tmp.zeros(Cp) : nullptr, *gk = bwd ? tmp.zeros(Cp) : nullptr;
+  float* scratch = bwd ? tmp.zeros((size_t)2 * N * 4 * Cp) : nullptr;
+  if (tmp.err) return tmp.report();
+  TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S),
+     v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_attn_train(q, k, v, dqw_in, dkw_in, (const float*)dout_cb8, (float*)o_cb8, (float*)dq_cb8, (float*)dk_cb8,
+                                   (float*)dv_cb8, gq, gk, scratch, bwd, st);
+  if (int rc = finish(st, e, "window attention (training)")) return rc;
+  if (bwd) {
+    HIP_TRY(download_rows(dqw_host, gq, 1, C, Cp));
+    HIP_TRY(download_rows(dkw_host, gk, 1, C, Cp));
+  }
+  return TM_OK;
+}
+
+extern "C" int tm_op_gemm_f32(const void* A_dev, const void* B_dev, const void* bias_dev, void* C_dev, int M, int N, int K,
+                              const long* strides9_host, int batch, int bias_mode, int accumulate, float alpha, void* stream) {
+  if (!A_dev || !B_dev || !C_dev || !strides9_host || M < 1 || N < 1 || K < 1 || batch < 1 || bias_mode < 0 || bias_mode > 2 ||
+      (bias_mode && !bias_dev))
+    return fail(TM_ERR_ARG, "bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_gemm_f32((const float*)A_dev, (const float*)B_dev, (const float*)bias_dev, (float*)C_dev, M, N, K, strides9_host,
+                                    batch, bias_mode, accumulate, alpha, st), "gemm");
+}
+
+extern "C" int tm_op_rows(int op, const void* x_dev, const void* w_dev, const void* g_dev, void* y_dev, void* dw_dev, long rows, int D,
+                          void* stream) {
+  if (op < 0 || op > 3 || !x_dev || !y_dev || rows < 1 || D < 1 || D > 8192) return fail(TM_ERR_ARG, "bad argument");
+  if (op == 1 && D > 4096) return fail(TM_ERR_ARG, "op 1: D = %d > 4096 (its workgroup keeps 4 * D floats of dynamic LDS, 64 KiB at most)", D);
+  if ((op <= 1 && !w_dev) || ((op == 1 || op == 3) && !g_dev) || (op == 1 && !dw_dev)) return fail(TM_ERR_ARG, "op %d: missing operand", op);
+  DevTmp tmp;
+  float* scratch = op == 1 ? tmp.zeros((size_t)((rows + 3) / 4) * D) : nullptr;
+  if (tmp.err) return tmp.report();
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_rows(op, (const float*)x_dev, (const float*)w_dev, (const float*)g_dev, (float*)y_dev, (float*)dw_dev, scratch,
+                                rows, D, st), "row op");
+}
+
+extern "C" int tm_op_resample(const void* x_cb8, void* y_cb8, int N, int C, int Z, int S_out, int mode, void* stream) {
+  if (!x_cb8 || !y_cb8 || (mode != 1 && mode != 2) || (mode == 1 && (S_out & 1))) return fail(TM_ERR_ARG, "bad argument");
+  const int S_in = mode == 1 ? S_out / 2 : S_out * 2;
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S_in, S_in), y = view_cb8(y_cb8, N, C, Z, S_out, S_out);
+  PrepLaunch P;
+  P.nsrc = 1;
+  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  P.resample = mode == 1 ? RS_UP2 : RS_DOWN2;
+  P.N = N; P.Z = Z; P.S = S_out; P.inv_c = 1.0f / (float)C;
+  P.out = y.p; P.out_nstride = y.nstride;
+  return finish((hipStream_t)stream, launch_prep(P, (hipStream_t)stream), "resample");
+}
+
+extern "C" int tm_op_sumsq(const void* x_dev, long n, float* out_host, void* stream) {
+  if (!x_dev || n < 1 || !out_host) return fail(TM_ERR_ARG, "bad argument");
+  const int nwg = (int)std::min<long>(1024, (n + 255) / 256);
+  DevTmp tmp;
+  float* scratch = tmp.zeros((size_t)nwg + 8);
+  if (tmp.err) return tmp.report();
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = finish(st, launch_sumsq((const float*)x_dev, n, scratch + nwg, scratch, nwg, st), "sum of squares")) return rc;
+  HIP_TRY(hipMemcpy(out_host, scratch + nwg, sizeof(float), hipMemcpyDeviceToHost));
+  return TM_OK;
+}
+
+extern "C" int tm_op_adam(void* p_dev, const void* g_dev, void* m_dev, void* v_dev, long n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int step, float grad_scale, void* stream) {
+  if (!p_dev || !g_dev || !m_dev || !v_dev || n < 1 || step < 1) return fail(TM_ERR_ARG, "bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_adam((float*)p_dev, (const float*)g_dev, (float*)m_dev, (float*)v_dev, n, lr, beta1, beta2, eps, weight_decay,
+                                step, grad_scale, st), "adam");
+}
+
+// dX of Conv3d(k = 3x3x3 pad 1 | 1x1x1), stride 1: the forward MFMA conv of dY with the kernel flipped in z, y, x and
+// cin <-> cout transposed (w_host [Cout][Cin][taps] as in the reference state_dict)
+extern "C" int tm_op_conv_dgrad(const void* dy_cb8, const void* w_host, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,
+                                int ksize, void* stream) {
+  if (!dy_cb8 || !w_host || !dx_cb8 || (ksize != 1 && ksize != 3)) return fail(TM_ERR_ARG, "bad argument");
+  const int taps = ksize == 1 ? 1 : 27;
+  const float* w = (const float*)w_host;
+  std::vector<float> wt((size_t)Cin * Cout * taps);
+  for (int co = 0; co < Cout; ++co)
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int t = 0; t < taps; ++t) wt[((size_t)ci * Cout + co) * taps + (taps - 1 - t)] = w[((size_t)co * Cin + ci) * taps + t];
+  std::vector<float> zb(Cin, 0.f);
+  return tm_op_conv_mfma(dy_cb8, wt.data(), zb.data(), dx_cb8, N, Cout, Cin, Z, S, ksize, ZM_PAD1, 0, 0, stream);
+}
+
+// dW [Cout][Cin][taps] and db [Cout] (HOST outputs) of the same convs from the forward input x and dY
+extern "C" int tm_op_conv_wgrad(const void* x_cb8, const void* dy_cb8, void* dw_host, void* db_host_or_null, int N, int Cin,
+                                int Cout, int Z, int S, int ksize, void* stream) {
+  if (!x_cb8 || !dy_cb8 || !dw_host || (ksize != 1 && ksize != 3)) return fail(TM_ERR_ARG, "bad argument");
+  if (Z < 1 || Z > 4) return fail(TM_ERR_ARG, "weight gradient: Z must be 1 .. 4 (the kernel stages up to four z planes)");
+  const int taps = ksize == 1 ? 1 : 27;
+  hipStream_t st = (hipStream_t)stream;
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = view_cb8(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
+  DevTmp tmp;
+  const size_t nw = (size_t)Cout * Cin * taps;
+  float* ddw = tmp.zeros(nw);
+  float* ddb = tmp.zeros((size_t)dy.Cb * 8);
+  if (tmp.err) return tmp.report();
+  hipError_t e = launch_conv_wgrad(x, dy, ddw, Cin, Cout, taps, st);
+  if (e == hipSuccess && db_host_or_null) e = launch_chan_sum(dy, ddb, Cout, st);
+  if (int rc = finish(st, e, "conv wgrad")) return rc;
+  HIP_TRY(hipMemcpy(dw_host, ddw, nw * sizeof(float), hipMemcpyDeviceToHost));
+  if (db_host_or_null) HIP_TRY(hipMemcpy(db_host_or_null, ddb, Cout * sizeof(float), hipMemcpyDeviceToHost));
+  return TM_OK;
+}

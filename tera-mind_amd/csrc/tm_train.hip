@@ -4,7 +4,7 @@
 //   chan_sum_kernel    bias gradients (sum over voxels per channel)
 // The data gradient of the convs (dgrad) needs no kernel of its own: a stride-1 "same" conv's dgrad is the forward conv of
 // dY with the kernel flipped in every axis and cin <-> cout transposed, so it runs on conv3d_mfma / conv1_mfma with weights
-// re-packed by the host (tm_op_conv_dgrad in tm_model.hip).
+// re-packed by the host (tm_op_conv_dgrad in tm_ops.hip).
 // fp32 throughout (training in the reference is fp16-mixed on top of fp32 master weights; the slice checks gradients
 // against torch.autograd of the fp32 oracle).  Layout: CB8 fp32 [N][Cb][Z][H][W][8] as everywhere.
 #include "tm_device.h"
@@ -754,7 +754,7 @@ __global__ __launch_bounds__(256) void rows_kernel(int op, const float* x, const
 }
 hipError_t launch_rows(int op, const float* x, const float* w, const float* g, float* y, float* dw, float* scratch, long rows, int D,
                        hipStream_t s) {
-  if (op < 0 || op > 3 || !x || !y || rows < 1 || D < 1 || D > 8192) return hipErrorInvalidValue;
+  if (op < 0 || op > 3 || !x || !y || rows < 1 || D < 1 || D > (op == 1 ? 4096 : 8192)) return hipErrorInvalidValue;   // op 1: 4 * D floats of LDS
   if ((op <= 1 && !w) || ((op == 1 || op == 3) && !g) || (op == 1 && (!dw || !scratch))) return hipErrorInvalidValue;
   const long nwg = (rows + 3) / 4;
   hipLaunchKernelGGL(rows_kernel, dim3((unsigned)nwg), dim3(256), op == 1 ? (size_t)4 * D * sizeof(float) : 0, s, op, x, w, g, y, scratch, rows, D);

@@ -50,6 +50,29 @@ def test_error_paths_without_device():
     assert L.tm_model_destroy(h) == 0
 
 
+def test_op_argument_checks_without_device():
+    """The single-operator hooks reject bad arguments (TM_ERR_ARG = -1) before their first HIP call."""
+    L = _lib.lib()
+    buf = (C.c_float * 64)()
+    p = C.cast(buf, C.c_void_p)
+    ms = C.c_float(0)
+    # row op 1 keeps 4 * D floats of dynamic LDS per workgroup: D <= 4096
+    assert L.tm_op_rows(1, p, p, p, p, p, 4, 4097, None) == -1
+    assert b"4096" in L.tm_last_error() and b"LDS" in L.tm_last_error()
+    # conv27 timing hook: waves 0, 4, 8 or 9 (args: N Cin Cout S dtype waves ups with_res fused iters)
+    assert L.tm_op_conv27_time(1, 64, 64, 16, 1, 5, 0, 0, 0, 1, C.byref(ms), None) == -1
+    assert b"waves" in L.tm_last_error()
+    # 16-bit conv27 without weights
+    assert L.tm_op_conv27_bf16(p, None, p, p, 1, 64, 64, 16, 1, 0, None, None, 0, 0, None) == -1
+    assert b"null" in L.tm_last_error()
+    # training attention core: Z = 2, S = 6 is a window of 18 tokens
+    assert L.tm_op_window_attn_train(p, p, p, p, p, None, p, None, None, None, None, None, 1, 64, 2, 6, None) == -1
+    assert b"18 tokens" in L.tm_last_error()
+    # prep backward: scale without shift
+    assert L.tm_op_prep_bwd(p, p, p, p, None, None, C.c_float(1.0), 1, p, p, p, p, 1, 8, 2, 4, None) == -1
+    assert b"scale without shift" in L.tm_last_error()
+
+
 def test_product_path_has_no_cpu_fallback():
     import torch
     from teramind_amd.config import PathConfig
