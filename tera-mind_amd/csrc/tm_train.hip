@@ -551,7 +551,10 @@ __global__ __launch_bounds__(256) void attn_train_kernel(AttnTrainArgs a) {
       __syncthreads();
       for (int u = 0; u < cps; ++u) {
         const int cc = sub * cps + u, c = c0 + cc;
-        if (c >= C) continue;
+        if (c >= C) {                                    // zero the pad slots of the last channel block (chunks of 16 cover them)
+          if (c < a.Cb * 8) put(out, row, c, 0.f);
+          continue;
+        }
         float s_ = 0.f;
         for (int k = 0; k < T; ++k) s_ = fmaf(trans ? Mat[k * T + row] : Mat[row * T + k], B[k * AT_CH + cc], s_);
         put(out, row, c, s_);
