@@ -199,8 +199,9 @@ int tm_blosc_decompress(const void* src, size_t src_bytes, void* dst, size_t dst
  * event, adds up the bracketed durations and the per-launch work, and resets the counters.
  *   nominal_flops  = 2*Cin*Cout*27*voxels per launch (dense-conv convention; what
  *                    torch.utils.flop_counter counts for the reference's Conv3d)
- *   executed_flops = 2/3 of that for z_size 2 (the always-zero z tap is not issued), 1/3 for z_size 1 (centre
- *                    slice only), all of it for z_size 4 / 8
+ *   executed_flops = the MFMA FLOPs actually issued: for z_size 2, fp32, 1/2 of that (pair form: three in-plane products per
+ *                    plane pair, 27 of the nominal 54 taps; 2/3 with TM_CONV_ZPAIR=0 and in the 16-bit modes, where only the
+ *                    always-zero z tap is skipped), 1/3 for z_size 1 (centre slice only), all of it for z_size 4 / 8
  *   alg_bytes      = input + packed weights + output bytes, each counted once per launch */
 typedef struct tm_prof_stats {
   uint64_t launches;
@@ -237,6 +238,12 @@ int tm_op_from_cb8(const void* x_cb8, void* y_ncdhw, int N, int C, int Z, int H,
 int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8,
                     int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
                     int tile_variant, void* stream);
+/* The same with the epilogue's residual (ksize 3, not zmode 3): y = res + conv + bias, res CB8 DEVICE in y's geometry, or with
+ * res_half != 0 at half the in-plane resolution ([N][ceil(Cout/8)][Zout][S/2][S/2][8], read at (z, y >> 1, x >> 1): the
+ * residual of a ResBlock(up=True)).  res_cb8 NULL: tm_op_conv_mfma. */
+int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                        int res_half, int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
+                        int tile_variant, void* stream);
 
 /* 16-bit variant of the 3x3x3 pad-1 conv (Z == 2): x fp32 CB8 is rounded to `dtype` (TM_DTYPE_BF16 | TM_DTYPE_F16, RNE) on
  * the device, w rounded on the host; fp32 accumulate, fp32 CB8 output.  waves: 0 = the launcher's choice, 4 | 8 = force

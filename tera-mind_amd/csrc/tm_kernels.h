@@ -32,6 +32,7 @@ struct ConvW {
   const float* w = nullptr;     // device
   const float* bias = nullptr;  // device, [ntile*64]
   int Cout = 0, Cbi = 0, taps = 0, ntile = 0;
+  int zpair = 0;                // taps == 27 packed by conv_pack_zpair_host: ZM_PAD1 at Z == 2 runs the pair form (conv3d_zpair)
 };
 size_t conv_pack_floats(int Cout, int Cbi, int taps);
 // host-side packing; seg_c[i] = real channels of concat segment i (each padded to x8).
@@ -39,6 +40,8 @@ void conv_pack_host(const float* w /*[Cout][Cin][taps]*/, int Cout, const int* s
                     int taps, float* out);
 size_t conv_pack_ups_floats(int Cout, int Cbi);          // phase weights of the upsampled-input conv (ZM_UPS), taps = 12
 void conv_pack_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
+bool conv_zpair_enabled();                               // false with TM_CONV_ZPAIR=0 (A/B timing): keep the 18-tap z-skip form
+void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out);  // per-cin vector -> virtual order
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_UP2 = 2 };

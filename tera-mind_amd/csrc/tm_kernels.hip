@@ -199,6 +199,168 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
   conv_epilogue<WM>(a, acc, nt, h, on, ooff, 2 * S);
 }
 
+// ---- pair form of the 3x3x3 pad-1 conv at Z == 2 (fp32) ----
+// With W0, W1, W2 the kz = 0, 1, 2 slices of the filter and X0, X1 the two input planes (`*` = in-plane 3 x 3 conv summed over
+// cin) the z structure is a 2 x 2 block Toeplitz product, Y0 = W1*X0 + W2*X1, Y1 = W0*X0 + W1*X1: four in-plane products in
+// the z-skip form above (36 taps per plane pair).  Three are enough:
+//   P1 = W1 * (X0 + X1)    P2 = (W2 - W1) * X1    P3 = (W0 - W1) * X0        Y0 = P1 + P2    Y1 = P1 + P3
+// (27 taps per plane pair, a quarter fewer MFMAs).  The weight slices are differenced once at pack time
+// (conv_pack_zpair_host: W1, W2 - W1, W0 - W1, nine taps each), the two planes are added while staging.  Products and
+// accumulation are fp32 as everywhere; the z association differs from F.conv3d's, like the in-plane association of UPS.
+// One workgroup owns an in-plane tile of MV voxels, BOTH output planes and 64 couts.  HALF = 0: 128 voxels, wave = 32 voxels x
+// 64 couts (3 x 2 accumulators); HALF = 1: 64 voxels, wave = 32 voxels x 32 couts (small launches).  Every output element
+// sees the same order in both -- cin block outer, then product, tap, k -- so the two tiles give identical bits.
+template <int HALF, int TW>
+struct ZPGeo {
+  static constexpr int MV = HALF ? 64 : 128;                     // in-plane voxels per workgroup (2 MV outputs)
+  static constexpr int TR = (MV / TW < TW) ? (MV / TW) : TW;     // tile rows
+  static constexpr int NPB = MV / (TR * TW);                     // patches per workgroup
+  static constexpr int HR = TR + 2, HC = TW + 2;
+  static constexpr int XV = NPB * HR * HC;                       // halo voxels of ONE staged plane
+  static constexpr int XPIECES = XV * 2;                         // 16-byte pieces per plane
+  static constexpr int PX = (XPIECES + 255) / 256;
+  static constexpr int WFLOATS = 27 * 512;
+  static constexpr int WPIECES = WFLOATS / 4;
+  static constexpr int PW = (WPIECES + 255) / 256;
+  static constexpr int LDS_BYTES = (WFLOATS + 3 * XV * 8) * 4;  // weights + the planes X0 + X1, X1, X0
+};
+
+template <int HALF, int TW>
+__global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
+  using G = ZPGeo<HALF, TW>;
+  constexpr int NC = HALF ? 1 : 2;                               // 32-cout sub-tiles per wave
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* lw = lds;                                               // [27][512]
+  float* lx = lds + G::WFLOATS;                                  // [3][XV][8]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+
+  const int S = a.S;
+  const int tiles_c = S / TW, tiles_r = S / G::TR;
+  const int tiles = tiles_c * tiles_r;
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int nt = bid % a.ntile;
+  int mt_ = bid / a.ntile;
+  const int pg = mt_ / tiles;
+  mt_ -= pg * tiles;
+  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+
+  // ---- per-thread staging descriptors: the z = 0 piece of a halo position (the z = 1 piece is one plane further) ----
+  long xoff[G::PX];
+#pragma unroll
+  for (int k = 0; k < G::PX; ++k) {
+    const int i = tid + k * 256;
+    long off = -1;
+    if (i < G::XPIECES) {
+      const int half = i & 1;
+      int v = i >> 1;
+      const int hc = v % G::HC; v /= G::HC;
+      const int hr = v % G::HR;
+      const int ps = v / G::HR;
+      const int n = pg * G::NPB + ps;
+      const int y = tr * G::TR + hr - 1, x = tc * TW + hc - 1;
+      if (n < a.N && y >= 0 && y < S && x >= 0 && x < S) off = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
+    }
+    xoff[k] = off;
+  }
+  const long zplane = (long)S * S * 8;
+  const float* wsrc = a.w + (long)nt * a.Cbi * G::WFLOATS + tid * 4;
+
+  // ---- per-lane fragment addresses ----
+  const int vt = HALF ? (wv & 1) : wv;                           // 32-voxel tile of this wave
+  const int ct0 = HALF ? (wv >> 1) : 0;                          // its first 32-cout sub-tile
+  int xb, on[1], ooff0[1], ooff1[1];
+  {
+    const int v = vt * 32 + i32;
+    const int ps = v / (G::TR * TW);
+    const int rem = v - ps * (G::TR * TW);
+    const int r = rem / TW, c = rem - r * TW;
+    xb = ((ps * G::HR + r) * G::HC + c) * 8 + 4 * h;
+    const int n = pg * G::NPB + ps;
+    on[0] = n;
+    const int y = tr * G::TR + r, x = tc * TW + c;
+    if (n < a.N) {
+      if (a.flags & EPI_UP2) { ooff0[0] = (2 * y * 2 * S + 2 * x) * 8; ooff1[0] = ooff0[0] + 4 * S * S * 8; }
+      else { ooff0[0] = (y * S + x) * 8; ooff1[0] = ooff0[0] + S * S * 8; }
+    } else { ooff0[0] = -1; ooff1[0] = -1; }
+  }
+  const int wb = ct0 * 256 + i32 * 8 + 4 * h;
+
+  f32x16 acc[3][NC];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.f;
+
+  f32x4 xr[2][G::PX], wr[G::PW];
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  auto load_stage = [&](int cb) {
+    const float* xp = a.x + (long)cb * a.x_plane;
+#pragma unroll
+    for (int k = 0; k < G::PX; ++k) {
+      xr[0][k] = xoff[k] >= 0 ? *(const f32x4*)(xp + xoff[k]) : zero4;
+      xr[1][k] = xoff[k] >= 0 ? *(const f32x4*)(xp + xoff[k] + zplane) : zero4;
+    }
+    const float* wp = wsrc + (long)cb * G::WFLOATS;
+#pragma unroll
+    for (int k = 0; k < G::PW; ++k)
+      if (G::WPIECES % 256 == 0 || tid + k * 256 < G::WPIECES) wr[k] = *(const f32x4*)(wp + k * 1024);
+  };
+
+  load_stage(0);
+  for (int cb = 0; cb < a.Cbi; ++cb) {
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < G::PX; ++k)
+      if (tid + k * 256 < G::XPIECES) {
+        float* d = lx + (tid + k * 256) * 4;
+        *(f32x4*)(d) = xr[0][k] + xr[1][k];
+        *(f32x4*)(d + G::XV * 8) = xr[1][k];
+        *(f32x4*)(d + 2 * G::XV * 8) = xr[0][k];
+      }
+#pragma unroll
+    for (int k = 0; k < G::PW; ++k)
+      if (G::WPIECES % 256 == 0 || tid + k * 256 < G::WPIECES) *(f32x4*)(lw + (tid + k * 256) * 4) = wr[k];
+    __syncthreads();
+    if (cb + 1 < a.Cbi) load_stage(cb + 1);
+
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int tap = p * 9 + ky * 3 + kx;
+          f32x4 wf[NC];
+#pragma unroll
+          for (int ct = 0; ct < NC; ++ct) wf[ct] = *(const f32x4*)(lw + tap * 512 + ct * 256 + wb);
+          const f32x4 xf = *(const f32x4*)(lx + p * G::XV * 8 + (ky * G::HC + kx) * 8 + xb);
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int ct = 0; ct < NC; ++ct)
+              acc[p][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[ct][kk], xf[kk], acc[p][ct], 0, 0, 0);
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  }
+  // Y0 = P1 + P2, Y1 = P1 + P3: one epilogue per output plane (bias, residual, pad slots as in every other form)
+  f32x16 o[NC][1];
+  const int nte = HALF ? 2 * nt + ct0 : nt;                      // conv_epilogue counts cout blocks in units of its own tile
+#pragma unroll
+  for (int ct = 0; ct < NC; ++ct) o[ct][0] = acc[0][ct] + acc[1][ct];
+  conv_epilogue<1, NC>(a, o, nte, h, on, ooff0, 2 * S);
+#pragma unroll
+  for (int ct = 0; ct < NC; ++ct) o[ct][0] = acc[0][ct] + acc[2][ct];
+  conv_epilogue<1, NC>(a, o, nte, h, on, ooff1, 2 * S);
+}
+
 // ---- 1x1x1 conv / Linear over voxels (flat voxel tiles, KC channel blocks per stage) ----
 // Replaces the skip_connection Conv3d(k=1) (model/MBAblocks.py:220-224) and every nn.Linear
 // of AttnBlock / Attention / Mlp applied to '(z h w) c' tokens (model/MBAblocks.py:465,
@@ -365,6 +527,28 @@ void conv_pack_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int*
   free(weff);
 }
 
+// Pair-form weights (conv3d_zpair): per (cout tile, cin block) the 27 taps in the order the kernel consumes them -- W1, W2 - W1,
+// W0 - W1 (kz slices, nine in-plane taps each), differences in fp32.  Same size as the plain 27-tap pack.
+// TM_CONV_ZPAIR=0 (read once, at pack time) keeps the 18-tap z-skip form: A/B timing in separate processes only.
+bool conv_zpair_enabled() {
+  static const bool off = getenv("TM_CONV_ZPAIR") && atoi(getenv("TM_CONV_ZPAIR")) == 0;
+  return !off;
+}
+void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
+  int Cin = 0;
+  for (int s = 0; s < nseg; ++s) Cin += seg_c[s];
+  float* weff = (float*)malloc((size_t)Cout * Cin * 27 * sizeof(float));
+  for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
+    for (int t = 0; t < 9; ++t) {
+      const float w0 = w[i * 27 + t], w1 = w[i * 27 + 9 + t], w2 = w[i * 27 + 18 + t];
+      weff[i * 27 + t] = w1;
+      weff[i * 27 + 9 + t] = w2 - w1;
+      weff[i * 27 + 18 + t] = w0 - w1;
+    }
+  conv_pack_host(weff, Cout, seg_c, nseg, 27, out);
+  free(weff);
+}
+
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
   int ci0 = 0, cb0 = 0;
   for (int s = 0; s < nseg; ++s) {
@@ -418,7 +602,8 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     nzi = 1;
   } else if (L.zmode == ZM_PAD1) {             // 3x3x3 pad 1
     if (L.w.taps != 27 || L.y.Z != L.x.Z) return hipErrorInvalidValue;
-    if (L.x.Z == 2) nzi = 2;                   // z-skip form
+    if (L.x.Z == 2) nzi = 2;                   // z-skip form, or the pair form when the weights were packed for it
+    else if (L.w.zpair) return hipErrorInvalidValue;
     else { nzi = 3; a.zoff = -1; }
   } else if (L.zmode == ZM_INPLANE) {  // 1x3x3
     if (L.w.taps != 9 || L.y.Z != L.x.Z) return hipErrorInvalidValue;
@@ -464,6 +649,29 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     return hipGetLastError();
   }
   int variant = L.tile_variant ? L.tile_variant : ((ovox / 256) * a.ntile >= 512 ? 2 : 1);
+  if (L.w.zpair) {                             // the form is the layer's (fixed at pack time); the tile follows the launch size
+    if (L.zmode != ZM_PAD1 || nzi != 2) return hipErrorInvalidValue;
+#define TM_LAUNCHZ(HALF, TW)                                                                     \
+  do {                                                                                          \
+    using G = ZPGeo<HALF, TW>;                                                                  \
+    static DevOnce attr_once;                                                                   \
+    if (attr_once.need()) {                                                                     \
+      hipError_t e = hipFuncSetAttribute((const void*)conv3d_zpair<HALF, TW>,                   \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
+      if (e != hipSuccess) return e;                                                            \
+      attr_once.mark();                                                                         \
+    }                                                                                           \
+    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
+    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
+    const long grid = pgs * tiles * a.ntile;                                                    \
+    hipLaunchKernelGGL((conv3d_zpair<HALF, TW>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
+  } while (0)
+    if (S == 4) TM_LAUNCHZ(1, 4);              // 4 patches per workgroup (8 would not leave LDS for two workgroups per CU)
+    else if (variant == 2) { if (S >= 32) TM_LAUNCHZ(0, 32); else if (S == 16) TM_LAUNCHZ(0, 16); else TM_LAUNCHZ(0, 8); }
+    else { if (S >= 32) TM_LAUNCHZ(1, 32); else if (S == 16) TM_LAUNCHZ(1, 16); else TM_LAUNCHZ(1, 8); }
+#undef TM_LAUNCHZ
+    return hipGetLastError();
+  }
 #define TM_LAUNCH3(NZI, WM, TW)                                                                  \
   do {                                                                                          \
     using G = C3Geo<NZI, WM, TW>;                                                               \

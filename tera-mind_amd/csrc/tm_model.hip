@@ -75,6 +75,7 @@ struct DecEntry { int lvl; std::vector<Op> ops; };
 struct tm_model {
   tm_config cfg;
   int z = 0, gn = 0, D = 0, L = 4;
+  bool zpair = false;            // fp32, z == 2: the ResBlock 3x3x3 convs are packed for and run in the pair form (conv3d_zpair)
   int rw[4];                          // rna pyramid widths
   std::vector<std::pair<std::string, std::vector<int64_t>>> spec;
   std::map<std::string, HostParam> host;
@@ -310,6 +311,7 @@ extern "C" int tm_model_create(const tm_config* cfg, tm_model** out) {
   tm_model* m = new tm_model();
   m->cfg = *cfg;
   m->z = (cfg->rna_slc + 1) / 2;
+  m->zpair = m->z == 2 && !is_h16(cfg->dtype) && conv_zpair_enabled();
   m->gn = cfg->patch_size / 16;
   m->D = m->gn * m->gn * cfg->rna_slc;
   m->gene_mfma = m->D == 64 && cfg->rna_num <= 232 && cfg->rna_num != 81;
@@ -367,7 +369,8 @@ struct FixH { const uint16_t** slot; size_t off; };   // offsets in floats into 
 static const std::vector<float>& P(tm_model* m, const std::string& k) { return m->host[k].data; }
 
 static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, const std::string& wkey,
-                      const std::string& bkey, int Cout, const std::vector<int>& seg, int taps, bool centre_slice = false) {
+                      const std::string& bkey, int Cout, const std::vector<int>& seg, int taps, bool centre_slice = false,
+                      bool zpair = false) {
   int cbi = 0, cin = 0;
   for (int c : seg) { cbi += (c + 7) / 8; cin += c; }
   // centre_slice: a 3x3x3 pad-1 conv applied to ONE plane (z_size 1, rna_slc 1) only ever multiplies its kz = 1 slice
@@ -382,8 +385,11 @@ static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, 
     taps = 9;
   }
   cw.Cout = Cout; cw.Cbi = cbi; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
+  // zpair: a 3x3x3 pad-1 conv over TWO planes (z_size 2) packed for the pair form (three in-plane products per plane pair)
+  cw.zpair = (zpair && taps == 27) ? 1 : 0;
   size_t off = pk.reserve(conv_pack_floats(Cout, cbi, taps));
-  conv_pack_host(wsrc, Cout, seg.data(), (int)seg.size(), taps, pk.buf.data() + off);
+  if (cw.zpair) conv_pack_zpair_host(wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
+  else conv_pack_host(wsrc, Cout, seg.data(), (int)seg.size(), taps, pk.buf.data() + off);
   fx.push_back({&cw.w, off});
   size_t boff = pk.reserve((size_t)cw.ntile * 64);
   const std::vector<float>& b = P(m, bkey);
@@ -573,10 +579,12 @@ extern "C" int tm_model_finalize(tm_model* m) {
           fxh.push_back({&r.c1uh, off});
         }
       } else {
-        pack_conv(m, pk, fx, r.c1, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg, 27, m->z == 1);
+        pack_conv(m, pk, fx, r.c1, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg, 27, m->z == 1,
+                  m->zpair);
         if (r.up && m->z == 2) {                             // phase weights (conv3d_mfma UPS form) + their own copy of the bias
           r.c1u = r.c1;
           r.c1u.taps = 12;
+          r.c1u.zpair = 0;
           const size_t off = pk.reserve(conv_pack_ups_floats(r.cout, r.cbi));
           conv_pack_ups_host(P(m, r.pfx + ".in_layers.2.weight").data(), r.cout, r.seg.data(), (int)r.seg.size(), pk.buf.data() + off);
           fx.push_back({&r.c1u.w, off});
@@ -585,7 +593,8 @@ extern "C" int tm_model_finalize(tm_model* m) {
           for (int i = 0; i < r.cout; ++i) pk.buf[boff + i] = b[i];
           fx.push_back({&r.c1u.bias, boff});
         }
-        pack_conv(m, pk, fx, r.c2, r.pfx + ".out_layers.3.weight", r.pfx + ".out_layers.3.bias", r.cout, {r.cout}, 27, m->z == 1);
+        pack_conv(m, pk, fx, r.c2, r.pfx + ".out_layers.3.weight", r.pfx + ".out_layers.3.bias", r.cout, {r.cout}, 27, m->z == 1,
+                  m->zpair);
       }
       if (r.has_skip) {
         if (bf16) pack_linear_stack_h(m, pk, fx, fxh, r.skip, &r.skiph, {r.pfx + ".skip_connection"}, r.cout, r.seg);
@@ -658,10 +667,11 @@ extern "C" int tm_profile_collect(tm_model* m, tm_prof_stats* out) {
   m->prof_tag.clear();
   out->launches = m->prof_used;
   out->nominal_flops = m->prof_nominal;
-  // Z == 2: the z-skip form issues 18 of 27 taps; Z == 1: the centre slice only (9); Z >= 3: all 27 (zero planes staged)
+  // Z == 2: the pair form issues 27 taps per plane PAIR (27 of the nominal 54), the z-skip form 18 of 27 per plane; Z == 1: the
+  // centre slice only (9); Z >= 3: all 27 (zero planes staged)
   // (the 16-bit conv never stages z-padding planes: (3Z - 2) / 3Z of the taps for any Z)
   out->executed_flops = m->prof_nominal * (is_h16(m->cfg.dtype) ? (3.0 * m->z - 2.0) / (3.0 * m->z)
-                                                                 : (m->z == 2 ? 18.0 / 27.0 : (m->z == 1 ? 9.0 / 27.0 : 1.0)));
+                                           : (m->z == 2 ? (m->zpair ? 27.0 / 54.0 : 18.0 / 27.0) : (m->z == 1 ? 9.0 / 27.0 : 1.0)));
   out->alg_bytes = m->prof_bytes;
   m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0;
   return TM_OK;

@@ -118,17 +118,26 @@ extern "C" int tm_op_from_cb8(const void* x, void* y, int N, int C, int Z, int H
 }
 extern "C" int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                                int Cout, int Z, int S, int ksize, int zmode, int up2, int tile_variant, void* stream) {
+  return tm_op_conv_mfma_res(x_cb8, w_host, bias_host, y_cb8, nullptr, 0, N, Cin, Cout, Z, S, ksize, zmode, up2, tile_variant, stream);
+}
+extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                                   int res_half, int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
+                                   int tile_variant, void* stream) {
   if (ksize != 1 && ksize != 3) return fail(TM_ERR_ARG, "ksize must be 1 or 3");
   if (zmode != ZM_PAD1 && zmode != ZM_INPLANE && zmode != ZM_VALID && zmode != ZM_UPS) return fail(TM_ERR_ARG, "bad zmode");
   const bool ups = ksize == 3 && zmode == ZM_UPS;       // w [Cout][Cin][27]: conv of the nearest-x2 upsampled x (y at 2S)
   if (zmode == ZM_UPS && (ksize != 3 || up2)) return fail(TM_ERR_ARG, "ZM_UPS: ksize 3, no fused upsample of the output");
+  if (res_cb8 && (ksize != 3 || zmode == ZM_UPS)) return fail(TM_ERR_ARG, "residual: k x 3 x 3 forms other than ZM_UPS only");
+  if (res_half && (!res_cb8 || up2 || S < 2)) return fail(TM_ERR_ARG, "res_half: needs a residual, S >= 2 and no fused upsample");
   const int taps = ksize == 1 ? 1 : (zmode == ZM_INPLANE ? 9 : (ups ? 12 : 27));
   const int Zout = (ksize == 3 && zmode == ZM_VALID) ? Z - 2 : Z;
   const int So = (up2 || ups) ? 2 * S : S;
   ConvW cw;
   cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
+  cw.zpair = (ksize == 3 && zmode == ZM_PAD1 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;    // as tm_model_finalize packs c1 / c2
   std::vector<float> pk(ups ? conv_pack_ups_floats(Cout, cw.Cbi) : conv_pack_floats(Cout, cw.Cbi, taps));
   if (ups) conv_pack_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
+  else if (cw.zpair) conv_pack_zpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
   else conv_pack_host((const float*)w_host, Cout, &Cin, 1, taps, pk.data());
   DevTmp tmp;
   std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
@@ -140,6 +149,12 @@ extern "C" int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void
   L.tile_variant = tile_variant;
   L.zmode = zmode;
   L.flags = up2 ? EPI_UP2 : 0;
+  TV res;
+  if (res_cb8) {
+    res = view_cb8(const_cast<void*>(res_cb8), N, Cout, Zout, res_half ? So / 2 : So, res_half ? So / 2 : So);
+    L.res = &res;
+    L.res_half = res_half ? 1 : 0;
+  }
   return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_mfma");
 }
 
