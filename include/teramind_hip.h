@@ -173,6 +173,18 @@ size_t tm_gene_attn_workspace_bytes(const tm_model* m, int B);
 int tm_gene_attn(tm_model* m, const void* rna_dense, int B, void* attn_out, void* rna_mid,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* The pathway read-out of the attention driver (test_attn.py:404-423) without the maps:
+ *   rna_dense [B, gn, gn, 4*500], glst = K host gene indices (1 <= K <= 8, distinct, each in [0, rna_num)) ->
+ *   out [B, 4K, 2*gn*gn] fp32: rows (map 0 | map 1) x middle slice 0 and (map 1 | map 2) x middle slice 1 side by side,
+ *       then map 3 x both middle slices, then the raw counts of the K genes;
+ *   sub [4, B, K, K] fp32 (optional, may be NULL): the K x K blocks attn[:, :, glst][..., glst] of tm_gene_attn's maps.
+ * For the checkpoint geometry (gn^2 * 4 = 64 features, rna_num <= 232) one fused kernel computes only the K query rows of the
+ * logits and no G x G map is written: the workspace is 256 bytes whatever B.  Every other rna_slc = 4 configuration runs the
+ * map kernels over chunks of 8 patches into the workspace (bounded independently of B) and gathers from there. */
+size_t tm_gene_attn_readout_workspace_bytes(const tm_model* m, int B, int K);
+int tm_gene_attn_readout(tm_model* m, const void* rna_dense, int B, const int* glst, int K, void* out, void* sub,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 int tm_model_destroy(tm_model* m);
 
 /* ---- tile I/O either side of the path ----------------------------

@@ -60,6 +60,9 @@ SIGNATURES = {
     "tm_pad_patchify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
     "tm_gene_attn_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "tm_gene_attn": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "tm_gene_attn_readout_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
+    "tm_gene_attn_readout": (c_int, [c_void_p, c_void_p, c_int, C.POINTER(C.c_int), c_int, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
     "tm_model_destroy": (c_int, [c_void_p]),
     "tm_gene_tile_dense": (c_int, [c_void_p, c_void_p, C.c_int64] + [c_int] * 6 + [c_void_p, c_void_p]),
     "tm_blosc_decompress": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, C.POINTER(c_size_t)]),

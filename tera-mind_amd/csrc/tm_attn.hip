@@ -548,6 +548,234 @@ hipError_t launch_rna_mid(const float* rna, int B, int gn, int zs, int G, float*
 }
 
 // ==========================================================================================
+// Pathway read-out without the maps (attention driver, test_attn.py:404-423 on model/unet_attn.py:143-173).
+// The driver keeps, of each of the four softmax maps, the K x K block of the pathway genes `glst` and
+// contracts it with their counts.  gene_readout_kernel computes exactly that per patch, one workgroup per
+// patch, and never forms a G x G map:
+//   * the pre-norm q is linear in the token's z slices, so ONE pass of Wq over the tokens yields the four
+//     per-slice partial products part_z (MFMA, K range = the slice's 16 features), and the q of map i is
+//     part_i + part_{i+1} + bq (maps 0..2: slices outside [i, i+2) zeroed) or sum_z part_z + bq (map 3);
+//   * k = q, so only the K query rows of the logits are needed: every key's qn_i (registers, transposed:
+//     lane = gene, rows = features) is dotted with the K query vectors qn_i[glst[k]] (LDS broadcast);
+//   * fp32 softmax over all G keys (max-subtracted, expf, division), the K selected columns are kept.
+// The summation order of q differs from gene_attn_mfma_kernel (slice partials are added after their chains
+// instead of one chain over 64 features); both are fp32 fma chains, see tests/test_gpu_attn_readout.py.
+// ==========================================================================================
+#define RO_KMAX 8
+#define RO_LGP 256                                       // logit row pitch (keys padded to 8 tiles of 32)
+struct ReadoutArgs {
+  const float* rna; int B, G, K;
+  int glst[RO_KMAX];
+  const float *wq_t, *bq, *qnorm;
+  float* out;                                            // [B][4K][2 * 16]
+  float* sub;                                            // [4][B][K][K] or null
+};
+// LDS floats: wq 4096 | bq 64 | qnorm 64 | tsel [8][64] | psel [4][8][64] | qsel [4][8][64] | lg [32][256] | subs [4][8][8]
+#define RO_LDS_FLOATS (4096 + 128 + 512 + 2048 + 2048 + 32 * RO_LGP + 256)
+
+// out rows: slice-pair products (maps 0,1 x middle slice 0 | maps 1,2 x middle slice 1), ensemble product, raw counts;
+// tmid(g, col) = count of selected gene g at middle-slice column col = s * gg + hw
+template <typename F>
+__device__ __forceinline__ void readout_contract(const float* subs, int K, int gg, float* out_n, F&& tmid) {
+  const int cols = 2 * gg;
+  for (int idx = threadIdx.x; idx < 4 * K * cols; idx += blockDim.x) {
+    const int row = idx / cols, col = idx - row * cols;
+    const int blk = row / K, c = row - blk * K;
+    float v;
+    if (blk == 3) {
+      v = tmid(c, col);
+    } else {
+      const int map = (blk == 2) ? 3 : blk + (col >= gg ? 1 : 0);
+      const float* sr = subs + (map * K + c) * K;
+      v = 0.f;
+      for (int g = 0; g < K; ++g) v = fmaf(sr[g], tmid(g, col), v);
+    }
+    out_n[idx] = v;
+  }
+}
+
+// two workgroups per CU (234 VGPRs, 69 KB of LDS each): one workgroup's load and softmax phases overlap the other's MFMA pass
+__global__ __launch_bounds__(256, 2) void gene_readout_kernel(ReadoutArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* wq = sm;                        // [64 in][64 out]
+  float* cst = wq + 4096;                // bq 64 | qnorm 64
+  float* tsel = cst + 128;               // [K][64]   tokens of the selected genes
+  float* psel = tsel + 512;              // [4 z][K][64] their per-slice partial q
+  float* qsel = psel + 2048;             // [4 maps][K][64] their qn per map
+  float* lg = qsel + 2048;               // [4 maps * K][RO_LGP] logits of the K query rows
+  float* subs = lg + 32 * RO_LGP;        // [4][K][K]
+  const int G = a.G, K = a.K;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+  const int n = blockIdx.x;
+  const float* rna = a.rna + (long)n * 16 * 4 * 500;     // [hw 16][z 4][500]
+  for (int i = tid; i < 1024; i += 256) ((f32x4*)wq)[i] = ((const f32x4*)a.wq_t)[i];
+  if (tid < 64) { cst[tid] = a.bq[tid]; cst[64 + tid] = a.qnorm[tid]; }
+  for (int i = tid; i < K * 64; i += 256) {
+    const int k = i >> 6, d = i & 63;
+    tsel[i] = rna[((d & 15) * 4 + (d >> 4)) * 500 + a.glst[k]];
+  }
+  __syncthreads();
+  // ---- (A1) per-slice partial q of the K query genes: wave = slice z, lane = output feature j ----
+  for (int k = 0; k < K; ++k) {
+    float acc = 0.f;
+#pragma unroll
+    for (int hw = 0; hw < 16; ++hw) acc = fmaf(tsel[k * 64 + 16 * wv + hw], wq[(16 * wv + hw) * 64 + lane], acc);
+    psel[(wv * K + k) * 64 + lane] = acc;
+  }
+  __syncthreads();
+  // ---- (A2) qn of the query genes: wave = map i, lane = feature j ----
+  {
+    const int lo = (wv < 3) ? wv : 0, hi = (wv < 3) ? wv + 2 : 4;
+    for (int k = 0; k < K; ++k) {
+      float q = 0.f;
+      for (int z = lo; z < hi; ++z) q += psel[(z * K + k) * 64 + lane];
+      q += cst[lane];
+      const float rstd = 1.0f / sqrtf(wave_sum(q * q) * (1.0f / 64) + TM_EPS);
+      qsel[(wv * K + k) * 64 + lane] = cst[64 + lane] * (q * rstd);
+    }
+  }
+  __syncthreads();
+  // ---- (B) all keys: part_z^T[j][g] on MFMA, then per map qn (registers) . the K query vectors ----
+  const int ntile = (G + 31) >> 5;
+  for (int gt = wv; gt < ntile; gt += 4) {
+    const int g = gt * 32 + i32;
+    const bool gok = g < G;
+    float tv[4][8];                                       // this lane's token features d = 16 z + 2 s + h
+#pragma unroll
+    for (int z = 0; z < 4; ++z)
+#pragma unroll
+      for (int s = 0; s < 8; ++s) tv[z][s] = gok ? rna[((2 * s + h) * 4 + z) * 500 + g] : 0.f;
+    f32x16 P[4][2];
+#pragma unroll
+    for (int z = 0; z < 4; ++z)
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) P[z][jt][r] = 0.f;
+#pragma unroll
+    for (int z = 0; z < 4; ++z) {
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const float* wrow = wq + (16 * z + 2 * s + h) * 64 + i32;
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt) P[z][jt] = __builtin_amdgcn_mfma_f32_32x32x2f32(wrow[jt * 32], tv[z][s], P[z][jt], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float qn[2][16];
+      float ss = 0.f;
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float q = (i < 3) ? P[i][jt][r] + P[i + 1][jt][r] : (P[0][jt][r] + P[1][jt][r]) + (P[2][jt][r] + P[3][jt][r]);
+          q += cst[jt * 32 + mfma_row(r, h)];
+          qn[jt][r] = q;
+          ss = fmaf(q, q, ss);
+        }
+      ss += __shfl_xor(ss, 32, 64);
+      const float rstd = 1.0f / sqrtf(ss * (1.0f / 64) + TM_EPS);
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) qn[jt][r] = cst[64 + jt * 32 + mfma_row(r, h)] * (qn[jt][r] * rstd);
+      for (int k = 0; k < K; ++k) {
+        const float* qs = qsel + (i * K + k) * 64 + 4 * h;
+        float dot = 0.f;
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+          for (int q4 = 0; q4 < 4; ++q4) {
+            const f32x4 qv = *(const f32x4*)(qs + jt * 32 + 8 * q4);      // features mfma_row(4 q4 .. 4 q4 + 3, h)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) dot = fmaf(qn[jt][4 * q4 + c], qv[c], dot);
+          }
+        dot += __shfl_xor(dot, 32, 64);
+        if (h == 0 && gok) lg[(i * K + k) * RO_LGP + g] = dot * 0.015625f;   // (q*scale).k*scale, scale = 1/8
+      }
+    }
+  }
+  __syncthreads();
+  // ---- (C) softmax of the 4K query rows over all G keys, K selected columns kept ----
+  for (int row = wv; row < 4 * K; row += 4) {
+    const float* lr = lg + row * RO_LGP;
+    float v[4];
+    float m = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { const int u = lane + 64 * c; v[c] = (u < G) ? lr[u] : -INFINITY; m = fmaxf(m, v[c]); }
+    m = wave_max(m);
+    float ssum = 0.f;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ssum += (lane + 64 * c < G) ? expf(v[c] - m) : 0.f;
+    ssum = wave_sum(ssum);
+    if (lane < K) {
+      const float p = expf(lr[a.glst[lane]] - m) / ssum;
+      subs[row * K + lane] = p;
+      if (a.sub) { const int i = row / K, k = row - i * K; a.sub[(((long)i * a.B + n) * K + k) * K + lane] = p; }
+    }
+  }
+  __syncthreads();
+  // ---- (D) contraction with the counts of the two middle slices (features 16 .. 47 of a token) ----
+  readout_contract(subs, K, 16, a.out + (long)n * 4 * K * 32, [&](int g, int col) { return tsel[g * 64 + 16 + col]; });
+}
+
+hipError_t launch_gene_readout(const float* rna, int B, int gn, int zs, int G, const GeneW& w, const int* glst, int K,
+                               float* out, float* sub, hipStream_t s) {
+  if (gn != 4 || zs != 4 || G < 1 || G > GROWS || K < 1 || K > RO_KMAX) return hipErrorInvalidValue;
+  ReadoutArgs a;
+  a.rna = rna; a.B = B; a.G = G; a.K = K;
+  for (int k = 0; k < RO_KMAX; ++k) a.glst[k] = k < K ? glst[k] : 0;
+  a.wq_t = w.wq_t; a.bq = w.bq; a.qnorm = w.qnorm; a.out = out; a.sub = sub;
+  const size_t lds = (size_t)RO_LDS_FLOATS * sizeof(float);
+  static DevOnce attr;
+  if (attr.need()) {
+    hipError_t e = hipFuncSetAttribute((const void*)gene_readout_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    attr.mark();
+  }
+  hipLaunchKernelGGL(gene_readout_kernel, dim3(B), dim3(256), lds, s, a);
+  return hipGetLastError();
+}
+
+// Finish of the read-out for the geometries without the fused kernel: the four maps of a batch chunk were written by the
+// map kernels into maps [4][Bc][G][G]; gather the K x K blocks and contract.  One workgroup per patch of the chunk.
+struct ReadoutGatherArgs {
+  const float* maps; const float* rna; int Bc, G, K, gn, zs;
+  int glst[RO_KMAX];
+  const int* gidx;
+  float* out;                                            // chunk base, [Bc][4K][2 gn gn]
+  float* sub; long sub_map_stride;                       // chunk base of [4][B][K][K] (stride between maps) or null
+};
+__global__ __launch_bounds__(256) void gene_readout_gather_kernel(ReadoutGatherArgs a) {
+  __shared__ float subs[4 * RO_KMAX * RO_KMAX];
+  const int n = blockIdx.x, K = a.K, G = a.G, gg = a.gn * a.gn;
+  for (int i = threadIdx.x; i < 4 * K * K; i += blockDim.x) {
+    const int map = i / (K * K), r = i - map * K * K, k = r / K, c = r - k * K;
+    const float p = a.maps[(((long)map * a.Bc + n) * G + a.glst[k]) * G + a.glst[c]];
+    subs[i] = p;
+    if (a.sub) a.sub[map * a.sub_map_stride + (long)n * K * K + r] = p;
+  }
+  __syncthreads();
+  const float* rna = a.rna + (long)n * gg * a.zs * 500;
+  readout_contract(subs, K, gg, a.out + (long)n * 4 * K * 2 * gg, [&](int g, int col) {
+    const int s = col / gg, hw = col - s * gg, slot = a.gidx ? a.gidx[a.glst[g]] : a.glst[g];
+    return rna[((long)hw * a.zs + 1 + s) * 500 + slot];
+  });
+}
+hipError_t launch_gene_readout_gather(const float* maps, const float* rna, int Bc, int gn, int zs, int G, const int* gidx,
+                                      const int* glst, int K, float* out, float* sub, long sub_map_stride, hipStream_t s) {
+  if (K < 1 || K > RO_KMAX || zs != 4) return hipErrorInvalidValue;
+  ReadoutGatherArgs a;
+  a.maps = maps; a.rna = rna; a.Bc = Bc; a.G = G; a.K = K; a.gn = gn; a.zs = zs; a.gidx = gidx;
+  for (int k = 0; k < RO_KMAX; ++k) a.glst[k] = k < K ? glst[k] : 0;
+  a.out = out; a.sub = sub; a.sub_map_stride = sub_map_stride;
+  hipLaunchKernelGGL(gene_readout_gather_kernel, dim3(Bc), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// ==========================================================================================
 // Windowed gene-patch cross attention core (Attention.forward with n_h=2, one head:
 // model/MBAblocks.py:555-595): per (patch, window) RMSNorm(q), RMSNorm(k) over C,
 // softmax(q.k^T / C) . v.  One workgroup per (patch, window); T = tokens per window.

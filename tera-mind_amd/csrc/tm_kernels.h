@@ -240,6 +240,13 @@ size_t gene_generic_ws_floats(int G, int D);
 hipError_t launch_gene_attn_generic(const float* rna, int B, int gn, int zs, int G, int D, const GeneW& w, const int* gidx,
                                     float* out_tok, float* attn_map, int zmask_lo, int zmask_hi, float* ws, hipStream_t s);
 hipError_t launch_rna_mid(const float* rna, int B, int gn, int zs, int G, float* out, hipStream_t s);
+// pathway read-out (attention driver): out [B][4K][2 gn gn], sub [4][B][K][K] or null; glst = K host gene indices.
+// launch_gene_readout: fused, no map is formed (gn = 4, zs = 4, G <= 232); launch_gene_readout_gather finishes a batch chunk whose
+// four maps [4][Bc][G][G] the map kernels wrote (out / sub / rna point at the chunk)
+hipError_t launch_gene_readout(const float* rna, int B, int gn, int zs, int G, const GeneW& w, const int* glst, int K,
+                               float* out, float* sub, hipStream_t s);
+hipError_t launch_gene_readout_gather(const float* maps, const float* rna, int Bc, int gn, int zs, int G, const int* gidx,
+                                      const int* glst, int K, float* out, float* sub, long sub_map_stride, hipStream_t s);
 
 // ---- windowed cross attention core -----------------------------------------------------
 // q, k, v: CB8 token tensors (tokens = voxels (z h w)); n_h x n_h windows over (H, W).

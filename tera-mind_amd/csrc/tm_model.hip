@@ -1611,3 +1611,52 @@ extern "C" int tm_gene_attn(tm_model* m, const void* rna_dense, int B, void* att
   if (rna_mid) HIP_TRY(launch_rna_mid((const float*)rna_dense, B, m->gn, zs, G, (float*)rna_mid, s));
   return TM_OK;
 }
+
+// Patches per chunk of the read-out on the geometries without the fused kernel: bounds the map scratch (4 maps of a chunk) and
+// the generic kernel's slabs independently of B
+static const int RO_CHUNK = 8;
+
+extern "C" size_t tm_gene_attn_readout_workspace_bytes(const tm_model* m, int B, int K) {
+  if (!m || B < 1 || m->gene_mfma) return 256;
+  const size_t bc = (size_t)(B < RO_CHUNK ? B : RO_CHUNK), G = (size_t)m->cfg.rna_num;
+  return 256 + (4 * bc * G * G + bc * gene_generic_split((int)bc) * gene_generic_ws_floats(m->cfg.rna_num, m->D)) * sizeof(float);
+}
+
+extern "C" int tm_gene_attn_readout(tm_model* m, const void* rna_dense, int B, const int* glst, int K, void* out, void* sub,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  if (!m || !rna_dense || !glst || !out || B < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (!m->finalized) return fail(TM_ERR_STATE, "tm_model_finalize has not been called");
+  const tm_config& c = m->cfg;
+  const int G = c.rna_num, zs = c.rna_slc, gg = m->gn * m->gn;
+  if (zs != 4) return fail(TM_ERR_ARG, "the attention-map read-out is defined for rna_slc = 4 (three slice pairs, model/unet_attn.py:162-172)");
+  if (K < 1 || K > 8) return fail(TM_ERR_ARG, "read-out gene list length K = %d outside [1, 8]", K);
+  for (int k = 0; k < K; ++k) {
+    if (glst[k] < 0 || glst[k] >= G) return fail(TM_ERR_ARG, "read-out gene index glst[%d] = %d outside [0, %d)", k, glst[k], G);
+    for (int j = 0; j < k; ++j)
+      if (glst[j] == glst[k]) return fail(TM_ERR_ARG, "read-out gene index %d is repeated (glst[%d] and glst[%d])", glst[k], j, k);
+  }
+  const size_t need = tm_gene_attn_readout_workspace_bytes(m, B, K);
+  if (workspace_bytes < need || (!m->gene_mfma && !workspace)) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  const float* rna = (const float*)rna_dense;
+  hipStream_t s = (hipStream_t)stream;
+  if (m->gene_mfma) {
+    HIP_TRY(launch_gene_readout(rna, B, m->gn, zs, G, m->gene, glst, K, (float*)out, (float*)sub, s));
+    return TM_OK;
+  }
+  // other geometries: the map kernels over chunks of RO_CHUNK patches into the bounded scratch, then gather-and-contract
+  const int bc = B < RO_CHUNK ? B : RO_CHUNK;
+  float* maps = (float*)workspace;
+  float* gws = maps + (size_t)4 * bc * G * G;
+  for (int n0 = 0; n0 < B; n0 += bc) {
+    const int nb = B - n0 < bc ? B - n0 : bc;
+    const float* rc = rna + (size_t)n0 * gg * zs * 500;
+    for (int i = 0; i < 4; ++i) {
+      const int lo = (i < 3) ? i : 0, hi = (i < 3) ? i + 2 : zs;
+      HIP_TRY(launch_gene_attn_generic(rc, nb, m->gn, zs, G, m->D, m->gene, m->gene_idx, nullptr, maps + (size_t)i * nb * G * G,
+                                       lo, hi, gws, s));
+    }
+    HIP_TRY(launch_gene_readout_gather(maps, rc, nb, m->gn, zs, G, m->gene_idx, glst, K, (float*)out + (size_t)n0 * 4 * K * 2 * gg,
+                                       sub ? (float*)sub + (size_t)n0 * K * K : nullptr, (long)B * K * K, s));
+  }
+  return TM_OK;
+}

@@ -129,9 +129,10 @@ def read_zarr_zip(path) -> np.ndarray:
     return out
 
 
-def write_zarr_zip(path, arr: np.ndarray, compressor: Optional[str] = None, level: int = 1):
+def write_zarr_zip(path, arr: np.ndarray, compressor: Optional[str] = None, level: int = 1, date_time=None):
     """A single-chunk zarr-v2 array in a ZIP_STORED ZipStore (the layout zarr.save_array produces, with the
-    chunk either raw or zlib-compressed so that no Blosc encoder is needed)."""
+    chunk either raw or zlib-compressed so that no Blosc encoder is needed).  date_time: a fixed
+    (y, m, d, H, M, S) for the members instead of the clock, for files that must be reproducible byte for byte."""
     arr = np.ascontiguousarray(arr)
     if compressor not in (None, "zlib"):
         raise NotImplementedError("writer supports compressor None or 'zlib'")
@@ -142,9 +143,16 @@ def write_zarr_zip(path, arr: np.ndarray, compressor: Optional[str] = None, leve
     if compressor == "zlib":
         payload = zlib.compress(payload, level)
     tmp = str(path) + ".tmp"
+    def member(name):
+        if date_time is None:
+            return name
+        zi = zipfile.ZipInfo(name, date_time=tuple(date_time))
+        zi.compress_type, zi.external_attr = zipfile.ZIP_STORED, 0o600 << 16
+        return zi
+
     with zipfile.ZipFile(tmp, "w", compression=zipfile.ZIP_STORED, allowZip64=True) as z:
-        z.writestr(".zarray", json.dumps(meta, indent=4, sort_keys=True))
-        z.writestr(".".join("0" for _ in arr.shape) if arr.ndim else "0", payload)
+        z.writestr(member(".zarray"), json.dumps(meta, indent=4, sort_keys=True))
+        z.writestr(member(".".join("0" for _ in arr.shape) if arr.ndim else "0"), payload)
     os.replace(tmp, path)                                  # a reader never sees a half-written tile
 
 

@@ -61,3 +61,27 @@ def save_slices(mosaic, odir, names: Optional[Sequence[int]] = None, jpeg: bool 
         im.save(os.path.join(str(odir), f"all_{sl}.tif"))
         if jpeg:
             im.save(os.path.join(str(odir), f"all_{sl}.jpg"))
+
+
+# ---- attention read-out tiles (infer_attn.py:9-39) -----------------------------------------------------------
+def stitch_attn_dir(adir, hst: int, wst: int, hnm: int, wnm: int, size: int = tiles.TILE) -> np.ndarray:
+    """Mosaic of a directory of attention read-out tiles ('{r0}_{r1}_{c0}_{c1}.zip', float16 [50, 4K, 16, 16] each) ->
+    float16 [50, 4K, hnm*16, wnm*16]: `gen_col` concatenates the tiles of a tile column on axis -2, `gen_mba` joins the
+    columns on axis -1."""
+    cols = []
+    for pw in range(wnm):
+        col = []
+        for ph in range(hnm):
+            r0, c0 = hst + ph * size, wst + pw * size
+            col.append(formats.read_zarr_zip(os.path.join(str(adir), f"{r0}_{r0 + size}_{c0}_{c0 + size}.zip")))
+        cols.append(np.concatenate(col, -2))
+    return np.concatenate(cols, -1)
+
+
+def save_attn_slices(mosaic, odir, names: Optional[Sequence[int]] = None):
+    """'{odir}/all_{sl}.zip' per slice (zarr v2), the files infer_attn.gen_mba leaves (infer_attn.py:36-38)."""
+    os.makedirs(str(odir), exist_ok=True)
+    arr = mosaic.cpu().numpy() if isinstance(mosaic, torch.Tensor) else np.asarray(mosaic)
+    for k in range(arr.shape[0]):
+        sl = k if names is None else names[k]
+        formats.write_zarr_zip(os.path.join(str(odir), f"all_{sl}.zip"), arr[k])

@@ -297,6 +297,28 @@ class GeneAttnModel(_HipModel):
                                             _lib.ptr(ws), ws.numel(), _lib.current_stream_ptr()), "tm_gene_attn")
         return attn, mid
 
+    def readout(self, rna, glst, want_sub=False):
+        """The pathway read-out of the attention driver for the gene indices `glst` (1 <= K <= 8) without the maps:
+        rna [B, gn, gn, 4*500] -> out [B, 4K, 2*gn*gn] fp32, the tensor attn_maps.pathway_readout(*self(rna=rna), glst) returns
+        (tm_gene_attn_readout).  want_sub: also the K x K blocks attn[:, :, glst][..., glst] as sub [4, B, K, K]."""
+        if not self._finalized:
+            raise RuntimeError("load_state_dict() must be called before readout")
+        rna_d = densify_rna(rna, self.device)
+        B, gn = rna_d.shape[0], self.conf.gn_sz
+        zs = self.conf.rna_slc
+        if tuple(rna_d.shape) != (B, gn, gn, zs * 500):
+            raise ValueError(f"rna has shape {tuple(rna_d.shape)}, expected {(B, gn, gn, zs * 500)}")
+        g = [int(v) for v in glst]
+        K = len(g)
+        out = torch.empty((B, 4 * K, 2 * gn * gn), dtype=torch.float32, device=self.device)
+        sub = torch.empty((4, B, K, K), dtype=torch.float32, device=self.device) if want_sub else None
+        gl = (C.c_int * max(1, K))(*g)
+        with torch.cuda.device(self.device):
+            ws = self._workspace(self._L.tm_gene_attn_readout_workspace_bytes(self._h, B, K))
+            _lib.check(self._L.tm_gene_attn_readout(self._h, _lib.ptr(rna_d), B, gl, K, _lib.ptr(out), _lib.ptr(sub),
+                                                    _lib.ptr(ws), ws.numel(), _lib.current_stream_ptr()), "tm_gene_attn_readout")
+        return (out, sub) if want_sub else out
+
 
 def make_model(conf: PathConfig, device="cuda:0", state_dict=None, vis_only=False):
     m = (GeneAttnModel if vis_only else BeatGANsUNetModel)(conf, device)
