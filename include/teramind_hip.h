@@ -199,6 +199,36 @@ int tm_model_destroy(tm_model* m);
 int tm_gene_tile_dense(const int32_t* crd, const void* dat, int64_t nnz, int gblk, int shift_h, int shift_w,
                        int gsz, int chan_in, int zpad_ch, void* out, void* stream);
 
+/* ---- training batches from resident tiles (utils/MBADataset.py:69-170, experiment.py:129) ----
+ * One descriptor per sample: the tile it is cut from, the crop corner in pixels, the first slice of its z window (in slices
+ * of the stack padded by spad = {1:0, 4:1, 8:1, 16:3}[snum] each side), `rot` quarter turns (0..3) and `flip` (0 / 1).
+ * Both calls take the descriptors twice: `desc` is the device array the kernels read, `desc_host` the same values in host
+ * memory, checked (tile index, crop inside the tile, snm, rot, flip ranges) before anything is launched.  Both are
+ * asynchronous on `stream` and return TM_ERR_ARG with a tm_last_error() text on a bad argument.  n_tiles tiles of
+ * [H, W] pixels and zt slices (50 in the data). */
+typedef struct tm_train_sample {
+  int32_t tile, top, left, snm, rot, flip;
+} tm_train_sample;
+
+/* MBADataset._getimg + the image half of _trans + `im / 127.5 - 1`:
+ *   img  uint8 (img_dtype 0) or float16 (1), device, [n_tiles][2 * zt][H][W], channel order (stain, z)
+ *   out  fp32 [B][C][sdim][sdim], C = (stain == 0 ? 2 : 1) * nz, nz = snum - 2 * (snum / 4) for snum > 1, 1 for snum = 1
+ *   stain 0 = all, 1 = DAPI, 2 = PolyT.   out = hflip^flip(rot90^rot(window of the crop)) / 127.5 - 1, the division a
+ *   correctly rounded fp32 division (bit-equal to torch); slices that fall in the z padding are 0 before scaling. */
+int tm_train_batch_images(const void* img, int img_dtype, int n_tiles, int zt, int H, int W, const tm_train_sample* desc,
+                          const tm_train_sample* desc_host, int B, int sdim, int snum, int stain, void* out, void* stream);
+
+/* MBADataset._getgene + the gene half of _trans + _to_sparse(pad = pdim) + sparse_coo_tensor(...).to_dense():
+ *   crd  int32 [3][nnz] device: (h, w, slice * 500 + gene) of ALL tiles' COO entries, tile after tile, each tile's entries
+ *        ordered by h;   dat fp32 [nnz] device: counts
+ *   tile_base  int64 [n_tiles + 1] device: first entry of each tile;   row_start int32 [n_tiles][H + 1] device: first
+ *        entry of each pixel row, relative to the tile's base (so a sample reads rows [top, top + sdim) only)
+ *   out  fp32 [B][gs + 2 pdim][gs + 2 pdim][snum * 500], gs = sdim / gblk: zero-filled by the call, then one atomic add per
+ *        entry inside the crop and the slice window.  Counts are integers: the result does not depend on the add order. */
+int tm_train_batch_genes(const int32_t* crd, const void* dat, int64_t nnz, const int64_t* tile_base, const int32_t* row_start,
+                         int n_tiles, int zt, int H, int W, const tm_train_sample* desc, const tm_train_sample* desc_host,
+                         int B, int sdim, int gblk, int pdim, int snum, void* out, void* stream);
+
 /* Host-side decoder of one Blosc-1 frame (lz4 codec, optional byte shuffle): the chunk encoding zarr 2.14.1 /
  * numcodecs 0.15.0 use by default for the state tiles the reference writes with zarr.save_array
  * (test_brn.py:225) and reads back with zarr.load (utils/MBADataset_tst.py:60, infer_brn.py:76).

@@ -65,6 +65,9 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     "tm_model_destroy": (c_int, [c_void_p]),
     "tm_gene_tile_dense": (c_int, [c_void_p, c_void_p, C.c_int64] + [c_int] * 6 + [c_void_p, c_void_p]),
+    "tm_train_batch_images": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p]),
+    "tm_train_batch_genes": (c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p] +
+                             [c_int] * 5 + [c_void_p, c_void_p]),
     "tm_blosc_decompress": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, C.POINTER(c_size_t)]),
     "tm_profile_enable": (c_int, [c_void_p, c_int]),
     "tm_profile_collect": (c_int, [c_void_p, C.POINTER(TmProfStats)]),

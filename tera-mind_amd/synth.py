@@ -65,3 +65,49 @@ def write_gene_tile_dir(gdir, hnm: int, wnm: int, nnz_per_block: int, hst: int =
                 data = np.concatenate([data, np.array([1], dtype=np.uint16)])
             v = (r * 256, r * 256 + 256, c * 256, c * 256 + 256, r * 256 - 128, r * 256 + 384, c * 256 - 128, c * 256 + 384)
             formats.write_gene_npz(os.path.join(gdir, "_".join(map(str, v)) + ".npz"), data, crd, (512, 512, chan))
+
+
+def image_tile(tag: str, shape, seed: int = 0, dtype=np.uint8) -> np.ndarray:
+    """A stain-image tile [(s z), H, W] of hashed integers 0..255 (uint8, or the same values as float16): a pure function of
+    (tag, seed), so that fixtures recorded from it need not store it."""
+    n = int(np.prod(shape))
+    v = np.floor((hashed_uniform(tag, n, seed) + 1.0) * 128.0).clip(0, 255)
+    return v.astype(dtype).reshape(shape)
+
+
+def train_gene_tile(tag: str, H: int, W: int, zt: int, nnz: int, seed: int = 0):
+    """One training gene tile as the reference stores it (utils/MBADataset.py:70: `sparse.load_npz` of a COO [H, W, zt * 500]
+    of uint16 counts): (data, coords int64 [3, nnz], shape), a tenth of the coordinates repeated."""
+    rng = np.random.default_rng([seed, zlib_crc(tag)])
+    crd = np.stack([rng.integers(0, H, nnz), rng.integers(0, W, nnz), rng.integers(0, zt * 500, nnz)]).astype(np.int64)
+    k = nnz // 10
+    crd[:, :k] = crd[:, k:2 * k]
+    return rng.integers(1, 4, nnz).astype(np.uint16), crd, (H, W, zt * 500)
+
+
+def zlib_crc(tag: str) -> int:
+    import zlib
+    return zlib.crc32(tag.encode())
+
+
+def write_train_tile_dir(root, n_tiles: int = 2, H: int = 512, W: int = 512, zt: int = 50, nnz: int = 200000, seed: int = 0,
+                         img_dtype=np.uint8):
+    """A synthetic training set in the reference's file layout: `<root>/gene/tile_XXXX.npz` (pydata/sparse COO archive) and
+    `<root>/img/tile_XXXX.zip` (zarr-v2 array [(s z) = 2 zt, H, W]), paired by MBADataset.py:101's path rule.
+    Returns the gene paths."""
+    import os
+    from . import formats
+    gdir, idir = os.path.join(str(root), "gene"), os.path.join(str(root), "img")
+    if "gene" in str(root):
+        raise ValueError("the root path must not contain 'gene' (the image path rule replaces every occurrence)")
+    os.makedirs(gdir, exist_ok=True)
+    os.makedirs(idir, exist_ok=True)
+    paths = []
+    for i in range(n_tiles):
+        data, crd, shape = train_gene_tile(f"train_tile/{i}", H, W, zt, nnz, seed)
+        p = os.path.join(gdir, f"tile_{i:04d}.npz")
+        formats.write_gene_npz(p, data, crd, shape)
+        formats.write_zarr_zip(os.path.join(idir, f"tile_{i:04d}.zip"), image_tile(f"train_tile/{i}/img", (2 * zt, H, W), seed, img_dtype),
+                               compressor="zlib")
+        paths.append(p)
+    return paths

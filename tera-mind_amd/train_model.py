@@ -521,7 +521,8 @@ def training_loss_and_grads(net: UNetTrain, sampler, x_start, r_start, t, loss_m
     restated forward-only in diffusion.SpacedDiffusionBeatGans.training_losses) + the backward of the whole model.
     dropout_p: the ResBlock dropout probability (None: keep the net's own, `UNetTrain(dropout_p=...)`, 0 unless set; a value
     is stored on the net); dropout_key: the 64-bit mask key of this evaluation (derive_dropout_key gives one per step and
-    micro-batch).  Returns (loss, grads)."""
+    micro-batch).  r_start: the reference's COO triple (dat, crd, ssz), or the same genes as a dense device tensor
+    [b, gh, gw, C] (both give the same loss and the same gradient bits).  Returns (loss, grads)."""
     from .diffusion import sparse_repatch
     from .unet import densify_rna
     dev = net.dev
@@ -530,15 +531,26 @@ def training_loss_and_grads(net: UNetTrain, sampler, x_start, r_start, t, loss_m
     t = t.to(dev).long()
     x_t = sampler.q_sample(x_start, t.repeat_interleave(x_start.shape[0] // t.shape[0]), noise) * loss_mask
     ix, iy = crop_index
-    dat, crd, ssz = r_start
-    r_size = patch_size // (x_start.shape[2] // ssz[1])
-    crd = crd.long()
-    keep = (ix * r_size <= crd[1]) & (crd[1] < (ix + 2) * r_size) & (iy * r_size <= crd[2]) & (crd[2] < (iy + 2) * r_size)
-    dat, crd = dat[keep], crd[:, keep].clone()
-    crd[1] -= ix * r_size
-    crd[2] -= iy * r_size
-    dat2, crd2, ssz2 = sparse_repatch((dat, crd, (ssz[0], 2 * r_size, 2 * r_size, ssz[-1])), r_size)
-    rna = densify_rna((dat2, crd2, ssz2), dev)
+    if torch.is_tensor(r_start):
+        # dense genes [b, gh, gw, C] on the device (dataset.TrainBatch.rna): the crop to the 2 x 2-patch window and the
+        # 'b (p1 h) (p2 w) c -> (b p1 p2) h w c' re-patching are a slice and a reshape
+        if r_start.dim() != 4:
+            raise ValueError(f"dense r_start must be [b, gh, gw, C], got {tuple(r_start.shape)}")
+        r_size = patch_size // (x_start.shape[2] // r_start.shape[1])
+        win = r_start.to(dev)[:, ix * r_size:(ix + 2) * r_size, iy * r_size:(iy + 2) * r_size]
+        b0, ch = win.shape[0], win.shape[-1]
+        rna = win.reshape(b0, 2, r_size, 2, r_size, ch).permute(0, 1, 3, 2, 4, 5).reshape(b0 * 4, r_size, r_size, ch)
+        rna = rna.to(torch.float32).contiguous()
+    else:
+        dat, crd, ssz = r_start
+        r_size = patch_size // (x_start.shape[2] // ssz[1])
+        crd = crd.long()
+        keep = (ix * r_size <= crd[1]) & (crd[1] < (ix + 2) * r_size) & (iy * r_size <= crd[2]) & (crd[2] < (iy + 2) * r_size)
+        dat, crd = dat[keep], crd[:, keep].clone()
+        crd[1] -= ix * r_size
+        crd[2] -= iy * r_size
+        dat2, crd2, ssz2 = sparse_repatch((dat, crd, (ssz[0], 2 * r_size, 2 * r_size, ssz[-1])), r_size)
+        rna = densify_rna((dat2, crd2, ssz2), dev)
     sl = (slice(None), slice(None), slice(ix * patch_size, (ix + 2) * patch_size), slice(iy * patch_size, (iy + 2) * patch_size))
 
     def tiles2(a):

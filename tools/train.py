@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Trains the patch UNet from a directory of tiles (reference train.py:9-39 -> experiment.py:121-219, 458-461) on one GPU:
+resident tiles, batches drawn on the device, gradient accumulation to 64 samples per optimizer step (config_parm.py:45),
+clip + Adam, a checkpoint every --save_every steps and at the end.  One JSON line per optimizer step.
+
+    python tools/make_train_tiles.py --out /tmp/tiles
+    python tools/train.py --data /tmp/tiles/gene --out /tmp/run --steps 2 --batch_size 2
+
+--ckpt: a checkpoint written by this tool (the run continues where it stopped, bit for bit) or any reference checkpoint
+(its weights are loaded, the optimizer starts fresh)."""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import teramind_amd  # noqa: E402,F401
+from teramind_amd.config import prep_config_parm  # noqa: E402
+from teramind_amd.dataset import TrainTileSet  # noqa: E402
+from teramind_amd.trainer import Trainer, load_checkpoint  # noqa: E402
+from teramind_amd.weights import hashed_state_dict, strip_lightning_state_dict  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch_size", "-b", type=int, default=32)
+    ap.add_argument("--patch_size", "-ps", type=int, default=64)
+    ap.add_argument("--rna_slc", type=int, choices=(1, 4), default=4, help="UNetTrain covers rna_slc 1 and 4")
+    ap.add_argument("--mouse", default="638850", choices=["609882", "609889", "638850"])
+    ap.add_argument("--stain", default="all", choices=["DAPI", "PolyT", "all"])
+    ap.add_argument("--data", required=True, help="directory of gene .npz tiles (images: the same paths with gene -> img, .npz -> .zip)")
+    ap.add_argument("--ckpt", default=None)
+    ap.add_argument("--out", required=True, help="directory for checkpoints")
+    ap.add_argument("--steps", type=int, default=1)
+    ap.add_argument("--save_every", type=int, default=10000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--repeat", type=int, default=10, help="repetitions of the tile list per epoch (MBADataset repeat)")
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    nrna = 500 if a.mouse in ("609882", "609889") else 229
+    cfg = prep_config_parm(a.data, a.batch_size, a.patch_size, 1, a.stain, a.mouse, nrna, a.rna_slc)
+    accum = max(1, 64 // a.batch_size)
+    tiles = TrainTileSet(a.data, cfg, a.device, seed=a.seed, repeat=a.repeat, accum_batches=accum)
+    os.makedirs(a.out, exist_ok=True)
+    if a.ckpt and "hparams" in load_checkpoint(a.ckpt):
+        tr = Trainer.resume(a.ckpt, tiles, cfg)
+    else:
+        state = strip_lightning_state_dict(load_checkpoint(a.ckpt)) if a.ckpt else hashed_state_dict(cfg, a.seed)
+        tr = Trainer(cfg, state, tiles, a.batch_size, accum, a.seed)
+    for _ in range(a.steps):
+        t0 = time.time()
+        info = tr.step()
+        info["seconds"] = round(time.time() - t0, 3)
+        print(json.dumps(info), flush=True)
+        if tr.global_step % a.save_every == 0:
+            tr.save(os.path.join(a.out, f"step_{tr.global_step}.ckpt"))
+    tr.save(os.path.join(a.out, "last.ckpt"))
+
+
+if __name__ == "__main__":
+    main()
