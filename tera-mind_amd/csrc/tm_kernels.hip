@@ -16,6 +16,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 namespace tmk {
 
 // NZI selects the z structure of the k x 3 x 3 kernel:
@@ -210,6 +212,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
 // One workgroup owns an in-plane tile of MV voxels, BOTH output planes and 64 couts.  HALF = 0: 128 voxels, wave = 32 voxels x
 // 64 couts (3 x 2 accumulators); HALF = 1: 64 voxels, wave = 32 voxels x 32 couts (small launches).  Every output element
 // sees the same order in both -- cin block outer, then product, tap, k -- so the two tiles give identical bits.
+typedef int rsrc_words __attribute__((ext_vector_type(4)));     // a buffer descriptor as four SGPRs of an asm statement
+
 template <int HALF, int TW>
 struct ZPGeo {
   static constexpr int MV = HALF ? 64 : 128;                     // in-plane voxels per workgroup (2 MV outputs)
@@ -219,9 +223,7 @@ struct ZPGeo {
   static constexpr int XV = NPB * HR * HC;                       // halo voxels of ONE staged plane
   static constexpr int XPIECES = XV * 2;                         // 16-byte pieces per plane
   static constexpr int PX = (XPIECES + 255) / 256;
-  static constexpr int WFLOATS = 27 * 512;
-  static constexpr int WPIECES = WFLOATS / 4;
-  static constexpr int PW = (WPIECES + 255) / 256;
+  static constexpr int WFLOATS = 27 * 512;                       // three 9-tap slots of the LDS-DMA weight ring
   static constexpr int LDS_BYTES = (WFLOATS + 3 * XV * 8) * 4;  // weights + the planes X0 + X1, X1, X0
 };
 
@@ -266,7 +268,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
     xoff[k] = off;
   }
   const long zplane = (long)S * S * 8;
-  const float* wsrc = a.w + (long)nt * a.Cbi * G::WFLOATS + tid * 4;
 
   // ---- per-lane fragment addresses ----
   const int vt = HALF ? (wv & 1) : wv;                           // 32-voxel tile of this wave
@@ -296,24 +297,54 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.f;
 
-  f32x4 xr[2][G::PX], wr[G::PW];
+  // ---- weights: global -> LDS by LDS-DMA (`buffer_load_dwordx4 ... offen lds`), no staging registers ----
+  // The packed weights of a (cout tile, cin block) ARE the LDS image, product by product, so lw is a ring of three 9-tap slots
+  // (18 432 B = 18 wave-instructions of 1 KiB; wave w issues pieces w, w + 4, ..: five for waves 0 and 1, four for 2 and 3).
+  // Slot p is refilled with product p of the NEXT cin block once every wave has finished product p of this one:
+  //   B0 | X -> LDS | B1 | P1 + pieces of W3(cb) | B2 | P2 + pieces of W1(cb+1) | vmcnt | B3 | P3 + pieces of W2(cb+1)
+  // W1 / W2 of a block are retired by the vmcnt(0) in front of B0 and first read behind B1; W3 has P1 and P2 to land and is
+  // retired by a counted wait in front of B3: at least the four W1 pieces every wave issued behind it may stay in flight.
+  // The pieces are inline asm (M0 = LDS address of the piece, set in the statement that uses it): hipcc does not count them,
+  // so it neither drains them at a barrier nor waits for them in front of the fragment reads of the other slots.
+  const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
+  const unsigned long wbase = (unsigned long)(a.w + (long)nt * a.Cbi * G::WFLOATS);
+  const rsrc_words wrs = {(int)(unsigned)wbase, (int)((wbase >> 32) & 0xffff), a.Cbi * G::WFLOATS * 4, 0x00020000};
+  const int wvo = lane * 16;
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);
+  auto issue_piece = [&](int cb, int p, int k) __attribute__((always_inline)) {
+    const int j = k * 4 + wvu;                                   // piece of the slot: 256 floats
+    if (k < 4 || j < 18) {
+      unsigned keep;
+      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                   : "=&s"(keep)
+                   : "s"(lw_lds + (unsigned)(p * 9 * 512 + j * 256) * 4u), "v"(wvo), "s"(wrs),
+                     "s"(((cb * 27 + p * 9) * 512 + j * 256) * 4)
+                   : "memory");
+    }
+  };
+
+  f32x4 xr[2][G::PX];
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  auto load_stage = [&](int cb) {
+  auto load_x = [&](int cb) {
     const float* xp = a.x + (long)cb * a.x_plane;
 #pragma unroll
     for (int k = 0; k < G::PX; ++k) {
       xr[0][k] = xoff[k] >= 0 ? *(const f32x4*)(xp + xoff[k]) : zero4;
       xr[1][k] = xoff[k] >= 0 ? *(const f32x4*)(xp + xoff[k] + zplane) : zero4;
     }
-    const float* wp = wsrc + (long)cb * G::WFLOATS;
-#pragma unroll
-    for (int k = 0; k < G::PW; ++k)
-      if (G::WPIECES % 256 == 0 || tid + k * 256 < G::WPIECES) wr[k] = *(const f32x4*)(wp + k * 1024);
   };
 
-  load_stage(0);
-  for (int cb = 0; cb < a.Cbi; ++cb) {
-    __syncthreads();
+  load_x(0);
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int k = 0; k < 5; ++k) issue_piece(0, p, k);
+  // one cin block; MORE = another block follows (the last block is its own instantiation: no branch around a piece)
+  auto stage = [&](int cb, auto more_c) __attribute__((always_inline)) {
+    constexpr bool more = decltype(more_c)::value;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // X(cb) in registers; this wave's pieces of W1(cb), W2(cb) landed
+    __builtin_amdgcn_s_barrier();                                // B0: every wave is through P3(cb - 1): lx and slot 2 are free
+    asm volatile("" ::: "memory");
 #pragma unroll
     for (int k = 0; k < G::PX; ++k)
       if (tid + k * 256 < G::XPIECES) {
@@ -322,15 +353,25 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
         *(f32x4*)(d + G::XV * 8) = xr[1][k];
         *(f32x4*)(d + 2 * G::XV * 8) = xr[0][k];
       }
-#pragma unroll
-    for (int k = 0; k < G::PW; ++k)
-      if (G::WPIECES % 256 == 0 || tid + k * 256 < G::WPIECES) *(f32x4*)(lw + (tid + k * 256) * 4) = wr[k];
-    __syncthreads();
-    if (cb + 1 < a.Cbi) load_stage(cb + 1);
+    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0) only
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                // B1
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) load_x(cb + 1);
 
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
+      if (p > 0) {
+        // B2: slot 0 is free.  B3: slot 1 is free, and W3(cb) has landed -- in the last block nothing was issued behind it
+        if (p == 2) { if (more) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
 #pragma unroll
@@ -345,11 +386,18 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
 #pragma unroll
             for (int ct = 0; ct < NC; ++ct)
               acc[p][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[ct][kk], xf[kk], acc[p][ct], 0, 0, 0);
+          // one piece behind each of the first five taps: W3(cb) under P1, W1(cb + 1) under P2, W2(cb + 1) under P3
+          if (ky * 3 + kx < 5) {
+            if (p == 0) issue_piece(cb, 2, ky * 3 + kx);
+            else if (more) issue_piece(cb + 1, p - 1, ky * 3 + kx);
+          }
         }
       }
     }
     __builtin_amdgcn_s_setprio(0);
-  }
+  };
+  for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
+  stage(a.Cbi - 1, std::false_type{});
   // Y0 = P1 + P2, Y1 = P1 + P3: one epilogue per output plane (bias, residual, pad slots as in every other form)
   f32x16 o[NC][1];
   const int nte = HALF ? 2 * nt + ct0 : nt;                      // conv_epilogue counts cout blocks in units of its own tile
