@@ -355,6 +355,18 @@ int tm_op_prep_h16(const void* const* src_h16, const int* src_c, const int* coll
 int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_dev, const void* kw_dev,
                       void* out, int N, int C, int Z, int S, int dtype, void* stream);
 
+/* The same core, reached the way the model reaches it: k and v are the two channel halves of ONE fp32 CB8 tensor
+ * kv [N, 2C, Z, Sc, Sc] (channels [0, C) = k, [C, 2C) = v; the kv Linear's output), so their n stride differs from q's.
+ * kv_half != 0: Sc = S / 2 and query token (z, y, x) reads k / v at (z, y >> 1, x >> 1) (the half-resolution conditioning
+ * side); otherwise Sc = S.  dtype TM_DTYPE_F32: out = fp32 CB8.  TM_DTYPE_BF16 / TM_DTYPE_F16: q and kv are rounded to that
+ * type on the device first, out = 16-bit CB8 [N][C/8][Z][S][S][8] of that type.
+ * Every form the launchers do not take returns TM_ERR_ARG with a tm_last_error() text before any device call: C not a
+ * multiple of 64, odd S, windows of more than 512 tokens; fp32: C > 512 (windows of 32 tokens with C % 128 == 0 excepted),
+ * kv_half unless the window has 128 or 32 tokens, C % 128 == 0 and S is a power of two >= 4; 16-bit: C > 512, windows other
+ * than 32 / 64 / 128 / 256 / 512 tokens, C > 256 or kv_half at 256 / 512 tokens, kv_half with S % 4 != 0. */
+int tm_op_window_attn_kv(const void* q_cb8, const void* kv_cb8, const void* qw_dev, const void* kw_dev, void* out, int N, int C,
+                         int Z, int S, int dtype, int kv_half, void* stream);
+
 /* Generic direct Conv3d (stem / head / RNA path), NCDHW in, NCDHW out. */
 int tm_op_conv_direct(const void* x, const void* w_host, const void* bias_host, void* y, int N,
                       int Cin, int Cout, int Zin, int S, int kz, int ky, int kx, int pz, int py,

@@ -406,6 +406,56 @@ extern "C" int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const voi
   if (e == hipSuccess) e = launch_window_attn_bf16(hq, hk, hv, qw, kw, o, st);
   return finish(st, e, "window attention");
 }
+// The forms launch_window_attn / launch_window_attn_bf16 / _f16 take, as one readable list: TM_OK, or TM_ERR_ARG with the reason
+// (the launchers themselves only answer hipErrorInvalidValue)
+static int window_attn_form(int N, int C, int Z, int S, int dtype, int kv_half) {
+  if (dtype != TM_DTYPE_F32 && !is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_F32, TM_DTYPE_BF16 or TM_DTYPE_F16");
+  if (N < 1 || Z < 1 || S < 2 || (S & 1)) return fail(TM_ERR_ARG, "N = %d, Z = %d, S = %d: N, Z >= 1 and an even S >= 2 (2 x 2 windows)", N, Z, S);
+  if (C < 64 || C % 64) return fail(TM_ERR_ARG, "C = %d must be a positive multiple of 64", C);
+  const long Tl = (long)Z * (S / 2) * (S / 2);
+  if (Tl > 512) return fail(TM_ERR_ARG, "window of %ld tokens: the attention cores take at most 512", Tl);
+  const int T = (int)Tl;
+  const bool pow2 = !(S & (S - 1));
+  if (dtype == TM_DTYPE_F32) {
+    const bool mfma = T == 128 && C % 128 == 0, t32 = T == 32 && C % 128 == 0, lng = (T == 256 || T == 512) && C <= 256;
+    if (mfma && C > 512) return fail(TM_ERR_ARG, "C = %d > 512 at a window of 128 tokens", C);
+    if (!mfma && !t32 && !lng && C > 512) return fail(TM_ERR_ARG, "C = %d > 512: the generic fp32 core keeps C floats per query in LDS", C);
+    if (kv_half && !((mfma || t32) && pow2 && S >= 4))
+      return fail(TM_ERR_ARG, "half-resolution k / v (fp32): windows of 128 or 32 tokens, C a multiple of 128 and S a power of two >= 4 "
+                              "(got %d tokens, C = %d, S = %d)", T, C, S);
+    return TM_OK;
+  }
+  if (C > 512) return fail(TM_ERR_ARG, "C = %d > 512 (16-bit attention core)", C);
+  if (T == 256 || T == 512) {
+    if (C > 256) return fail(TM_ERR_ARG, "C = %d > 256 at a long window of %d tokens (16-bit two-pass core)", C, T);
+    if (kv_half) return fail(TM_ERR_ARG, "half-resolution k / v is not implemented for long windows (%d tokens)", T);
+    return TM_OK;
+  }
+  if (T != 128 && T != 64 && T != 32) return fail(TM_ERR_ARG, "window of %d tokens: the 16-bit attention cores take 32, 64, 128, 256 or 512", T);
+  if (kv_half && (S & 3)) return fail(TM_ERR_ARG, "half-resolution k / v (16-bit): S = %d must be a multiple of 4", S);
+  return TM_OK;
+}
+
+extern "C" int tm_op_window_attn_kv(const void* q_cb8, const void* kv_cb8, const void* qw_dev, const void* kw_dev, void* out, int N,
+                                    int C, int Z, int S, int dtype, int kv_half, void* stream) {
+  if (!q_cb8 || !kv_cb8 || !qw_dev || !kw_dev || !out) return fail(TM_ERR_ARG, "null argument");
+  if (int rc = window_attn_form(N, C, Z, S, dtype, kv_half)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const int cb = C / 8, Sc = kv_half ? S / 2 : S;
+  const TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), kv = view_cb8(const_cast<void*>(kv_cb8), N, 2 * C, Z, Sc, Sc);
+  const float *qw = (const float*)qw_dev, *kw = (const float*)kw_dev;
+  // k and v are the two channel-block halves of kv, as attn_block (tm_model.hip) hands them over: their n stride is kv's
+  if (dtype == TM_DTYPE_F32)
+    return finish(st, launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), qw, kw, view_cb8(out, N, C, Z, S, S), st), "window attention");
+  const bool f16 = dtype == TM_DTYPE_F16;
+  DevTmp tmp;
+  hipError_t e = hipSuccess;
+  const TVH hq = to_h16(tmp, q, f16, false, st, e), hkv = to_h16(tmp, kv, f16, false, st, e);
+  TVH o = hq;
+  o.p = (uint16_t*)out;
+  if (e == hipSuccess) e = (f16 ? launch_window_attn_f16 : launch_window_attn_bf16)(hq, hkv.blocks(0, cb), hkv.blocks(cb, cb), qw, kw, o, st);
+  return finish(st, e, "window attention");
+}
 extern "C" int tm_op_conv_direct(const void* x, const void* w_host, const void* bias_host, void* y, int N, int Cin,
                                  int Cout, int Zin, int S, int kz, int ky, int kx, int pz, int py, int px, int silu_in,
                                  int up2_out, void* stream) {

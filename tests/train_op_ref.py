@@ -137,6 +137,144 @@ def window_attn_mag(q, k, v, qw, kw, dout, Z, S):
     return dict(o=F(o), dq=F(dq), dk=F(dk), dv=F(dv), dqw=dqw, dkw=dkw), float(lmag.max())
 
 
+# ---- inference attention cores (tm_op_window_attn_kv: tm_attn.hip window_attn_*, tm_conv_bf16.hip window_attn_bf16 / _long) --
+# 16-bit type -> (torch dtype, smallest normal number)
+H16 = {"bf16": (torch.bfloat16, 2.0 ** -126), "f16": (torch.float16, 2.0 ** -14)}
+ATTN_WRONG = ("scale", "drop_key", "swap_v", "kw_is_qw", "hwz", "kv_mod")      # the deliberate errors of window_attn_fwd
+
+
+def r16(t, dt):
+    """Round to the nearest value of the 16-bit type (ties to even), returned as float64."""
+    return t.to(H16[dt][0]).double()
+
+
+def kv_full(t, S, mod=False):
+    """Half-resolution k / v [N, C, Z, S/2, S/2] -> what query token (z, y, x) reads: entry (z, y >> 1, x >> 1).
+    mod: the wrong read (y, x) mod S/2."""
+    i = torch.arange(S) % t.shape[-1] if mod else torch.arange(S) >> 1
+    return t[:, :, :, i][:, :, :, :, i]
+
+
+def to_windows_hwz(t, Z, S):
+    """to_windows with the tokens of a window ordered (h, w, z): the wrong partition."""
+    N, C = t.shape[:2]
+    h = S // 2
+    t = t.permute(0, 2, 3, 4, 1).reshape(N, Z, 2, h, 2, h, C).permute(0, 2, 4, 3, 5, 1, 6)
+    return t.reshape(N, 4, Z * h * h, C)
+
+
+def window_attn_fwd(q, kv, qw, kw, Z, S, dt=None, kv_half=False, wrong=None, mag=False):
+    """The inference attention core as the kernels compute it, in float64, and the bound a kernel's result must meet.
+
+    q [N, C, Z, S, S], kv [N, 2C, Z, Sc, Sc] (k = channels [0, C), v = [C, 2C); Sc = S / 2 with kv_half) float64 NCDHW;
+    qw, kw fp32 [C].  dt None: the fp32 kernels, no rounding in the model.  dt "bf16" / "f16": the 16-bit kernels, with their
+    roundings where they place them:
+      * q, k, v are rounded to the type on entry (the q / kv Linears emit them so);
+      * the Q operand is round16(fl32(q * fl32(q_norm.w * k_norm.w))), K is used as it is;
+      * both rstd factors and 1 / C multiply the fp32 logits; the softmax is fp32;
+      * P is rounded to the type, P.V accumulates in fp32 and the output is rounded once.
+    Returns (o, bound), NCDHW float64: |kernel - o| <= bound element by element.  mag: also the magnitude companion, a dict
+    of the same sums over |terms| (lmag [N, 4, T, T] for the logits l, omag NCDHW for the output before its rounding).
+
+    Derivation, first order in U = 2^-24 (the matrix unit's adder is taken as 2 U per addition, not round to nearest):
+      logit: a C-term sum (2 C U of its magnitude), two rstd factors ((C + 5) U each: C-term sum of squares, mean, + eps,
+        sqrt and reciprocal, halved by the square root) and at most 10 single roundings (q_norm.w k_norm.w, its product with
+        the operand, 1 / C, the three scale products): |dl| <= (4 C + 20) U lmag, lmag = sum_c |Q K| rq rk / C.  16-bit
+        operands below the smallest normal number may be flushed by the matrix unit: their terms are added to |dl| whole.
+      e = exp(l - m): |dl| from the logit, U |l - m| from the subtraction, exp_rel_bound(l - m) from the device expf.
+      p = e / sum: e's error, the p-weighted mean of all e errors of the row (the sum), T additions, the reciprocal and its
+        product (3 U).  The two-pass long-window kernels walk the keys in T / 128 blocks and rescale the running sum by
+        exp(m_old - m_new) per block: 3 U span + 7 U more per block, span = max |l - m| of the row, which also replaces
+        |l - m| there (pass 1 subtracts the running maximum, not the final one).
+      fp32: o = sum_u p v over T terms: sum_u |dp| |v| + (2 T + 2) U sum_u p |v|.
+      16-bit: rounding is monotone, so the kernel's P lies between round16(p (1 - e_p)) and round16(p (1 + e_p)): dP is the
+        larger distance to round16(p) (zero wherever the interval holds no rounding boundary; down to 0 where P is below the
+        smallest normal number).  The fp32 output before its rounding is then within b = sum_u dP |v| + (2 T + 2) U sum_u P |v|
+        (+ the terms of flushed v), and the stored value between round16(o - b) and round16(o + b); b is widened by 2 U |o|
+        for the fp32 value the accumulator holds and the float64 -> float32 -> 16-bit path of the conversion used here.
+    wrong: one of ATTN_WRONG, a deliberately wrong variant (tests/test_window_attn_ref.py shows the bound rejects each)."""
+    assert wrong is None or wrong in ATTN_WRONG
+    C = q.shape[1]
+    T = Z * (S // 2) ** 2
+    k, v = kv[:, :C], kv[:, C:]
+    if dt:
+        q, k, v = r16(q, dt), r16(k, dt), r16(v, dt)
+    if kv_half:
+        k, v = kv_full(k, S, wrong == "kv_mod"), kv_full(v, S, wrong == "kv_mod")
+    qs = (to_windows_hwz if wrong == "hwz" else to_windows)(q, Z, S)
+    ks, vs = to_windows(k, Z, S), to_windows(v, Z, S)
+    rq = torch.rsqrt(qs.pow(2).mean(-1, keepdim=True) + EPS)
+    rk = torch.rsqrt(ks.pow(2).mean(-1, keepdim=True) + EPS).transpose(-2, -1)
+    kw_used = qw if wrong == "kw_is_qw" else kw
+    if dt:
+        w2 = qw.float() * kw_used.float()                              # fp32, as the kernel forms it
+        qf = (qs.float() * w2).to(H16[dt][0]).double()
+    else:
+        qf = qs * (qw.double() * kw_used.double())
+    scale = C ** -0.5 if wrong == "scale" else 1.0 / C
+    fac = rq * rk * scale
+    l = (qf @ ks.transpose(-2, -1)) * fac
+    lmag = (qf.abs() @ ks.abs().transpose(-2, -1)) * fac
+    dl = (4 * C + 20) * U * lmag
+    if dt:
+        tiny = H16[dt][1]
+        sub = lambda t: t.abs() * (t.abs() < tiny)
+        dl = dl + (sub(qf) @ ks.abs().transpose(-2, -1) + qf.abs() @ sub(ks).transpose(-2, -1)) * fac
+    if wrong == "drop_key" and T > 1:
+        l = l.clone()
+        l[..., T - 1] = -math.inf
+    p = torch.softmax(l, dim=-1)
+    t = (l - l.max(-1, keepdim=True).values).abs()
+    t = torch.where(torch.isinf(t), torch.zeros_like(t), t)
+    kbn = T // 128 if T in (256, 512) else 0
+    if kbn:
+        t = t.max(-1, keepdim=True).values.expand_as(t)
+    e_e = dl + U * t + exp_rel_bound(t)
+    e_p = e_e + (p * e_e).sum(-1, keepdim=True) + (T + 3) * U + kbn * (3 * U * t + 7 * U)
+    e_p = e_p / (1.0 - e_p).clamp_min(0.5)                            # the product of the (1 + e) factors, not only their sum
+    if wrong == "swap_v" and T > 1:
+        vs = vs.clone()
+        vs[:, :, [0, T - 1]] = vs[:, :, [T - 1, 0]]       # first and last token: distinct k / v entries at half resolution too
+    if not dt:
+        o = p @ vs
+        omag = p @ vs.abs()
+        b = (p * e_p) @ vs.abs() + (2 * T + 2) * U * omag + FLT_MIN
+        res = (from_windows(o, Z, S), from_windows(b, Z, S))
+        return res + (dict(l=l, lmag=lmag, omag=from_windows(omag, Z, S)),) if mag else res
+    p16, lo, hi = r16(p, dt), r16(p * (1.0 - e_p), dt), r16(p * (1.0 + e_p), dt)
+    lo = torch.where(hi < tiny, torch.zeros_like(lo), lo)
+    dp = torch.maximum(hi - p16, p16 - lo)
+    o = p16 @ vs
+    omag = p16 @ vs.abs()
+    b = dp @ vs.abs() + (2 * T + 2) * U * omag + p16 @ sub(vs)
+    o16, olo, ohi = r16(o, dt), r16(o - b - 2 * U * o.abs(), dt), r16(o + b + 2 * U * o.abs(), dt)
+    bound = torch.maximum(ohi - o16, o16 - olo)
+    res = (from_windows(o16, Z, S), from_windows(bound, Z, S))
+    return res + (dict(l=l, lmag=lmag, omag=from_windows(omag, Z, S)),) if mag else res
+
+
+def attn_inputs(N, C, Z, S, kv_half=False, kind="plain", seed=0):
+    """fp32 q [N, C, Z, S, S], kv [N, 2C, Z, Sc, Sc], qw, kw [C] of an attention-core case.  k is correlated with the q of the
+    voxel it is read for, so the softmax is far from uniform.  kind "sharp": q_norm.weight times 60, the logits span several
+    tens and the softmax is close to one-hot (q w2 stays below 2000, inside f16).  kind "zeros": the first row of q, the first
+    column of k / v and the whole last patch of k / v are zero: rms(0) = 0 * rsqrt(1e-6) = 0, those rows get a uniform
+    softmax (the zero half-patch borders of a sweep)."""
+    g = torch.Generator().manual_seed(1000 * seed + 7 * C + 3 * S + Z + (50 if kv_half else 0))
+    Sc = S // 2 if kv_half else S
+    q = torch.randn((N, C, Z, S, S), generator=g) * 1.5
+    k = torch.randn((N, C, Z, Sc, Sc), generator=g) * 2.1 + 0.5 * (q[..., ::2, ::2] if kv_half else q)
+    v = torch.randn((N, C, Z, Sc, Sc), generator=g)
+    qw, kw = torch.rand(C, generator=g) + 0.5, torch.rand(C, generator=g) + 0.5
+    kv = torch.cat([k, v], 1)
+    if kind == "sharp":
+        qw = qw * 60.0
+    if kind == "zeros":
+        q[:, :, :, 0, :] = 0.0
+        kv[:, :, :, :, 0] = 0.0
+        kv[N - 1] = 0.0
+    return q, kv, qw, kw
+
+
 # ---- optimizer (tm_op_sumsq / tm_op_adam) --------------------------------------------------------------------------------
 def adam(p, g, m, v, lr, b1, b2, eps, wd, step, gscale):
     """torch.optim.Adam._single_tensor_adam (amsgrad off) with the gradient scaled first; float64 in, float64 out.
