@@ -413,6 +413,31 @@ int tm_op_conv_dgrad(const void* dy_cb8, const void* w_host, void* dx_cb8, int N
 int tm_op_conv_wgrad(const void* x_cb8, const void* dy_cb8, void* dw_host, void* db_host_or_null, int N, int Cin,
                      int Cout, int Z, int S, int ksize, void* stream);
 
+/* ---- resident conv ops of the training tape: weights packed on the device once, gradients to DEVICE pointers.  None of these
+ * synchronises `stream` or touches host memory (scratch is stream-ordered); bad arguments return TM_ERR_ARG before any device call.
+ *   role 0: the forward pack of w [Cout][Cin][k^3] (DEVICE, reference layout) -- the bytes tm_op_conv_mfma(zmode 0) packs on the host,
+ *           the pair form (W1, W2 - W1, W0 - W1) at ksize 3, Z == 2;
+ *   role 1: the pack tm_op_conv_dgrad builds: the filter flipped in z, y, x with cin <-> cout transposed. */
+long tm_conv_pack_floats(int Cout, int Cin, int ksize, int Z, int role);      /* floats of one pack; -1: bad argument */
+int tm_op_conv_pack_dev(const void* w_dev, void* pack_dev, int Cout, int Cin, int ksize, int Z, int role, void* stream);
+/* tm_op_conv_mfma(..., zmode 0, up2 0, variant 0) on a role-0 pack; bias_dev [Cout] DEVICE */
+int tm_op_conv_mfma_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout,
+                           int Z, int S, int ksize, void* stream);
+/* tm_op_conv_dgrad on a role-1 pack */
+int tm_op_conv_dgrad_packed(const void* dy_cb8, const void* pack_dev, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,
+                            int ksize, void* stream);
+/* dL/dw [Cout][Cin][k^3] and dL/dbias [Cout] (may be NULL) to DEVICE pointers, on the fp32 MFMA pipe; accumulate 1 adds into what
+ * is there.  Z 1 .. 4, square S x S planes.  Partial sums over chunks of the voxel range are added in chunk order (no atomics);
+ * the chunk count depends on (N, Z, S, Cin, Cout) only, so every run on every device gives the same bits. */
+int tm_op_conv_wgrad_dev(const void* x_cb8, const void* dy_cb8, void* dw_dev, void* db_dev_or_null, int accumulate, int N,
+                         int Cin, int Cout, int Z, int S, int ksize, void* stream);
+
+/* Timing hook (tools/bench_train.py): the weight gradient of one layer on random device data, engine 0 = the VALU kernel of
+ * tm_op_conv_wgrad, 1 = the MFMA kernel of tm_op_conv_wgrad_dev (with its chunk reduction).  After one warm-up launch,
+ * ms_per_launch_host[r], r < reps, is the time per launch of `iters` launches between two events. */
+int tm_op_conv_wgrad_time(int N, int Cin, int Cout, int Z, int S, int ksize, int engine, int iters, int reps,
+                          float* ms_per_launch_host, void* stream);
+
 /* ---- training slice, AttnBlock (model/MBAblocks.py:428-514 AttnBlock.forward, :517-601 Attention, :608-614 modulate) -----
  *   m = adaLN(SiLU(y));  (shift, scale, gate) x (msa, mlp) = m.chunk(6)
  *   x = x + gate_msa * proj(core(q(modulate(norm1(x))), k(y), v(y)));   x = x + gate_mlp * fc2(GELU(fc1(modulate(norm2(x)))))

@@ -89,6 +89,12 @@ SIGNATURES = {
     "tm_op_dropout_mask": (c_int, [C.c_uint64, C.c_uint, c_float, c_void_p] + [c_int] * 4 + [c_void_p]),
     "tm_op_conv_dgrad": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
     "tm_op_conv_wgrad": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p]),
+    "tm_conv_pack_floats": (C.c_long, [c_int] * 5),
+    "tm_op_conv_pack_dev": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
+    "tm_op_conv_mfma_packed": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "tm_op_conv_dgrad_packed": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p]),
+    "tm_op_conv_wgrad_dev": (c_int, [c_void_p] * 4 + [c_int] * 7 + [c_void_p]),
+    "tm_op_conv_wgrad_time": (c_int, [c_int] * 9 + [c_void_p, c_void_p]),
     "tm_op_ew": (c_int, [c_int] + [c_void_p] * 5 + [C.c_long, c_void_p]),
     "tm_op_gemm_f32": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] + [c_int] * 3 + [c_float, c_void_p]),
     "tm_op_rows": (c_int, [c_int] + [c_void_p] * 5 + [C.c_long, c_int, c_void_p]),

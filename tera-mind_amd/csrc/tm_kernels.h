@@ -271,7 +271,14 @@ hipError_t launch_prep_bwd(const float* x, long x_ns, const float* g, long g_ns,
                            const DropRng* rng = nullptr);             // non-null: mask drawn in the kernel (mask must be null)
 size_t prep_bwd_scratch_floats(int N, int Cb, int Z, int S, bool with_mod);
 hipError_t launch_conv_wgrad(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, hipStream_t s);
-hipError_t launch_chan_sum(const TV& x, float* out, int C, hipStream_t s);
+hipError_t launch_chan_sum(const TV& x, float* out, int C, hipStream_t s, int accumulate = 0);
+// the same dW on the matrix pipe, to a device pointer; scratch: conv_wgrad_scratch_floats(...) floats (0: none needed)
+hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, int accumulate, float* scratch,
+                                  hipStream_t s);
+int conv_wgrad_chunks(int N, int Z, int S, int Cin, int Cout, int* per_out);
+size_t conv_wgrad_scratch_floats(int N, int Z, int S, int Cin, int Cout, int taps);
+// device twin of conv_pack_host / conv_pack_zpair_host (pair); role 1: the data-gradient filter (flipped, cin <-> cout)
+hipError_t launch_conv_pack(const float* w, float* out, int Cout, int Cin, int taps, int role, int pair, hipStream_t s);
 // AttnBlock pieces (model/MBAblocks.py:428-614)
 hipError_t launch_ew(int op, const float* a, const float* b, const float* c, float* o1, float* o2, long n, hipStream_t s);
 hipError_t launch_modnorm_bwd(const TV& x, const float* g, const float* w, const float* scale, float* dx, float* dscale, float* dshift,

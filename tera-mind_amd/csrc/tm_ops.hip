@@ -21,12 +21,37 @@ struct DevTmp {
   std::vector<hipEvent_t> events;
   hipError_t err = hipSuccess;
   const char* what = "";
+  // stream-ordered form (the resident hooks, which may neither synchronise nor touch host memory): buffers come from the
+  // device's memory pool in `st`'s order and go back to it in that order when the call returns
+  bool ordered = false;
+  hipStream_t st = nullptr;
   DevTmp() = default;
+  explicit DevTmp(hipStream_t stream) : ordered(true), st(stream) { keep_pool(); }
+  // The pool's default release threshold is 0: it would hand its memory back to the system at every synchronisation and map it
+  // again at the next call.  Raised once per device, so the scratch of a step (at most 64 MB, conv_wgrad_chunks) is reused.
+  // This is a setting of the process's default pool, not of this library: once a resident hook has run, every other
+  // hipMallocAsync user of the process keeps its freed memory in the pool too (hipMemPoolTrimTo gives it back).  The `done`
+  // flags are unguarded: two threads racing here set the same value twice, which is harmless.
+  static void keep_pool() {
+    static bool done[64] = {};
+    int dev = 0;
+    hipMemPool_t pool = nullptr;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64 || done[dev]) return;
+    uint64_t keep = UINT64_MAX;
+    if (hipDeviceGetDefaultMemPool(&pool, dev) == hipSuccess && hipMemPoolSetAttribute(pool, hipMemPoolAttrReleaseThreshold, &keep) == hipSuccess)
+      done[dev] = true;
+  }
   DevTmp(const DevTmp&) = delete;
   DevTmp& operator=(const DevTmp&) = delete;
   ~DevTmp() {
     for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-    for (void* p : ptrs) (void)hipFree(p);
+    for (void* p : ptrs) (void)(ordered ? hipFreeAsync(p, st) : hipFree(p));
+  }
+  float* ordered_floats(size_t n, bool zero) {
+    void* p = nullptr;
+    if (err != hipSuccess || !ok(hipMallocAsync(&p, n * sizeof(float), st), "hipMallocAsync")) return nullptr;
+    ptrs.push_back(p);
+    return !zero || ok(hipMemsetAsync(p, 0, n * sizeof(float), st), "hipMemsetAsync") ? (float*)p : nullptr;
   }
   bool ok(hipError_t e, const char* call) {
     if (e != hipSuccess) { err = e; what = call; }
@@ -751,5 +776,120 @@ extern "C" int tm_op_conv_wgrad(const void* x_cb8, const void* dy_cb8, void* dw_
   if (int rc = finish(st, e, "conv wgrad")) return rc;
   HIP_TRY(hipMemcpy(dw_host, ddw, nw * sizeof(float), hipMemcpyDeviceToHost));
   if (db_host_or_null) HIP_TRY(hipMemcpy(db_host_or_null, ddb, Cout * sizeof(float), hipMemcpyDeviceToHost));
+  return TM_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// resident conv ops of the training tape: weights packed on the device, gradients to device pointers.  None of them
+// synchronises `stream` or touches host memory; their scratch is stream-ordered (DevTmp(stream)).
+// ------------------------------------------------------------------------------------------
+static int packed_form(int Cout, int Cin, int ksize, int Z, int role) {
+  if (ksize != 1 && ksize != 3) return fail(TM_ERR_ARG, "ksize must be 1 or 3");
+  if (Cout < 1 || Cin < 1 || Z < 1) return fail(TM_ERR_ARG, "Cout, Cin and Z must be positive");
+  if (role != 0 && role != 1) return fail(TM_ERR_ARG, "role must be 0 (forward) or 1 (data gradient)");
+  return TM_OK;
+}
+extern "C" long tm_conv_pack_floats(int Cout, int Cin, int ksize, int Z, int role) {
+  if (packed_form(Cout, Cin, ksize, Z, role)) return -1;
+  const int taps = ksize == 1 ? 1 : 27;
+  return (long)(role ? conv_pack_floats(Cin, (Cout + 7) / 8, taps) : conv_pack_floats(Cout, (Cin + 7) / 8, taps));
+}
+extern "C" int tm_op_conv_pack_dev(const void* w_dev, void* pack_dev, int Cout, int Cin, int ksize, int Z, int role, void* stream) {
+  if (!w_dev || !pack_dev) return fail(TM_ERR_ARG, "null argument");
+  if (int rc = packed_form(Cout, Cin, ksize, Z, role)) return rc;
+  const int pair = (ksize == 3 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;               // as tm_op_conv_mfma picks the pair form
+  HIP_TRY(launch_conv_pack((const float*)w_dev, (float*)pack_dev, Cout, Cin, ksize == 1 ? 1 : 27, role, pair, (hipStream_t)stream));
+  return TM_OK;
+}
+// y = conv(x) on a ready pack of Cout x Cin; bias_dev [Cout] or null (zero)
+static int conv_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout, int Z, int S,
+                       int ksize, hipStream_t st) {
+  DevTmp tmp(st);
+  ConvW cw;
+  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = ksize == 1 ? 1 : 27; cw.ntile = (Cout + 63) / 64;
+  cw.zpair = (ksize == 3 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;
+  float* b = tmp.ordered_floats((size_t)cw.ntile * 64, true);       // the epilogues read the bias zero padded to 64 couts
+  if (tmp.err) return tmp.report();
+  if (bias_dev) HIP_TRY(hipMemcpyAsync(b, bias_dev, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+  cw.w = (const float*)pack_dev; cw.bias = b;
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.zmode = ZM_PAD1;
+  HIP_TRY(launch_conv_mfma(L, st));
+  return TM_OK;
+}
+static int resident_geo(int N, int Cin, int Cout, int Z, int S, int ksize) {
+  if (ksize != 1 && ksize != 3) return fail(TM_ERR_ARG, "ksize must be 1 or 3");
+  if (N < 1 || Cin < 1 || Cout < 1 || S < 1) return fail(TM_ERR_ARG, "N, Cin, Cout and S must be positive");
+  if (Z < 1 || Z > 4) return fail(TM_ERR_ARG, "Z must be 1 .. 4");
+  return TM_OK;
+}
+extern "C" int tm_op_conv_mfma_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout,
+                                      int Z, int S, int ksize, void* stream) {
+  if (!x_cb8 || !pack_dev || !bias_dev || !y_cb8) return fail(TM_ERR_ARG, "null argument");
+  if (int rc = resident_geo(N, Cin, Cout, Z, S, ksize)) return rc;
+  return conv_packed(x_cb8, pack_dev, bias_dev, y_cb8, N, Cin, Cout, Z, S, ksize, (hipStream_t)stream);
+}
+extern "C" int tm_op_conv_dgrad_packed(const void* dy_cb8, const void* pack_dev, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,
+                                       int ksize, void* stream) {
+  if (!dy_cb8 || !pack_dev || !dx_cb8) return fail(TM_ERR_ARG, "null argument");
+  if (int rc = resident_geo(N, Cin, Cout, Z, S, ksize)) return rc;
+  return conv_packed(dy_cb8, pack_dev, nullptr, dx_cb8, N, Cout, Cin, Z, S, ksize, (hipStream_t)stream);
+}
+extern "C" int tm_op_conv_wgrad_dev(const void* x_cb8, const void* dy_cb8, void* dw_dev, void* db_dev_or_null, int accumulate, int N,
+                                    int Cin, int Cout, int Z, int S, int ksize, void* stream) {
+  if (!x_cb8 || !dy_cb8 || !dw_dev) return fail(TM_ERR_ARG, "null argument");
+  if (int rc = resident_geo(N, Cin, Cout, Z, S, ksize)) return rc;
+  if (accumulate != 0 && accumulate != 1) return fail(TM_ERR_ARG, "accumulate must be 0 or 1");
+  const int taps = ksize == 1 ? 1 : 27;
+  hipStream_t st = (hipStream_t)stream;
+  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = view_cb8(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
+  DevTmp tmp(st);
+  const size_t ns = conv_wgrad_scratch_floats(N, Z, S, Cin, Cout, taps);
+  float* scratch = ns ? tmp.ordered_floats(ns, false) : nullptr;
+  if (tmp.err) return tmp.report();
+  HIP_TRY(launch_conv_wgrad_mfma(x, dy, (float*)dw_dev, Cin, Cout, taps, accumulate, scratch, st));
+  if (db_dev_or_null) HIP_TRY(launch_chan_sum(dy, (float*)db_dev_or_null, Cout, st, accumulate));
+  return TM_OK;
+}
+
+// Timing hook of the conv weight gradient on random device data (uniform in [-1, 1)): engine 0 = conv_wgrad_kernel (VALU),
+// 1 = conv_wgrad_mfma_kernel + its chunk reduction.  One warm-up launch, then `reps` measurements of `iters` launches between two
+// events each: ms_per_launch_host[r] = milliseconds per launch of repetition r (their spread is the noise of identical calls).
+__global__ void fill_f32_kernel(float* p, size_t n, unsigned seed) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned hsh = (unsigned)i * 2654435761u ^ (unsigned)(i >> 32) * 40503u ^ seed;
+    hsh ^= hsh >> 15; hsh *= 2246822519u; hsh ^= hsh >> 13; hsh *= 3266489917u; hsh ^= hsh >> 16;
+    p[i] = (float)(hsh >> 8) * (1.0f / 8388608.0f) - 1.0f;
+  }
+}
+extern "C" int tm_op_conv_wgrad_time(int N, int Cin, int Cout, int Z, int S, int ksize, int engine, int iters, int reps,
+                                     float* ms_per_launch_host, void* stream) {
+  if (!ms_per_launch_host || iters < 1 || reps < 1 || (engine != 0 && engine != 1)) return fail(TM_ERR_ARG, "bad argument");
+  if (int rc = resident_geo(N, Cin, Cout, Z, S, ksize)) return rc;
+  const int taps = ksize == 1 ? 1 : 27;
+  hipStream_t st = (hipStream_t)stream;
+  TV x = view_cb8(nullptr, N, Cin, Z, S, S), dy = view_cb8(nullptr, N, Cout, Z, S, S);
+  const size_t nx = (size_t)N * x.nstride, ny = (size_t)N * dy.nstride, ns = conv_wgrad_scratch_floats(N, Z, S, Cin, Cout, taps);
+  DevTmp tmp;
+  x.p = tmp.alloc<float>(nx); dy.p = tmp.alloc<float>(ny);
+  float* dw = tmp.alloc<float>((size_t)Cout * Cin * taps);
+  float* scratch = (engine && ns) ? tmp.alloc<float>(ns) : nullptr;
+  hipEvent_t e0 = tmp.event(), e1 = tmp.event();
+  if (tmp.err) return tmp.report();
+  hipLaunchKernelGGL(fill_f32_kernel, dim3(2048), dim3(256), 0, st, x.p, nx, 11u);
+  hipLaunchKernelGGL(fill_f32_kernel, dim3(2048), dim3(256), 0, st, dy.p, ny, 23u);
+  auto run = [&]() { return engine ? launch_conv_wgrad_mfma(x, dy, dw, Cin, Cout, taps, 0, scratch, st) : launch_conv_wgrad(x, dy, dw, Cin, Cout, taps, st); };
+  if (int rc = finish(st, run(), "conv wgrad (timing warm-up)")) return rc;
+  for (int r = 0; r < reps; ++r) {
+    hipError_t e = hipEventRecord(e0, st);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = run();
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (int rc = finish(st, e, "conv wgrad (timing)")) return rc;
+    HIP_TRY(hipEventElapsedTime(ms_per_launch_host + r, e0, e1));
+    ms_per_launch_host[r] /= (float)iters;
+  }
   return TM_OK;
 }

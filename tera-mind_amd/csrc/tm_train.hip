@@ -9,6 +9,8 @@
 // against torch.autograd of the fp32 oracle).  Layout: CB8 fp32 [N][Cb][Z][H][W][8] as everywhere.
 #include "tm_device.h"
 
+#include <algorithm>
+
 namespace tmk {
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -308,7 +310,7 @@ hipError_t launch_conv_wgrad(const TV& x, const TV& dy, float* dw, int Cin, int 
 }
 
 // per-channel sum over (n, voxels) of a CB8 tensor: bias gradients.  One workgroup per channel block.
-__global__ __launch_bounds__(256) void chan_sum_kernel(const float* x, long x_ns, int N, long vpn, float* out, int C) {
+__global__ __launch_bounds__(256) void chan_sum_kernel(const float* x, long x_ns, int N, long vpn, float* out, int C, int accumulate) {
   __shared__ float red[4][8];
   const int cb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   float s[8];
@@ -324,10 +326,258 @@ __global__ __launch_bounds__(256) void chan_sum_kernel(const float* x, long x_ns
 #pragma unroll
   for (int j = 0; j < 8; ++j) { s[j] = wave_sum(s[j]); if (lane == 0) red[wv][j] = s[j]; }
   __syncthreads();
-  if (tid < 8 && cb * 8 + tid < C) out[cb * 8 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+  if (tid < 8 && cb * 8 + tid < C) {
+    const float v = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    out[cb * 8 + tid] = accumulate ? out[cb * 8 + tid] + v : v;
+  }
 }
-hipError_t launch_chan_sum(const TV& x, float* out, int C, hipStream_t s) {
-  hipLaunchKernelGGL(chan_sum_kernel, dim3((unsigned)x.Cb), dim3(256), 0, s, x.p, x.nstride, x.N, (long)x.Z * x.H * x.W, out, C);
+hipError_t launch_chan_sum(const TV& x, float* out, int C, hipStream_t s, int accumulate) {
+  hipLaunchKernelGGL(chan_sum_kernel, dim3((unsigned)x.Cb), dim3(256), 0, s, x.p, x.nstride, x.N, (long)x.Z * x.H * x.W, out, C, accumulate);
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same weight gradient on the matrix pipe (v_mfma_f32_32x32x2_f32).  Per tap it is a GEMM with M = cout, N = cin and
+// K = voxels: a workgroup owns a 32-cout x 32-cin tile and one chunk of the list of spatial tiles (n, ty, tx); per spatial
+// tile (TH x TW in plane, every z plane) it stages dY and the halo'd X of its 4 + 4 channel blocks in LDS, channel-minor
+// ([voxel][32 channels]: the two half-waves of an operand read take two adjacent voxels = 64 consecutive floats, no bank
+// conflict), and runs one MFMA per (tap, voxel pair).  taps 27: wave q owns the taps t = q + 4 i (7 / 7 / 7 / 6) in 7 x 16
+// accumulator registers, and a (tap, z) pair whose input plane z + kz - 1 lies outside [0, Z) is skipped (wave-uniform),
+// so the executed tap count is z-aware.  taps 1: the four waves split the voxel pairs and are summed through LDS in the
+// order 0, 1, 2, 3.  chunks == 1 writes dW (or adds into it) directly; otherwise the partial goes to
+// part[chunk][Cout][Cin][taps] and conv_wgrad_reduce_kernel adds the chunks in index order.  No atomics: the bits are a
+// function of the geometry alone (conv_wgrad_chunks).  Pad channel slots of x / dY are zero and rows / columns beyond
+// Cout / Cin are never written.
+// ------------------------------------------------------------------------------------------------------------------
+struct WgradMfmaArgs {
+  const float* x; long x_ns; int Cbi;
+  const float* dy; long dy_ns; int Cbo;
+  float* out;                    // dW [Cout][Cin][taps] (chunks == 1) or the partials [chunk][Cout][Cin][taps]
+  int N, Z, S, Cout, Cin;
+  int tiles, per, accumulate;    // spatial tiles in all, tiles per chunk; accumulate: direct form adds into dW
+};
+
+template <int TAPS, int TH, int TW>
+__global__ __launch_bounds__(256) void conv_wgrad_mfma_kernel(WgradMfmaArgs a) {
+  constexpr int XH = TH + 2, XW = TW + 2, NA = TAPS == 27 ? 7 : 1;
+  __shared__ __attribute__((aligned(16))) float ys[4096];       // [z][TH][TW][32 cout]:  Z * TH * TW <= 128
+  __shared__ __attribute__((aligned(16))) float xs[7680];       // [z][XH][XW][32 cin]:   Z * XH * XW <= 240
+  const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int S = a.S, Z = a.Z;
+  const long plane = (long)Z * S * S * 8;
+  const int tiy = (S + TH - 1) / TH, tix = (S + TW - 1) / TW;
+  f32x16 acc[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  const int t0 = blockIdx.z * a.per, t1 = min(t0 + a.per, a.tiles);
+  for (int tl = t0; tl < t1; ++tl) {
+    const int n = tl / (tiy * tix), rem = tl - n * (tiy * tix), ty = rem / tix, tx = rem - ty * tix;
+    __syncthreads();
+    for (int i = tid; i < Z * XH * XW * 4; i += 256) {
+      const int cbl = i & 3;
+      int r = i >> 2;
+      const int hx = r % XW; r /= XW;
+      const int hy = r % XH;
+      const int z = r / XH;
+      const int y = ty * TH + hy - 1, x = tx * TW + hx - 1, cb = blockIdx.y * 4 + cbl;
+      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+      if (cb < a.Cbi && y >= 0 && y < S && x >= 0 && x < S) {
+        const float* p = a.x + (long)n * a.x_ns + (long)cb * plane + ((long)(z * S + y) * S + x) * 8;
+        v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);
+      }
+      float* d = xs + ((z * XH + hy) * XW + hx) * 32 + cbl * 8;
+      *(f32x4*)d = v0; *(f32x4*)(d + 4) = v1;
+    }
+    for (int i = tid; i < Z * TH * TW * 4; i += 256) {
+      const int cbl = i & 3;
+      int r = i >> 2;
+      const int lx = r % TW; r /= TW;
+      const int ly = r % TH;
+      const int z = r / TH;
+      const int y = ty * TH + ly, x = tx * TW + lx, cb = blockIdx.x * 4 + cbl;
+      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+      if (cb < a.Cbo && y < S && x < S) {
+        const float* p = a.dy + (long)n * a.dy_ns + (long)cb * plane + ((long)(z * S + y) * S + x) * 8;
+        v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);
+      }
+      float* d = ys + ((z * TH + ly) * TW + lx) * 32 + cbl * 8;
+      *(f32x4*)d = v0; *(f32x4*)(d + 4) = v1;
+    }
+    __syncthreads();
+    if (TAPS == 27) {
+      for (int z = 0; z < Z; ++z)
+        for (int ly = 0; ly < TH; ++ly)
+#pragma unroll
+          for (int px = 0; px < TW / 2; ++px) {
+            const int lx = 2 * px + h;
+            const float av = ys[((z * TH + ly) * TW + lx) * 32 + c];
+            const float* xb = xs + ((z * XH + ly) * XW + lx) * 32 + c;
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+              const int t = q + 4 * i, kz = t / 9, ky = (t / 3) % 3, kx = t % 3, zi = z + kz - 1;
+              if (t < 27 && zi >= 0 && zi < Z)
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xb[(((kz - 1) * XH + ky) * XW + kx) * 32], acc[i], 0, 0, 0);
+            }
+          }
+    } else {
+      // voxel pair j of the tile belongs to wave j % 4
+      for (int j = q; j < Z * TH * TW / 2; j += 4) {
+        const int v = 2 * j + h, lx = v % TW, ly = (v / TW) % TH, z = v / (TW * TH);
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ys[v * 32 + c], xs[((z * XH + ly + 1) * XW + lx + 1) * 32 + c], acc[0], 0, 0, 0);
+      }
+    }
+  }
+  if (TAPS == 1) {
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) xs[(q * 16 + r) * 64 + lane] = acc[0][r];
+    __syncthreads();
+    if (q == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[0][r] = ((xs[r * 64 + lane] + xs[(16 + r) * 64 + lane]) + xs[(32 + r) * 64 + lane]) + xs[(48 + r) * 64 + lane];
+    }
+  }
+  // D register r of a lane: row (cout) 8 (r / 4) + 4 h + r % 4, column (cin) c
+  const int ic = blockIdx.y * 32 + c;
+  float* out = a.out + (gridDim.z > 1 ? (long)blockIdx.z * a.Cout * a.Cin * TAPS : 0);
+  const bool add = gridDim.z == 1 && a.accumulate;
+  if (TAPS == 27) {
+    // 27-tap form: through LDS, 8 cout rows at a time, so that a row of the tile leaves as one run of (cins of the tile) x 27
+    // consecutive floats and not as 4-byte stores 108 bytes apart.  xs [8 rows][32 cin][27 taps]: 6912 floats.
+    const int ic0 = blockIdx.y * 32, run = min(32, a.Cin - ic0) * 27;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int t = q + 4 * i;
+        if (t < 27) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) xs[((4 * h + k) * 32 + c) * 27 + t] = acc[i][4 * g + k];
+        }
+      }
+      __syncthreads();
+      for (int row = 0; row < 8; ++row) {
+        const int oc = blockIdx.x * 32 + 8 * g + row;
+        if (oc >= a.Cout) break;
+        float* d = out + ((long)oc * a.Cin + ic0) * 27;
+        for (int e = tid; e < run; e += 256) d[e] = add ? d[e] + xs[row * 864 + e] : xs[row * 864 + e];
+      }
+    }
+  } else if (ic < a.Cin && q == 0) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int t = TAPS == 27 ? q + 4 * i : 0;
+      if (t >= TAPS) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int oc = blockIdx.x * 32 + 8 * (r / 4) + 4 * h + (r % 4);
+        if (oc < a.Cout) {
+          float* d = out + ((long)oc * a.Cin + ic) * TAPS + t;
+          *d = add ? *d + acc[i][r] : acc[i][r];
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* part, long nw, int chunks, float* dw, int accumulate) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= nw) return;
+  float s_ = part[i];
+  for (int k = 1; k < chunks; ++k) s_ += part[(long)k * nw + i];
+  dw[i] = accumulate ? dw[i] + s_ : s_;
+}
+
+// in-plane tile of the MFMA weight gradient: 8 x 8 up to Z = 2, 4 x 8 at Z = 3, 4 (LDS), 4 x 4 below S = 8; edge tiles are zero filled
+static void wgrad_tile(int Z, int S, int& th, int& tw) {
+  tw = S >= 8 ? 8 : 4;
+  th = (S >= 8 && Z <= 2) ? 8 : 4;
+}
+// Chunks of the voxel range: about 1024 workgroups in all, at most one chunk per spatial tile, at most 256, and at most 16 Mi
+// floats (64 MB) of 27-tap partials, so that a narrow layer (64 -> 64: a 442 KB dW) does not spend its time writing and
+// re-reading copies of dW and the partials stay within the 256 MB last-level cache.  A function of the layer geometry only,
+// never of the device: the summation order, and with it every bit of dW, is the same on every box.
+int conv_wgrad_chunks(int N, int Z, int S, int Cin, int Cout, int* per_out) {
+  int th, tw;
+  wgrad_tile(Z, S, th, tw);
+  const int tiles = N * ((S + th - 1) / th) * ((S + tw - 1) / tw);
+  const long ct = (long)((Cout + 31) / 32) * ((Cin + 31) / 32);
+  const long cap = (16L << 20) / ((long)Cout * Cin * 27);
+  int chunks = (int)std::max<long>(1, std::min<long>(std::min<long>(std::min<long>(256, tiles), 1024 / ct), cap));
+  const int per = (tiles + chunks - 1) / chunks;
+  chunks = (tiles + per - 1) / per;
+  if (per_out) *per_out = per;
+  return chunks;
+}
+size_t conv_wgrad_scratch_floats(int N, int Z, int S, int Cin, int Cout, int taps) {
+  const int chunks = conv_wgrad_chunks(N, Z, S, Cin, Cout, nullptr);
+  return chunks > 1 ? (size_t)chunks * Cout * Cin * taps : 0;
+}
+hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, int accumulate, float* scratch,
+                                  hipStream_t s) {
+  const int S = x.H, Z = x.Z;
+  if ((taps != 27 && taps != 1) || x.Z != dy.Z || x.H != dy.H || x.N != dy.N || Z < 1 || Z > 4 || x.H != x.W || dy.H != dy.W || S < 1 ||
+      x.N < 1 || Cin < 1 || Cout < 1 || x.Cb != (Cin + 7) / 8 || dy.Cb != (Cout + 7) / 8)
+    return hipErrorInvalidValue;
+  int th, tw, per;
+  wgrad_tile(Z, S, th, tw);
+  const int chunks = conv_wgrad_chunks(x.N, Z, S, Cin, Cout, &per);
+  if (chunks > 1 && !scratch) return hipErrorInvalidValue;
+  WgradMfmaArgs a{x.p, x.nstride, x.Cb, dy.p, dy.nstride, dy.Cb, chunks > 1 ? scratch : dw, x.N, Z, S, Cout, Cin,
+                  x.N * ((S + th - 1) / th) * ((S + tw - 1) / tw), per, accumulate};
+  const dim3 grid((unsigned)((Cout + 31) / 32), (unsigned)((Cin + 31) / 32), (unsigned)chunks);
+#define TM_WGRAD(TAPS, TH, TW) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<TAPS, TH, TW>), grid, dim3(256), 0, s, a)
+  if (taps == 27) {
+    if (th == 8) TM_WGRAD(27, 8, 8); else if (tw == 8) TM_WGRAD(27, 4, 8); else TM_WGRAD(27, 4, 4);
+  } else {
+    if (th == 8) TM_WGRAD(1, 8, 8); else if (tw == 8) TM_WGRAD(1, 4, 8); else TM_WGRAD(1, 4, 4);
+  }
+#undef TM_WGRAD
+  if (chunks > 1) {
+    const long nw = (long)Cout * Cin * taps;
+    hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, scratch, nw, chunks, dw, accumulate);
+  }
+  return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Conv weights packed on the device: w [Cout][Cin][taps] (reference layout) -> the bytes conv_pack_host (pair == 0) or
+// conv_pack_zpair_host (pair == 1: W1, W2 - W1, W0 - W1 per in-plane tap, plain fp32 subtractions) write, pad slots
+// zero.  role 1 packs the filter of the data gradient: flipped in every axis and cin <-> cout transposed, so the pack
+// has Cin "output" channels over ceil(Cout / 8) "input" blocks.  One thread per packed float.
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, float* out, int Cout, int Cin, int taps, int role, int pair,
+                                                        long total) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int Co = role ? Cin : Cout, Ci = role ? Cout : Cin, Cbi = (Ci + 7) / 8;
+  const int c8 = (int)(i & 7), col = (int)((i >> 3) & 63);
+  long r = i >> 9;
+  const int t = (int)(r % taps); r /= taps;
+  const int cb = (int)(r % Cbi), nt = (int)(r / Cbi);
+  const int co = nt * 64 + col, ci = cb * 8 + c8;
+  float v = 0.f;
+  if (co < Co && ci < Ci) {
+    // effective filter e[co][ci][u] = role ? w[ci][co][taps - 1 - u] : w[co][ci][u]
+    const float* src = role ? w + ((long)ci * Cin + co) * taps : w + ((long)co * Cin + ci) * taps;
+    auto e = [&](int u) { return src[role ? taps - 1 - u : u]; };
+    if (!pair) v = e(t);
+    else {
+      const int k = t % 9, g = t / 9;
+      const float w1 = e(9 + k);
+      v = g == 0 ? w1 : __fsub_rn(e(g == 1 ? 18 + k : k), w1);
+    }
+  }
+  out[i] = v;
+}
+hipError_t launch_conv_pack(const float* w, float* out, int Cout, int Cin, int taps, int role, int pair, hipStream_t s) {
+  const int Co = role ? Cin : Cout, Ci = role ? Cout : Cin;
+  const long total = (long)((Co + 63) / 64) * ((Ci + 7) / 8) * taps * 512;
+  hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, out, Cout, Cin, taps, role, pair, total);
   return hipGetLastError();
 }
 

@@ -21,7 +21,14 @@ second conv, p = 0.1 in the reference, config_parm.py:46) is live when `UNetTrai
 mask is drawn on the GPU from (per-forward key, block site, p) by the forward prep kernel and drawn again by its backward
 (tm_op_prep_train_rng / tm_op_prep_bwd_rng; the rule is DESIGN.md §8), so no mask is stored.  p = 0 (the default) is the
 model as in `.eval()`.  Functional, not tuned: every op synchronises, weights are re-packed per call.
+
+`UNetTrain(..., resident=True)` runs the conv ops of the tape on a second engine (same kernels forward, same numerics contract):
+the parameters live in one flat fp32 device arena (shared with AdamTrainer), a conv weight is packed on the device once per role
+(forward / data gradient) per optimizer step (tm_op_conv_pack_dev), the convs read the ready packs (tm_op_conv_mfma_packed /
+tm_op_conv_dgrad_packed) and the weight gradient runs on the matrix pipe straight into device gradient tensors
+(tm_op_conv_wgrad_dev).  The prep / row / GEMM ops keep their host-pointer arguments in both modes.
 """
+import collections
 import ctypes as C
 import hashlib
 import math
@@ -93,10 +100,12 @@ def derive_dropout_key(seed: int, step: int, micro: int = 0) -> int:
 
 class UNetTrain:
     """forward(x_p, t_map, rna_dense, b, dropout_key) -> (pred, pred2); backward(dpred, dpred2) -> {state_dict key: gradient
-    (host fp32)}.  `state` = the reference state_dict (host tensors / arrays); `dropout_p` = the ResBlock dropout probability
-    (0: none, as in `.eval()`)."""
+    (host fp32; device fp32 with resident=True)}.  `state` = the reference state_dict (host tensors / arrays); `dropout_p` = the
+    ResBlock dropout probability (0: none, as in `.eval()`); `resident`: conv weights packed on the device, conv gradients kept
+    there (module docstring).  `W` is the host state_dict; in resident mode it is fetched from the arena when first read after
+    an optimizer step."""
 
-    def __init__(self, cfg: PathConfig, state: Dict[str, "object"], device="cuda:0", dropout_p: float = 0.0):
+    def __init__(self, cfg: PathConfig, state: Dict[str, "object"], device="cuda:0", dropout_p: float = 0.0, resident: bool = False):
         if not 0.0 <= dropout_p < 1.0:
             raise ValueError(f"dropout_p must lie in [0, 1), got {dropout_p}")
         self.cfg = cfg
@@ -105,7 +114,19 @@ class UNetTrain:
         self._drop_key: Optional[int] = None
         self._drop_calls: Dict[str, int] = {}
         self.dev = torch.device(device)
-        self.W = {k: _host(torch.as_tensor(v)) for k, v in state.items()}
+        self._W: Optional[Dict[str, torch.Tensor]] = {k: _host(torch.as_tensor(v)) for k, v in state.items()}
+        self.keys = list(self._W)
+        self._shape = {k: tuple(v.shape) for k, v in self._W.items()}
+        self._off, n = {}, 0
+        for k in self.keys:
+            self._off[k] = n
+            n += self._W[k].numel()
+        self.resident = bool(resident)
+        self.P: Optional[torch.Tensor] = None                           # resident: the one master copy, flat fp32 on the device
+        self._packs: Dict[Tuple[str, int], Tuple[torch.Tensor, int]] = {}
+        self.pack_count = collections.Counter()                         # (conv key, role) -> packs built so far
+        if self.resident:
+            self.P = torch.cat([self._W[k].reshape(-1) for k in self.keys]).to(self.dev)
         self._Wd: Dict[str, torch.Tensor] = {}
         self.tape: List = []
         self.grads: Dict[str, torch.Tensor] = {}
@@ -119,13 +140,51 @@ class UNetTrain:
     def _st(self):
         return _lib.current_stream_ptr()
 
+    @property
+    def W(self) -> Dict[str, torch.Tensor]:
+        if self._W is None:
+            host = self.P.cpu()
+            self._W = {k: host[self._off[k]:self._off[k] + math.prod(self._shape[k])].reshape(self._shape[k]) for k in self.keys}
+        return self._W
+
+    def _pd(self, key):
+        """resident: the parameter `key` as a view of the device arena"""
+        return self.P[self._off[key]:self._off[key] + math.prod(self._shape[key])].reshape(self._shape[key])
+
+    def params_updated(self):
+        """resident: the arena changed (AdamTrainer.step): the host copy and every pack are stale"""
+        self._W = None
+        self._packs.clear()
+
+    def _pack(self, key, role, co, ci, ks, Z, embed):
+        """The device pack of conv `key` for role 0 (forward) / 1 (data gradient), built on first use after an optimizer step."""
+        hit = self._packs.get((key, role))
+        if hit is not None:
+            assert hit[1] == Z, (key, hit[1], Z)
+            return hit[0]
+        w = self._pd(key + ".weight")
+        if embed:
+            wf = torch.zeros((co, ci, 3, 3, 3), dtype=torch.float32, device=self.dev)
+            wf[:, :, 1] = w[:, :, 0]
+        else:
+            wf = w
+        pk = torch.empty((_lib.lib().tm_conv_pack_floats(co, ci, ks, Z, role),), dtype=torch.float32, device=self.dev)
+        _lib.check(_lib.lib().tm_op_conv_pack_dev(_lib.ptr(wf), _lib.ptr(pk), co, ci, ks, Z, role, self._st()), "tm_op_conv_pack_dev")
+        self._packs[(key, role)] = (pk, Z)
+        self.pack_count[(key, role)] += 1
+        return pk
+
     def _wd(self, key):
+        if self.resident:
+            return self._pd(key)
         if key not in self._Wd:
             self._Wd[key] = self.W[key].to(self.dev).contiguous()
         return self._Wd[key]
 
     def _gacc(self, key, g):
-        g = g.reshape(self.W[key].shape)
+        g = g.reshape(self._shape[key])
+        if self.resident:
+            g = g.to(self.dev)
         self.grads[key] = g.clone() if key not in self.grads else self.grads[key] + g
 
     def _acc(self, v: _V, g: torch.Tensor):
@@ -147,6 +206,8 @@ class UNetTrain:
     def conv(self, x: _V, key: str) -> _V:
         """Conv3d with the reference weight `key`.weight [Co, Ci, kz, ky, kx]: 3x3x3 pad 1, 1x1x1, or (1,3,3) pad (0,1,1)
         embedded into the middle z slice of a 3x3x3 kernel."""
+        if self.resident:
+            return self._conv_resident(x, key)
         w = self.W[key + ".weight"]
         b = self.W[key + ".bias"]
         co, ci = w.shape[:2]
@@ -172,6 +233,45 @@ class UNetTrain:
             self._gacc(key + ".bias", db)
             dx = torch.zeros_like(x.t)
             _lib.check(_lib.lib().tm_op_conv_dgrad(_lib.ptr(g), _hp(wf), _lib.ptr(dx), N, ci, co, Z, S, ks, self._st()), "tm_op_conv_dgrad")
+            self._acc(x, dx)
+        self.tape.append(bwd)
+        return out
+
+    def _conv_resident(self, x: _V, key: str) -> _V:
+        """conv() on the device-resident engine: ready packs, the weight gradient straight into device gradient tensors
+        (accumulate = 1 for the second use of a weight in one backward), nothing synchronised, no host memory touched."""
+        kw, kb = key + ".weight", key + ".bias"
+        shp = self._shape[kw]
+        co, ci = shp[:2]
+        assert ci == x.C, (key, ci, x.C)
+        ks = 1 if shp[2:] == (1, 1, 1) else 3
+        embed = shp[2:] == (1, 3, 3)
+        N, Z, S = self._geo(x.t)
+        L = _lib.lib()
+        y = torch.zeros((N, (co + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
+        _lib.check(L.tm_op_conv_mfma_packed(_lib.ptr(x.t), _lib.ptr(self._pack(key, 0, co, ci, ks, Z, embed)), _lib.ptr(self._pd(kb)),
+                                            _lib.ptr(y), N, ci, co, Z, S, ks, self._st()), "tm_op_conv_mfma_packed")
+        out = _V(y, co)
+
+        def bwd():
+            g = out.g
+            acc = 1 if kw in self.grads else 0
+            if not acc:
+                self.grads[kb] = torch.empty((co,), dtype=torch.float32, device=self.dev)
+            if embed:
+                # the (1,3,3) filter is the middle z slice of the 3x3x3 gradient: sliced on the device
+                dw = (torch.zeros if acc else torch.empty)((co, ci, 3, 3, 3), dtype=torch.float32, device=self.dev)
+            else:
+                if not acc:
+                    self.grads[kw] = torch.empty(shp, dtype=torch.float32, device=self.dev)
+                dw = self.grads[kw]
+            _lib.check(L.tm_op_conv_wgrad_dev(_lib.ptr(x.t), _lib.ptr(g), _lib.ptr(dw), _lib.ptr(self.grads[kb]), acc, N, ci, co, Z, S, ks,
+                                              self._st()), "tm_op_conv_wgrad_dev")
+            if embed:
+                self._gacc(kw, dw[:, :, 1:2])
+            dx = torch.zeros_like(x.t)
+            _lib.check(L.tm_op_conv_dgrad_packed(_lib.ptr(g), _lib.ptr(self._pack(key, 1, co, ci, ks, Z, embed)), _lib.ptr(dx), N, ci, co, Z,
+                                                 S, ks, self._st()), "tm_op_conv_dgrad_packed")
             self._acc(x, dx)
         self.tape.append(bwd)
         return out
@@ -595,13 +695,15 @@ class AdamTrainer:
             n += net.W[k].numel()
         self.n = n
         dev = net.dev
-        self.p = torch.cat([net.W[k].reshape(-1) for k in self.keys]).to(dev)
+        # a resident net keeps its parameters in the same flat layout on the device: one master copy, shared
+        self.p = net.P if net.resident else torch.cat([net.W[k].reshape(-1) for k in self.keys]).to(dev)
         self.g = torch.zeros(n, dtype=torch.float32, device=dev)
         self.m, self.v = torch.zeros_like(self.g), torch.zeros_like(self.g)
         self.t, self._micro = 0, 0
 
     def accumulate(self, grads: Dict[str, torch.Tensor]):
-        """Adds one micro-batch's gradients (host tensors keyed like the state_dict) into the arena."""
+        """Adds one micro-batch's gradients (tensors keyed like the state_dict; host, or device ones from a resident net, which
+        never cross the host) into the arena."""
         flat = torch.cat([grads[k].reshape(-1) for k in self.keys]).to(self.net.dev)
         self.g = flat if self._micro == 0 else self.net._ew(6, self.g, flat)
         self._micro += 1
@@ -620,6 +722,9 @@ class AdamTrainer:
         _lib.check(_lib.lib().tm_op_adam(_lib.ptr(self.p), _lib.ptr(self.g), _lib.ptr(self.m), _lib.ptr(self.v), self.n, self.lr, self.betas[0],
                                          self.betas[1], self.eps, self.wd, self.t, coef * avg, self.net._st()), "tm_op_adam")
         self._micro = 0
+        if self.net.resident:
+            self.net.params_updated()
+            return {"grad_norm": total, "clip_coef": coef}
         host = self.p.cpu()
         for k in self.keys:
             self.net.W[k] = host[self.off[k]:self.off[k] + self.net.W[k].numel()].reshape(self.net.W[k].shape).clone()

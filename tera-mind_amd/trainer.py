@@ -89,7 +89,7 @@ def load_checkpoint(path) -> Dict[str, object]:
 class Trainer:
     def __init__(self, cfg: PathConfig, state: Dict[str, "object"], tiles: TrainTileSet, batch_size: int, accum_batches: int = 1,
                  seed: int = 0, dropout_p: float = 0.1, lr: float = 2e-5, grad_clip: float = 1.0, loss_type: str = "mse",
-                 rank: int = 0, world: int = 1):
+                 rank: int = 0, world: int = 1, resident: bool = False):
         if loss_type not in ("mse", "l1"):
             raise ValueError(f"loss_type {loss_type!r}")
         g = tiles.geo
@@ -97,7 +97,7 @@ class Trainer:
             raise ValueError("tile set geometry does not match the model config")
         self.cfg, self.tiles, self.batch, self.accum, self.seed = cfg, tiles, int(batch_size), int(accum_batches), int(seed)
         self.loss_type, self.rank, self.world = loss_type, int(rank), int(world)
-        self.net = UNetTrain(cfg, state, tiles.dev, dropout_p=dropout_p)
+        self.net = UNetTrain(cfg, state, tiles.dev, dropout_p=dropout_p, resident=resident)
         self.opt = AdamTrainer(self.net, lr=lr, grad_clip=grad_clip)
         self.diffusion = SpacedDiffusionBeatGans(cfg.T, "ddpm", cfg.T, cfg.beta_scheduler)
         s = tiles.sampler
@@ -136,6 +136,8 @@ class Trainer:
         epoch, k = self.sampler.position(self.batch, self.global_step, 0, self.world)
         hp = {"batch_size": self.batch, "accum_batches": self.accum, "dropout_p": self.net.dropout_p, "lr": self.opt.lr,
               "grad_clip": self.opt.clip, "loss_type": self.loss_type}
+        if self.net.resident:
+            hp["resident"] = True
         return make_checkpoint(self.cfg, self.net.W, self.global_step, self._split(self.opt.m), self._split(self.opt.v), self.opt.t,
                                self.seed, epoch, k, hp)
 
@@ -143,8 +145,10 @@ class Trainer:
         torch.save(self.checkpoint(), path)
 
     @classmethod
-    def resume(cls, path, tiles: TrainTileSet, cfg: Optional[PathConfig] = None, rank: int = 0, world: int = 1) -> "Trainer":
-        """A trainer that continues the run saved at `path`; cfg defaults to the one stored in the checkpoint."""
+    def resume(cls, path, tiles: TrainTileSet, cfg: Optional[PathConfig] = None, rank: int = 0, world: int = 1,
+               resident: Optional[bool] = None) -> "Trainer":
+        """A trainer that continues the run saved at `path`; cfg defaults to the one stored in the checkpoint, `resident` to the
+        engine the run was saved with."""
         from .weights import strip_lightning_state_dict
         ck = load_checkpoint(path)
         cfg = cfg or config_from_dict(ck["config"])
@@ -152,7 +156,7 @@ class Trainer:
             raise ValueError(f"checkpoint of {ck['config_name']!r} resumed with config {cfg.name!r}")
         hp = ck["hparams"]
         tr = cls(cfg, strip_lightning_state_dict(ck), tiles, hp["batch_size"], hp["accum_batches"], ck["seed"], hp["dropout_p"], hp["lr"],
-                 hp["grad_clip"], hp["loss_type"], rank, world)
+                 hp["grad_clip"], hp["loss_type"], rank, world, bool(hp.get("resident", False)) if resident is None else bool(resident))
         tr.global_step = int(ck["global_step"])
         if "adam_m" in ck:
             o = tr.opt

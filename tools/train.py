@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--repeat", type=int, default=10, help="repetitions of the tile list per epoch (MBADataset repeat)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--resident", action="store_true", help="conv weights packed on the GPU once per optimizer step, conv gradients "
+                    "kept there, weight gradient on the matrix pipe (UNetTrain(resident=True))")
     a = ap.parse_args()
     nrna = 500 if a.mouse in ("609882", "609889") else 229
     cfg = prep_config_parm(a.data, a.batch_size, a.patch_size, 1, a.stain, a.mouse, nrna, a.rna_slc)
@@ -44,10 +46,10 @@ def main():
     tiles = TrainTileSet(a.data, cfg, a.device, seed=a.seed, repeat=a.repeat, accum_batches=accum)
     os.makedirs(a.out, exist_ok=True)
     if a.ckpt and "hparams" in load_checkpoint(a.ckpt):
-        tr = Trainer.resume(a.ckpt, tiles, cfg)
+        tr = Trainer.resume(a.ckpt, tiles, cfg, resident=True if a.resident else None)
     else:
         state = strip_lightning_state_dict(load_checkpoint(a.ckpt)) if a.ckpt else hashed_state_dict(cfg, a.seed)
-        tr = Trainer(cfg, state, tiles, a.batch_size, accum, a.seed)
+        tr = Trainer(cfg, state, tiles, a.batch_size, accum, a.seed, resident=a.resident)
     for _ in range(a.steps):
         t0 = time.time()
         info = tr.step()
