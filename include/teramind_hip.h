@@ -116,6 +116,12 @@ int tm_unet_forward(tm_model* m, const void* x, const int64_t* t, const void* rn
  *   tm_rna_pyramid_bytes   size of that buffer for (b, p1, p2)
  *   tm_rna_pyramid         rna_dense [b*p1*p2, gn, gn, rna_slc*500] fp32 -> pyramid (opaque; valid for this model, b, p1, p2)
  *   tm_unet_forward_rna    tm_unet_forward with the precomputed pyramid in place of rna_dense; bit-identical results.
+ * The buffer also holds what every AttnBlock derives from its pyramid level and its weights alone (MBAblocks.py:484-489:
+ * the 7C adaLN tensor Linear(SiLU(cond)) and k / v = Linear(cross-cond chunk), 9C values per conditioning voxel) for the
+ * blocks of the encoder, the middle and the `pred` decoder, so that a step runs neither those Linears nor SiLU(cond); the
+ * `pred2` decoder pass computes its own.  With the checkpoint configuration that is 2.8 MiB per encoder patch and 3.4 MiB
+ * per interior patch in fp32 (half of it in the 16-bit modes), about as much again as the levels: sized for a sampler's
+ * batch, not for a sweep (tm_unet_forward and tm_unet_forward_level0 compute this part inside each step).
  * The pyramid buffer is only read by tm_unet_forward_rna and may be shared by any number of steps. */
 size_t tm_rna_pyramid_bytes(const tm_model* m, int b, int p1, int p2);
 int tm_rna_pyramid(tm_model* m, const void* rna_dense, int b, int p1, int p2, void* pyramid, size_t pyramid_bytes,

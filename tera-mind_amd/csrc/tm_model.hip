@@ -1049,93 +1049,96 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
   return out;
 }
 
-// AttnBlock._forward with cond (model/MBAblocks.py:484-489); x updated in place
-static void attn_block(Ctx& cx, const AttnW& w, TV x, const Src& cond, int per_image, const TV* cond_act = nullptr) {
-  const size_t mark = cx.top;
-  const int N = x.N, Z = x.Z, S = x.H, C = w.C, cb = C / 8;
+// The conditioning side of an AttnBlock: SiLU(cond), mod = the 7C adaLN tensor Linear(SiLU(cond)) (shift / scale / gate of
+// both halves and the cross-cond chunk) and kv = Linear(cross-cond chunk).  cond is an RNA pyramid level, so none of it
+// depends on x or t: a caller that keeps the pyramid over the steps of a reverse loop keeps these too (attn_cond_stage).
+struct AttnGeom { bool half = false, mfma_core = false; int Sc = 0; };
+struct AttnCond {
+  TV mod, kv;                 // fp32 mode; 16-bit modes: kv of the generic fp32 attention core
+  TVH mod_h, kv_h;            // 16-bit modes (kv_h: the MFMA attention cores)
+};
+
+static AttnGeom attn_geom(const tm_model* m, const AttnW& w, int Z, int S) {
+  // The conditioning side at HALF resolution.  cond is an RNA pyramid level, and every level leaves its stage through a
+  // nearest x2 Upsample (unet_ours.py:290-295, MBAblocks.py:472-479): it -- and with it SiLU(cond), the 7C adaLN modulation
+  // Linear(SiLU(cond)) (MBAblocks.py:463-466,487), the cross-cond chunk, k and v (no positional term, :551-556) -- is
+  // constant over aligned 2 x 2 voxel blocks, also after to_collage (a shift by S/2, even).  So these tensors are computed
+  // once per block of four voxels ([.., Z, S/2, S/2]: a quarter of the Linear work and of the bytes of the largest tensor
+  // of the block) and their consumers read entry (z, y >> 1, x >> 1).  Same numbers, bit for bit (TM_ATTN_HALF=0: the
+  // full-resolution form, for A/B timing and the equality test).
+  static const bool no_half = getenv("TM_ATTN_HALF") && atoi(getenv("TM_ATTN_HALF")) == 0;
+  const int C = w.C, Tw = Z * (S / 2) * (S / 2);
+  AttnGeom g;
+  if (is_h16(m->cfg.dtype)) {
+    g.mfma_core = Tw == 128 || Tw == 64 || Tw == 32 || ((Tw == 256 || Tw == 512) && C <= 256);
+    g.half = !no_half && (Tw == 128 || Tw == 64 || Tw == 32) && S >= 4 && !(S & (S - 1));
+  } else {
+    // fp32: where the attention core has the k / v half-resolution read (T = 128 MFMA and T = 32 kernels, C a multiple of 128)
+    g.half = !no_half && S >= 4 && !(S & (S - 1)) && C % 128 == 0 && ((Tw == 128 && C <= 512) || Tw == 32);
+  }
+  g.Sc = g.half ? S / 2 : S;
+  return g;
+}
+
+// the block's mod and kv, allocated (nothing else: inside a pyramid buffer these are the persistent part)
+static AttnCond attn_cond_alloc(Ctx& cx, const AttnW& w, int N, int Z, int S) {
+  const AttnGeom g = attn_geom(cx.m, w, Z, S);
+  const int C = w.C, cb = C / 8;
+  AttnCond A;
   if (is_h16(cx.m->cfg.dtype)) {
+    A.mod_h = cx.tensor_h(N, 7 * cb, Z, g.Sc);
+    if (g.mfma_core) A.kv_h = cx.tensor_h(N, 2 * cb, Z, g.Sc);
+    else A.kv = cx.tensor(N, 2 * C, Z, S);
+  } else {
+    A.mod = cx.tensor(N, 7 * C, Z, g.Sc);
+    A.kv = cx.tensor(N, 2 * C, Z, g.Sc);
+  }
+  return A;
+}
+
+// computes them from cond; cond_act (fp32): SiLU(cond) where the pyramid has it and the cond is not re-tiled.  Scratch is released.
+static void attn_cond_run(Ctx& cx, const AttnW& w, const AttnCond& A, int N, int Z, int S, const Src& cond, int per_image,
+                          const TV* cond_act) {
+  const size_t mark = cx.top;
+  const AttnGeom g = attn_geom(cx.m, w, Z, S);
+  const bool half = g.half;
+  const int C = w.C, cb = C / 8, Sc = g.Sc;
+  if (is_h16(cx.m->cfg.dtype)) {
+    // bf16 operands for every Linear (fp32 accumulate).  Activations that only feed a Linear, and the 7C modulation tensor
+    // (shift/scale/gate/cross-cond chunks), are produced directly in bf16: the cross-cond chunk is the kv Linear's input as
+    // it stands.
     const int h_f16 = cx.m->cfg.dtype == TM_DTYPE_F16;
-    // bf16 operands for every Linear (fp32 accumulate); the residual stream x, q/k/v and the softmax stay fp32.
-    // Activations that only feed a Linear, and the 7C modulation tensor (shift/scale/gate/cross-cond chunks), are
-    // produced directly in bf16: the cross-cond chunk is the kv Linear's input as it stands.
     const int gbe = ((w.G + 7) / 8 + 1) / 2 * 2;
-    const int Tw = Z * (S / 2) * (S / 2);
-    const bool mfma_core = Tw == 128 || Tw == 64 || Tw == 32 || ((Tw == 256 || Tw == 512) && C <= 256);
-    // The conditioning side at HALF resolution.  cond is an RNA pyramid level, and every level leaves its stage through a
-    // nearest x2 Upsample (unet_ours.py:290-295, MBAblocks.py:472-479): it -- and with it SiLU(cond), the 7C adaLN modulation
-    // Linear(SiLU(cond)) (MBAblocks.py:463-466,487), the cross-cond chunk, k and v (no positional term, :551-556) -- is
-    // constant over aligned 2 x 2 voxel blocks, also after to_collage (a shift by S/2, even).  So these tensors are computed
-    // once per block of four voxels ([.., Z, S/2, S/2]: a quarter of the Linear work and of the bytes of the largest tensor
-    // of the block) and their consumers read entry (z, y >> 1, x >> 1).  Same numbers, bit for bit (TM_ATTN_HALF=0: the
-    // full-resolution form, for A/B timing and the equality test).
-    static const bool no_half = getenv("TM_ATTN_HALF") && atoi(getenv("TM_ATTN_HALF")) == 0;
-    const bool half = !no_half && (Tw == 128 || Tw == 64 || Tw == 32) && S >= 4 && !(S & (S - 1));
-    const int Sc = half ? S / 2 : S;
-    // src16: the source is a 16-bit stream tensor (x, the RNA level); otherwise an fp32 scratch tensor
-    auto prep_h = [&](const float* p, long ns, int Cbs, bool collage, const float* nw, const TVH* sc, const TVH* sh, int act,
-                      TVH dst, int Creal, bool src16 = true, int So = 0, int resample = RS_SAME) {
-      if (cx.dry) return;
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src_h = src16 ? 1 : 0;
-      P.src[0].p = p; P.src[0].nstride = ns; P.src[0].Cb = Cbs; P.src[0].collage = collage ? 1 : 0;
-      P.N = N; P.Z = Z; P.S = So ? So : S; P.p1 = cx.p1; P.p2 = cx.p2; P.act = act; P.per_image = per_image;
-      P.resample = resample;
-      P.norm_w = nw; P.inv_c = 1.0f / (float)Creal;
-      if (sc) { P.mod = MOD_VOXEL; P.mod_scale_h = sc->p; P.mod_shift_h = sh->p; P.mod_stride = sc->nstride; P.mod_half = half ? 1 : 0; }
-      P.out_h = dst.p; P.out_h_nstride = dst.nstride; P.pad_blocks = dst.Cb - Cbs; P.h_f16 = h_f16;
-      cx.check(launch_prep(P, cx.s));
-    };
     const long cplane = (long)Z * Sc * Sc * 8;                     // elements per channel block on the conditioning side
     TVH cact = cx.tensor_h(N, gbe, Z, Sc);
-    prep_h(cond.t.p, cond.t.nstride, cond.t.Cb, cond.collage, nullptr, nullptr, nullptr, 1, cact, w.G, true, Sc,
-           half ? RS_PICK2 : RS_SAME);
-    TVH mod = cx.tensor_h(N, 7 * cb, Z, Sc);
-    TV mod_geom = x; mod_geom.H = Sc; mod_geom.W = Sc; mod_geom.Cb = 7 * cb; mod_geom.C = 7 * C; mod_geom.p = nullptr;
-    mod_geom.nstride = (long)7 * cb * cplane;
-    run_conv1_h(cx, cact, w.adah, w.ada, mod_geom, nullptr, nullptr, 0, &mod);
-    // chunk order (MBAblocks.py:487): shift_msa, scale_msa, gate_msa, crss_cnd, shift_mlp, scale_mlp, gate_mlp
-    TVH sh_a = mod.blocks(0 * cb, cb), sc_a = mod.blocks(1 * cb, cb), g_a = mod.blocks(2 * cb, cb);
-    TVH crs = mod.blocks(3 * cb, cb), sh_m = mod.blocks(4 * cb, cb), sc_m = mod.blocks(5 * cb, cb), g_m = mod.blocks(6 * cb, cb);
-    TVH xa = cx.tensor_h(N, cb, Z, S), oh = cx.tensor_h(N, cb, Z, S);
-    prep_h(x.p, x.nstride, x.Cb, false, w.n1, &sc_a, &sh_a, 0, xa, C);
-    if (mfma_core) {
-      // q, k, v leave their Linears as 16-bit (the attention core's MFMA operands); softmax and accumulation are fp32
-      TVH q = cx.tensor_h(N, cb, Z, S), kv = cx.tensor_h(N, 2 * cb, Z, Sc);
-      TV q_geom = x; q_geom.p = nullptr;
-      TV kv_geom = x; kv_geom.H = Sc; kv_geom.W = Sc; kv_geom.Cb = 2 * cb; kv_geom.C = 2 * C; kv_geom.p = nullptr;
-      kv_geom.nstride = (long)2 * cb * cplane;
-      q_geom.nstride = (long)cb * x.plane();
-      run_conv1_h(cx, xa, w.qh, w.q, q_geom, nullptr, nullptr, 0, &q);
-      run_conv1_h(cx, crs, w.kvh, w.kv, kv_geom, nullptr, nullptr, 0, &kv);
-      if (!cx.dry) cx.check((h_f16 ? launch_window_attn_f16 : launch_window_attn_bf16)(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, oh, cx.s));
-    } else {
-      // other window sizes (z_size 1 / 4 / 8, patch_size 128): fp32 q / k / v into the generic fp32 attention core, its
-      // output rounded to the 16-bit type for proj
-      TV q = cx.tensor(N, C, Z, S), kv = cx.tensor(N, 2 * C, Z, S), o = cx.tensor(N, C, Z, S);
-      run_conv1_h(cx, xa, w.qh, w.q, q, nullptr, nullptr, 0);
-      run_conv1_h(cx, crs, w.kvh, w.kv, kv, nullptr, nullptr, 0);
-      if (!cx.dry) cx.check(launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, o, cx.s));
-      prep_h(o.p, o.nstride, o.Cb, false, nullptr, nullptr, nullptr, 0, oh, C, false);
+    if (!cx.dry) {
+      PrepLaunch P;
+      P.nsrc = 1;
+      P.src_h = 1;
+      P.src[0].p = cond.t.p; P.src[0].nstride = cond.t.nstride; P.src[0].Cb = cond.t.Cb; P.src[0].collage = cond.collage ? 1 : 0;
+      P.N = N; P.Z = Z; P.S = Sc; P.p1 = cx.p1; P.p2 = cx.p2; P.act = 1; P.per_image = per_image;
+      P.resample = half ? RS_PICK2 : RS_SAME;
+      P.inv_c = 1.0f / (float)w.G;
+      P.out_h = cact.p; P.out_h_nstride = cact.nstride; P.pad_blocks = cact.Cb - cond.t.Cb; P.h_f16 = h_f16;
+      cx.check(launch_prep(P, cx.s));
     }
-    // x <- x + gate * Linear(.): the 16-bit stream tensor is updated in place (each element is read and written by one lane)
-    TVH xh = as_h(x);
-    run_conv1_h(cx, oh, w.projh, w.proj, x, nullptr, nullptr, 0, &xh, &g_a, &xh, nullptr, half);
-    prep_h(x.p, x.nstride, x.Cb, false, w.n2, &sc_m, &sh_m, 0, xa, C);
-    TVH h1 = cx.tensor_h(N, 4 * cb, Z, S);
-    TV h1_geom = x; h1_geom.Cb = 4 * cb; h1_geom.C = 4 * C; h1_geom.p = nullptr; h1_geom.nstride = (long)4 * cb * x.plane();
-    run_conv1_h(cx, xa, w.fc1h, w.fc1, h1_geom, nullptr, nullptr, EPI_GELU, &h1);
-    run_conv1_h(cx, h1, w.fc2h, w.fc2, x, nullptr, nullptr, 0, &xh, &g_m, &xh, nullptr, half);
+    TV geom;
+    geom.N = N; geom.Z = Z; geom.H = Sc; geom.W = Sc;
+    TV mod_geom = geom; mod_geom.Cb = 7 * cb; mod_geom.C = 7 * C; mod_geom.nstride = (long)7 * cb * cplane;
+    TVH mod = A.mod_h;
+    run_conv1_h(cx, cact, w.adah, w.ada, mod_geom, nullptr, nullptr, 0, &mod);
+    const TVH crs = A.mod_h.blocks(3 * cb, cb);
+    if (g.mfma_core) {
+      // k, v leave their Linear as 16-bit (the attention core's MFMA operands)
+      TV kv_geom = geom; kv_geom.Cb = 2 * cb; kv_geom.C = 2 * C; kv_geom.nstride = (long)2 * cb * cplane;
+      TVH kv = A.kv_h;
+      run_conv1_h(cx, crs, w.kvh, w.kv, kv_geom, nullptr, nullptr, 0, &kv);
+    } else {
+      run_conv1_h(cx, crs, w.kvh, w.kv, A.kv, nullptr, nullptr, 0);
+    }
     cx.top = mark;
     return;
   }
-  // fp32: the same structure.  The conditioning side (SiLU(cond), the 7C modulation, k, v) at half resolution where the
-  // attention core has the k / v half-resolution read (T = 128 MFMA and T = 32 kernels, C a multiple of 128), see above;
-  // otherwise at full resolution, reusing the activated RNA level when the cond is not re-tiled (encoder / middle).
-  const int Tw = Z * (S / 2) * (S / 2);
-  static const bool no_half32 = getenv("TM_ATTN_HALF") && atoi(getenv("TM_ATTN_HALF")) == 0;
-  const bool half = !no_half32 && S >= 4 && !(S & (S - 1)) && C % 128 == 0 && ((Tw == 128 && C <= 512) || Tw == 32);
-  const int Sc = half ? S / 2 : S;
   TV cact = (cond_act && !half) ? *cond_act : cx.tensor(N, (w.G + 7) / 8 * 8, Z, Sc);
   if (!cx.dry && (half || !cond_act)) {
     PrepLaunch P;
@@ -1147,11 +1150,81 @@ static void attn_block(Ctx& cx, const AttnW& w, TV x, const Src& cond, int per_i
     P.out = cact.p; P.out_nstride = cact.nstride;
     cx.check(launch_prep(P, cx.s));
   }
-  TV mod = cx.tensor(N, 7 * C, Z, Sc);
-  run_conv(cx, cact, w.ada, mod, nullptr, nullptr, 0);
+  run_conv(cx, cact, w.ada, A.mod, nullptr, nullptr, 0);
+  run_conv(cx, A.mod.blocks(3 * cb, cb), w.kv, A.kv, nullptr, nullptr, 0);
+  cx.top = mark;
+}
+
+// AttnBlock._forward with cond (model/MBAblocks.py:484-489); x updated in place.  pre: the conditioning side computed
+// before (attn_cond_stage) for this block at this geometry; otherwise it is computed here, in the workspace.
+static void attn_block(Ctx& cx, const AttnW& w, TV x, const Src& cond, int per_image, const TV* cond_act = nullptr,
+                       const AttnCond* pre = nullptr) {
+  const size_t mark = cx.top;
+  const int N = x.N, Z = x.Z, S = x.H, C = w.C, cb = C / 8;
+  const AttnGeom g = attn_geom(cx.m, w, Z, S);
+  const bool half = g.half;
+  AttnCond loc;
+  if (!pre) {
+    loc = attn_cond_alloc(cx, w, N, Z, S);
+    attn_cond_run(cx, w, loc, N, Z, S, cond, per_image, cond_act);
+    pre = &loc;
+  }
+  if (is_h16(cx.m->cfg.dtype)) {
+    const int h_f16 = cx.m->cfg.dtype == TM_DTYPE_F16;
+    // The residual stream x, q/k/v and the softmax stay fp32; the Linears take 16-bit operands (see attn_cond_run).
+    // src16: the source is a 16-bit stream tensor (x); otherwise an fp32 scratch tensor
+    auto prep_h = [&](const float* p, long ns, int Cbs, const float* nw, const TVH* sc, const TVH* sh, TVH dst, int Creal,
+                      bool src16 = true) {
+      if (cx.dry) return;
+      PrepLaunch P;
+      P.nsrc = 1;
+      P.src_h = src16 ? 1 : 0;
+      P.src[0].p = p; P.src[0].nstride = ns; P.src[0].Cb = Cbs;
+      P.N = N; P.Z = Z; P.S = S; P.p1 = cx.p1; P.p2 = cx.p2; P.per_image = per_image;
+      P.norm_w = nw; P.inv_c = 1.0f / (float)Creal;
+      if (sc) { P.mod = MOD_VOXEL; P.mod_scale_h = sc->p; P.mod_shift_h = sh->p; P.mod_stride = sc->nstride; P.mod_half = half ? 1 : 0; }
+      P.out_h = dst.p; P.out_h_nstride = dst.nstride; P.pad_blocks = dst.Cb - Cbs; P.h_f16 = h_f16;
+      cx.check(launch_prep(P, cx.s));
+    };
+    const TVH mod = pre->mod_h;
+    // chunk order (MBAblocks.py:487): shift_msa, scale_msa, gate_msa, crss_cnd, shift_mlp, scale_mlp, gate_mlp
+    TVH sh_a = mod.blocks(0 * cb, cb), sc_a = mod.blocks(1 * cb, cb), g_a = mod.blocks(2 * cb, cb);
+    TVH sh_m = mod.blocks(4 * cb, cb), sc_m = mod.blocks(5 * cb, cb), g_m = mod.blocks(6 * cb, cb);
+    TVH xa = cx.tensor_h(N, cb, Z, S), oh = cx.tensor_h(N, cb, Z, S);
+    prep_h(x.p, x.nstride, x.Cb, w.n1, &sc_a, &sh_a, xa, C);
+    if (g.mfma_core) {
+      // q leaves its Linear as 16-bit like k, v (the attention core's MFMA operands); softmax and accumulation are fp32
+      TVH q = cx.tensor_h(N, cb, Z, S);
+      const TVH kv = pre->kv_h;
+      TV q_geom = x; q_geom.p = nullptr;
+      q_geom.nstride = (long)cb * x.plane();
+      run_conv1_h(cx, xa, w.qh, w.q, q_geom, nullptr, nullptr, 0, &q);
+      if (!cx.dry) cx.check((h_f16 ? launch_window_attn_f16 : launch_window_attn_bf16)(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, oh, cx.s));
+    } else {
+      // other window sizes (z_size 1 / 4 / 8, patch_size 128): fp32 q / k / v into the generic fp32 attention core, its
+      // output rounded to the 16-bit type for proj
+      TV q = cx.tensor(N, C, Z, S), o = cx.tensor(N, C, Z, S);
+      const TV kv = pre->kv;
+      run_conv1_h(cx, xa, w.qh, w.q, q, nullptr, nullptr, 0);
+      if (!cx.dry) cx.check(launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, o, cx.s));
+      prep_h(o.p, o.nstride, o.Cb, nullptr, nullptr, nullptr, oh, C, false);
+    }
+    // x <- x + gate * Linear(.): the 16-bit stream tensor is updated in place (each element is read and written by one lane)
+    TVH xh = as_h(x);
+    run_conv1_h(cx, oh, w.projh, w.proj, x, nullptr, nullptr, 0, &xh, &g_a, &xh, nullptr, half);
+    prep_h(x.p, x.nstride, x.Cb, w.n2, &sc_m, &sh_m, xa, C);
+    TVH h1 = cx.tensor_h(N, 4 * cb, Z, S);
+    TV h1_geom = x; h1_geom.Cb = 4 * cb; h1_geom.C = 4 * C; h1_geom.p = nullptr; h1_geom.nstride = (long)4 * cb * x.plane();
+    run_conv1_h(cx, xa, w.fc1h, w.fc1, h1_geom, nullptr, nullptr, EPI_GELU, &h1);
+    run_conv1_h(cx, h1, w.fc2h, w.fc2, x, nullptr, nullptr, 0, &xh, &g_m, &xh, nullptr, half);
+    cx.top = mark;
+    return;
+  }
+  // fp32: the same structure
+  const TV mod = pre->mod, kv = pre->kv;
   // chunk order (MBAblocks.py:487): shift_msa, scale_msa, gate_msa, crss_cnd, shift_mlp, scale_mlp, gate_mlp
   TV sh_a = mod.blocks(0 * cb, cb), sc_a = mod.blocks(1 * cb, cb), g_a = mod.blocks(2 * cb, cb);
-  TV crs = mod.blocks(3 * cb, cb), sh_m = mod.blocks(4 * cb, cb), sc_m = mod.blocks(5 * cb, cb), g_m = mod.blocks(6 * cb, cb);
+  TV sh_m = mod.blocks(4 * cb, cb), sc_m = mod.blocks(5 * cb, cb), g_m = mod.blocks(6 * cb, cb);
   TV xa = cx.tensor(N, C, Z, S);
   auto modulate = [&](const float* nw, const TV& sc, const TV& sh, TV dst) {
     if (cx.dry) return;
@@ -1164,9 +1237,8 @@ static void attn_block(Ctx& cx, const AttnW& w, TV x, const Src& cond, int per_i
     cx.check(launch_prep(P, cx.s));
   };
   modulate(w.n1, sc_a, sh_a, xa);
-  TV q = cx.tensor(N, C, Z, S), kv = cx.tensor(N, 2 * C, Z, Sc), o = cx.tensor(N, C, Z, S);
+  TV q = cx.tensor(N, C, Z, S), o = cx.tensor(N, C, Z, S);
   run_conv(cx, xa, w.q, q, nullptr, nullptr, 0);
-  run_conv(cx, crs, w.kv, kv, nullptr, nullptr, 0);
   if (!cx.dry) cx.check(launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, o, cx.s));
   run_conv(cx, o, w.proj, x, &x, &g_a, 0, 0, ZM_PAD1, half);
   modulate(w.n2, sc_m, sh_m, xa);
@@ -1191,7 +1263,9 @@ static void run_direct(Ctx& cx, const DirectW& w, const float* x, Acc5 ax, float
 // in the 16-bit modes) and, in fp32 mode, SiLU(level) of the first three (pyramid conv input and adaLN input of the
 // non-re-tiled AttnBlocks).  It depends on the genes only, not on t or x: a sampler that runs many steps on the same genes
 // (mode A, LitModel.gen_sample) computes it once (tm_rna_pyramid) and hands it to every step (tm_unet_forward_rna).
-struct RnaOut { TV rl[4]; TV rs[3]; };
+// ac: the conditioning side of the AttnBlocks of the encoder, the middle and the collage decoder, by index into
+// tm_model::attn (attn_cond_stage); empty where the caller computes it inside each block.
+struct RnaOut { TV rl[4]; TV rs[3]; std::vector<AttnCond> ac; };
 
 // Allocates the persistent outputs FIRST (so that their layout inside a caller-provided pyramid buffer is a pure function
 // of (b, p1, p2)), computes them, and releases the scratch.  rna == nullptr: layout only.
@@ -1326,6 +1400,38 @@ static void rna_stage(Ctx& cx, const float* rna, RnaOut& R, const void* l0_in = 
   cx.top = rna_mark;                                              // tok / fp32 scratch are dead (the stream orders reuse)
 }
 
+// The step-invariant part of the AttnBlocks behind the levels of a pyramid buffer: mod and kv (attn_cond_alloc) of every
+// AttnBlock of the encoder, the middle and the `pred` decoder, each with the geometry it has there (encoder / middle: Ne
+// patches of the encoder grid; decoder: Nd patches, cond through the collage remap).  Called with cx.top behind the levels
+// (rna_stage has released its scratch): all persistent tensors first, so that the layout is a pure function of
+// (b, p1, p2), then one block after the other with its scratch.  run == false: layout only.  The `pred2` decoder pass is
+// not covered (another geometry of the same blocks, and not on the sampler's path): it computes its own in-step.
+static void attn_cond_stage(Ctx& cx, RnaOut& R, bool run) {
+  tm_model* m = cx.m;
+  const int Z = m->z, L = m->L, ps = m->cfg.patch_size;
+  const int ne_img = cx.p1 * cx.p2, nd_img = (cx.p1 - 1) * (cx.p2 - 1);
+  const bool h16 = is_h16(m->cfg.dtype);
+  struct Site { int idx, lvl; bool col; };
+  std::vector<Site> sites;
+  for (const EncEntry& e : m->enc)
+    for (const Op& op : e.ops) if (op.kind == 1) sites.push_back({op.idx, e.lvl, false});
+  sites.push_back({m->mid[1].idx, L - 1, false});
+  for (const DecEntry& e : m->dec)
+    for (const Op& op : e.ops) if (op.kind == 1) sites.push_back({op.idx, e.lvl, true});
+  R.ac.assign(m->attn.size(), AttnCond());
+  for (const Site& st : sites) R.ac[st.idx] = attn_cond_alloc(cx, m->attn[st.idx], st.col ? cx.Nd : cx.Ne, Z, ps >> st.lvl);
+  const size_t mark = cx.top;
+  const bool was_dry = cx.dry;
+  cx.dry = was_dry || !run;
+  for (const Site& st : sites) {
+    const int ri = L - 1 - st.lvl;
+    attn_cond_run(cx, m->attn[st.idx], R.ac[st.idx], st.col ? cx.Nd : cx.Ne, Z, ps >> st.lvl, {R.rl[ri], st.col},
+                  st.col ? nd_img : ne_img, (!st.col && !h16 && ri < 3) ? &R.rs[ri] : nullptr);
+  }
+  cx.dry = was_dry;
+  cx.top = mark;
+}
+
 // rna != nullptr: compute the conditioning inside this call's workspace; otherwise R_in (tm_rna_pyramid) is used
 static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* rna, const RnaOut* R_in, float* pred,
                         float* pred2, const void* l0_in = nullptr) {
@@ -1348,6 +1454,7 @@ static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* 
   TV rl[4], rs[3];
   for (int i = 0; i < 4; ++i) rl[i] = R_in->rl[i];
   for (int i = 0; i < 3; ++i) rs[i] = R_in->rs[i];
+  auto pre = [&](int idx) -> const AttnCond* { return R_in->ac.empty() ? nullptr : &R_in->ac[idx]; };
   for (int i = 0; i < 4; ++i) { TV v = rl[i]; v.C = m->rw[i]; dump_tv(cx, "rna." + std::to_string(i), v); }
   // ---- stem ----
   std::vector<std::vector<TV>> skips(L);
@@ -1365,7 +1472,7 @@ static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* 
     if (e.cat) src.push_back({cond, false});
     for (const Op& op : e.ops) {
       if (op.kind == 0) h = res_block(cx, m->res[op.idx], src, Ne, ne_img, So, op.mode, nullptr);
-      else attn_block(cx, m->attn[op.idx], h, {cond, false}, ne_img, (L - 1 - e.lvl) < 3 ? &rs[L - 1 - e.lvl] : nullptr);
+      else attn_block(cx, m->attn[op.idx], h, {cond, false}, ne_img, (L - 1 - e.lvl) < 3 ? &rs[L - 1 - e.lvl] : nullptr, pre(op.idx));
     }
     skips[e.lvl].push_back(h);
     const Op& last = e.ops.back();
@@ -1376,7 +1483,7 @@ static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* 
     std::vector<Src> src = {{h, false}, {rl[0], false}};
     const int So = ps >> (L - 1);
     h = res_block(cx, m->res[m->mid[0].idx], src, Ne, ne_img, So, RS_SAME, nullptr);
-    attn_block(cx, m->attn[m->mid[1].idx], h, {rl[0], false}, ne_img, &rs[0]);
+    attn_block(cx, m->attn[m->mid[1].idx], h, {rl[0], false}, ne_img, &rs[0], pre(m->mid[1].idx));
     std::vector<Src> src2 = {{h, false}};
     h = res_block(cx, m->res[m->mid[2].idx], src2, Ne, ne_img, So, RS_SAME, nullptr);
     dump_tv(cx, "middle_block", h);
@@ -1397,7 +1504,7 @@ static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* 
         if (op.kind == 0) {
           if (op.mode == RS_SAME) hd = res_block(cx, m->res[op.idx], src, N, per, So, RS_SAME, nullptr);
           else { std::vector<Src> s1 = {{hd, false}}; hd = res_block(cx, m->res[op.idx], s1, N, per, So * 2, RS_UP2, nullptr); }
-        } else attn_block(cx, m->attn[op.idx], hd, cond, per);
+        } else attn_block(cx, m->attn[op.idx], hd, cond, per, nullptr, col ? pre(op.idx) : nullptr);
       }
       hd_col = false;
       if (col) { const std::string& p0 = m->res[e.ops[0].idx].pfx; dump_tv(cx, p0.substr(0, p0.size() - 2), hd); }
@@ -1473,6 +1580,7 @@ extern "C" size_t tm_rna_pyramid_bytes(const tm_model* m, int b, int p1, int p2)
   pyramid_ctx(cx, const_cast<tm_model*>(m), b, p1, p2, nullptr, 0, nullptr);
   RnaOut R;
   rna_stage(cx, nullptr, R);
+  attn_cond_stage(cx, R, false);
   return cx.peak + 512;
 }
 extern "C" int tm_rna_pyramid(tm_model* m, const void* rna_dense, int b, int p1, int p2, void* pyramid, size_t pyramid_bytes,
@@ -1486,6 +1594,7 @@ extern "C" int tm_rna_pyramid(tm_model* m, const void* rna_dense, int b, int p1,
   pyramid_ctx(cx, m, b, p1, p2, pyramid, pyramid_bytes, (hipStream_t)stream);
   RnaOut R;
   rna_stage(cx, (const float*)rna_dense, R);
+  attn_cond_stage(cx, R, true);
   if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
   return TM_OK;
 }
@@ -1551,6 +1660,10 @@ extern "C" int tm_unet_forward_rna(tm_model* m, const void* x, const int64_t* t,
   pyramid_ctx(px, m, b, p1, p2, const_cast<void*>(pyramid), pyramid_bytes, (hipStream_t)stream);
   RnaOut R;
   rna_stage(px, nullptr, R);
+  attn_cond_stage(px, R, false);
+  // TM_ATTN_HOIST=0: every AttnBlock computes its conditioning side in-step, as tm_unet_forward does (A/B timing)
+  static const bool no_hoist = getenv("TM_ATTN_HOIST") && atoi(getenv("TM_ATTN_HOIST")) == 0;
+  if (no_hoist) R.ac.clear();
   Ctx cx;
   cx.m = m; cx.s = (hipStream_t)stream;
   cx.base = (char*)(((uintptr_t)workspace + 255) / 256 * 256);
