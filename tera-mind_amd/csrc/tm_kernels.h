@@ -286,6 +286,10 @@ hipError_t launch_modnorm_bwd(const TV& x, const float* g, const float* w, const
 hipError_t launch_attn_train(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
                              float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd,
                              hipStream_t s);                                            // scratch (bwd): 2 * N * 4 * Cb * 8 floats
+// windows of 256 / 512 tokens, C <= 256 (key-blocked fp32 MFMA form); scratch: attn_train_long_scratch_floats(...) floats, always
+hipError_t launch_attn_train_long(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
+                                  float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd, hipStream_t s);
+size_t attn_train_long_scratch_floats(int N, int Cb, int Z, int S, bool bwd);
 
 hipError_t launch_gemm_f32(const float* A, const float* B, const float* bias, float* C, int M, int N, int K, const long* strides9, int batch,
                            int bias_mode, int accumulate, float alpha, hipStream_t s);   // strides: sam sak sbk sbn scm scn sab sbb scb

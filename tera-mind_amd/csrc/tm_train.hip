@@ -886,6 +886,357 @@ hipError_t launch_attn_train(const TV& q, const TV& k, const TV& v, const float*
   return hipGetLastError();
 }
 
+// ---- the same core for long windows (T = 256 / 512 tokens: Z = 4 / 8 at the resolution-16 AttnBlocks), fp32 MFMA ----------
+// No T x T matrix exists anywhere: tokens are walked in blocks of 128 and every workgroup handles one 128-token block of
+// one window against the T / 128 blocks of the other side, through one [128][132] LDS tile.  All four matrix products and
+// both logit-like products (qh kh^T, do v^T) run on v_mfma_f32_32x32x2_f32.  Five kernels, launched in this order:
+//
+//   attn_long_norm_kernel      per voxel (64 per workgroup): qh = (q r) qw, kh = (k r) kw into scratch (CB8, pad channels 0),
+//                              r = 1 / sqrt(sum_c x^2 / C + eps); the sum of squares is taken per wave over its channel
+//                              blocks in index order, then (w0 + w1 + w2 + w3).
+//   attn_long_stats_kernel     workgroup = (patch, window, query block).  Lane = one query (the two half-waves of a query
+//                              hold complementary keys).  Pass 1: m = max_j s over all keys.  Pass 2: l = sum_j expf(s - m)
+//                              and, backward only, E = sum_j expf(s - m) dP, dP = do . v.  Writes m, 1 / l and
+//                              D = E / l = rowsum(dP o P) per query.  Exact two-pass softmax: nothing is rescaled.
+//   attn_long_prod_kernel<R>   workgroup = (patch, window, 128-token block of the OWNING side); it alone writes its rows:
+//                                R = 0  o   = P  v      owner: query block      R = 2  dv  = P^T  do    owner: key block
+//                                R = 1  dqh = dS kh     owner: query block      R = 3  dkh = dS^T qh    owner: key block
+//                              For every block of the other side, in index order: logits (and dP for R = 1, 3) by MFMA,
+//                              p = expf(s - m) * (1 / l), dS = p (dP - D) / C with the saved m, 1 / l, D of the QUERY of the
+//                              pair -- the expression of the stats kernel, no fast-math form anywhere -- into the LDS tile
+//                              [own token][other token]; then out^T[c][own] += X^T[c][other] . tile^T, X staged 32 channels
+//                              at a time.  dqh / dkh go to dq / dk.
+//   attn_long_norm_bwd_kernel  per voxel, in place on dq / dk: g = dxh w;  dx = r g - x r^3 mean_c(g x);  partial of
+//                              d(norm weight)[c] = wave_sum over the workgroup's 64 voxels of dxh x r.
+//   prep_bwd_reduce_dw_kernel  the per-workgroup partials in index order (as modnorm_bwd).
+//
+// Accumulation orders (what tests/test_gpu_window_attn_train_long.py derives its bounds from):
+//   logit / dP   one MFMA chain per element over the channel blocks in index order; step (cb, kk) adds channels
+//                cb * 8 + kk and cb * 8 + 4 + kk: C terms (the pad channels of the last block add exact zeros).
+//   m, l, E      per lane the 64 values of a key block in (ct, r) register order, plus the other half-wave's partial
+//                (lane ^ 32); the blocks' partials are added in block order: T terms, depth 64 + 1 + T / 128.
+//   o, dv, dqh, dkh   one MFMA chain per element: other-side blocks in index order, inside a block tokens u0 + kk and
+//                u0 + 4 + kk per step, u0 = 0, 8, ..: T terms.
+// Every element of o, dq, dk, dv has one owning workgroup and one chain: no atomics, two calls give the same bits.
+// LDS (dynamic): tile 128 * 132 + X^T 32 * 132 + token offsets T + (m, 1 / l, D) 3 T floats = 88,576 B at T = 256 and
+// 92,672 B at T = 512.  C <= 256 (eight 32-channel accumulator tiles per lane).
+// The tile is lane-private staging, not shared state: a lane writes columns ct * 32 + 8 g + 4 h + j of its own token's row and
+// reads back exactly those (u0 + 4 h + kk) -- it turns the logit accumulators' register layout into the B operand's k order;
+// only X^T crosses waves.  Its 67,584 B hold the product kernels at one workgroup per CU, which the 134 - 164 VGPRs + 192 - 256
+// AGPRs per lane (one wave per SIMD) do anyway: shrinking the tile alone buys no occupancy.
+struct AttnLongArgs {
+  const float *q, *k, *v, *qh, *kh, *dout, *qw, *kw;
+  float *stats;                         // [patch][window][3][T]: m, 1 / l, D
+  float *o, *dq, *dk, *dv;
+  long ns, plane; int N, C, Cb, Z, S;
+};
+constexpr int AL_PS = 132;              // row pitch (floats) of the LDS tile and of an X^T row
+
+// per voxel: xh = (x r) w for q (blockIdx.y = 0) and k (1)
+__global__ __launch_bounds__(256) void attn_long_norm_kernel(AttnLongArgs a, float* qh, float* kh) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* x = blockIdx.y ? a.k : a.q;
+  const float* w = blockIdx.y ? a.kw : a.qw;
+  float* y = blockIdx.y ? kh : qh;
+  const long vpn = a.plane / 8, vidx = (long)blockIdx.x * 64 + lane;
+  const bool valid = vidx < vpn * a.N;
+  const int n = valid ? (int)(vidx / vpn) : 0;
+  const long base = (long)n * a.ns + (valid ? (vidx - (long)n * vpn) * 8 : 0);
+  float ssq = 0.f;
+  if (valid)
+    for (int cb = wv; cb < a.Cb; cb += 4)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float v = cb * 8 + j < a.C ? x[base + (long)cb * a.plane + j] : 0.f; ssq += v * v; }
+  red[wv][lane] = ssq;
+  __syncthreads();
+  const float r = 1.0f / sqrtf((red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) / (float)a.C + TM_EPS);
+  if (!valid) return;
+  for (int cb = wv; cb < a.Cb; cb += 4)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = cb * 8 + j;
+      y[base + (long)cb * a.plane + j] = c < a.C ? x[base + (long)cb * a.plane + j] * r * w[c] : 0.f;
+    }
+}
+
+// token t of window (wy, wx) -> float offset inside one channel block: tokens in (z, h, w) order
+__device__ __forceinline__ void attn_long_tokoff(int* tokoff, int T, int S, int win) {
+  const int hs = S / 2, wy = win >> 1, wx = win & 1;
+  for (int t = threadIdx.x; t < T; t += 256) {
+    const int z = t / (hs * hs), r = t - z * hs * hs, yl = r / hs, xl = r - yl * hs;
+    tokoff[t] = ((z * S + wy * hs + yl) * S + wx * hs + xl) * 8;
+  }
+}
+// acc[ct][r] = sum_c own[c] * other[oblk * 128 + ct * 32 + (r & 3) + 8 (r >> 2) + 4 h][c]: lane = own token, registers = the
+// tokens of the other side's block.  ownp / otherb: CB8 tensors of one patch; channels >= C count as zero on both
+// sides (v and dout are the caller's tensors: a NaN in a pad slot must not reach 0 * NaN).
+__device__ __forceinline__ void attn_long_dots(f32x16 (&acc)[4], const float* ownp, const float* otherb, const int* tokoff, int oblk,
+                                               int C, int Cb, long plane) {
+  const int i32 = threadIdx.x & 31, h = (threadIdx.x & 63) >> 5;
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+  const float* op[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) op[ct] = otherb + tokoff[oblk * 128 + ct * 32 + i32] + 4 * h;
+  f32x4 wn = *(const f32x4*)(ownp + 4 * h), on[4];
+#pragma unroll
+  for (int ct = 0; ct < 4; ++ct) on[ct] = *(const f32x4*)op[ct];
+  for (int cb = 0; cb < Cb; ++cb) {
+    f32x4 wf = wn, of[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) of[ct] = on[ct];
+    if (cb * 8 + 8 > C) {                  // the last block's pad channels: exact zeros on both sides, whatever the slots hold
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) {
+        const bool in = cb * 8 + 4 * h + kk < C;
+        wf[kk] = in ? wf[kk] : 0.f;
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) of[ct][kk] = in ? of[ct][kk] : 0.f;
+      }
+    }
+    if (cb + 1 < Cb) {
+      const long po = (long)(cb + 1) * plane;
+      wn = *(const f32x4*)(ownp + 4 * h + po);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) on[ct] = *(const f32x4*)(op[ct] + po);
+    }
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(of[ct][kk], wf[kk], acc[ct], 0, 0, 0);
+  }
+}
+
+template <int T, bool BWD>
+__global__ __launch_bounds__(256) void attn_long_stats_kernel(AttnLongArgs a) {
+#pragma clang fp contract(off)          // s / C - m, e * dP stay separate roundings here and in the product kernel: one P
+  constexpr int NB = T / 128;
+  __shared__ int tokoff[T];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i32 = lane & 31;
+  const int qblk = blockIdx.x % NB, win = (blockIdx.x / NB) & 3, n = blockIdx.x / (4 * NB);
+  attn_long_tokoff(tokoff, T, a.S, win);
+  __syncthreads();
+  const long nb = (long)n * a.ns;
+  const int qt = qblk * 128 + wv * 32 + i32;
+  const float invC = 1.0f / (float)a.C;
+  f32x16 sa[4], da[4];
+  float m = -INFINITY;
+  for (int kblk = 0; kblk < NB; ++kblk) {
+    attn_long_dots(sa, a.qh + nb + tokoff[qt], a.kh + nb, tokoff, kblk, a.C, a.Cb, a.plane);
+    float bm = -INFINITY;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) bm = fmaxf(bm, sa[ct][r] * invC);
+    m = fmaxf(m, fmaxf(bm, __shfl_xor(bm, 32, 64)));
+  }
+  float l = 0.f, E = 0.f;
+  for (int kblk = 0; kblk < NB; ++kblk) {
+    attn_long_dots(sa, a.qh + nb + tokoff[qt], a.kh + nb, tokoff, kblk, a.C, a.Cb, a.plane);
+    if (BWD) attn_long_dots(da, a.dout + nb + tokoff[qt], a.v + nb, tokoff, kblk, a.C, a.Cb, a.plane);
+    float bs = 0.f, be = 0.f;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const float e = expf(sa[ct][r] * invC - m);
+        bs += e;
+        if (BWD) be += e * da[ct][r];
+      }
+    l += bs + __shfl_xor(bs, 32, 64);
+    if (BWD) E += be + __shfl_xor(be, 32, 64);
+  }
+  if (lane < 32) {
+    float* st = a.stats + ((long)n * 4 + win) * 3 * T;
+    const float inv = 1.0f / l;
+    st[qt] = m; st[T + qt] = inv; st[2 * T + qt] = BWD ? E * inv : 0.f;
+  }
+}
+
+// ROLE 0: o = P v;  1: dqh = dS kh;  2: dv = P^T do;  3: dkh = dS^T qh   (see the header above)
+template <int T, int ROLE>
+__global__ __launch_bounds__(256) void attn_long_prod_kernel(AttnLongArgs a) {
+#pragma clang fp contract(off)
+  constexpr int NB = T / 128, PS = AL_PS;
+  constexpr bool OWN_Q = ROLE < 2, NEED_DS = (ROLE & 1) != 0;
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* Pm = sm;                          // [128 own tokens][PS]: P or dS against the current block of the other side
+  float* Xt = Pm + 128 * PS;               // [32 channels][PS]: X^T of the current block
+  int* tokoff = (int*)(Xt + 32 * PS);      // [T]
+  float* st = (float*)(tokoff + T);        // [3][T]: m, 1 / l, D of every query of the window
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, i32 = lane & 31, h = lane >> 5;
+  const int blk = blockIdx.x % NB, win = (blockIdx.x / NB) & 3, n = blockIdx.x / (4 * NB);
+  attn_long_tokoff(tokoff, T, a.S, win);
+  for (int i = tid; i < 3 * T; i += 256) st[i] = a.stats[((long)n * 4 + win) * 3 * T + i];
+  __syncthreads();
+  const long nb = (long)n * a.ns;
+  const int C = a.C, Cb = a.Cb;
+  const int ownloc = wv * 32 + i32, ownt = blk * 128 + ownloc, ownoff = tokoff[ownt];
+  const float invC = 1.0f / (float)C;
+  const float* s_own = (OWN_Q ? a.qh : a.kh) + nb + ownoff;       // logits: own . other
+  const float* s_oth = (OWN_Q ? a.kh : a.qh) + nb;
+  const float* d_own = (OWN_Q ? a.dout : a.v) + nb + ownoff;      // dP: do . v
+  const float* d_oth = (OWN_Q ? a.v : a.dout) + nb;
+  const float* X = (ROLE == 0 ? a.v : ROLE == 1 ? a.kh : ROLE == 2 ? a.dout : a.qh) + nb;
+  float* out = (ROLE == 0 ? a.o : ROLE == 1 ? a.dq : ROLE == 2 ? a.dv : a.dk) + nb;
+  f32x16 sa[4], da[4], oc[8];
+#pragma unroll
+  for (int tI = 0; tI < 8; ++tI)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) oc[tI][r] = 0.f;
+  const int su = tid & 127, scb = tid >> 7;                        // X staging: token su of the block, channel blocks scb, scb + 2
+  float* prow = Pm + ownloc * PS;
+  const float* pfrag = prow + 4 * h;                               // B operand: tile[own][other0 + 4h ..]
+  const float* xfrag = Xt + i32 * PS + 4 * h;                      // A operand: X^T[channel][other0 + 4h ..]
+  for (int oblk = 0; oblk < NB; ++oblk) {
+    attn_long_dots(sa, s_own, s_oth, tokoff, oblk, C, Cb, a.plane);
+    if (NEED_DS) attn_long_dots(da, d_own, d_oth, tokoff, oblk, C, Cb, a.plane);
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 pk;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int qi = OWN_Q ? ownt : oblk * 128 + ct * 32 + 8 * g + 4 * h + j;     // the query of this pair
+          const float p = expf(sa[ct][4 * g + j] * invC - st[qi]) * st[T + qi];
+          pk[j] = NEED_DS ? p * (da[ct][4 * g + j] - st[2 * T + qi]) * invC : p;
+        }
+        *(f32x4*)(prow + ct * 32 + 8 * g + 4 * h) = pk;
+      }
+    const float* xsrc = X + tokoff[oblk * 128 + su];
+    for (int c0 = 0; c0 < C; c0 += 32) {
+      __syncthreads();                                             // X^T free (the tile needs no barrier: lane-private, see header)
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int cb = c0 / 8 + scb + 2 * half;
+        f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+        if (cb < Cb) { v0 = *(const f32x4*)(xsrc + (long)cb * a.plane); v1 = *(const f32x4*)(xsrc + (long)cb * a.plane + 4); }
+        float* d = Xt + ((scb + 2 * half) * 8) * PS + su;
+        d[0 * PS] = v0[0]; d[1 * PS] = v0[1]; d[2 * PS] = v0[2]; d[3 * PS] = v0[3];
+        d[4 * PS] = v1[0]; d[5 * PS] = v1[1]; d[6 * PS] = v1[2]; d[7 * PS] = v1[3];
+      }
+      __syncthreads();
+      const int tI = c0 / 32;
+#pragma unroll
+      for (int cc = 0; cc < 8; ++cc)
+        if (cc == tI) {
+#pragma unroll 4
+          for (int u0 = 0; u0 < 128; u0 += 8) {
+            const f32x4 af = *(const f32x4*)(xfrag + u0), bf = *(const f32x4*)(pfrag + u0);
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) oc[cc] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[kk], bf[kk], oc[cc], 0, 0, 0);
+          }
+        }
+    }
+    __syncthreads();                                               // X^T consumed before the next block restages it
+  }
+  // lane = own token; accumulator quad g of tile tI = channels tI * 32 + 8 g + 4 h .. + 3; pad channels are written as zeros
+#pragma unroll
+  for (int tI = 0; tI < 8; ++tI)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int cb = tI * 4 + g, c = cb * 8 + 4 * h;
+      if (cb < Cb)
+        *(f32x4*)(out + ownoff + (long)cb * a.plane + 4 * h) = f32x4{c < C ? oc[tI][4 * g] : 0.f, c + 1 < C ? oc[tI][4 * g + 1] : 0.f,
+                                                                    c + 2 < C ? oc[tI][4 * g + 2] : 0.f, c + 3 < C ? oc[tI][4 * g + 3] : 0.f};
+    }
+}
+
+// per voxel (64 per workgroup, a wave per channel block): the RMSNorm backward in place on dx (holding dxh), q (y = 0) / k (1)
+__global__ __launch_bounds__(256) void attn_long_norm_bwd_kernel(AttnLongArgs a, float* part_q, float* part_k) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const float* x = blockIdx.y ? a.k : a.q;
+  const float* w = blockIdx.y ? a.kw : a.qw;
+  float* dx = blockIdx.y ? a.dk : a.dq;
+  float* part = blockIdx.y ? part_k : part_q;
+  const long vpn = a.plane / 8, vidx = (long)blockIdx.x * 64 + lane;
+  const bool valid = vidx < vpn * a.N;
+  const int n = valid ? (int)(vidx / vpn) : 0;
+  const long base = (long)n * a.ns + (valid ? (vidx - (long)n * vpn) * 8 : 0);
+  float ssq = 0.f;
+  if (valid)
+    for (int cb = wv; cb < a.Cb; cb += 4)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float v = cb * 8 + j < a.C ? x[base + (long)cb * a.plane + j] : 0.f; ssq += v * v; }
+  red[wv][lane] = ssq;
+  __syncthreads();
+  const float r = 1.0f / sqrtf((red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) / (float)a.C + TM_EPS);
+  __syncthreads();
+  float dot = 0.f;
+  for (int cb = wv; cb < a.Cb; cb += 4)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = cb * 8 + j;
+      float g = 0.f, xv = 0.f;
+      if (valid && c < a.C) { g = dx[base + (long)cb * a.plane + j]; xv = x[base + (long)cb * a.plane + j]; }
+      dot += g * w[c] * xv;
+      const float pw = wave_sum(g * xv * r);
+      if (lane == 0) part[(long)blockIdx.x * a.Cb * 8 + c] = pw;
+    }
+  red[wv][lane] = dot;
+  __syncthreads();
+  const float mean_dot = (red[0][lane] + red[1][lane] + red[2][lane] + red[3][lane]) / (float)a.C;
+  if (!valid) return;
+  for (int cb = wv; cb < a.Cb; cb += 4)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = cb * 8 + j;
+      const long o = base + (long)cb * a.plane + j;
+      dx[o] = c < a.C ? r * dx[o] * w[c] - x[o] * r * r * r * mean_dot : 0.f;
+    }
+}
+
+size_t attn_train_long_scratch_floats(int N, int Cb, int Z, int S, bool bwd) {
+  const size_t vox = (size_t)N * Z * S * S;                         // qh, kh; m, 1 / l, D; the two norm-weight partials
+  return 2 * vox * Cb * 8 + 3 * vox + (bwd ? 2 * ((vox + 63) / 64) * Cb * 8 : 0);
+}
+template <int T>
+static hipError_t launch_attn_train_long_t(AttnLongArgs a, float* dqw, float* dkw, float* scratch, bool bwd, hipStream_t s) {
+  const size_t vox = (size_t)a.N * a.Z * a.S * a.S, nv = (vox + 63) / 64;
+  const int Cp = a.Cb * 8;
+  float *qh = scratch, *kh = qh + vox * Cp, *part_q = kh + vox * Cp + 3 * vox, *part_k = part_q + nv * Cp;
+  a.qh = qh; a.kh = kh; a.stats = kh + vox * Cp;
+  const size_t lds = ((size_t)(128 + 32) * AL_PS + 4 * T) * sizeof(float);
+  static DevOnce attr_done;
+  if (attr_done.need()) {
+    const void* f[4] = {(const void*)attn_long_prod_kernel<T, 0>, (const void*)attn_long_prod_kernel<T, 1>,
+                        (const void*)attn_long_prod_kernel<T, 2>, (const void*)attn_long_prod_kernel<T, 3>};
+    for (const void* fn : f) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) return e;
+    }
+    attr_done.mark();
+  }
+  const dim3 gv((unsigned)nv, 2), gw((unsigned)(a.N * 4 * (T / 128)));
+  hipLaunchKernelGGL(attn_long_norm_kernel, gv, dim3(256), 0, s, a, qh, kh);
+  if (!bwd) {
+    hipLaunchKernelGGL((attn_long_stats_kernel<T, false>), gw, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((attn_long_prod_kernel<T, 0>), gw, dim3(256), lds, s, a);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL((attn_long_stats_kernel<T, true>), gw, dim3(256), 0, s, a);
+  hipLaunchKernelGGL((attn_long_prod_kernel<T, 1>), gw, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((attn_long_prod_kernel<T, 2>), gw, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((attn_long_prod_kernel<T, 3>), gw, dim3(256), lds, s, a);
+  hipLaunchKernelGGL(attn_long_norm_bwd_kernel, gv, dim3(256), 0, s, a, part_q, part_k);
+  hipLaunchKernelGGL(prep_bwd_reduce_dw_kernel, dim3((unsigned)((Cp + 63) / 64)), dim3(64), 0, s, part_q, (long)nv, Cp, dqw);
+  hipLaunchKernelGGL(prep_bwd_reduce_dw_kernel, dim3((unsigned)((Cp + 63) / 64)), dim3(64), 0, s, part_k, (long)nv, Cp, dkw);
+  return hipGetLastError();
+}
+hipError_t launch_attn_train_long(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
+                                  float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd, hipStream_t s) {
+  const int S = q.H, T = q.Z * (S / 2) * (S / 2);
+  if (q.H != q.W || (S & 1) || (T != 256 && T != 512) || q.C > 256 || k.nstride != q.nstride || v.nstride != q.nstride || !scratch)
+    return hipErrorInvalidValue;
+  AttnLongArgs a{q.p, k.p, v.p, nullptr, nullptr, dout, qw, kw, nullptr, o, dq, dk, dv, q.nstride, q.plane(), q.N, q.C, q.Cb, q.Z, S};
+  return T == 256 ? launch_attn_train_long_t<256>(a, dqw, dkw, scratch, bwd, s) : launch_attn_train_long_t<512>(a, dqw, dkw, scratch, bwd, s);
+}
+
 
 // ==================================================================================================================
 // Small dense pieces of the training path that are not convs over the patch volume: the Linears over [tokens][features]

@@ -6,7 +6,8 @@ The reference trains through torch.autograd over stock modules (experiment.py:12
 model/unet_ours.py).  Here `UNetTrain.forward` records a tape of ops, each with a hand-written adjoint:
 
     conv3 / conv1     tm_op_conv_mfma          | tm_op_conv_dgrad (same kernel, transposed + flipped weights), tm_op_conv_wgrad
-                      ((1,3,3) and the down_z (kz,3,3) kernels run embedded in the 3x3x3 'same' conv, sliced afterwards)
+                      ((1,3,3) and the down_z (kz,3,3) kernels run embedded in the 3x3x3 'same' conv, sliced afterwards; down_z at
+                      kz = 5 (rna_slc 8) is training.DownZTrain: its z taps as five shifted in-plane convs)
     SiLU(RMSNorm * w [* (1 + scale) + shift])   tm_op_prep_train | tm_op_prep_bwd     (ResBlock in / out layers, the head)
     nearest x2 / AvgPool(1,2,2)                 tm_op_resample   | the other mode, x 4 or / 4 (tm_op_ew 7 / 8)
     AttnBlock with gene cross-attention         training.AttnBlockTrain (modulate(norm), windowed attention core, MLP, gates)
@@ -39,7 +40,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .config import PathConfig
-from .training import AttnBlockTrain, _cb8, _host, _hp, _ncdhw
+from .training import AttnBlockTrain, DownZTrain, _cb8, _host, _hp, _ncdhw
 
 
 class _V:
@@ -131,8 +132,11 @@ class UNetTrain:
         self.tape: List = []
         self.grads: Dict[str, torch.Tensor] = {}
         self._one = None
-        if cfg.down_z_kernel not in (1, 3):
-            raise NotImplementedError("UNetTrain: down_z kernels of depth 1 and 3 (rna_slc 1, 4)")
+        self._downz: Optional[DownZTrain] = None
+        self._downz_src: Tuple = (None, None)
+        if cfg.down_z_kernel not in (1, 3, 5):
+            raise NotImplementedError(f"UNetTrain: rna_slc {cfg.rna_slc} runs its convs at Z = {cfg.z_size}; the conv gradients (both weight-"
+                                      "gradient kernels, the device pack, the data gradient) take Z <= 4 (rna_slc 1, 4, 8)")
 
     # ------------------------------------------------------------------------------------------------------------------
     # plumbing
@@ -155,6 +159,8 @@ class UNetTrain:
         """resident: the arena changed (AdamTrainer.step): the host copy and every pack are stale"""
         self._W = None
         self._packs.clear()
+        if self._downz is not None:
+            self._downz.params_updated()
 
     def _pack(self, key, role, co, ci, ks, Z, embed):
         """The device pack of conv `key` for role 0 (forward) / 1 (data gradient), built on first use after an optimizer step."""
@@ -519,6 +525,27 @@ class UNetTrain:
         self.tape.append(bwd)
         return out
 
+    def down_z(self, x: _V, key: str) -> _V:
+        """The (kz,3,3) conv without z padding at kz > 3 (rna_slc 8: kz = 5): training.DownZTrain on this engine's weights."""
+        kw, kb = key + ".weight", key + ".bias"
+        if not self.resident:
+            # host weights are replaced, never written in place (AdamTrainer.step): the block and its embedded filters hold
+            # as long as W[kw] / W[kb] are the tensors it was built from
+            if self._downz is None or self._downz_src[0] is not self.W[kw] or self._downz_src[1] is not self.W[kb]:
+                self._downz, self._downz_src = DownZTrain(self.W[kw], self.W[kb], self.dev), (self.W[kw], self.W[kb])
+        elif self._downz is None:
+            self._downz = DownZTrain(self._pd(kw), self._pd(kb), self.dev, resident=True)     # views of the arena: updated in place
+        blk = self._downz
+        out = _V(blk.forward_cb(x.t), blk.co)
+
+        def bwd():
+            dx, dw, db = blk.backward_cb(out.g)
+            self._gacc(kw, dw)
+            self._gacc(kb, db)
+            self._acc(x, dx)
+        self.tape.append(bwd)
+        return out
+
     # ------------------------------------------------------------------------------------------------------------------
     # the model
     # ------------------------------------------------------------------------------------------------------------------
@@ -533,7 +560,7 @@ class UNetTrain:
         D = zs * gh * gw
         tok = self.gene_attention(rna_h.reshape(n * G, D), n, G, D)
         x = self.rows_to_cb8(tok, (n, G, zs, gh, gw), G)
-        x = self.conv(x, "rna_blocks.0.0.down_z")
+        x = self.down_z(x, "rna_blocks.0.0.down_z") if cfg.down_z_kernel == 5 else self.conv(x, "rna_blocks.0.0.down_z")
         if cfg.down_z_kernel == 3:
             x = self.zslice(x, 1, zs - 1)                                  # padding 0 along z: the interior planes of the 'same' conv
         out = [self.resample(x, 1)]

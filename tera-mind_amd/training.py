@@ -147,6 +147,134 @@ class ResBlockTrain:
         return _ncdhw(dx, Cin), dscale, dshift, grads
 
 
+class DownZTrain:
+    """The unpadded-z conv at the top of the RNA pyramid, Conv3d(G, Co, (kz, 3, 3), padding (0, 1, 1)) with kz > 3 (kz = 5:
+    8 gene planes in, 4 out; kz = 9: 16 in, 8 out), forward and backward without a kernel of its own: the z taps are separated,
+
+        y              = b + sum_dz conv_(1,3,3)(x[:, :, dz:dz + Zo], w[:, :, dz])            dz = 0 .. kz - 1, Zo = Zi - kz + 1
+        dx[dz:dz + Zo] += conv_(1,3,3)^T(dy, w[:, :, dz])
+        dw[:, :, dz]   = the middle z plane of the 3x3x3 weight gradient of x[:, :, dz:dz + Zo] against dy;  db = sum dy
+
+    every term an in-plane conv embedded in the middle z slice of the 3x3x3 'same' conv at Zo planes, summed in dz order
+    (tm_op_ew 6), so the result is deterministic.  Zo <= 4 (the weight-gradient kernels stage four planes).
+    Untuned: every tap after the first is a conv into a second buffer plus a separate add launch (the backward also copies
+    the z slice of dx out and back per tap) where an accumulating epilogue would do; the conv runs once per step.
+
+    Two engines, as UNetTrain: host weight / bias (tm_op_conv_mfma, _dgrad, _wgrad; gradients on the host), or with
+    resident=True device weight / bias (views of a parameter arena), packed on the device per tap and role on first use after
+    params_updated() and read by tm_op_conv_mfma_packed / _dgrad_packed / _wgrad_dev (gradients on the device, nothing
+    synchronised).  forward(x [N, Ci, Zi, S, S]) -> y [N, Co, Zo, S, S]; backward(dy) -> (dx, dw [Co, Ci, kz, 3, 3], db)."""
+
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, device="cuda:0", resident: bool = False):
+        self.dev = torch.device(device)
+        self.resident = bool(resident)
+        self.co, self.ci, self.kz = weight.shape[:3]
+        if tuple(weight.shape[3:]) != (3, 3) or self.kz < 1:
+            raise ValueError(f"DownZTrain: weight must be [Co, Ci, kz, 3, 3], got {tuple(weight.shape)}")
+        self.w = weight.detach().to(self.dev, torch.float32) if resident else _host(weight)
+        self.b = bias.detach().to(self.dev, torch.float32) if resident else _host(bias)
+        self._packs: Dict = {}
+        self._emb: Dict = {}
+        self._saved = None
+
+    def params_updated(self):
+        """the weight changed in place (resident: an optimizer step on the arena): every pack and embedded filter is stale"""
+        self._packs.clear()
+        self._emb.clear()
+
+    def _embedded(self, dz):
+        """tap dz as the middle z slice of a 3x3x3 filter (on the weight's own device); the host engine keeps it for the
+        backward and later forwards, the resident one needs it only while a pack is built"""
+        wf = self._emb.get(dz)
+        if wf is None:
+            wf = torch.zeros((self.co, self.ci, 3, 3, 3), dtype=torch.float32, device=self.w.device)
+            wf[:, :, 1] = self.w[:, :, dz]
+            if not self.resident:
+                self._emb[dz] = wf
+        return wf
+
+    def _pack(self, dz, role, Z):
+        hit = self._packs.get((dz, role))
+        if hit is None:
+            L = _lib.lib()
+            hit = torch.empty((L.tm_conv_pack_floats(self.co, self.ci, 3, Z, role),), dtype=torch.float32, device=self.dev)
+            wf = self._embedded(dz)
+            _lib.check(L.tm_op_conv_pack_dev(_lib.ptr(wf), _lib.ptr(hit), self.co, self.ci, 3, Z, role,
+                                             _lib.current_stream_ptr()), "tm_op_conv_pack_dev")
+            self._packs[(dz, role)] = hit
+        return hit
+
+    def _add(self, a, b, out=None):
+        """a + b (tm_op_ew 6) into `out` (may be a: elementwise), or into a new tensor"""
+        o = torch.empty_like(a) if out is None else out
+        _lib.check(_lib.lib().tm_op_ew(6, _lib.ptr(a), _lib.ptr(b), None, _lib.ptr(o), None, a.numel(), _lib.current_stream_ptr()), "tm_op_ew")
+        return o
+
+    def forward_cb(self, x_cb: torch.Tensor) -> torch.Tensor:
+        """CB8 in, CB8 out: x_cb [N, ceil(Ci/8), Zi, S, S, 8] -> [N, ceil(Co/8), Zi - kz + 1, S, S, 8]."""
+        N, _, Zi, S, _, _ = x_cb.shape
+        Zo = Zi - self.kz + 1
+        if not 1 <= Zo <= 4:
+            raise ValueError(f"DownZTrain: {Zi} planes under a depth-{self.kz} kernel leave {Zo}; 1 .. 4 are supported")
+        L, st = _lib.lib(), _lib.current_stream_ptr()
+        zero_b = torch.zeros((self.co,), dtype=torch.float32, device=self.dev if self.resident else "cpu")
+        xs = []
+        y = torch.zeros((N, (self.co + 7) // 8, Zo, S, S, 8), dtype=torch.float32, device=self.dev)
+        tap = torch.zeros_like(y) if self.kz > 1 else None      # one buffer for the taps 1 .. kz - 1 (stream-ordered reuse)
+        for dz in range(self.kz):
+            xd = x_cb[:, :, dz:dz + Zo].contiguous()
+            t = y if dz == 0 else tap
+            b = self.b if dz == 0 else zero_b
+            if self.resident:
+                _lib.check(L.tm_op_conv_mfma_packed(_lib.ptr(xd), _lib.ptr(self._pack(dz, 0, Zo)), _lib.ptr(b), _lib.ptr(t), N, self.ci,
+                                                    self.co, Zo, S, 3, st), "tm_op_conv_mfma_packed")
+            else:
+                wf = self._embedded(dz)
+                _lib.check(L.tm_op_conv_mfma(_lib.ptr(xd), _hp(wf), _hp(b), _lib.ptr(t), N, self.ci, self.co, Zo, S, 3, 0, 0, 0,
+                                             st), "tm_op_conv_mfma")
+            xs.append(xd)
+            if dz:
+                self._add(y, t, out=y)
+        self._saved = dict(xs=xs, shape=(N, Zi, Zo, S), like=x_cb)
+        return y
+
+    def backward_cb(self, g: torch.Tensor):
+        N, Zi, Zo, S = self._saved["shape"]
+        L, st = _lib.lib(), _lib.current_stream_ptr()
+        co, ci = self.co, self.ci
+        host = torch.device("cpu")
+        gdev = self.dev if self.resident else host
+        dw = torch.empty((co, ci, self.kz, 3, 3), dtype=torch.float32, device=gdev)
+        db = torch.empty((co,), dtype=torch.float32, device=gdev)
+        dx = torch.zeros_like(self._saved["like"])
+        g = g.contiguous()
+        for dz in range(self.kz):
+            xd = self._saved["xs"][dz]
+            dwf = torch.empty((co, ci, 3, 3, 3), dtype=torch.float32, device=gdev)
+            d = torch.zeros_like(xd)
+            if self.resident:
+                _lib.check(L.tm_op_conv_wgrad_dev(_lib.ptr(xd), _lib.ptr(g), _lib.ptr(dwf), _lib.ptr(db) if dz == 0 else None, 0, N, ci, co, Zo,
+                                                  S, 3, st), "tm_op_conv_wgrad_dev")
+                _lib.check(L.tm_op_conv_dgrad_packed(_lib.ptr(g), _lib.ptr(self._pack(dz, 1, Zo)), _lib.ptr(d), N, ci, co, Zo, S, 3, st),
+                           "tm_op_conv_dgrad_packed")
+            else:
+                _lib.check(L.tm_op_conv_wgrad(_lib.ptr(xd), _lib.ptr(g), _hp(dwf), _hp(db) if dz == 0 else None, N, ci, co, Zo, S, 3, st),
+                           "tm_op_conv_wgrad")
+                wf = self._embedded(dz)
+                _lib.check(L.tm_op_conv_dgrad(_lib.ptr(g), _hp(wf), _lib.ptr(d), N, ci, co, Zo, S, 3, st), "tm_op_conv_dgrad")
+            dw[:, :, dz] = dwf[:, :, 1]
+            dx[:, :, dz:dz + Zo] = self._add(dx[:, :, dz:dz + Zo].contiguous(), d)
+        return dx, dw, db
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        assert x.shape[1] == self.ci
+        return _ncdhw(self.forward_cb(_cb8(x.to(self.dev).float())), self.co)
+
+    def backward(self, dout: torch.Tensor):
+        dx, dw, db = self.backward_cb(_cb8(dout.to(self.dev).float()))
+        return _ncdhw(dx, self.ci), dw, db
+
+
 class AttnBlockTrain:
     """One AttnBlock with gene cross-attention (model/MBAblocks.py:428-514: gene_trans=True, cond given, num_heads 1, n_h 2)
     forward and backward on the HIP kernels.  Parameters as a dict with the reference's key suffixes: norm1.weight,
@@ -158,7 +286,8 @@ class AttnBlockTrain:
         out = x1 + gate_mlp * fc2(GELU_tanh(fc1(modulate(norm2, x1, shift_mlp, scale_mlp))))
 
     Every Linear runs as a 1x1x1 conv on the MFMA conv kernel (forward, data gradient with transposed weights) and
-    conv_wgrad_kernel; modulate(norm) on prep_kernel / modnorm_bwd_kernel; the windowed attention core on attn_train_kernel;
+    conv_wgrad_kernel; modulate(norm) on prep_kernel / modnorm_bwd_kernel; the windowed attention core on attn_train_kernel (windows of 32 - 128
+    tokens) or the key-blocked attn_long_* kernels (256 / 512 tokens);
     the gates and activations on ew_kernel (csrc/tm_train.hip).  Channel chunks / concatenations of the CB8 tensors are torch
     slices on the device (C a multiple of 8)."""
 
