@@ -465,10 +465,11 @@ int tm_op_modnorm_bwd(const void* x_cb8, const void* g_cb8, const void* norm_w_h
 
 /* The attention core (q/k RMSNorm, softmax(q k^T / C) v per 2 x 2 window over (h, w) and all z; one head, n_h = 2):
  * dout_cb8 == NULL: forward, writes o_cb8.  dout_cb8 != NULL: backward, writes dq / dk / dv (CB8) and the q/k norm weight
- * gradients [C] (HOST).  Windows of 32, 64 or 128 tokens, C <= 512 (one workgroup per window, P in LDS), and windows of 256 or
- * 512 tokens, C <= 256 (key-blocked fp32 MFMA kernels, no T x T matrix anywhere; C > 256 is refused).  Any other token count is
- * TM_ERR_ARG.  C need not be a multiple of 8; the pad channels of the last CB8 block are written as zeros (and, at 256 /
- * 512 tokens, never read as values on the input side: whatever q, k, v, dout hold there changes no bit).  Deterministic. */
+ * gradients [C] (HOST).  Windows of 4, 8 or 16 tokens, C <= 512 (one workgroup per patch, one wave per window), of 32, 64 or
+ * 128 tokens, C <= 512 (one workgroup per window, P in LDS), and of 256 or 512 tokens, C <= 256 (key-blocked fp32 MFMA kernels,
+ * no T x T matrix anywhere; C > 256 is refused).  Any other token count is TM_ERR_ARG.  C need not be a multiple of 8; the pad
+ * channels of the last CB8 block are written as zeros (and, at 4 - 16 and 256 / 512 tokens, never read as values on the input
+ * side: whatever q, k, v, dout hold there changes no bit).  Deterministic. */
 int tm_op_window_attn_train(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_host,
                             const void* kw_host, const void* dout_cb8, void* o_cb8, void* dq_cb8, void* dk_cb8,
                             void* dv_cb8, void* dqw_host, void* dkw_host, int N, int C, int Z, int S, void* stream);

@@ -286,6 +286,9 @@ hipError_t launch_modnorm_bwd(const TV& x, const float* g, const float* w, const
 hipError_t launch_attn_train(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
                              float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd,
                              hipStream_t s);                                            // scratch (bwd): 2 * N * 4 * Cb * 8 floats
+// windows of 4 / 8 / 16 tokens, C <= 512 (one workgroup per patch, one wave per window); scratch (bwd): 2 * N * 4 * Cb * 8 floats
+hipError_t launch_attn_train_short(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
+                                   float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd, hipStream_t s);
 // windows of 256 / 512 tokens, C <= 256 (key-blocked fp32 MFMA form); scratch: attn_train_long_scratch_floats(...) floats, always
 hipError_t launch_attn_train_long(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
                                   float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd, hipStream_t s);

@@ -666,9 +666,10 @@ extern "C" int tm_op_window_attn_train(const void* q_cb8, const void* k_cb8, con
   if (!q_cb8 || !k_cb8 || !v_cb8 || !qw_host || !kw_host) return fail(TM_ERR_ARG, "bad argument");
   if (bwd ? (!dq_cb8 || !dk_cb8 || !dv_cb8 || !dqw_host || !dkw_host) : !o_cb8) return fail(TM_ERR_ARG, "missing output");
   const int T = Z * (S / 2) * (S / 2);
-  const bool lng = T == 256 || T == 512;
-  if ((S & 1) || (T != 32 && T != 64 && T != 128 && !lng) || C > 512 || C < 1)
-    return fail(TM_ERR_ARG, "window of %d tokens / C = %d: the training attention core takes 32, 64, 128, 256 or 512 tokens and C <= 512", T, C);
+  const bool lng = T == 256 || T == 512, shrt = T == 4 || T == 8 || T == 16;
+  if ((S & 1) || (T != 32 && T != 64 && T != 128 && !lng && !shrt) || C > 512 || C < 1)
+    return fail(TM_ERR_ARG, "window of %d tokens / C = %d: the training attention core takes 4, 8, 16, 32, 64, 128, 256 or 512 tokens and "
+                "C <= 512", T, C);
   if (lng && C > 256)
     return fail(TM_ERR_ARG, "window of %d tokens / C = %d: the long-window core holds a token's output in eight 32-channel accumulator "
                 "tiles, C <= 256", T, C);
@@ -681,7 +682,7 @@ extern "C" int tm_op_window_attn_train(const void* q_cb8, const void* k_cb8, con
   TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S),
      v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e = (lng ? launch_attn_train_long : launch_attn_train)(q, k, v, dqw_in, dkw_in, (const float*)dout_cb8, (float*)o_cb8,
+  hipError_t e = (lng ? launch_attn_train_long : shrt ? launch_attn_train_short : launch_attn_train)(q, k, v, dqw_in, dkw_in, (const float*)dout_cb8, (float*)o_cb8,
                                                                     (float*)dq_cb8, (float*)dk_cb8, (float*)dv_cb8, gq, gk, scratch, bwd, st);
   if (int rc = finish(st, e, "window attention (training)")) return rc;
   if (bwd) {

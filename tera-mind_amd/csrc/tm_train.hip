@@ -122,7 +122,7 @@ __global__ __launch_bounds__(256) void prep_bwd_kernel(PrepBwdArgs a) {
     }
     if (a.part_ds) {
       // the 64 voxels of a wave may belong to two images only at an image boundary: reduce per image of lane 0 and of
-      // the last lane (per_image * vpn >= 64 for every geometry of the model: one patch has >= 128 voxels)
+      // the last lane (per_image * vpn >= 64, or = 32: two aligned images per workgroup, the collage decoder of patch size 32)
       const int img_lo = __shfl(img, 0, 64);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -200,7 +200,9 @@ hipError_t launch_prep_bwd(const float* x, long x_ns, const float* g, long g_ns,
                            const float* w, const float* scale, const float* shift, long mod_stride, int per_image, float* dx,
                            long dx_ns, float* dw, float* dscale, float* dshift, int N, int Cb, int C_real, int Z, int S,
                            float* scratch, hipStream_t s, const DropRng* rng) {
-  if (per_image < 1 || (long)per_image * Z * S * S < 64 || !scratch) return hipErrorInvalidValue;
+  // a 64-voxel workgroup may hold voxels of two images at most: images of 64 voxels or more, or of exactly 32 (aligned halves)
+  const long vimg = (long)per_image * Z * S * S;
+  if (per_image < 1 || (vimg < 64 && vimg != 32) || !scratch) return hipErrorInvalidValue;
   const long vox = (long)N * Z * S * S, nwg = (vox + 63) / 64;
   const int C8 = Cb * 8;
   float* part_dw = scratch;
@@ -882,6 +884,243 @@ hipError_t launch_attn_train(const TV& q, const TV& k, const TV& v, const float*
     hipLaunchKernelGGL(prep_bwd_reduce_dw_kernel, dim3((unsigned)((q.Cb * 8 + 63) / 64)), dim3(64), 0, s, a.part_kw, nwg, q.Cb * 8, dkw);
   } else {
     hipLaunchKernelGGL(attn_train_kernel<false>, dim3((unsigned)nwg), dim3(256), lds, s, a);
+  }
+  return hipGetLastError();
+}
+
+// ---- the same core for short windows (T = 4 / 8 / 16 tokens: the middle-block AttnBlock of rna_slc 1 and of patch size 32) ----
+// One workgroup per patch, one wave per window (a patch has exactly four), VALU products.  Lane = (t, blk): t = lane % T its
+// token, blk = lane / T one of the NB = 64 / T channel blocks of a staged chunk (CH = 8 NB = 128 / 64 / 32 channels at T = 4 /
+// 8 / 16), so a wave stages T x CH = 512 floats of one operand per chunk whatever T is, each lane the 8 channels of one
+// (token, channel block) as two float4.  The token map is the (z, h, w) one of attn_train_kernel, computed per lane; nothing is
+// assumed about Z.  Pad channels (c >= C) of the last block are masked to zero on every read and written as zero.
+//   r_q, r_k       r = rsq(ss / C + eps) (v_rsq_f32, 1 ulp; 1 / C is a host-rounded factor: no IEEE division anywhere).
+//   P              logits of the window in LDS [T][T] (element (i, j): lane j + T (i % NB), slot i / NB), softmax per row by the
+//                  lane blk == 0 of the row: max, expf(s - m), sum, v_rcp_f32 of the sum, product.
+//   o / dv         lane (t, blk) owns out[t][8 channels of its block] of every chunk: sum over the window's tokens.
+//   backward       dP = do v^T like the logits; D = rowsum(dP o P) by the row's lane; dS = P (dP - D) / C in LDS;
+//                  dqh = dS kh (dkh = dS^T qh) by the owner lane of (t, block) into dq (dk), which also adds its part of
+//                  sum_c (dqh qw q) and forms the window's d(q_norm weight) partial; then, the dot complete, the same lane
+//                  reads its dqh back and writes dq = r dqh qw - q r^3 dot / C.
+// Accumulation orders (what tests/train_short_cases.py derives its bounds from):
+//   ss             per lane the channel blocks blk, blk + NB, .. in index order, 8 channels each in order (8 ceil(Cb / NB)
+//                  additions), then log2(NB) butterfly levels over the token's lanes (xor T, 2 T, .. 32).
+//   logit / dP     one fmaf chain per element over the channels in index order: C terms (pad channels add exact zeros).
+//   softmax sum, D one chain over the row's T entries in index order.
+//   o, dv, dqh, dkh   one fmaf chain per element over the window's T tokens in index order.
+//   dot            sum_c (dqh qw q): per lane its 8 ceil(Cb / NB) channels in the order of ss, then the same butterfly.
+//   dqw, dkw       per window: log2(T) butterfly levels over the token lanes (xor 1, .. T / 2); the 4 N window partials in
+//                  index order by prep_bwd_reduce_dw_kernel.
+// Every output element has one owner lane and one chain: no atomics, two calls give the same bits.
+// LDS (static): two staged operands [T][CH + 4] and P, dP [T][T] per wave: 26,880 B (T = 16, backward) .. 17,152 B (T = 4, forward) per
+// workgroup.  92 / 134 / 176 VGPRs backward at T = 4 / 8 / 16, no scratch (profiles/attn_train_short.txt).
+struct AttnShortArgs {
+  const float *q, *k, *v, *qw, *kw, *dout;
+  float *o, *dq, *dk, *dv, *part_qw, *part_kw;     // part_*: [patch][window][Cb * 8]
+  long ns, plane; int C, Cb, S; float inv_c;
+};
+
+template <int T, bool BWD>
+__global__ __launch_bounds__(256) void attn_short_kernel(AttnShortArgs a) {
+  constexpr int NB = 64 / T, CH = NB * 8, PS = CH + 4, NE = (T + NB - 1) / NB;
+  __shared__ __attribute__((aligned(16))) float sA[4][T * PS];
+  __shared__ __attribute__((aligned(16))) float sB[4][T * PS];
+  __shared__ float sP[4][T * T], sD[4][BWD ? T * T : 1], sRow[4][T];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, t = lane % T, blk = lane / T;
+  float *A = sA[wv], *B = sB[wv], *Pm = sP[wv], *Dm = sD[wv], *rowv = sRow[wv];
+  const int S = a.S, hs = S / 2, C = a.C, Cb = a.Cb;
+  const long nb = (long)blockIdx.x * a.ns;
+  long tok;                                                  // float offset of this lane's token inside a channel block
+  {
+    const int z = t / (hs * hs), r = t - z * hs * hs, yl = r / hs, xl = r - yl * hs;
+    tok = ((long)(z * S + (wv >> 1) * hs + yl) * S + (wv & 1) * hs + xl) * 8;
+  }
+  // the 8 channels of (this lane's token, channel block cb), pad channels and blocks past the tensor as zeros
+  auto load8 = [&](const float* src, int cb, float (&x)[8]) {
+    f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+    if (cb < Cb) { const float* p = src + nb + (long)cb * a.plane + tok; v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4); }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { const float v = j < 4 ? v0[j] : v1[j - 4]; x[j] = cb * 8 + j < C ? v : 0.f; }
+  };
+  auto store8 = [&](float* dst, int cb, const float (&x)[8]) {
+    f32x4 v0, v1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v0[j] = cb * 8 + j < C ? x[j] : 0.f; v1[j] = cb * 8 + 4 + j < C ? x[4 + j] : 0.f; }
+    float* p = dst + nb + (long)cb * a.plane + tok;
+    *(f32x4*)p = v0;
+    *(f32x4*)(p + 4) = v1;
+  };
+  // sum over the NB lanes of a token
+  auto token_sum = [&](float v) {
+#pragma unroll
+    for (int o = T; o < 64; o <<= 1) v += __shfl_xor(v, o, 64);
+    return v;
+  };
+  float rq, rk;
+  {
+    float sq = 0.f, sk = 0.f;
+    for (int cb = blk; cb < Cb; cb += NB) {
+      float x[8], y[8];
+      load8(a.q, cb, x);
+      load8(a.k, cb, y);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { sq += x[j] * x[j]; sk += y[j] * y[j]; }
+    }
+    rq = __builtin_amdgcn_rsqf(token_sum(sq) * a.inv_c + TM_EPS);
+    rk = __builtin_amdgcn_rsqf(token_sum(sk) * a.inv_c + TM_EPS);
+  }
+  // dst[t][blk * 8 ..] = the chunk's values of `src` (first channel block c0b), times r and w[c] when w is given
+  auto stage = [&](float* dst, const float* src, int c0b, float r, const float* w) {
+    const int cb = c0b + blk;
+    float x[8];
+    load8(src, cb, x);
+    if (w && cb < Cb) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = x[j] * r * w[cb * 8 + j];
+    }
+    f32x4 v0, v1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v0[j] = x[j]; v1[j] = x[4 + j]; }
+    *(f32x4*)(dst + t * PS + blk * 8) = v0;
+    *(f32x4*)(dst + t * PS + blk * 8 + 4) = v1;
+  };
+  // M[i][j] = mul * sum_c X[i][c] Y[j][c]; this lane owns j = t and the rows i = blk + u NB
+  auto gemm_nt = [&](float* M, const float* X, float xr, const float* xw, const float* Y, float yr, const float* yw, float mul) {
+    float acc[NE];
+#pragma unroll
+    for (int u = 0; u < NE; ++u) acc[u] = 0.f;
+    for (int c0b = 0; c0b < Cb; c0b += NB) {
+      __syncthreads();
+      stage(A, X, c0b, xr, xw);
+      stage(B, Y, c0b, yr, yw);
+      __syncthreads();
+#pragma unroll 4
+      for (int cc = 0; cc < CH; cc += 4) {
+        const f32x4 y = *(const f32x4*)(B + t * PS + cc);
+#pragma unroll
+        for (int u = 0; u < NE; ++u) {
+          const int i = blk + u * NB;
+          if (i < T) {
+            const f32x4 x = *(const f32x4*)(A + i * PS + cc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[u] = fmaf(x[j], y[j], acc[u]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < NE; ++u) { const int i = blk + u * NB; if (i < T) M[i * T + t] = acc[u] * mul; }
+    __syncthreads();
+  };
+  // out[t][c] = sum_j M(t, j) Y[j][c], M(t, j) = trans ? Mat[j][t] : Mat[t][j].  With xsrc: `out` receives dXh, the lane adds
+  // its share of sum_c (dXh xw x) to `dot` and the window's partial of d(norm weight)[c] = sum_t dXh x xr goes to `part`.
+  auto matmul_out = [&](const float* Mat, bool trans, const float* Y, float yr, const float* yw, float* out, const float* xsrc,
+                        const float* xw, float xr, float* part, float& dot) {
+    for (int c0b = 0; c0b < Cb; c0b += NB) {
+      __syncthreads();
+      stage(B, Y, c0b, yr, yw);
+      __syncthreads();
+      const int cb = c0b + blk;
+      float acc[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+      for (int j = 0; j < T; ++j) {
+        const float m = trans ? Mat[j * T + t] : Mat[t * T + j];
+        const f32x4 y0 = *(const f32x4*)(B + j * PS + blk * 8), y1 = *(const f32x4*)(B + j * PS + blk * 8 + 4);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { acc[c] = fmaf(m, y0[c], acc[c]); acc[4 + c] = fmaf(m, y1[c], acc[4 + c]); }
+      }
+      if (cb < Cb) store8(out, cb, acc);
+      if (xsrc) {
+        float x[8];
+        load8(xsrc, cb, x);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float w = cb < Cb ? xw[cb * 8 + j] : 0.f;
+          dot += acc[j] * w * x[j];
+          float pw = acc[j] * x[j] * xr;
+#pragma unroll
+          for (int o = 1; o < T; o <<= 1) pw += __shfl_xor(pw, o, 64);
+          if (t == 0 && cb < Cb) part[((long)blockIdx.x * 4 + wv) * Cb * 8 + cb * 8 + j] = cb * 8 + j < C ? pw : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+  };
+  float nodot = 0.f;
+  // P = softmax(qh kh^T / C)
+  gemm_nt(Pm, a.q, rq, a.qw, a.k, rk, a.kw, a.inv_c);
+  if (blk == 0) {
+    float m = -INFINITY;
+    for (int j = 0; j < T; ++j) m = fmaxf(m, Pm[t * T + j]);
+    float sum = 0.f;
+    for (int j = 0; j < T; ++j) { const float e = expf(Pm[t * T + j] - m); Pm[t * T + j] = e; sum += e; }
+    const float inv = __builtin_amdgcn_rcpf(sum);
+    for (int j = 0; j < T; ++j) Pm[t * T + j] *= inv;
+  }
+  __syncthreads();
+  if (!BWD) {
+    matmul_out(Pm, false, a.v, 1.f, nullptr, a.o, nullptr, nullptr, 0.f, nullptr, nodot);
+    return;
+  }
+  // dv = P^T dout
+  matmul_out(Pm, true, a.dout, 1.f, nullptr, a.dv, nullptr, nullptr, 0.f, nullptr, nodot);
+  // dP = dout v^T;  dS = P (dP - rowsum(dP P)) / C
+  gemm_nt(Dm, a.dout, 1.f, nullptr, a.v, 1.f, nullptr, 1.0f);
+  if (blk == 0) {
+    float rd = 0.f;
+    for (int j = 0; j < T; ++j) rd += Dm[t * T + j] * Pm[t * T + j];
+    rowv[t] = rd;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int u = 0; u < NE; ++u) {
+    const int i = blk + u * NB;
+    if (i < T) Dm[i * T + t] = Pm[i * T + t] * (Dm[i * T + t] - rowv[i]) * a.inv_c;
+  }
+  __syncthreads();
+  // dqh = dS kh into dq, dkh = dS^T qh into dk; then the RMSNorm backward in place, each lane on the values it wrote
+  for (int pass = 0; pass < 2; ++pass) {
+    const float* Xsrc = pass == 0 ? a.q : a.k;
+    const float* Ysrc = pass == 0 ? a.k : a.q;
+    const float xr = pass == 0 ? rq : rk, yr = pass == 0 ? rk : rq;
+    const float* xw = pass == 0 ? a.qw : a.kw;
+    const float* yw = pass == 0 ? a.kw : a.qw;
+    float* dX = pass == 0 ? a.dq : a.dk;
+    float dot = 0.f;
+    matmul_out(Dm, pass == 1, Ysrc, yr, yw, dX, Xsrc, xw, xr, pass == 0 ? a.part_qw : a.part_kw, dot);
+    const float md = token_sum(dot) * a.inv_c, r3 = xr * xr * xr;
+    for (int cb = blk; cb < Cb; cb += NB) {
+      float g[8], x[8];
+      load8(dX, cb, g);
+      load8(Xsrc, cb, x);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) g[j] = xr * g[j] * xw[cb * 8 + j] - x[j] * r3 * md;
+      store8(dX, cb, g);
+    }
+  }
+}
+
+template <int T>
+static void launch_attn_short_t(const AttnShortArgs& a, int N, bool bwd, hipStream_t s) {
+  if (bwd) hipLaunchKernelGGL((attn_short_kernel<T, true>), dim3((unsigned)N), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((attn_short_kernel<T, false>), dim3((unsigned)N), dim3(256), 0, s, a);
+}
+hipError_t launch_attn_train_short(const TV& q, const TV& k, const TV& v, const float* qw, const float* kw, const float* dout, float* o,
+                                   float* dq, float* dk, float* dv, float* dqw, float* dkw, float* scratch, bool bwd, hipStream_t s) {
+  const int S = q.H, T = q.Z * (S / 2) * (S / 2);
+  if (q.H != q.W || (S & 1) || (T != 4 && T != 8 && T != 16) || q.C < 1 || q.C > 512 || k.nstride != q.nstride || v.nstride != q.nstride ||
+      q.N < 1 || (bwd && !scratch))
+    return hipErrorInvalidValue;
+  const long nwin = (long)q.N * 4;
+  AttnShortArgs a{q.p, k.p, v.p, qw, kw, dout, o, dq, dk, dv, scratch, scratch ? scratch + nwin * q.Cb * 8 : nullptr, q.nstride,
+                  (long)q.Z * S * S * 8, q.C, q.Cb, S, 1.0f / (float)q.C};
+  if (T == 4) launch_attn_short_t<4>(a, q.N, bwd, s);
+  else if (T == 8) launch_attn_short_t<8>(a, q.N, bwd, s);
+  else launch_attn_short_t<16>(a, q.N, bwd, s);
+  if (bwd) {
+    hipLaunchKernelGGL(prep_bwd_reduce_dw_kernel, dim3((unsigned)((q.Cb * 8 + 63) / 64)), dim3(64), 0, s, a.part_qw, nwin, q.Cb * 8, dqw);
+    hipLaunchKernelGGL(prep_bwd_reduce_dw_kernel, dim3((unsigned)((q.Cb * 8 + 63) / 64)), dim3(64), 0, s, a.part_kw, nwin, q.Cb * 8, dkw);
   }
   return hipGetLastError();
 }

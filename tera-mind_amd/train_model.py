@@ -134,6 +134,10 @@ class UNetTrain:
         self._one = None
         self._downz: Optional[DownZTrain] = None
         self._downz_src: Tuple = (None, None)
+        if cfg.rna_slc == 1 and cfg.patch_size == 32:
+            raise NotImplementedError("UNetTrain: rna_slc 1 at patch size 32 has patches of 16 voxels at the lowest level (Z = 1, S = 4); the "
+                                      "ResBlock norm backward sums the per-image scale / shift gradients of at most two images per "
+                                      "64-voxel workgroup, so an image needs 32 voxels or more")
         if cfg.down_z_kernel not in (1, 3, 5):
             raise NotImplementedError(f"UNetTrain: rna_slc {cfg.rna_slc} runs its convs at Z = {cfg.z_size}; the conv gradients (both weight-"
                                       "gradient kernels, the device pack, the data gradient) take Z <= 4 (rna_slc 1, 4, 8)")
@@ -209,6 +213,22 @@ class UNetTrain:
     # ------------------------------------------------------------------------------------------------------------------
     # tape ops on CB8 values
     # ------------------------------------------------------------------------------------------------------------------
+    # The k x 3 x 3 conv kernels take planes of S = 4 .. 128.  A 2 x 2 plane (the gene grid of patch size 32) runs in the corner of
+    # a zero 4 x 4 plane: the zeros right of and below the corner are the conv's own zero padding, so the corner of the result
+    # is the 'same' conv of the 2 x 2 plane, forward and data gradient alike (a re-indexing on both sides, no arithmetic); the
+    # weight gradient kernels take any S and read the tensors as they are.
+    @staticmethod
+    def _conv_plane(ks, S):
+        return 4 if ks == 3 and S == 2 else S
+
+    @staticmethod
+    def _corner_in(t, S, Sc):
+        return t if Sc == S else F.pad(t, (0, 0, 0, Sc - S, 0, Sc - S)).contiguous()
+
+    @staticmethod
+    def _corner_out(t, S, Sc):
+        return t if Sc == S else t[:, :, :, :S, :S].contiguous()
+
     def conv(self, x: _V, key: str) -> _V:
         """Conv3d with the reference weight `key`.weight [Co, Ci, kz, ky, kx]: 3x3x3 pad 1, 1x1x1, or (1,3,3) pad (0,1,1)
         embedded into the middle z slice of a 3x3x3 kernel."""
@@ -226,9 +246,11 @@ class UNetTrain:
         else:
             wf = w.contiguous()
         N, Z, S = self._geo(x.t)
-        y = torch.zeros((N, (co + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_mfma(_lib.ptr(x.t), _hp(wf), _hp(b), _lib.ptr(y), N, ci, co, Z, S, ks, 0, 0, 0, self._st()), "tm_op_conv_mfma")
-        out = _V(y, co)
+        Sc = self._conv_plane(ks, S)
+        xin = self._corner_in(x.t, S, Sc)
+        y = torch.zeros((N, (co + 7) // 8, Z, Sc, Sc, 8), dtype=torch.float32, device=self.dev)
+        _lib.check(_lib.lib().tm_op_conv_mfma(_lib.ptr(xin), _hp(wf), _hp(b), _lib.ptr(y), N, ci, co, Z, Sc, ks, 0, 0, 0, self._st()), "tm_op_conv_mfma")
+        out = _V(self._corner_out(y, S, Sc), co)
 
         def bwd():
             g = out.g
@@ -237,9 +259,11 @@ class UNetTrain:
             _lib.check(_lib.lib().tm_op_conv_wgrad(_lib.ptr(x.t), _lib.ptr(g), _hp(dw), _hp(db), N, ci, co, Z, S, ks, self._st()), "tm_op_conv_wgrad")
             self._gacc(key + ".weight", dw[:, :, 1:2].contiguous() if embed else dw)
             self._gacc(key + ".bias", db)
-            dx = torch.zeros_like(x.t)
-            _lib.check(_lib.lib().tm_op_conv_dgrad(_lib.ptr(g), _hp(wf), _lib.ptr(dx), N, ci, co, Z, S, ks, self._st()), "tm_op_conv_dgrad")
-            self._acc(x, dx)
+            dx = torch.zeros_like(xin)
+            gin = self._corner_in(g, S, Sc)                               # named: it must outlive the call that reads it
+            _lib.check(_lib.lib().tm_op_conv_dgrad(_lib.ptr(gin), _hp(wf), _lib.ptr(dx), N, ci, co, Z, Sc, ks, self._st()),
+                       "tm_op_conv_dgrad")
+            self._acc(x, self._corner_out(dx, S, Sc))
         self.tape.append(bwd)
         return out
 
@@ -254,10 +278,12 @@ class UNetTrain:
         embed = shp[2:] == (1, 3, 3)
         N, Z, S = self._geo(x.t)
         L = _lib.lib()
-        y = torch.zeros((N, (co + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(L.tm_op_conv_mfma_packed(_lib.ptr(x.t), _lib.ptr(self._pack(key, 0, co, ci, ks, Z, embed)), _lib.ptr(self._pd(kb)),
-                                            _lib.ptr(y), N, ci, co, Z, S, ks, self._st()), "tm_op_conv_mfma_packed")
-        out = _V(y, co)
+        Sc = self._conv_plane(ks, S)
+        xin = self._corner_in(x.t, S, Sc)
+        y = torch.zeros((N, (co + 7) // 8, Z, Sc, Sc, 8), dtype=torch.float32, device=self.dev)
+        _lib.check(L.tm_op_conv_mfma_packed(_lib.ptr(xin), _lib.ptr(self._pack(key, 0, co, ci, ks, Z, embed)), _lib.ptr(self._pd(kb)),
+                                            _lib.ptr(y), N, ci, co, Z, Sc, ks, self._st()), "tm_op_conv_mfma_packed")
+        out = _V(self._corner_out(y, S, Sc), co)
 
         def bwd():
             g = out.g
@@ -275,10 +301,14 @@ class UNetTrain:
                                               self._st()), "tm_op_conv_wgrad_dev")
             if embed:
                 self._gacc(kw, dw[:, :, 1:2])
-            dx = torch.zeros_like(x.t)
-            _lib.check(L.tm_op_conv_dgrad_packed(_lib.ptr(g), _lib.ptr(self._pack(key, 1, co, ci, ks, Z, embed)), _lib.ptr(dx), N, ci, co, Z,
-                                                 S, ks, self._st()), "tm_op_conv_dgrad_packed")
-            self._acc(x, dx)
+            dx = torch.zeros_like(xin)
+            # named, and the pack built first: a temporary would be released before the (asynchronous) call, and the pack's
+            # allocation could take its memory
+            pk = self._pack(key, 1, co, ci, ks, Z, embed)
+            gin = self._corner_in(g, S, Sc)
+            _lib.check(L.tm_op_conv_dgrad_packed(_lib.ptr(gin), _lib.ptr(pk), _lib.ptr(dx), N, ci, co, Z, Sc, ks, self._st()),
+                       "tm_op_conv_dgrad_packed")
+            self._acc(x, self._corner_out(dx, S, Sc))
         self.tape.append(bwd)
         return out
 

@@ -286,8 +286,8 @@ class AttnBlockTrain:
         out = x1 + gate_mlp * fc2(GELU_tanh(fc1(modulate(norm2, x1, shift_mlp, scale_mlp))))
 
     Every Linear runs as a 1x1x1 conv on the MFMA conv kernel (forward, data gradient with transposed weights) and
-    conv_wgrad_kernel; modulate(norm) on prep_kernel / modnorm_bwd_kernel; the windowed attention core on attn_train_kernel (windows of 32 - 128
-    tokens) or the key-blocked attn_long_* kernels (256 / 512 tokens);
+    conv_wgrad_kernel; modulate(norm) on prep_kernel / modnorm_bwd_kernel; the windowed attention core on attn_short_kernel (windows of 4 - 16 tokens),
+    attn_train_kernel (32 - 128 tokens) or the key-blocked attn_long_* kernels (256 / 512 tokens);
     the gates and activations on ew_kernel (csrc/tm_train.hip).  Channel chunks / concatenations of the CB8 tensors are torch
     slices on the device (C a multiple of 8)."""
 

@@ -26,7 +26,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch_size", "-b", type=int, default=32)
     ap.add_argument("--patch_size", "-ps", type=int, default=64)
-    ap.add_argument("--rna_slc", type=int, choices=(1, 4, 8), default=4, help="UNetTrain covers rna_slc 1, 4 and 8")
+    ap.add_argument("--rna_slc", type=int, choices=(1, 4, 8), default=4, help="UNetTrain covers rna_slc 1 (patch 64, 128), 4 and 8")
     ap.add_argument("--mouse", default="638850", choices=["609882", "609889", "638850"])
     ap.add_argument("--stain", default="all", choices=["DAPI", "PolyT", "all"])
     ap.add_argument("--data", required=True, help="directory of gene .npz tiles (images: the same paths with gene -> img, .npz -> .zip)")
