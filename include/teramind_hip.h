@@ -502,6 +502,20 @@ int tm_op_sumsq(const void* x_dev, long n, float* out_host, void* stream);
 int tm_op_adam(void* p_dev, const void* g_dev, void* m_dev, void* v_dev, long n, float lr, float beta1, float beta2,
                float eps, float weight_decay, int step, float grad_scale, void* stream);
 
+/* ---- data-parallel training: the rank-ordered sum of the gradient exchange (teramind_amd.train_dist.GradExchange) ---------- */
+
+/* parts_dev [W][n] fp32 contiguous -> out_dev [n]:  out[i] = ((parts[0][i] + parts[1][i]) + parts[2][i]) + ...  -- plain fp32
+ * additions in slice order, starting from slice 0's value and not from zero (W = 1 is a bit copy; -0.0 stays -0.0).  One owner
+ * thread per element, no atomics: the same inputs give the same bits on every device.  Queued on `stream`; nothing is
+ * synchronised.  1 <= W <= 64, n >= 0 (n = 0: nothing is written).  out_dev must not overlap parts_dev: an overlapping call, a
+ * null pointer or a bad W / n is TM_ERR_ARG before any launch.  Pointers need 4-byte alignment; 16-byte aligned pointers with
+ * n % 4 == 0 give aligned 16-byte accesses throughout. */
+int tm_op_rank_sum(const void* parts_dev, void* out_dev, int W, long n, void* stream);
+
+/* Timing hook (tools/bench_rank_sum.py): tm_op_rank_sum's kernel on random device data.  After one warm-up launch,
+ * ms_per_launch_host[r], r < reps, is the time per launch of `iters` launches between two events. */
+int tm_op_rank_sum_time(int W, long n, int iters, int reps, float* ms_per_launch_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

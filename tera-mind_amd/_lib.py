@@ -101,6 +101,8 @@ SIGNATURES = {
     "tm_op_resample": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_void_p]),
     "tm_op_sumsq": (c_int, [c_void_p, C.c_long, c_void_p, c_void_p]),
     "tm_op_adam": (c_int, [c_void_p] * 4 + [C.c_long] + [c_float] * 5 + [c_int, c_float, c_void_p]),
+    "tm_op_rank_sum": (c_int, [c_void_p, c_void_p, c_int, C.c_long, c_void_p]),
+    "tm_op_rank_sum_time": (c_int, [c_int, C.c_long, c_int, c_int, c_void_p, c_void_p]),
     "tm_op_modnorm": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p]),
     "tm_op_modnorm_bwd": (c_int, [c_void_p] * 8 + [c_int] * 4 + [c_void_p]),
     "tm_op_window_attn_train": (c_int, [c_void_p] * 12 + [c_int] * 4 + [c_void_p]),

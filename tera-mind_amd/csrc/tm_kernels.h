@@ -301,6 +301,8 @@ hipError_t launch_rows(int op, const float* x, const float* w, const float* g, f
 hipError_t launch_sumsq(const float* x, long n, float* out, float* scratch, int nwg, hipStream_t s);      // scratch: nwg floats
 hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd, int step,
                        float gscale, hipStream_t s);
+// out[i] = ((parts[0][i] + parts[1][i]) + ...) over W slices of n floats, in slice order; queued on s, nothing awaited
+hipError_t launch_rank_sum(const float* parts, float* out, int W, long n, hipStream_t s);
 
 // ---- tile I/O (tm_io.hip) --------------------------------------------------------------
 hipError_t launch_gene_tile_scatter(const int32_t* crd, const float* dat, long nnz, int gblk, int shift_h, int shift_w,

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -748,6 +749,25 @@ extern "C" int tm_op_adam(void* p_dev, const void* g_dev, void* m_dev, void* v_d
                                 step, grad_scale, st), "adam");
 }
 
+// Rank-ordered sum of W gradient slices (train_dist.GradExchange): queued on `stream`, no synchronisation, no scratch
+static int rank_sum_args(int W, long n) {
+  if (W < 1 || W > 64) return fail(TM_ERR_ARG, "rank sum: W = %d, must be 1 .. 64", W);
+  if (n < 0) return fail(TM_ERR_ARG, "rank sum: n = %ld, must be >= 0", n);
+  if ((unsigned long)n > (1UL << 60) / 64) return fail(TM_ERR_ARG, "rank sum: n = %ld is too large", n);
+  return TM_OK;
+}
+extern "C" int tm_op_rank_sum(const void* parts_dev, void* out_dev, int W, long n, void* stream) {
+  if (!parts_dev || !out_dev) return fail(TM_ERR_ARG, "rank sum: null pointer");
+  if (int rc = rank_sum_args(W, n)) return rc;
+  if (n == 0) return TM_OK;
+  const uintptr_t p0 = (uintptr_t)parts_dev, p1 = p0 + (uintptr_t)W * (uintptr_t)n * sizeof(float);
+  const uintptr_t o0 = (uintptr_t)out_dev, o1 = o0 + (uintptr_t)n * sizeof(float);
+  if (o0 < p1 && p0 < o1) return fail(TM_ERR_ARG, "rank sum: out overlaps parts (every slice is read after out may have been written)");
+  if ((p0 | o0) & 3) return fail(TM_ERR_ARG, "rank sum: pointers must be 4-byte aligned");
+  HIP_TRY(launch_rank_sum((const float*)parts_dev, (float*)out_dev, W, n, (hipStream_t)stream));
+  return TM_OK;
+}
+
 // dX of Conv3d(k = 3x3x3 pad 1 | 1x1x1), stride 1: the forward MFMA conv of dY with the kernel flipped in z, y, x and
 // cin <-> cout transposed (w_host [Cout][Cin][taps] as in the reference state_dict)
 extern "C" int tm_op_conv_dgrad(const void* dy_cb8, const void* w_host, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,
@@ -893,6 +913,31 @@ extern "C" int tm_op_conv_wgrad_time(int N, int Cin, int Cout, int Z, int S, int
     for (int i = 0; i < iters && e == hipSuccess; ++i) e = run();
     if (e == hipSuccess) e = hipEventRecord(e1, st);
     if (int rc = finish(st, e, "conv wgrad (timing)")) return rc;
+    HIP_TRY(hipEventElapsedTime(ms_per_launch_host + r, e0, e1));
+    ms_per_launch_host[r] /= (float)iters;
+  }
+  return TM_OK;
+}
+
+// Timing hook of the rank sum on random device data (fill_f32_kernel): one warm-up launch, then `reps` measurements of `iters`
+// launches between two events each
+extern "C" int tm_op_rank_sum_time(int W, long n, int iters, int reps, float* ms_per_launch_host, void* stream) {
+  if (!ms_per_launch_host || iters < 1 || reps < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (int rc = rank_sum_args(W, n)) return rc;
+  if (n < 1) return fail(TM_ERR_ARG, "rank sum timing: n must be positive");
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp;
+  float* parts = tmp.alloc<float>((size_t)W * n);
+  float* out = tmp.alloc<float>((size_t)n);
+  hipEvent_t e0 = tmp.event(), e1 = tmp.event();
+  if (tmp.err) return tmp.report();
+  hipLaunchKernelGGL(fill_f32_kernel, dim3(2048), dim3(256), 0, st, parts, (size_t)W * n, 11u);
+  if (int rc = finish(st, launch_rank_sum(parts, out, W, n, st), "rank sum (timing warm-up)")) return rc;
+  for (int r = 0; r < reps; ++r) {
+    hipError_t e = hipEventRecord(e0, st);
+    for (int i = 0; i < iters && e == hipSuccess; ++i) e = launch_rank_sum(parts, out, W, n, st);
+    if (e == hipSuccess) e = hipEventRecord(e1, st);
+    if (int rc = finish(st, e, "rank sum (timing)")) return rc;
     HIP_TRY(hipEventElapsedTime(ms_per_launch_host + r, e0, e1));
     ms_per_launch_host[r] /= (float)iters;
   }

@@ -10,6 +10,7 @@
 #include "tm_device.h"
 
 #include <algorithm>
+#include <atomic>
 
 namespace tmk {
 
@@ -1647,6 +1648,82 @@ hipError_t launch_adam(float* p, const float* g, float* m, float* v, long n, flo
   long grid = (n + 255) / 256;
   if (grid > 8192) grid = 8192;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)grid), dim3(256), 0, s, p, g, m, v, n, lr, b1, b2, eps, wd, bc1, sqrtf(bc2), gscale);
+  return hipGetLastError();
+}
+
+// ==================================================================================================================
+// Rank-ordered sum of the data-parallel gradient exchange (train_dist.GradExchange): parts [W][n] -> out [n],
+//   out[i] = ((parts[0][i] + parts[1][i]) + parts[2][i]) + ...      plain fp32 adds in slice order, starting from slice 0's value
+// One owner thread per element, no atomics: the bits depend on (parts, W) alone.  HBM bound, (W + 1) * 4 bytes per element: a
+// thread owns four consecutive floats, issues the 16-byte loads of up to eight slices before the first add (8 x 16 B in flight
+// per lane), then stores 16 bytes; the grid is sized to the chip and strides over n.  The 16-byte accesses ask for 4-byte
+// alignment only (slice k starts at parts + k n, which is 16-byte aligned for every k only when n % 4 == 0: the exchange's
+// shards are, train_dist.shard_layout); gfx950 serves dword-aligned dwordx4 global accesses.  The last n % 4 elements are
+// summed one float at a time by the first threads of workgroup 0.
+// ==================================================================================================================
+typedef float rs_f4 __attribute__((ext_vector_type(4)));
+typedef rs_f4 rs_f4u __attribute__((aligned(4)));
+
+template <int G>
+__device__ __forceinline__ rs_f4 rank_sum_group(const float* p, long n, rs_f4 acc, bool first) {
+  rs_f4 r[G];
+#pragma unroll
+  for (int j = 0; j < G; ++j) r[j] = *(const rs_f4u*)(p + (long)j * n);
+  acc = first ? r[0] : acc + r[0];
+#pragma unroll
+  for (int j = 1; j < G; ++j) acc = acc + r[j];
+  return acc;
+}
+
+__device__ __forceinline__ rs_f4 rank_sum_rest(int g, const float* p, long n, rs_f4 acc, bool first) {
+  switch (g) {                                                       // g is uniform over the grid: a scalar branch
+    case 1: return rank_sum_group<1>(p, n, acc, first);
+    case 2: return rank_sum_group<2>(p, n, acc, first);
+    case 3: return rank_sum_group<3>(p, n, acc, first);
+    case 4: return rank_sum_group<4>(p, n, acc, first);
+    case 5: return rank_sum_group<5>(p, n, acc, first);
+    case 6: return rank_sum_group<6>(p, n, acc, first);
+    default: return rank_sum_group<7>(p, n, acc, first);
+  }
+}
+
+__global__ __launch_bounds__(256) void rank_sum_kernel(const float* __restrict__ parts, float* __restrict__ out, int W, long n) {
+  const long nv = n >> 2, stride = (long)gridDim.x * 256;
+  for (long v = (long)blockIdx.x * 256 + threadIdx.x; v < nv; v += stride) {
+    const float* p = parts + 4 * v;
+    rs_f4 acc = {0.f, 0.f, 0.f, 0.f};
+    int k = 0;
+    for (; W - k >= 8; k += 8) acc = rank_sum_group<8>(p + (long)k * n, n, acc, k == 0);
+    if (W - k) acc = rank_sum_rest(W - k, p + (long)k * n, n, acc, k == 0);
+    *(rs_f4u*)(out + 4 * v) = acc;
+  }
+  if (blockIdx.x == 0 && (long)threadIdx.x < (n & 3)) {
+    const long i = 4 * nv + threadIdx.x;
+    float s_ = parts[i];
+    for (int k = 1; k < W; ++k) s_ += parts[(long)k * n + i];
+    out[i] = s_;
+  }
+}
+
+// workgroups that fill the chip: 8 of 256 threads per compute unit (one wave of each on every SIMD twice over), cached per device
+static long rank_sum_chip_grid() {
+  static std::atomic<int> cus[128];
+  int d = 0;
+  if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 128) return 8 * 256;
+  int c = cus[d].load();
+  if (!c) {
+    if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || c < 1) c = 256;
+    cus[d].store(c);
+  }
+  return 8L * c;
+}
+
+hipError_t launch_rank_sum(const float* parts, float* out, int W, long n, hipStream_t s) {
+  if (!parts || !out || W < 1 || W > 64 || n < 0) return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  const long need = ((n >> 2) + 255) / 256;
+  const long grid = std::max<long>(1, std::min<long>(need, rank_sum_chip_grid()));
+  hipLaunchKernelGGL(rank_sum_kernel, dim3((unsigned)grid), dim3(256), 0, s, parts, out, W, n);
   return hipGetLastError();
 }
 

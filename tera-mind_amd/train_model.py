@@ -92,10 +92,11 @@ def dropout_sites(keys) -> Dict[str, int]:
     return {p: j for j, p in enumerate(sorted(k[:-len(_OUT_NORM)] for k in keys if k.endswith(_OUT_NORM)))}
 
 
-def derive_dropout_key(seed: int, step: int, micro: int = 0) -> int:
-    """A 64-bit dropout key for one forward of a training loop: distinct per (base seed, optimizer step, micro-batch), so that no
-    two forwards of a run share masks."""
-    h = hashlib.blake2b(f"teramind-dropout/{int(seed)}/{int(step)}/{int(micro)}".encode(), digest_size=8).digest()
+def derive_dropout_key(seed: int, step: int, micro: int = 0, rank: int = 0) -> int:
+    """A 64-bit dropout key for one forward of a training loop: distinct per (base seed, optimizer step, micro-batch, rank), so
+    that no two forwards of a run share masks.  Rank 0 hashes what a single-device run hashes; rank r > 0 appends `/r`."""
+    tag = f"teramind-dropout/{int(seed)}/{int(step)}/{int(micro)}" + (f"/{int(rank)}" if int(rank) else "")
+    h = hashlib.blake2b(tag.encode(), digest_size=8).digest()
     return int.from_bytes(h, "little")
 
 
@@ -740,11 +741,15 @@ class AdamTrainer:
     """The optimizer half of the reference's training step (experiment.py:207-219, 394-414): clip_grad_norm_(max_norm =
     conf.grad_clip = 1) over all parameters, then torch.optim.Adam(lr = 2e-5, weight_decay = 0; config_parm.py:48, config.py:
     76-88) -- on one flat fp32 device arena (parameters, gradients, both moments), two kernels per step (tm_op_sumsq,
-    tm_op_adam).  `accum` micro-batches' gradients are averaged before the step (conf.accum_batches, config_parm.py:45)."""
+    tm_op_adam).  `accum` micro-batches' gradients are averaged before the step (conf.accum_batches, config_parm.py:45).
+    `exchange` (data-parallel training; an object with `world` and `reduce_(g)`, train_dist.GradExchange): step() first replaces
+    the accumulated gradient by its sum over ranks in rank order and averages over micro * world; clip and Adam then run
+    replicated on every rank, on bit-equal inputs.  Without one, nothing changes."""
 
     def __init__(self, net: UNetTrain, lr: float = 2e-5, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 grad_clip: float = 1.0):
+                 grad_clip: float = 1.0, exchange=None):
         self.net, self.lr, self.betas, self.eps, self.wd, self.clip = net, lr, betas, eps, weight_decay, grad_clip
+        self.exchange = exchange
         self.keys = list(net.W)
         self.off, n = {}, 0
         for k in self.keys:
@@ -771,8 +776,10 @@ class AdamTrainer:
         if self._micro == 0:
             raise RuntimeError("AdamTrainer.step: no gradients accumulated")
         ss = C.c_float(0.0)
+        if self.exchange is not None:
+            self.exchange.reduce_(self.g)
         _lib.check(_lib.lib().tm_op_sumsq(_lib.ptr(self.g), self.n, C.cast(C.byref(ss), C.c_void_p), self.net._st()), "tm_op_sumsq")
-        avg = 1.0 / self._micro
+        avg = 1.0 / (self._micro * self.exchange.world) if self.exchange is not None else 1.0 / self._micro
         total = math.sqrt(ss.value) * avg
         coef = min(1.0, self.clip / (total + 1e-6)) if self.clip > 0 else 1.0
         self.t += 1

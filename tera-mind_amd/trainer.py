@@ -8,7 +8,10 @@ followed by AdamTrainer.step().  Every random quantity is a pure function of (se
 (t, ix, iy) come from dataset.keyed_rng, the noise from a device generator seeded from the same key, the dropout masks from
 train_model.derive_dropout_key.  A run resumed from a checkpoint therefore continues bit for bit.
 
-Single device: `rank` / `world` only select the data share; gradients are not averaged across ranks.
+Data-parallel (`world` > 1, one process per rank in a process group: launch.spawn_ranks / launch.init_distributed): `rank` /
+`world` select the data share, and every optimizer step sums the ranks' accumulated gradients in rank order before clip + Adam
+(train_dist.GradExchange), so all ranks hold bit-identical parameters after every step with nothing broadcast.  `world` = 1 runs
+no exchange.
 """
 import dataclasses
 import hashlib
@@ -21,6 +24,7 @@ import torch.nn.functional as F
 from .config import PathConfig
 from .dataset import STREAM_STEP, TileSampler, TrainTileSet, keyed_rng
 from .diffusion import SpacedDiffusionBeatGans
+from .train_dist import GradExchange, require_group
 from .train_model import AdamTrainer, UNetTrain, derive_dropout_key, training_loss_and_grads
 
 CKPT_FORMAT = 1
@@ -43,6 +47,14 @@ def step_noise(seed: int, step: int, micro: int, rank: int, shape, device) -> to
     g = torch.Generator(device=device)
     g.manual_seed(int.from_bytes(h, "little") >> 1)
     return torch.randn(tuple(shape), generator=g, device=device, dtype=torch.float32)
+
+
+def rank_mean(values) -> float:
+    """Mean of one float per rank, added in rank order in float64 (the logged loss of a data-parallel step)."""
+    s = 0.0
+    for v in values:
+        s += float(v)
+    return s / len(values)
 
 
 def pad_and_mask(img: torch.Tensor, patch_size: int):
@@ -89,9 +101,15 @@ def load_checkpoint(path) -> Dict[str, object]:
 class Trainer:
     def __init__(self, cfg: PathConfig, state: Dict[str, "object"], tiles: TrainTileSet, batch_size: int, accum_batches: int = 1,
                  seed: int = 0, dropout_p: float = 0.1, lr: float = 2e-5, grad_clip: float = 1.0, loss_type: str = "mse",
-                 rank: int = 0, world: int = 1, resident: bool = False):
+                 rank: int = 0, world: int = 1, resident: bool = False, exchange=None):
+        """`exchange`: with world > 1, the gradient exchange to use in place of a train_dist.GradExchange over the process group
+        (an object with `world`, `reduce_(g)` and `all_gather_scalars(x)`; tests emulate the ranks in one process with it)."""
         if loss_type not in ("mse", "l1"):
             raise ValueError(f"loss_type {loss_type!r}")
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"rank {rank} of world {world}")
+        if world > 1 and exchange is None:
+            require_group(world)                                           # raises before anything is built
         g = tiles.geo
         if g.sdim % cfg.patch_size or g.snum != cfg.rna_slc:
             raise ValueError("tile set geometry does not match the model config")
@@ -99,6 +117,8 @@ class Trainer:
         self.loss_type, self.rank, self.world = loss_type, int(rank), int(world)
         self.net = UNetTrain(cfg, state, tiles.dev, dropout_p=dropout_p, resident=resident)
         self.opt = AdamTrainer(self.net, lr=lr, grad_clip=grad_clip)
+        if self.world > 1:
+            self.opt.exchange = exchange or GradExchange(self.opt.n, self.rank, self.world, self.net.dev)
         self.diffusion = SpacedDiffusionBeatGans(cfg.T, "ddpm", cfg.T, cfg.beta_scheduler)
         s = tiles.sampler
         self.sampler = TileSampler(s.entries, s.H, s.W, g, self.seed, gmax=s.gmax, accum_batches=self.accum)
@@ -113,7 +133,7 @@ class Trainer:
         x_pad, mask = pad_and_mask(bt.img, self.cfg.patch_size)
         t, ix, iy = step_randoms(self.seed, step, micro, self.rank, self.batch, self.tiles.geo.sdim // self.cfg.patch_size)
         noise = step_noise(self.seed, step, micro, self.rank, x_pad.shape, self.tiles.dev)
-        return x_pad, bt.rna, torch.from_numpy(t), mask, noise, (ix, iy), derive_dropout_key(self.seed, step, micro)
+        return x_pad, bt.rna, torch.from_numpy(t), mask, noise, (ix, iy), derive_dropout_key(self.seed, step, micro, self.rank)
 
     def step(self) -> Dict[str, float]:
         losses = []
@@ -125,7 +145,10 @@ class Trainer:
             losses.append(loss)
         info = self.opt.step()
         self.global_step += 1
-        return {"step": self.global_step, "loss": float(np.mean(losses)), "grad_norm": info["grad_norm"], "clip_coef": info["clip_coef"]}
+        loss = float(np.mean(losses))
+        if self.opt.exchange is not None:                                  # the mean over ranks, added in rank order on the host
+            loss = rank_mean(self.opt.exchange.all_gather_scalars(loss))
+        return {"step": self.global_step, "loss": loss, "grad_norm": info["grad_norm"], "clip_coef": info["clip_coef"]}
 
     # -- checkpoints -----------------------------------------------------------------------------
     def _split(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -138,25 +161,30 @@ class Trainer:
               "grad_clip": self.opt.clip, "loss_type": self.loss_type}
         if self.net.resident:
             hp["resident"] = True
+        if self.world > 1:
+            hp["world"] = self.world
         return make_checkpoint(self.cfg, self.net.W, self.global_step, self._split(self.opt.m), self._split(self.opt.v), self.opt.t,
                                self.seed, epoch, k, hp)
 
     def save(self, path):
+        """Every rank holds the same state; in a data-parallel run rank 0 saves."""
         torch.save(self.checkpoint(), path)
 
     @classmethod
     def resume(cls, path, tiles: TrainTileSet, cfg: Optional[PathConfig] = None, rank: int = 0, world: int = 1,
-               resident: Optional[bool] = None) -> "Trainer":
+               resident: Optional[bool] = None, exchange=None) -> "Trainer":
         """A trainer that continues the run saved at `path`; cfg defaults to the one stored in the checkpoint, `resident` to the
-        engine the run was saved with."""
+        engine the run was saved with.  A data-parallel run (hparams['world']) is resumed by every rank from rank 0's file."""
         from .weights import strip_lightning_state_dict
         ck = load_checkpoint(path)
         cfg = cfg or config_from_dict(ck["config"])
         if cfg.name != ck["config_name"]:
             raise ValueError(f"checkpoint of {ck['config_name']!r} resumed with config {cfg.name!r}")
         hp = ck["hparams"]
+        if int(hp.get("world", 1)) != int(world):
+            raise ValueError(f"checkpoint of a world = {hp.get('world', 1)} run resumed with world = {world}: the data shares differ")
         tr = cls(cfg, strip_lightning_state_dict(ck), tiles, hp["batch_size"], hp["accum_batches"], ck["seed"], hp["dropout_p"], hp["lr"],
-                 hp["grad_clip"], hp["loss_type"], rank, world, bool(hp.get("resident", False)) if resident is None else bool(resident))
+                 hp["grad_clip"], hp["loss_type"], rank, world, bool(hp.get("resident", False)) if resident is None else bool(resident), exchange)
         tr.global_step = int(ck["global_step"])
         if "adam_m" in ck:
             o = tr.opt
