@@ -94,6 +94,24 @@ static TV view_cb8(void* p, int N, int C, int Z, int H, int W) {
 }
 static TVH view_h16(void* p, int N, int C, int Z, int H, int W) { return as_h(view_cb8(p, N, C, Z, H, W)); }
 
+// the prep kernel's one plain fp32 CB8 source
+static void prep_single_src(PrepLaunch& P, const TV& x) {
+  P.nsrc = 1;
+  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+}
+
+// The weight geometry of the fp32 MFMA conv, and the ONE statement of which convs run in the z-pair form: 3x3x3, pad 1 along z, over
+// two planes (three in-plane products per plane pair, conv3d_zpair).  The host pack (tm_op_conv_mfma_res), the device pack
+// (tm_op_conv_pack_dev) and the launch on a ready pack (conv_packed) all ask here, so a pack and its launch cannot disagree on the
+// layout.  w / bias are left for the caller.
+static ConvW conv_form(int Cin, int Cout, int ksize, int zmode, int Z) {
+  ConvW cw;
+  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.ntile = (Cout + 63) / 64;
+  cw.taps = ksize == 1 ? 1 : (zmode == ZM_INPLANE ? 9 : (zmode == ZM_UPS ? 12 : 27));
+  cw.zpair = (ksize == 3 && zmode == ZM_PAD1 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;
+  return cw;
+}
+
 // fp32 CB8 x -> a 16-bit CB8 copy in `tmp` (prep kernel, no norm / act); `pair`: even block count (zero pad blocks), the
 // operand form of the 16-bit conv kernels.  Launches nothing once `e` holds an error.
 static TVH to_h16(DevTmp& tmp, const TV& x, bool f16, bool pair, hipStream_t st, hipError_t& e) {
@@ -102,8 +120,7 @@ static TVH to_h16(DevTmp& tmp, const TV& x, bool f16, bool pair, hipStream_t st,
   const TVH h = view_h16(tmp.alloc<uint16_t>((size_t)x.N * Cb * x.plane()), x.N, Cb * 8, x.Z, x.H, x.W);
   if (tmp.err) { e = tmp.err; return h; }
   PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  prep_single_src(P, x);
   P.N = x.N; P.Z = x.Z; P.S = x.H; P.h_f16 = f16 ? 1 : 0;
   P.out_h = h.p; P.out_h_nstride = h.nstride; P.pad_blocks = Cb - x.Cb;
   e = launch_prep(P, st);
@@ -155,16 +172,13 @@ extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const 
   if (zmode == ZM_UPS && (ksize != 3 || up2)) return fail(TM_ERR_ARG, "ZM_UPS: ksize 3, no fused upsample of the output");
   if (res_cb8 && (ksize != 3 || zmode == ZM_UPS)) return fail(TM_ERR_ARG, "residual: k x 3 x 3 forms other than ZM_UPS only");
   if (res_half && (!res_cb8 || up2 || S < 2)) return fail(TM_ERR_ARG, "res_half: needs a residual, S >= 2 and no fused upsample");
-  const int taps = ksize == 1 ? 1 : (zmode == ZM_INPLANE ? 9 : (ups ? 12 : 27));
   const int Zout = (ksize == 3 && zmode == ZM_VALID) ? Z - 2 : Z;
   const int So = (up2 || ups) ? 2 * S : S;
-  ConvW cw;
-  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
-  cw.zpair = (ksize == 3 && zmode == ZM_PAD1 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;    // as tm_model_finalize packs c1 / c2
-  std::vector<float> pk(ups ? conv_pack_ups_floats(Cout, cw.Cbi) : conv_pack_floats(Cout, cw.Cbi, taps));
+  ConvW cw = conv_form(Cin, Cout, ksize, zmode, Z);                   // the pair form as tm_model_finalize packs c1 / c2
+  std::vector<float> pk(ups ? conv_pack_ups_floats(Cout, cw.Cbi) : conv_pack_floats(Cout, cw.Cbi, cw.taps));
   if (ups) conv_pack_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
   else if (cw.zpair) conv_pack_zpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  else conv_pack_host((const float*)w_host, Cout, &Cin, 1, taps, pk.data());
+  else conv_pack_host((const float*)w_host, Cout, &Cin, 1, cw.taps, pk.data());
   DevTmp tmp;
   std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
   if (tmp.err) return tmp.report();
@@ -529,8 +543,7 @@ static int prep_train_impl(const void* x_cb8, const void* norm_w_host, const voi
   if (tmp.err) return tmp.report();
   TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
   PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  prep_single_src(P, x);
   P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 1; P.per_image = per_image;
   if (dsc) { P.mod = MOD_IMAGE; P.mod_scale = dsc; P.mod_shift = dsh; P.mod_stride = Cp; }
   if (mask_cb8) { P.drop_mask = (const float*)mask_cb8; P.drop_ns = x.nstride; P.drop_scale = drop_scale; }
@@ -632,8 +645,7 @@ extern "C" int tm_op_modnorm(const void* x_cb8, const void* norm_w_host, const v
   if (tmp.err) return tmp.report();
   TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
   PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  prep_single_src(P, x);
   P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 0;
   P.mod = MOD_VOXEL; P.mod_scale = (const float*)scale_cb8; P.mod_shift = (const float*)shift_cb8; P.mod_stride = x.nstride;
   P.out = y.p; P.out_nstride = y.nstride;
@@ -721,8 +733,7 @@ extern "C" int tm_op_resample(const void* x_cb8, void* y_cb8, int N, int C, int 
   const int S_in = mode == 1 ? S_out / 2 : S_out * 2;
   TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S_in, S_in), y = view_cb8(y_cb8, N, C, Z, S_out, S_out);
   PrepLaunch P;
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+  prep_single_src(P, x);
   P.resample = mode == 1 ? RS_UP2 : RS_DOWN2;
   P.N = N; P.Z = Z; P.S = S_out; P.inv_c = 1.0f / (float)C;
   P.out = y.p; P.out_nstride = y.nstride;
@@ -822,17 +833,15 @@ extern "C" long tm_conv_pack_floats(int Cout, int Cin, int ksize, int Z, int rol
 extern "C" int tm_op_conv_pack_dev(const void* w_dev, void* pack_dev, int Cout, int Cin, int ksize, int Z, int role, void* stream) {
   if (!w_dev || !pack_dev) return fail(TM_ERR_ARG, "null argument");
   if (int rc = packed_form(Cout, Cin, ksize, Z, role)) return rc;
-  const int pair = (ksize == 3 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;               // as tm_op_conv_mfma picks the pair form
-  HIP_TRY(launch_conv_pack((const float*)w_dev, (float*)pack_dev, Cout, Cin, ksize == 1 ? 1 : 27, role, pair, (hipStream_t)stream));
+  const ConvW cw = conv_form(role ? Cout : Cin, role ? Cin : Cout, ksize, ZM_PAD1, Z);   // of the conv that reads the pack
+  HIP_TRY(launch_conv_pack((const float*)w_dev, (float*)pack_dev, Cout, Cin, cw.taps, role, cw.zpair, (hipStream_t)stream));
   return TM_OK;
 }
 // y = conv(x) on a ready pack of Cout x Cin; bias_dev [Cout] or null (zero)
 static int conv_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout, int Z, int S,
                        int ksize, hipStream_t st) {
   DevTmp tmp(st);
-  ConvW cw;
-  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = ksize == 1 ? 1 : 27; cw.ntile = (Cout + 63) / 64;
-  cw.zpair = (ksize == 3 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;
+  ConvW cw = conv_form(Cin, Cout, ksize, ZM_PAD1, Z);
   float* b = tmp.ordered_floats((size_t)cw.ntile * 64, true);       // the epilogues read the bias zero padded to 64 couts
   if (tmp.err) return tmp.report();
   if (bias_dev) HIP_TRY(hipMemcpyAsync(b, bias_dev, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));

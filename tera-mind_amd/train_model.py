@@ -5,15 +5,15 @@ forward conv / prep kernels -- no torch.autograd, no torch arithmetic on the mod
 The reference trains through torch.autograd over stock modules (experiment.py:121-193 -> diffusion/base.py:181-289 ->
 model/unet_ours.py).  Here `UNetTrain.forward` records a tape of ops, each with a hand-written adjoint:
 
-    conv3 / conv1     tm_op_conv_mfma          | tm_op_conv_dgrad (same kernel, transposed + flipped weights), tm_op_conv_wgrad
+    conv3 / conv1     the conv engine (train_conv.py): forward | data gradient (same kernel, transposed + flipped weights), weight gradient
                       ((1,3,3) and the down_z (kz,3,3) kernels run embedded in the 3x3x3 'same' conv, sliced afterwards; down_z at
                       kz = 5 (rna_slc 8) is training.DownZTrain: its z taps as five shifted in-plane convs)
     SiLU(RMSNorm * w [* (1 + scale) + shift])   tm_op_prep_train | tm_op_prep_bwd     (ResBlock in / out layers, the head)
-    nearest x2 / AvgPool(1,2,2)                 tm_op_resample   | the other mode, x 4 or / 4 (tm_op_ew 7 / 8)
+    nearest x2 / AvgPool(1,2,2)                 tm_op_resample   | the other mode, x 4 or / 4 (training.ew 7 / 8)
     AttnBlock with gene cross-attention         training.AttnBlockTrain (modulate(norm), windowed attention core, MLP, gates)
     Linears over rows (time embedding, emb_layers, the gene-gene AttnBlock)   tm_op_gemm_f32 in its three roles
     row RMSNorm / softmax of the gene-gene block                              tm_op_rows
-    SiLU / GELU / adds                                                        tm_op_ew
+    SiLU / GELU / adds                                                        training.ew
 
 Channel concatenation, the half-patch collage (model/unet_ours.py:325-341) and the z slice of down_z are re-indexings of
 device tensors (torch views / cat / pad: no arithmetic); the loss and d(loss)/d(pred) are a handful of elementwise torch
@@ -23,13 +23,13 @@ mask is drawn on the GPU from (per-forward key, block site, p) by the forward pr
 (tm_op_prep_train_rng / tm_op_prep_bwd_rng; the rule is DESIGN.md §8), so no mask is stored.  p = 0 (the default) is the
 model as in `.eval()`.  Functional, not tuned: every op synchronises, weights are re-packed per call.
 
-`UNetTrain(..., resident=True)` runs the conv ops of the tape on a second engine (same kernels forward, same numerics contract):
-the parameters live in one flat fp32 device arena (shared with AdamTrainer), a conv weight is packed on the device once per role
-(forward / data gradient) per optimizer step (tm_op_conv_pack_dev), the convs read the ready packs (tm_op_conv_mfma_packed /
-tm_op_conv_dgrad_packed) and the weight gradient runs on the matrix pipe straight into device gradient tensors
-(tm_op_conv_wgrad_dev).  The prep / row / GEMM ops keep their host-pointer arguments in both modes.
+There is one conv() over two engines with the same methods (train_conv.py): HostConvs (host weights, packed and uploaded per call,
+gradients added on the host) and, with `UNetTrain(..., resident=True)`, ResidentConvs (same kernels forward, same numerics contract):
+the parameters live in one flat fp32 device arena (ParamLayout, shared with AdamTrainer), a conv weight is packed on the device once per
+role (forward / data gradient) per optimizer step, the convs read the ready packs and the weight gradient runs on the matrix pipe
+straight into device gradient tensors.  The engine owns the pack cache and the lifetime rules of its asynchronous calls (stated in the
+train_conv.py docstring).  The prep / row / GEMM ops keep their host-pointer arguments in both modes.
 """
-import collections
 import ctypes as C
 import hashlib
 import math
@@ -40,7 +40,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from .config import PathConfig
-from .training import AttnBlockTrain, DownZTrain, _cb8, _host, _hp, _ncdhw
+from .train_conv import HostConvs, ParamLayout, ResidentConvs
+from .training import AttnBlockTrain, DownZTrain, _cb8, _host, _hp, _ncdhw, ew
 
 
 class _V:
@@ -117,24 +118,19 @@ class UNetTrain:
         self._drop_calls: Dict[str, int] = {}
         self.dev = torch.device(device)
         self._W: Optional[Dict[str, torch.Tensor]] = {k: _host(torch.as_tensor(v)) for k, v in state.items()}
-        self.keys = list(self._W)
-        self._shape = {k: tuple(v.shape) for k, v in self._W.items()}
-        self._off, n = {}, 0
-        for k in self.keys:
-            self._off[k] = n
-            n += self._W[k].numel()
+        self.layout = ParamLayout(self._W)                              # the one arena layout: P, AdamTrainer's p / g / m / v
+        self.keys, self._shape = self.layout.keys, self.layout.shape
         self.resident = bool(resident)
         self.P: Optional[torch.Tensor] = None                           # resident: the one master copy, flat fp32 on the device
-        self._packs: Dict[Tuple[str, int], Tuple[torch.Tensor, int]] = {}
-        self.pack_count = collections.Counter()                         # (conv key, role) -> packs built so far
         if self.resident:
-            self.P = torch.cat([self._W[k].reshape(-1) for k in self.keys]).to(self.dev)
-        self._Wd: Dict[str, torch.Tensor] = {}
+            self.P = self.layout.flatten(self._W).to(self.dev)
+        self.convs = (ResidentConvs if self.resident else HostConvs)(self.dev)
+        self.pack_count = self.convs.pack_count                         # resident: (conv key, role) -> packs built so far
+        self._Wd: Dict[str, torch.Tensor] = {}                          # parameters on the device, by key (_wd)
         self.tape: List = []
         self.grads: Dict[str, torch.Tensor] = {}
         self._one = None
-        self._downz: Optional[DownZTrain] = None
-        self._downz_src: Tuple = (None, None)
+        self._downz, self._downz_src = None, (None, None)               # the DownZTrain block and the (weight, bias) it was built from
         if cfg.rna_slc == 1 and cfg.patch_size == 32:
             raise NotImplementedError("UNetTrain: rna_slc 1 at patch size 32 has patches of 16 voxels at the lowest level (Z = 1, S = 4); the "
                                       "ResBlock norm backward sums the per-image scale / shift gradients of at most two images per "
@@ -152,45 +148,23 @@ class UNetTrain:
     @property
     def W(self) -> Dict[str, torch.Tensor]:
         if self._W is None:
-            host = self.P.cpu()
-            self._W = {k: host[self._off[k]:self._off[k] + math.prod(self._shape[k])].reshape(self._shape[k]) for k in self.keys}
+            self._W = self.layout.split(self.P.cpu())
         return self._W
 
-    def _pd(self, key):
-        """resident: the parameter `key` as a view of the device arena"""
-        return self.P[self._off[key]:self._off[key] + math.prod(self._shape[key])].reshape(self._shape[key])
+    def _wd(self, key):
+        """the parameter `key` on the device: a view of the arena (it holds: P is never replaced), or a copy of W[key] until the next step"""
+        if key not in self._Wd:
+            self._Wd[key] = self.layout.view(self.P, key) if self.resident else self.W[key].to(self.dev).contiguous()
+        return self._Wd[key]
+
+    def _wc(self, key):
+        """the parameter `key` where this net's conv engine reads it: the arena view, or the host tensor"""
+        return self._wd(key) if self.resident else self.W[key]
 
     def params_updated(self):
-        """resident: the arena changed (AdamTrainer.step): the host copy and every pack are stale"""
+        """resident: the arena changed (AdamTrainer.step): the host copy and every pack (down_z taps included) are stale"""
         self._W = None
-        self._packs.clear()
-        if self._downz is not None:
-            self._downz.params_updated()
-
-    def _pack(self, key, role, co, ci, ks, Z, embed):
-        """The device pack of conv `key` for role 0 (forward) / 1 (data gradient), built on first use after an optimizer step."""
-        hit = self._packs.get((key, role))
-        if hit is not None:
-            assert hit[1] == Z, (key, hit[1], Z)
-            return hit[0]
-        w = self._pd(key + ".weight")
-        if embed:
-            wf = torch.zeros((co, ci, 3, 3, 3), dtype=torch.float32, device=self.dev)
-            wf[:, :, 1] = w[:, :, 0]
-        else:
-            wf = w
-        pk = torch.empty((_lib.lib().tm_conv_pack_floats(co, ci, ks, Z, role),), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_pack_dev(_lib.ptr(wf), _lib.ptr(pk), co, ci, ks, Z, role, self._st()), "tm_op_conv_pack_dev")
-        self._packs[(key, role)] = (pk, Z)
-        self.pack_count[(key, role)] += 1
-        return pk
-
-    def _wd(self, key):
-        if self.resident:
-            return self._pd(key)
-        if key not in self._Wd:
-            self._Wd[key] = self.W[key].to(self.dev).contiguous()
-        return self._Wd[key]
+        self.convs.invalidate()
 
     def _gacc(self, key, g):
         g = g.reshape(self._shape[key])
@@ -199,13 +173,7 @@ class UNetTrain:
         self.grads[key] = g.clone() if key not in self.grads else self.grads[key] + g
 
     def _acc(self, v: _V, g: torch.Tensor):
-        v.g = g if v.g is None else self._ew(6, v.g, g)
-
-    def _ew(self, op, a, b=None, c=None, two=False):
-        o1 = torch.empty_like(a)
-        o2 = torch.empty_like(a) if two else None
-        _lib.check(_lib.lib().tm_op_ew(op, _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), _lib.ptr(o1), _lib.ptr(o2), a.numel(), self._st()), "tm_op_ew")
-        return (o1, o2) if two else o1
+        v.g = g if v.g is None else ew(6, v.g, g)
 
     @staticmethod
     def _geo(cb):
@@ -214,102 +182,17 @@ class UNetTrain:
     # ------------------------------------------------------------------------------------------------------------------
     # tape ops on CB8 values
     # ------------------------------------------------------------------------------------------------------------------
-    # The k x 3 x 3 conv kernels take planes of S = 4 .. 128.  A 2 x 2 plane (the gene grid of patch size 32) runs in the corner of
-    # a zero 4 x 4 plane: the zeros right of and below the corner are the conv's own zero padding, so the corner of the result
-    # is the 'same' conv of the 2 x 2 plane, forward and data gradient alike (a re-indexing on both sides, no arithmetic); the
-    # weight gradient kernels take any S and read the tensors as they are.
-    @staticmethod
-    def _conv_plane(ks, S):
-        return 4 if ks == 3 and S == 2 else S
-
-    @staticmethod
-    def _corner_in(t, S, Sc):
-        return t if Sc == S else F.pad(t, (0, 0, 0, Sc - S, 0, Sc - S)).contiguous()
-
-    @staticmethod
-    def _corner_out(t, S, Sc):
-        return t if Sc == S else t[:, :, :, :S, :S].contiguous()
-
     def conv(self, x: _V, key: str) -> _V:
         """Conv3d with the reference weight `key`.weight [Co, Ci, kz, ky, kx]: 3x3x3 pad 1, 1x1x1, or (1,3,3) pad (0,1,1)
-        embedded into the middle z slice of a 3x3x3 kernel."""
-        if self.resident:
-            return self._conv_resident(x, key)
-        w = self.W[key + ".weight"]
-        b = self.W[key + ".bias"]
-        co, ci = w.shape[:2]
-        assert ci == x.C, (key, ci, x.C)
-        ks = 1 if w.shape[2:] == (1, 1, 1) else 3
-        embed = tuple(w.shape[2:]) == (1, 3, 3)
-        if embed:
-            wf = torch.zeros((co, ci, 3, 3, 3), dtype=torch.float32)
-            wf[:, :, 1] = w[:, :, 0]
-        else:
-            wf = w.contiguous()
-        N, Z, S = self._geo(x.t)
-        Sc = self._conv_plane(ks, S)
-        xin = self._corner_in(x.t, S, Sc)
-        y = torch.zeros((N, (co + 7) // 8, Z, Sc, Sc, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_mfma(_lib.ptr(xin), _hp(wf), _hp(b), _lib.ptr(y), N, ci, co, Z, Sc, ks, 0, 0, 0, self._st()), "tm_op_conv_mfma")
-        out = _V(self._corner_out(y, S, Sc), co)
-
-        def bwd():
-            g = out.g
-            dw = torch.empty((co, ci) + ((3, 3, 3) if ks == 3 else (1, 1, 1)), dtype=torch.float32)
-            db = torch.empty((co,), dtype=torch.float32)
-            _lib.check(_lib.lib().tm_op_conv_wgrad(_lib.ptr(x.t), _lib.ptr(g), _hp(dw), _hp(db), N, ci, co, Z, S, ks, self._st()), "tm_op_conv_wgrad")
-            self._gacc(key + ".weight", dw[:, :, 1:2].contiguous() if embed else dw)
-            self._gacc(key + ".bias", db)
-            dx = torch.zeros_like(xin)
-            gin = self._corner_in(g, S, Sc)                               # named: it must outlive the call that reads it
-            _lib.check(_lib.lib().tm_op_conv_dgrad(_lib.ptr(gin), _hp(wf), _lib.ptr(dx), N, ci, co, Z, Sc, ks, self._st()),
-                       "tm_op_conv_dgrad")
-            self._acc(x, self._corner_out(dx, S, Sc))
-        self.tape.append(bwd)
-        return out
-
-    def _conv_resident(self, x: _V, key: str) -> _V:
-        """conv() on the device-resident engine: ready packs, the weight gradient straight into device gradient tensors
-        (accumulate = 1 for the second use of a weight in one backward), nothing synchronised, no host memory touched."""
+        embedded into the middle z slice of a 3x3x3 kernel; on this net's conv engine (geometry, packs, lifetimes: train_conv.py)."""
         kw, kb = key + ".weight", key + ".bias"
-        shp = self._shape[kw]
-        co, ci = shp[:2]
-        assert ci == x.C, (key, ci, x.C)
-        ks = 1 if shp[2:] == (1, 1, 1) else 3
-        embed = shp[2:] == (1, 3, 3)
-        N, Z, S = self._geo(x.t)
-        L = _lib.lib()
-        Sc = self._conv_plane(ks, S)
-        xin = self._corner_in(x.t, S, Sc)
-        y = torch.zeros((N, (co + 7) // 8, Z, Sc, Sc, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(L.tm_op_conv_mfma_packed(_lib.ptr(xin), _lib.ptr(self._pack(key, 0, co, ci, ks, Z, embed)), _lib.ptr(self._pd(kb)),
-                                            _lib.ptr(y), N, ci, co, Z, Sc, ks, self._st()), "tm_op_conv_mfma_packed")
-        out = _V(self._corner_out(y, S, Sc), co)
+        f = self.convs.filter(key, self._wc(kw))
+        assert f.ci == x.C, (key, f.ci, x.C)
+        out = _V(self.convs.conv(x.t, f, self._wc(kb)), f.co)
 
         def bwd():
-            g = out.g
-            acc = 1 if kw in self.grads else 0
-            if not acc:
-                self.grads[kb] = torch.empty((co,), dtype=torch.float32, device=self.dev)
-            if embed:
-                # the (1,3,3) filter is the middle z slice of the 3x3x3 gradient: sliced on the device
-                dw = (torch.zeros if acc else torch.empty)((co, ci, 3, 3, 3), dtype=torch.float32, device=self.dev)
-            else:
-                if not acc:
-                    self.grads[kw] = torch.empty(shp, dtype=torch.float32, device=self.dev)
-                dw = self.grads[kw]
-            _lib.check(L.tm_op_conv_wgrad_dev(_lib.ptr(x.t), _lib.ptr(g), _lib.ptr(dw), _lib.ptr(self.grads[kb]), acc, N, ci, co, Z, S, ks,
-                                              self._st()), "tm_op_conv_wgrad_dev")
-            if embed:
-                self._gacc(kw, dw[:, :, 1:2])
-            dx = torch.zeros_like(xin)
-            # named, and the pack built first: a temporary would be released before the (asynchronous) call, and the pack's
-            # allocation could take its memory
-            pk = self._pack(key, 1, co, ci, ks, Z, embed)
-            gin = self._corner_in(g, S, Sc)
-            _lib.check(L.tm_op_conv_dgrad_packed(_lib.ptr(gin), _lib.ptr(pk), _lib.ptr(dx), N, ci, co, Z, Sc, ks, self._st()),
-                       "tm_op_conv_dgrad_packed")
-            self._acc(x, self._corner_out(dx, S, Sc))
+            self.convs.wgrad_into(self.grads, self._gacc, kw, kb, x.t, out.g, f)
+            self._acc(x, self.convs.dgrad(out.g, f))
         self.tape.append(bwd)
         return out
 
@@ -364,17 +247,17 @@ class UNetTrain:
 
         def bwd():
             # up2^T = 4 * avgpool;  avgpool^T = up2 / 4
-            self._acc(x, self._ew(7 if mode == 1 else 8, self._resample_raw(out.g, x.C, 2 if mode == 1 else 1)))
+            self._acc(x, ew(7 if mode == 1 else 8, self._resample_raw(out.g, x.C, 2 if mode == 1 else 1)))
         self.tape.append(bwd)
         return out
 
     def silu(self, x: _V) -> _V:
-        out = _V(self._ew(4, x.t), x.C)
-        self.tape.append(lambda: self._acc(x, self._ew(5, out.g, x.t)))
+        out = _V(ew(4, x.t), x.C)
+        self.tape.append(lambda: self._acc(x, ew(5, out.g, x.t)))
         return out
 
     def add(self, a: _V, b: _V) -> _V:
-        out = _V(self._ew(6, a.t, b.t), a.C)
+        out = _V(ew(6, a.t, b.t), a.C)
 
         def bwd():
             self._acc(a, out.g)
@@ -498,8 +381,8 @@ class UNetTrain:
 
     def act_rows(self, x: _V, fwd_op: int) -> _V:
         """fwd_op 2 = GELU(tanh), 4 = SiLU on a plain tensor."""
-        out = _V(self._ew(fwd_op, x.t))
-        self.tape.append(lambda: self._acc(x, self._ew(fwd_op + 1, out.g.contiguous(), x.t)))
+        out = _V(ew(fwd_op, x.t))
+        self.tape.append(lambda: self._acc(x, ew(fwd_op + 1, out.g.contiguous(), x.t)))
         return out
 
     def gene_attention(self, tok: torch.Tensor, n: int, G: int, D: int) -> _V:
@@ -557,15 +440,13 @@ class UNetTrain:
         return out
 
     def down_z(self, x: _V, key: str) -> _V:
-        """The (kz,3,3) conv without z padding at kz > 3 (rna_slc 8: kz = 5): training.DownZTrain on this engine's weights."""
+        """The (kz,3,3) conv without z padding at kz > 3 (rna_slc 8: kz = 5): training.DownZTrain on this net's engine and weights."""
         kw, kb = key + ".weight", key + ".bias"
-        if not self.resident:
-            # host weights are replaced, never written in place (AdamTrainer.step): the block and its embedded filters hold
-            # as long as W[kw] / W[kb] are the tensors it was built from
-            if self._downz is None or self._downz_src[0] is not self.W[kw] or self._downz_src[1] is not self.W[kb]:
-                self._downz, self._downz_src = DownZTrain(self.W[kw], self.W[kb], self.dev), (self.W[kw], self.W[kb])
-        elif self._downz is None:
-            self._downz = DownZTrain(self._pd(kw), self._pd(kb), self.dev, resident=True)     # views of the arena: updated in place
+        w, b = self._wc(kw), self._wc(kb)
+        # host weights are replaced, never written in place (AdamTrainer.step): the block and its embedded filters hold as long as W[kw] /
+        # W[kb] are the tensors it was built from.  Resident ones are the same views of the arena for the net's life: its packs go stale
+        if self._downz is None or self._downz_src[0] is not w or self._downz_src[1] is not b:
+            self._downz, self._downz_src = DownZTrain(w, b, self.dev, self.resident, engine=self.convs, key=key), (w, b)
         blk = self._downz
         out = _V(blk.forward_cb(x.t), blk.co)
 
@@ -750,24 +631,20 @@ class AdamTrainer:
                  grad_clip: float = 1.0, exchange=None):
         self.net, self.lr, self.betas, self.eps, self.wd, self.clip = net, lr, betas, eps, weight_decay, grad_clip
         self.exchange = exchange
-        self.keys = list(net.W)
-        self.off, n = {}, 0
-        for k in self.keys:
-            self.off[k] = n
-            n += net.W[k].numel()
-        self.n = n
+        self.layout = net.layout
+        self.keys, self.off, self.n = self.layout.keys, self.layout.off, self.layout.n
         dev = net.dev
-        # a resident net keeps its parameters in the same flat layout on the device: one master copy, shared
-        self.p = net.P if net.resident else torch.cat([net.W[k].reshape(-1) for k in self.keys]).to(dev)
-        self.g = torch.zeros(n, dtype=torch.float32, device=dev)
+        # a resident net keeps its parameters in this layout on the device: one master copy, shared
+        self.p = net.P if net.resident else self.layout.flatten(net.W).to(dev)
+        self.g = torch.zeros(self.n, dtype=torch.float32, device=dev)
         self.m, self.v = torch.zeros_like(self.g), torch.zeros_like(self.g)
         self.t, self._micro = 0, 0
 
     def accumulate(self, grads: Dict[str, torch.Tensor]):
         """Adds one micro-batch's gradients (tensors keyed like the state_dict; host, or device ones from a resident net, which
         never cross the host) into the arena."""
-        flat = torch.cat([grads[k].reshape(-1) for k in self.keys]).to(self.net.dev)
-        self.g = flat if self._micro == 0 else self.net._ew(6, self.g, flat)
+        flat = self.layout.flatten(grads).to(self.net.dev)
+        self.g = flat if self._micro == 0 else ew(6, self.g, flat)
         self._micro += 1
 
     def step(self) -> Dict[str, float]:
@@ -788,9 +665,9 @@ class AdamTrainer:
         self._micro = 0
         if self.net.resident:
             self.net.params_updated()
-            return {"grad_norm": total, "clip_coef": coef}
-        host = self.p.cpu()
-        for k in self.keys:
-            self.net.W[k] = host[self.off[k]:self.off[k] + self.net.W[k].numel()].reshape(self.net.W[k].shape).clone()
-        self.net._Wd.clear()
+        else:
+            host = self.p.cpu()
+            for k in self.keys:
+                self.net.W[k] = self.layout.view(host, k).clone()
+            self.net._Wd.clear()
         return {"grad_norm": total, "clip_coef": coef}

@@ -152,8 +152,7 @@ class Trainer:
 
     # -- checkpoints -----------------------------------------------------------------------------
     def _split(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
-        o, host = self.opt, flat.cpu()
-        return {k: host[o.off[k]:o.off[k] + self.net.W[k].numel()].reshape(self.net.W[k].shape) for k in o.keys}
+        return self.opt.layout.split(flat.cpu())
 
     def checkpoint(self) -> Dict[str, object]:
         epoch, k = self.sampler.position(self.batch, self.global_step, 0, self.world)
@@ -188,7 +187,7 @@ class Trainer:
         tr.global_step = int(ck["global_step"])
         if "adam_m" in ck:
             o = tr.opt
-            o.m = torch.cat([ck["adam_m"][k].reshape(-1) for k in o.keys]).to(tr.net.dev)
-            o.v = torch.cat([ck["adam_v"][k].reshape(-1) for k in o.keys]).to(tr.net.dev)
+            o.m = o.layout.flatten(ck["adam_m"]).to(tr.net.dev)
+            o.v = o.layout.flatten(ck["adam_v"]).to(tr.net.dev)
             o.t = int(ck["adam_step"])
         return tr

@@ -11,18 +11,19 @@ model/MBAblocks.py:237-299).  This module is the first slice of a native trainin
 and its backward with hand-written kernels: the conv data gradients on the forward MFMA conv kernel (flipped, transposed
 weights), `conv_wgrad_kernel`, `prep_bwd_kernel`, `chan_sum_kernel` (csrc/tm_train.hip).  The dropout keep mask is an
 INPUT here (the reference draws it inside nn.Dropout(p=0.1), config_parm.py:46), so that gradients can be compared with
-torch.autograd of the CPU oracle on the same mask; the whole-model step (train_model.py) draws it on the GPU instead.  `AttnBlockTrain` is the gene cross-attention block (MBAblocks.py:428-514)
-forward and backward, checked against the reference module's own autograd.  The whole-model training step (both decoder
+torch.autograd of the CPU oracle on the same mask; the whole-model step (train_model.py) draws it on the GPU instead.  `AttnBlockTrain` is the gene cross-attention block
+(MBAblocks.py:428-514) forward and backward, checked against the reference module's own autograd.  Every conv and Linear of the blocks
+is a call on a conv engine (train_conv.py), which owns geometry, output allocation and the lifetime rules of asynchronous calls.  The whole-model training step (both decoder
 passes, the gene-gene attention block, time embedding, loss, clip + Adam) is composed in train_model.py.  Not covered:
 mixed precision (the reference trains under fp16 autocast; this slice is fp32), EMA (commented out upstream,
 experiment.py:200), the data loader -- see DESIGN.md section 8.
 """
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib
+from .train_conv import HostConvs, ResidentConvs, _hp  # noqa: F401  (_hp: tools import it from here)
 
 
 def _cb8(x: torch.Tensor) -> torch.Tensor:
@@ -43,8 +44,14 @@ def _host(t: Optional[torch.Tensor]):
     return None if t is None else t.detach().to("cpu", torch.float32).contiguous()
 
 
-def _hp(t):
-    return C.c_void_p(0) if t is None else C.c_void_p(t.data_ptr())
+def ew(op, a, b=None, c=None, two=False, out=None):
+    """The elementwise kernel (ew_kernel, csrc/tm_train.hip) over a.numel() floats: op 0 a + b c | 1 a b and a c (two=True) | 2 GELU(a) |
+    3 a GELU'(b) | 4 SiLU(a) | 5 a SiLU'(b) | 6 a + b | 7 4 a | 8 a / 4; into `out` (may be a: elementwise) or a new tensor."""
+    o1 = torch.empty_like(a) if out is None else out
+    o2 = torch.empty_like(a) if two else None
+    _lib.check(_lib.lib().tm_op_ew(op, _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), _lib.ptr(o1), _lib.ptr(o2), a.numel(), _lib.current_stream_ptr()),
+               "tm_op_ew")
+    return (o1, o2) if two else o1
 
 
 class ResBlockTrain:
@@ -56,9 +63,10 @@ class ResBlockTrain:
     def __init__(self, params: Dict[str, torch.Tensor], device="cuda:0"):
         self.p = {k: _host(v) for k, v in params.items()}
         self.dev = torch.device(device)
-        self.cin = self.p["in_layers.2.weight"].shape[1]
-        self.cout = self.p["in_layers.2.weight"].shape[0]
+        self.cout, self.cin = self.p["in_layers.2.weight"].shape[:2]
         self.has_skip = "skip_connection.weight" in self.p
+        self.convs = HostConvs(self.dev)
+        self.f = {k: self.convs.filter(k, self.p[k + ".weight"]) for k in ("in_layers.2", "out_layers.3", "skip_connection") if k + ".weight" in self.p}
         self._saved = None
 
     # -- pieces ---------------------------------------------------------------------------------
@@ -66,12 +74,6 @@ class ResBlockTrain:
         y = torch.empty_like(x_cb)
         _lib.check(_lib.lib().tm_op_prep_train(_lib.ptr(x_cb), _hp(nw), _hp(scale), _hp(shift), _lib.ptr(mask_cb), drop_scale, per_image,
                                                _lib.ptr(y), N, Cc, Z, S, _lib.current_stream_ptr()), "tm_op_prep_train")
-        return y
-
-    def _conv(self, x_cb, w, b, N, Cin, Cout, Z, S, ksize):
-        y = torch.zeros((N, (Cout + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_mfma(_lib.ptr(x_cb), _hp(w), _hp(b), _lib.ptr(y), N, Cin, Cout, Z, S, ksize, 0, 0, 0,
-                                              _lib.current_stream_ptr()), "tm_op_conv_mfma")
         return y
 
     def forward(self, x: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, keep_mask: Optional[torch.Tensor] = None,
@@ -86,31 +88,14 @@ class ResBlockTrain:
         mask_cb = _cb8(keep_mask.to(self.dev).float()) if keep_mask is not None else None
         ds = 1.0 / (1.0 - p_drop) if keep_mask is not None else 1.0
         A = self._prep(x_cb, w1n, None, None, None, 1.0, per_image, N, Cin, Z, S)
-        H1 = self._conv(A, P["in_layers.2.weight"], P["in_layers.2.bias"], N, Cin, self.cout, Z, S, 3)
+        conv = lambda t, k: self.convs.conv(t, self.f[k], P[k + ".bias"])                           # noqa: E731
+        H1 = conv(A, "in_layers.2")
         D = self._prep(H1, w2n, sc, sh, mask_cb, ds, per_image, N, self.cout, Z, S)
-        H2 = self._conv(D, P["out_layers.3.weight"], P["out_layers.3.bias"], N, self.cout, self.cout, Z, S, 3)
-        if self.has_skip:
-            sk = self._conv(x_cb, P["skip_connection.weight"], P["skip_connection.bias"], N, Cin, self.cout, Z, S, 1)
-        else:
-            sk = x_cb
+        H2 = conv(D, "out_layers.3")
+        sk = conv(x_cb, "skip_connection") if self.has_skip else x_cb
         out_cb = sk + H2                                          # the residual add (elementwise, torch on the device)
         self._saved = dict(x_cb=x_cb, A=A, H1=H1, D=D, mask_cb=mask_cb, ds=ds, sc=sc, sh=sh, per_image=per_image, shape=(N, Z, S))
         return _ncdhw(out_cb, self.cout)
-
-    def _dgrad(self, dy_cb, w, N, Cin, Cout, Z, S, ksize):
-        dx = torch.zeros((N, (Cin + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_dgrad(_lib.ptr(dy_cb), _hp(w), _lib.ptr(dx), N, Cin, Cout, Z, S, ksize,
-                                               _lib.current_stream_ptr()), "tm_op_conv_dgrad")
-        return dx
-
-    def _wgrad(self, x_cb, dy_cb, N, Cin, Cout, Z, S, ksize):
-        taps = 27 if ksize == 3 else 1
-        dw = torch.empty((Cout, Cin) + ((3, 3, 3) if ksize == 3 else (1, 1, 1)), dtype=torch.float32)
-        db = torch.empty((Cout,), dtype=torch.float32)
-        assert dw.numel() == Cout * Cin * taps
-        _lib.check(_lib.lib().tm_op_conv_wgrad(_lib.ptr(x_cb), _lib.ptr(dy_cb), _hp(dw), _hp(db), N, Cin, Cout, Z, S, ksize,
-                                               _lib.current_stream_ptr()), "tm_op_conv_wgrad")
-        return dw, db
 
     def _prep_bwd(self, x_cb, g_cb, nw, sc, sh, mask_cb, ds, per_image, N, Cc, Z, S):
         dx = torch.empty_like(x_cb)
@@ -123,6 +108,11 @@ class ResBlockTrain:
                    "tm_op_prep_bwd")
         return dx, dw, dsc, dsh
 
+    def _conv_bwd(self, x_cb, g_cb, k, grads):
+        dx = self.convs.dgrad(g_cb, self.f[k])
+        grads[k + ".weight"], grads[k + ".bias"] = self.convs.wgrad(x_cb, g_cb, self.f[k])
+        return dx
+
     def backward(self, dout: torch.Tensor):
         s, P = self._saved, self.p
         N, Z, S = s["shape"]
@@ -130,18 +120,15 @@ class ResBlockTrain:
         g = _cb8(dout.to(self.dev).float())
         grads = {}
         # out = skip(x) + conv2(D)
-        dD = self._dgrad(g, P["out_layers.3.weight"], N, Cout, Cout, Z, S, 3)
-        grads["out_layers.3.weight"], grads["out_layers.3.bias"] = self._wgrad(s["D"], g, N, Cout, Cout, Z, S, 3)
+        dD = self._conv_bwd(s["D"], g, "out_layers.3", grads)
         dH1, dw2, dscale, dshift = self._prep_bwd(s["H1"], dD, P["out_layers.0.weight"].reshape(-1), s["sc"], s["sh"], s["mask_cb"],
                                                   s["ds"], s["per_image"], N, Cout, Z, S)
         grads["out_layers.0.weight"] = dw2.reshape(P["out_layers.0.weight"].shape)
-        dA = self._dgrad(dH1, P["in_layers.2.weight"], N, Cin, Cout, Z, S, 3)
-        grads["in_layers.2.weight"], grads["in_layers.2.bias"] = self._wgrad(s["A"], dH1, N, Cin, Cout, Z, S, 3)
+        dA = self._conv_bwd(s["A"], dH1, "in_layers.2", grads)
         dx, dw1, _, _ = self._prep_bwd(s["x_cb"], dA, P["in_layers.0.weight"].reshape(-1), None, None, None, 1.0, s["per_image"], N, Cin, Z, S)
         grads["in_layers.0.weight"] = dw1.reshape(P["in_layers.0.weight"].shape)
         if self.has_skip:
-            dx = dx + self._dgrad(g, P["skip_connection.weight"], N, Cin, Cout, Z, S, 1)
-            grads["skip_connection.weight"], grads["skip_connection.bias"] = self._wgrad(s["x_cb"], g, N, Cin, Cout, Z, S, 1)
+            dx = dx + self._conv_bwd(s["x_cb"], g, "skip_connection", grads)
         else:
             dx = dx + g
         return _ncdhw(dx, Cin), dscale, dshift, grads
@@ -156,16 +143,16 @@ class DownZTrain:
         dw[:, :, dz]   = the middle z plane of the 3x3x3 weight gradient of x[:, :, dz:dz + Zo] against dy;  db = sum dy
 
     every term an in-plane conv embedded in the middle z slice of the 3x3x3 'same' conv at Zo planes, summed in dz order
-    (tm_op_ew 6), so the result is deterministic.  Zo <= 4 (the weight-gradient kernels stage four planes).
+    (ew op 6), so the result is deterministic.  Zo <= 4 (the weight-gradient kernels stage four planes).
     Untuned: every tap after the first is a conv into a second buffer plus a separate add launch (the backward also copies
     the z slice of dx out and back per tap) where an accumulating epilogue would do; the conv runs once per step.
 
-    Two engines, as UNetTrain: host weight / bias (tm_op_conv_mfma, _dgrad, _wgrad; gradients on the host), or with
-    resident=True device weight / bias (views of a parameter arena), packed on the device per tap and role on first use after
-    params_updated() and read by tm_op_conv_mfma_packed / _dgrad_packed / _wgrad_dev (gradients on the device, nothing
-    synchronised).  forward(x [N, Ci, Zi, S, S]) -> y [N, Co, Zo, S, S]; backward(dy) -> (dx, dw [Co, Ci, kz, 3, 3], db)."""
+    A loop over the taps on a conv engine (train_conv.py): HostConvs on host weight / bias (each tap's embedded filter is kept), or with
+    resident=True ResidentConvs on device weight / bias (views of a parameter arena; taps packed per role on first use after
+    convs.invalidate()).  `engine`, `key`: the engine to run on and the weight's id in its pack cache (UNetTrain passes its own).
+    forward(x [N, Ci, Zi, S, S]) -> y [N, Co, Zo, S, S]; backward(dy) -> (dx, dw [Co, Ci, kz, 3, 3], db) on the engine's gdev."""
 
-    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, device="cuda:0", resident: bool = False):
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, device="cuda:0", resident: bool = False, engine=None, key="down_z"):
         self.dev = torch.device(device)
         self.resident = bool(resident)
         self.co, self.ci, self.kz = weight.shape[:3]
@@ -173,42 +160,9 @@ class DownZTrain:
             raise ValueError(f"DownZTrain: weight must be [Co, Ci, kz, 3, 3], got {tuple(weight.shape)}")
         self.w = weight.detach().to(self.dev, torch.float32) if resident else _host(weight)
         self.b = bias.detach().to(self.dev, torch.float32) if resident else _host(bias)
-        self._packs: Dict = {}
-        self._emb: Dict = {}
+        self.convs = engine if engine is not None else (ResidentConvs if resident else HostConvs)(self.dev)
+        self.taps = [self.convs.filter((key, dz), self.w, dz) for dz in range(self.kz)]
         self._saved = None
-
-    def params_updated(self):
-        """the weight changed in place (resident: an optimizer step on the arena): every pack and embedded filter is stale"""
-        self._packs.clear()
-        self._emb.clear()
-
-    def _embedded(self, dz):
-        """tap dz as the middle z slice of a 3x3x3 filter (on the weight's own device); the host engine keeps it for the
-        backward and later forwards, the resident one needs it only while a pack is built"""
-        wf = self._emb.get(dz)
-        if wf is None:
-            wf = torch.zeros((self.co, self.ci, 3, 3, 3), dtype=torch.float32, device=self.w.device)
-            wf[:, :, 1] = self.w[:, :, dz]
-            if not self.resident:
-                self._emb[dz] = wf
-        return wf
-
-    def _pack(self, dz, role, Z):
-        hit = self._packs.get((dz, role))
-        if hit is None:
-            L = _lib.lib()
-            hit = torch.empty((L.tm_conv_pack_floats(self.co, self.ci, 3, Z, role),), dtype=torch.float32, device=self.dev)
-            wf = self._embedded(dz)
-            _lib.check(L.tm_op_conv_pack_dev(_lib.ptr(wf), _lib.ptr(hit), self.co, self.ci, 3, Z, role,
-                                             _lib.current_stream_ptr()), "tm_op_conv_pack_dev")
-            self._packs[(dz, role)] = hit
-        return hit
-
-    def _add(self, a, b, out=None):
-        """a + b (tm_op_ew 6) into `out` (may be a: elementwise), or into a new tensor"""
-        o = torch.empty_like(a) if out is None else out
-        _lib.check(_lib.lib().tm_op_ew(6, _lib.ptr(a), _lib.ptr(b), None, _lib.ptr(o), None, a.numel(), _lib.current_stream_ptr()), "tm_op_ew")
-        return o
 
     def forward_cb(self, x_cb: torch.Tensor) -> torch.Tensor:
         """CB8 in, CB8 out: x_cb [N, ceil(Ci/8), Zi, S, S, 8] -> [N, ceil(Co/8), Zi - kz + 1, S, S, 8]."""
@@ -216,34 +170,21 @@ class DownZTrain:
         Zo = Zi - self.kz + 1
         if not 1 <= Zo <= 4:
             raise ValueError(f"DownZTrain: {Zi} planes under a depth-{self.kz} kernel leave {Zo}; 1 .. 4 are supported")
-        L, st = _lib.lib(), _lib.current_stream_ptr()
-        zero_b = torch.zeros((self.co,), dtype=torch.float32, device=self.dev if self.resident else "cpu")
+        zero_b = torch.zeros((self.co,), dtype=torch.float32, device=self.b.device)
         xs = []
         y = torch.zeros((N, (self.co + 7) // 8, Zo, S, S, 8), dtype=torch.float32, device=self.dev)
         tap = torch.zeros_like(y) if self.kz > 1 else None      # one buffer for the taps 1 .. kz - 1 (stream-ordered reuse)
         for dz in range(self.kz):
             xd = x_cb[:, :, dz:dz + Zo].contiguous()
-            t = y if dz == 0 else tap
-            b = self.b if dz == 0 else zero_b
-            if self.resident:
-                _lib.check(L.tm_op_conv_mfma_packed(_lib.ptr(xd), _lib.ptr(self._pack(dz, 0, Zo)), _lib.ptr(b), _lib.ptr(t), N, self.ci,
-                                                    self.co, Zo, S, 3, st), "tm_op_conv_mfma_packed")
-            else:
-                wf = self._embedded(dz)
-                _lib.check(L.tm_op_conv_mfma(_lib.ptr(xd), _hp(wf), _hp(b), _lib.ptr(t), N, self.ci, self.co, Zo, S, 3, 0, 0, 0,
-                                             st), "tm_op_conv_mfma")
+            self.convs.conv(xd, self.taps[dz], self.b if dz == 0 else zero_b, out=y if dz == 0 else tap)
             xs.append(xd)
             if dz:
-                self._add(y, t, out=y)
-        self._saved = dict(xs=xs, shape=(N, Zi, Zo, S), like=x_cb)
+                ew(6, y, tap, out=y)
+        self._saved = dict(xs=xs, like=x_cb)
         return y
 
     def backward_cb(self, g: torch.Tensor):
-        N, Zi, Zo, S = self._saved["shape"]
-        L, st = _lib.lib(), _lib.current_stream_ptr()
-        co, ci = self.co, self.ci
-        host = torch.device("cpu")
-        gdev = self.dev if self.resident else host
+        co, ci, gdev, Zo = self.co, self.ci, self.convs.gdev, g.shape[2]
         dw = torch.empty((co, ci, self.kz, 3, 3), dtype=torch.float32, device=gdev)
         db = torch.empty((co,), dtype=torch.float32, device=gdev)
         dx = torch.zeros_like(self._saved["like"])
@@ -251,19 +192,10 @@ class DownZTrain:
         for dz in range(self.kz):
             xd = self._saved["xs"][dz]
             dwf = torch.empty((co, ci, 3, 3, 3), dtype=torch.float32, device=gdev)
-            d = torch.zeros_like(xd)
-            if self.resident:
-                _lib.check(L.tm_op_conv_wgrad_dev(_lib.ptr(xd), _lib.ptr(g), _lib.ptr(dwf), _lib.ptr(db) if dz == 0 else None, 0, N, ci, co, Zo,
-                                                  S, 3, st), "tm_op_conv_wgrad_dev")
-                _lib.check(L.tm_op_conv_dgrad_packed(_lib.ptr(g), _lib.ptr(self._pack(dz, 1, Zo)), _lib.ptr(d), N, ci, co, Zo, S, 3, st),
-                           "tm_op_conv_dgrad_packed")
-            else:
-                _lib.check(L.tm_op_conv_wgrad(_lib.ptr(xd), _lib.ptr(g), _hp(dwf), _hp(db) if dz == 0 else None, N, ci, co, Zo, S, 3, st),
-                           "tm_op_conv_wgrad")
-                wf = self._embedded(dz)
-                _lib.check(L.tm_op_conv_dgrad(_lib.ptr(g), _hp(wf), _lib.ptr(d), N, ci, co, Zo, S, 3, st), "tm_op_conv_dgrad")
+            self.convs.wgrad(xd, g, self.taps[dz], dwf, db if dz == 0 else None)
+            d = self.convs.dgrad(g, self.taps[dz])
             dw[:, :, dz] = dwf[:, :, 1]
-            dx[:, :, dz:dz + Zo] = self._add(dx[:, :, dz:dz + Zo].contiguous(), d)
+            dx[:, :, dz:dz + Zo] = ew(6, dx[:, :, dz:dz + Zo].contiguous(), d)
         return dx, dw, db
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -301,39 +233,20 @@ class AttnBlockTrain:
         self.hid = self.p["mlp.fc1.weight"].shape[0]
         if self.C % 8:
             raise ValueError("AttnBlockTrain: hidden size must be a multiple of 8")
+        self.convs = HostConvs(self.dev)
+        self.f = {k: self.convs.filter(k, self.p[k + ".weight"]) for k in self.LIN}
         self._saved = None
 
     # -- pieces ---------------------------------------------------------------------------------
     def _geo(self):
         return self._saved["shape"]
 
-    def _lin(self, x_cb, name, cin, cout):
-        N, Z, S = self._geo()
-        y = torch.zeros((N, (cout + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_mfma(_lib.ptr(x_cb), _hp(self.p[name + ".weight"]), _hp(self.p[name + ".bias"]), _lib.ptr(y), N, cin,
-                                              cout, Z, S, 1, 0, 0, 0, _lib.current_stream_ptr()), "tm_op_conv_mfma")
-        return y
+    def _lin(self, x_cb, name):
+        return self.convs.conv(x_cb, self.f[name], self.p[name + ".bias"])
 
-    def _lin_bwd(self, x_cb, dy_cb, name, cin, cout, grads, need_dx=True):
-        N, Z, S = self._geo()
-        dw = torch.empty((cout, cin), dtype=torch.float32)
-        db = torch.empty((cout,), dtype=torch.float32)
-        _lib.check(_lib.lib().tm_op_conv_wgrad(_lib.ptr(x_cb), _lib.ptr(dy_cb), _hp(dw), _hp(db), N, cin, cout, Z, S, 1,
-                                               _lib.current_stream_ptr()), "tm_op_conv_wgrad")
-        grads[name + ".weight"], grads[name + ".bias"] = dw, db
-        if not need_dx:
-            return None
-        dx = torch.zeros((N, (cin + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=self.dev)
-        _lib.check(_lib.lib().tm_op_conv_dgrad(_lib.ptr(dy_cb), _hp(self.p[name + ".weight"]), _lib.ptr(dx), N, cin, cout, Z, S, 1,
-                                               _lib.current_stream_ptr()), "tm_op_conv_dgrad")
-        return dx
-
-    def _ew(self, op, a, b=None, c=None, two=False):
-        o1 = torch.empty_like(a)
-        o2 = torch.empty_like(a) if two else None
-        _lib.check(_lib.lib().tm_op_ew(op, _lib.ptr(a), _lib.ptr(b), _lib.ptr(c), _lib.ptr(o1), _lib.ptr(o2), a.numel(),
-                                       _lib.current_stream_ptr()), "tm_op_ew")
-        return (o1, o2) if two else o1
+    def _lin_bwd(self, x_cb, dy_cb, name, grads):
+        grads[name + ".weight"], grads[name + ".bias"] = self.convs.wgrad(x_cb, dy_cb, self.f[name])
+        return self.convs.dgrad(dy_cb, self.f[name])
 
     def _modnorm(self, x_cb, w, scale, shift):
         N, Z, S = self._geo()
@@ -381,21 +294,21 @@ class AttnBlockTrain:
         N, _, Z, S, _, _ = x_cb.shape
         P, Cb = self.p, self.C // 8
         self._saved = dict(shape=(N, Z, S))
-        sc = self._ew(4, cond_cb)
-        m = self._lin(sc, "adaLN_modulation.1", self.G, 7 * self.C)
+        sc = ew(4, cond_cb)
+        m = self._lin(sc, "adaLN_modulation.1")
         shift_msa, scale_msa, gate_msa, crss, shift_mlp, scale_mlp, gate_mlp = (m[:, i * Cb:(i + 1) * Cb].contiguous() for i in range(7))
         n1 = self._modnorm(x_cb, P["norm1.weight"], scale_msa, shift_msa)
-        q = self._lin(n1, "attn.q", self.C, self.C)
-        k = self._lin(crss, "attn.k", self.C, self.C)
-        v = self._lin(crss, "attn.v", self.C, self.C)
+        q = self._lin(n1, "attn.q")
+        k = self._lin(crss, "attn.k")
+        v = self._lin(crss, "attn.v")
         o = self._core(q, k, v)
-        pr = self._lin(o, "attn.proj", self.C, self.C)
-        x1 = self._ew(0, x_cb, gate_msa, pr)
+        pr = self._lin(o, "attn.proj")
+        x1 = ew(0, x_cb, gate_msa, pr)
         n2 = self._modnorm(x1, P["norm2.weight"], scale_mlp, shift_mlp)
-        h = self._lin(n2, "mlp.fc1", self.C, self.hid)
-        a = self._ew(2, h)
-        f = self._lin(a, "mlp.fc2", self.hid, self.C)
-        out = self._ew(0, x1, gate_mlp, f)
+        h = self._lin(n2, "mlp.fc1")
+        a = ew(2, h)
+        f = self._lin(a, "mlp.fc2")
+        out = ew(0, x1, gate_mlp, f)
         self._saved.update(x_cb=x_cb, cond_cb=cond_cb, sc=sc, scale_msa=scale_msa, gate_msa=gate_msa, crss=crss, scale_mlp=scale_mlp,
                            gate_mlp=gate_mlp, n1=n1, q=q, k=k, v=v, o=o, pr=pr, x1=x1, n2=n2, h=h, a=a, f=f)
         return out
@@ -405,21 +318,21 @@ class AttnBlockTrain:
         C_, G, hid = self.C, self.G, self.hid
         grads: Dict[str, torch.Tensor] = {}
         # out = x1 + gate_mlp * f
-        d_f, d_gate_mlp = self._ew(1, g, s["gate_mlp"], s["f"], two=True)
-        d_a = self._lin_bwd(s["a"], d_f, "mlp.fc2", hid, C_, grads)
-        d_h = self._ew(3, d_a, s["h"])
-        d_n2 = self._lin_bwd(s["n2"], d_h, "mlp.fc1", C_, hid, grads)
+        d_f, d_gate_mlp = ew(1, g, s["gate_mlp"], s["f"], two=True)
+        d_a = self._lin_bwd(s["a"], d_f, "mlp.fc2", grads)
+        d_h = ew(3, d_a, s["h"])
+        d_n2 = self._lin_bwd(s["n2"], d_h, "mlp.fc1", grads)
         dx1b, dscale_mlp, dshift_mlp, grads["norm2.weight"] = self._modnorm_bwd(s["x1"], d_n2, P["norm2.weight"], s["scale_mlp"])
-        dx1 = self._ew(6, g, dx1b)
+        dx1 = ew(6, g, dx1b)
         # x1 = x + gate_msa * pr
-        d_pr, d_gate_msa = self._ew(1, dx1, s["gate_msa"], s["pr"], two=True)
-        d_o = self._lin_bwd(s["o"], d_pr, "attn.proj", C_, C_, grads)
+        d_pr, d_gate_msa = ew(1, dx1, s["gate_msa"], s["pr"], two=True)
+        d_o = self._lin_bwd(s["o"], d_pr, "attn.proj", grads)
         dq, dk, dv, grads["attn.q_norm.weight"], grads["attn.k_norm.weight"] = self._core(s["q"], s["k"], s["v"], d_o)
-        d_n1 = self._lin_bwd(s["n1"], dq, "attn.q", C_, C_, grads)
-        d_crss = self._ew(6, self._lin_bwd(s["crss"], dk, "attn.k", C_, C_, grads), self._lin_bwd(s["crss"], dv, "attn.v", C_, C_, grads))
+        d_n1 = self._lin_bwd(s["n1"], dq, "attn.q", grads)
+        d_crss = ew(6, self._lin_bwd(s["crss"], dk, "attn.k", grads), self._lin_bwd(s["crss"], dv, "attn.v", grads))
         dxa, dscale_msa, dshift_msa, grads["norm1.weight"] = self._modnorm_bwd(s["x_cb"], d_n1, P["norm1.weight"], s["scale_msa"])
-        dx = self._ew(6, dx1, dxa)
+        dx = ew(6, dx1, dxa)
         dm = torch.cat([dshift_msa, dscale_msa, d_gate_msa, d_crss, dshift_mlp, dscale_mlp, d_gate_mlp], dim=1).contiguous()
-        d_sc = self._lin_bwd(s["sc"], dm, "adaLN_modulation.1", G, 7 * C_, grads)
-        dcond = self._ew(5, d_sc, s["cond_cb"])
+        d_sc = self._lin_bwd(s["sc"], dm, "adaLN_modulation.1", grads)
+        dcond = ew(5, d_sc, s["cond_cb"])
         return dx, dcond, grads

@@ -142,7 +142,7 @@ def test_each_conv_weight_packed_once_per_role_per_optimizer_step(cfg, tiles):
         assert sorted(now) == sorted((c, r) for c in convs for r in (0, 1)), set(now) ^ {(c, r) for c in convs for r in (0, 1)}
         assert all(now[k] - seen.get(k, 0) == 1 for k in now), {k: now[k] - seen.get(k, 0) for k in now if now[k] - seen.get(k, 0) != 1}
         seen = now
-        assert not tr.net._packs                             # stale after AdamTrainer.step()
+        assert not tr.net.convs._packs                           # stale after AdamTrainer.step()
 
 
 def test_next_forward_uses_the_updated_weights(cfg):
