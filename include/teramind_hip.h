@@ -278,7 +278,8 @@ int tm_op_from_cb8(const void* x_cb8, void* y_ncdhw, int N, int C, int Z, int H,
 /* Conv3d on the MFMA implicit-GEMM kernels (replaces nn.Conv3d as used in ResBlock,
  * model/MBAblocks.py:146-148,182-186,220-224, the RNA pyramid convs model/unet_ours.py:290-295
  * and down_z model/MBAblocks.py:472-474).  ksize 1: 1x1x1.  ksize 3 with zmode
- *   0: 3x3x3 pad (1,1,1), Z == 2      1: 1x3x3 pad (0,1,1)      2: 3x3x3 pad (0,1,1) (Zout = Z-2)
+ *   0: 3x3x3 pad (1,1,1), any Z >= 1 (the plane-pair form at Z == 2, the three-plane form otherwise)
+ *   1: 1x3x3 pad (0,1,1)      2: 3x3x3 pad (0,1,1) (Zout = Z-2)
  *   3: 3x3x3 pad (1,1,1) of the nearest-x2 UPSAMPLED x (Upsample then Conv3d as in ResBlock(up=True), model/MBAblocks.py:254-258,
  *      blocks.py:362-371), Z == 2, computed on x itself with per-phase 2x2 in-plane weights: y is [N, Cout, Z, 2S, 2S].
  * up2: nearest x2 on (H, W) applied to the output (not with zmode 3).  w [Cout][Cin][kz][3][3] HOST fp32,
@@ -306,6 +307,12 @@ int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const void* bias_
 int tm_op_conv27_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8,
                       int N, int Cin, int Cout, int S, int dtype, int waves, const void* res_h16, void* y_h16,
                       int ups, int res_half, void* stream);
+/* The same on Z planes, 1 <= Z <= 8 (every tensor above with Z in place of 2): the 16x16x32 ping-pong kernel is the 8-wave
+ * form at Z == 2 only, the 32x32x16 one at every other Z.  ups and res_half need Z == 2 (TM_ERR_ARG otherwise, as for a Z
+ * out of range, before any device call).  tm_op_conv27_bf16 is this call with Z = 2. */
+int tm_op_conv27_h16_z(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8,
+                       int N, int Cin, int Cout, int S, int dtype, int waves, const void* res_h16, void* y_h16,
+                       int ups, int res_half, int Z, void* stream);
 
 /* Timing hook: `iters` launches of that conv in the forms the model uses (16-bit stream output, optional 16-bit
  * residual, fused norm epilogue, upsampled-input form) on random device data in [-1, 1); *ms_per_launch = mean launch
@@ -321,6 +328,10 @@ int tm_op_conv27_time(int N, int Cin, int Cout, int S, int dtype, int waves, int
 int tm_op_conv27_fused(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
                        const void* scale_host, const void* shift_host, void* a2_out, int N, int Cin, int Cout,
                        int S, int per_image, int dtype, int waves, void* stream);
+/* The same on Z planes, 1 <= Z <= 8 (a2_out [N][Cout/8][Z][S][S][8]); tm_op_conv27_fused is this call with Z = 2. */
+int tm_op_conv27_fused_z(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
+                         const void* scale_host, const void* shift_host, void* a2_out, int N, int Cin, int Cout,
+                         int S, int per_image, int dtype, int waves, int Z, void* stream);
 
 /* 16-bit 1x1x1 conv / Linear over '(z h w) c' tokens (x and w rounded to `dtype`, fp32 accumulate).  waves: 0 | 4 | 8
  * as above (two co-resident 4-wave workgroups per CU, or one 8-wave workgroup).  Epilogue (model/MBAblocks.py:486-489):

@@ -198,23 +198,27 @@ extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const 
   return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_mfma");
 }
 
-// The ConvLaunchH of the 16-bit 3x3x3 conv hooks (Z == 2): x N x Cin channels (blocks paired) at S x S, y Cout channels at
-// So = S, or 2S in the upsampled-input form; fused: the norm epilogue writes the 16-bit a2 at y's geometry.  Rejects the
-// forms the kernels do not take, before any device call; the caller sets the pointers.
-static int conv27_launch(ConvLaunchH& L, int N, int Cin, int Cout, int S, int waves, int ups, bool res, bool fused) {
+// The ConvLaunchH of the 16-bit 3x3x3 conv hooks: x N x Cin channels (blocks paired) on Z planes of S x S, y Cout channels at
+// So = S, or 2S in the upsampled-input form (Z == 2 only, as the half-resolution residual); fused: the norm epilogue writes the
+// 16-bit a2 at y's geometry.  Rejects the forms the kernels do not take, before any device call; the caller sets the pointers.
+static int conv27_launch(ConvLaunchH& L, int N, int Cin, int Cout, int Z, int S, int waves, int ups, bool res, bool fused,
+                         int res_half = 0) {
+  if (Z < 1 || Z > 8) return fail(TM_ERR_ARG, "Z must be in 1 .. 8 (got %d)", Z);
+  if (ups && Z != 2) return fail(TM_ERR_ARG, "upsampled-input form (ups): Z == 2 only (got Z = %d)", Z);
+  if (res_half && Z != 2) return fail(TM_ERR_ARG, "half-resolution residual (res_half): Z == 2 only (got Z = %d)", Z);
   if (waves != 0 && waves != 4 && waves != 8 && waves != 9) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4, 8 or 9 (lockstep 8-wave form)");
   if (fused && Cout != 64 && Cout != 128) return fail(TM_ERR_ARG, "fused epilogue needs Cout in {64, 128}");
   if (ups && (Cout % 128 || res)) return fail(TM_ERR_ARG, "upsampled-input form: Cout a multiple of 128, no residual");
   const int So = ups ? 2 * S : S;
-  L.x = view_h16(nullptr, N, ((Cin + 7) / 8 + 1) / 2 * 16, 2, S, S);
+  L.x = view_h16(nullptr, N, ((Cin + 7) / 8 + 1) / 2 * 16, Z, S, S);
   L.Cout = Cout; L.force_waves = waves; L.ups = ups;
-  L.y = view_cb8(nullptr, N, Cout, 2, So, So);
-  if (fused) { L.fuse_norm = 1; L.a2 = view_h16(nullptr, N, Cout, 2, So, So); }
+  L.y = view_cb8(nullptr, N, Cout, Z, So, So);
+  if (fused) { L.fuse_norm = 1; L.a2 = view_h16(nullptr, N, Cout, Z, So, So); }
   return TM_OK;
 }
 // shared body of the 16-bit 3x3x3 conv test entry points: fp32 CB8 input -> 16-bit CB8 (prep kernel), then the conv
 static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin, int Cout,
-                         int S, int dtype, int waves, const void* norm_w_host, const void* scale_host, const void* shift_host,
+                         int Z, int S, int dtype, int waves, const void* norm_w_host, const void* scale_host, const void* shift_host,
                          int per_image, void* a2_out, void* stream, const void* res_h16 = nullptr, void* y_h16 = nullptr,
                          int ups = 0, int res_half = 0) {
   if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
@@ -222,7 +226,7 @@ static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias
   if (fused && (!scale_host || !shift_host || !a2_out || per_image < 1))
     return fail(TM_ERR_ARG, "fused epilogue needs scale / shift / a2 and per_image >= 1");
   ConvLaunchH L;
-  if (int rc = conv27_launch(L, N, Cin, Cout, S, waves, ups, res_h16 != nullptr, fused)) return rc;
+  if (int rc = conv27_launch(L, N, Cin, Cout, Z, S, waves, ups, res_h16 != nullptr, fused, res_half)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int Cbi = (Cin + 7) / 8, nimg = (N + per_image - 1) / per_image;
   std::vector<uint16_t> pk(ups ? conv_bf16_pack_ups_elems(Cout, Cbi) : conv_bf16_pack_elems(Cout, Cbi));
@@ -238,7 +242,7 @@ static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias
   }
   if (tmp.err) return tmp.report();
   hipError_t e = hipSuccess;
-  L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, 2, S, S), f16, true, st, e);
+  L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
   L.y.p = (float*)y_cb8;
   L.res_half = res_half;
   TVH resh = as_h(L.y);
@@ -250,20 +254,31 @@ static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias
   if (e == hipSuccess) e = (f16 ? launch_conv27_f16 : launch_conv27_bf16)(L, st);
   return finish(st, e, "conv27 (16-bit)");
 }
+extern "C" int tm_op_conv27_h16_z(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                  int Cout, int S, int dtype, int waves, const void* res_h16, void* y_h16, int ups, int res_half,
+                                  int Z, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
+  return op_conv27_h16(x_cb8, w_host, bias_host, y_cb8 ? y_cb8 : y_h16, N, Cin, Cout, Z, S, dtype, waves, nullptr, nullptr, nullptr, 1,
+                       nullptr, stream, res_h16, y_h16, ups, res_half);
+}
 extern "C" int tm_op_conv27_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                                  int Cout, int S, int dtype, int waves, const void* res_h16, void* y_h16, int ups, int res_half,
                                  void* stream) {
-  if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
-  return op_conv27_h16(x_cb8, w_host, bias_host, y_cb8 ? y_cb8 : y_h16, N, Cin, Cout, S, dtype, waves, nullptr, nullptr, nullptr, 1,
-                       nullptr, stream, res_h16, y_h16, ups, res_half);
+  return tm_op_conv27_h16_z(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, dtype, waves, res_h16, y_h16, ups, res_half, 2, stream);
+}
+extern "C" int tm_op_conv27_fused_z(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
+                                    const void* scale_host, const void* shift_host, void* a2_out, int N, int Cin, int Cout,
+                                    int S, int per_image, int dtype, int waves, int Z, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || !norm_w_host || !a2_out) return fail(TM_ERR_ARG, "null argument");
+  // the launcher takes the output geometry from `y`; the fused form never writes it
+  return op_conv27_h16(x_cb8, w_host, bias_host, a2_out, N, Cin, Cout, Z, S, dtype, waves, norm_w_host, scale_host, shift_host,
+                       per_image, a2_out, stream);
 }
 extern "C" int tm_op_conv27_fused(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
                                   const void* scale_host, const void* shift_host, void* a2_out, int N, int Cin, int Cout,
                                   int S, int per_image, int dtype, int waves, void* stream) {
-  if (!x_cb8 || !w_host || !bias_host || !norm_w_host || !a2_out) return fail(TM_ERR_ARG, "null argument");
-  // the launcher takes the output geometry from `y`; the fused form never writes it
-  return op_conv27_h16(x_cb8, w_host, bias_host, a2_out, N, Cin, Cout, S, dtype, waves, norm_w_host, scale_host, shift_host,
-                       per_image, a2_out, stream);
+  return tm_op_conv27_fused_z(x_cb8, w_host, bias_host, norm_w_host, scale_host, shift_host, a2_out, N, Cin, Cout, S, per_image,
+                              dtype, waves, 2, stream);
 }
 // Timing hook of the 16-bit 3x3x3 conv on random device data (uniform in [-1, 1): the clock the chip holds depends on the
 // operand bits, cdna guide rule 25): the model's launch forms -- 16-bit stream output with an optional 16-bit residual, the
@@ -283,7 +298,7 @@ extern "C" int tm_op_conv27_time(int N, int Cin, int Cout, int S, int dtype, int
                                  int iters, float* ms_per_launch, void* stream) {
   if (!is_h16(dtype) || iters < 1 || !ms_per_launch || N < 1) return fail(TM_ERR_ARG, "bad argument");
   ConvLaunchH L;
-  if (int rc = conv27_launch(L, N, Cin, Cout, S, waves, ups, with_res, fused)) return rc;
+  if (int rc = conv27_launch(L, N, Cin, Cout, 2, S, waves, ups, with_res, fused)) return rc;
   const bool f16 = dtype == TM_DTYPE_F16;
   hipStream_t st = (hipStream_t)stream;
   const int Cbi = (Cin + 7) / 8, nt64 = (Cout + 63) / 64;

@@ -85,6 +85,21 @@ def test_conv_direct(N, Cin, Cout, Zin, S, k, pad, silu, up2):
     assert torch.allclose(got.cpu(), ref, atol=2e-5, rtol=1e-5), util.report("direct", got, ref)
 
 
+@pytest.mark.parametrize("Zin,kz", [(8, 5), (16, 9), (1, 1)])
+def test_conv_direct_down_z_depths_exact_integers(Zin, kz):
+    """down_z of rna_slc 8 / 16 / 1 on conv_direct: kz = 5 / 9 / 1 valid in z (Zin -> Zin - kz + 1 = 4 / 8 / 1 planes), 229 -> 229
+    channels on the 4 x 4 gene grid with the fused nearest-x2 store.  Integer operands (|sum| <= 81 * 229 * 6 + 4 < 2^24):
+    bit for bit."""
+    N, Cc, S = 3, 229, 4
+    x = util.rand_int((N, Cc, Zin, S, S), -3, 3, 111)
+    w = util.rand_int((Cc, Cc, kz, 3, 3), -2, 2, 112)
+    b = util.rand_int((Cc,), -4, 4, 113)
+    ref = F.conv3d(x, w, b, padding=(0, 1, 1)).repeat_interleave(2, -2).repeat_interleave(2, -1)
+    got = util.conv_direct(x.to(DEV), w, b, (0, 1, 1), False, True)
+    assert got.shape == (N, Cc, Zin - kz + 1, 2 * S, 2 * S)
+    assert torch.equal(got.cpu(), ref), util.report(f"down_z kz={kz}", got, ref)
+
+
 @pytest.mark.parametrize("N,Cin,Cout,S", [(3, 229, 128, 8), (2, 128, 64, 16), (2, 64, 32, 32), (5, 13, 40, 8)])
 @pytest.mark.parametrize("up2", [False, True])
 def test_conv_inplane_mfma_exact_integers(N, Cin, Cout, S, up2):
@@ -220,6 +235,21 @@ def test_conv1_16bit_stream_epilogue_plain_and_gelu(N, Cin, Cout, Z, S, waves, d
 def test_conv1_concat_collage_input_exact_integers(b, p1, p2, cins, flags, Cout, S, waves, dtype):
     """The skip conv reads th.cat((h, skip, rna), 1) -- and the collage re-tiling of the decoder's sources -- in place
     (model/unet_ours.py:325-341,384,418): exact-integer check against torch.cat + the oracle's to_collage."""
+    _conv1_concat_case(b, p1, p2, cins, flags, Cout, S, waves, dtype, 2)
+
+
+@pytest.mark.parametrize("b,p1,p2,cins,flags,Cout,S", [
+    (2, 3, 3, (64, 32), (0, 0), 64, 16),              # encoder block: plain sources
+    (2, 3, 2, (40, 24, 229), (0, 1, 1), 512, 8)])     # decoder block: h plain, skip / rna re-tiled; odd block counts
+@pytest.mark.parametrize("Z", [1, 4])
+@pytest.mark.parametrize("waves", [4, 8])
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_conv1_concat_collage_input_z_sizes_exact_integers(b, p1, p2, cins, flags, Cout, S, Z, waves, dtype):
+    """The same at Z = 1 and Z = 4 (rna_slc 1 / 8): the collage gather and the voxel tiles run over Z * S * S voxels per patch."""
+    _conv1_concat_case(b, p1, p2, cins, flags, Cout, S, waves, dtype, Z)
+
+
+def _conv1_concat_case(b, p1, p2, cins, flags, Cout, S, waves, dtype, Z):
     import ctypes as C
     from oracle import teramind_cpu as tc
     Nd, Ne = b * (p1 - 1) * (p2 - 1), b * p1 * p2
@@ -227,7 +257,7 @@ def test_conv1_concat_collage_input_exact_integers(b, p1, p2, cins, flags, Cout,
     N = Nd if any_col else Ne
     xs, parts = [], []
     for i, (c, f) in enumerate(zip(cins, flags)):
-        x = util.rand_int((Ne if f else N, c, 2, S, S), -3, 3, 90 + i)
+        x = util.rand_int((Ne if f else N, c, Z, S, S), -3, 3, 90 + i)
         xs.append(x)
         parts.append(tc.collage(x, b, p1, p2) if f else x)
     w = util.rand_int((Cout, sum(cins), 1, 1, 1), -2, 2, 95)
@@ -237,10 +267,10 @@ def test_conv1_concat_collage_input_exact_integers(b, p1, p2, cins, flags, Cout,
     ptrs = (C.c_void_p * len(xc))(*[t.data_ptr() for t in xc])
     cin = (C.c_int * len(xc))(*cins)
     col = (C.c_int * len(xc))(*flags)
-    yc = torch.zeros((N, (Cout + 7) // 8, 2, S, S, 8), dtype=torch.float32, device=DEV)
+    yc = torch.zeros((N, (Cout + 7) // 8, Z, S, S, 8), dtype=torch.float32, device=DEV)
     wh, bh = w.contiguous().float(), bias.contiguous().float()
     _lib.check(_lib.lib().tm_op_conv1_concat(ptrs, cin, col, len(xc), C.c_void_p(wh.data_ptr()), C.c_void_p(bh.data_ptr()),
-                                             _lib.ptr(yc), N, Cout, 2, S, p1, p2, util.H16[dtype][0], waves,
+                                             _lib.ptr(yc), N, Cout, Z, S, p1, p2, util.H16[dtype][0], waves,
                                              _lib.current_stream_ptr()), "tm_op_conv1_concat")
     got = util.from_cb8(yc, Cout)
     assert torch.equal(got.cpu(), ref), util.report("conv1 concat " + dtype, got, ref)
@@ -267,6 +297,27 @@ def test_prep_h16_forms_vs_torch(b, p1, p2, cins, flags, S, up2, mod, norm, vari
     """cat + to_collage / Upsample + LlamaRMSNorm + modulate + SiLU on the 16-bit stream (model/unet_ours.py:325-341,384,418,
     model/MBAblocks.py:21-43,254-261,356-367,484-489,608-614): every kernel form against fp32 torch on the same 16-bit
     inputs, to one 16-bit ulp (the forms differ in the order of the sum of squares and use the hardware exp / rcp)."""
+    _prep_forms_case(b, p1, p2, cins, flags, S, up2, mod, norm, variant, dtype, 2)
+
+
+# PREP_CASES rows at the other z sizes: (.., Z)
+PREP_Z_CASES = [
+    (2, 3, 3, (64, 32), (0, 0), 16, False, 0, True, 1),         # encoder block input: cat(h, rna) at Z = 1
+    (1, 2, 4, (128, 64, 32), (1, 1, 1), 8, False, 0, True, 4),  # decoder block input, every source re-tiled, at Z = 4
+    (5, 2, 2, (64,), (0,), 16, True, 0, True, 1),               # nearest x2 with the raw copy: at Z != 2 this pass is the up
+    (5, 2, 2, (64,), (0,), 16, True, 0, True, 4),               #   block's conv input (the upsampled-input conv is Z = 2 only)
+    (3, 2, 2, (256,), (0,), 8, False, 1, True, 8)]              # per-image scale / shift at Z = 8
+
+
+@pytest.mark.parametrize("b,p1,p2,cins,flags,S,up2,mod,norm,Z", PREP_Z_CASES)
+@pytest.mark.parametrize("variant", [0, 1, 2, 3])
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_prep_h16_forms_vs_torch_z_sizes(b, p1, p2, cins, flags, S, up2, mod, norm, Z, variant, dtype):
+    """The same forms and criteria on Z = 1 / 4 / 8 planes (rna_slc 1 / 8 / 16)."""
+    _prep_forms_case(b, p1, p2, cins, flags, S, up2, mod, norm, variant, dtype, Z)
+
+
+def _prep_forms_case(b, p1, p2, cins, flags, S, up2, mod, norm, variant, dtype, Z):
     from oracle import teramind_cpu as tc
     if variant == 2 and sum((c + 7) // 8 for c in cins) > 32:
         pytest.skip("one-wave form holds at most 32 channel blocks")
@@ -278,7 +329,7 @@ def test_prep_h16_forms_vs_torch(b, p1, p2, cins, flags, S, up2, mod, norm, vari
     Ss = S // 2 if up2 else S
     xs, parts = [], []
     for c, f in zip(cins, flags):
-        x = (torch.randn((Ne if f else N, c, 2, Ss, Ss), generator=g) * 1.5).to(td).float()
+        x = (torch.randn((Ne if f else N, c, Z, Ss, Ss), generator=g) * 1.5).to(td).float()
         xs.append(x)
         y = tc.collage(x, b, p1, p2) if f else x
         if up2:
@@ -409,10 +460,22 @@ def test_conv27_16bit_residual_at_half_resolution(dtype):
 def test_prep_h16_downsample_form_vs_torch(C_, S, variant, dtype):
     """ResBlock(down=True) input (model/MBAblocks.py:254-258, blocks.py:389-403): LlamaRMSNorm -> SiLU at full resolution,
     then the 2 x 2 average of the activated tensor and (raw) of x itself; the 16-bit kernel and the generic one."""
+    _prep_downsample_case(C_, S, variant, dtype, 2)
+
+
+@pytest.mark.parametrize("C_,S,Z", [(64, 16, 1), (40, 8, 1), (64, 16, 4), (40, 8, 4)])
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+def test_prep_h16_downsample_form_vs_torch_z_sizes(C_, S, Z, variant, dtype):
+    """The downsample form on Z = 1 / 4 planes, same criterion."""
+    _prep_downsample_case(C_, S, variant, dtype, Z)
+
+
+def _prep_downsample_case(C_, S, variant, dtype, Z):
     td = util.H16[dtype][1]
     g = torch.Generator().manual_seed(11)
     N = 3
-    x = (torch.randn((N, C_, 2, 2 * S, 2 * S), generator=g) * 1.5).to(td).float()
+    x = (torch.randn((N, C_, Z, 2 * S, 2 * S), generator=g) * 1.5).to(td).float()
     w = torch.randn((C_,), generator=g) * 0.3 + 1.0
     h = F.silu(w[None, :, None, None, None] * (x * torch.rsqrt(x.pow(2).mean(1, keepdim=True) + 1e-6)))
     pool = lambda t: F.avg_pool3d(t, (1, 2, 2))
@@ -438,7 +501,8 @@ def test_conv27_bf16_random_vs_bf16_rounded_reference():
 
 
 @pytest.mark.parametrize("N,Cin,Cout,Z,S", [(2, 229, 1792, 2, 8), (1, 64, 256, 2, 16), (3, 13, 40, 2, 8), (1, 96, 64, 2, 64),
-                                            (5, 512, 2048, 2, 8), (2, 1253, 512, 2, 8), (7, 128, 64, 2, 16)])
+                                            (5, 512, 2048, 2, 8), (2, 1253, 512, 2, 8), (7, 128, 64, 2, 16),
+                                            (3, 229, 192, 1, 8), (3, 229, 192, 8, 8)])
 @pytest.mark.parametrize("waves", [4, 8])
 @pytest.mark.parametrize("dtype", ["bf16", "f16"])
 def test_conv1_bf16_exact_integers(N, Cin, Cout, Z, S, waves, dtype):

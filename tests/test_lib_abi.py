@@ -65,6 +65,18 @@ def test_op_argument_checks_without_device():
     # 16-bit conv27 without weights
     assert L.tm_op_conv27_bf16(p, None, p, p, 1, 64, 64, 16, 1, 0, None, None, 0, 0, None) == -1
     assert b"null" in L.tm_last_error()
+    # the Z-taking twins: 1 <= Z <= 8; the upsampled-input form and the half-resolution residual are Z == 2 only
+    # (args: x w b y N Cin Cout S dtype waves res_h16 y_h16 ups res_half Z)
+    assert L.tm_op_conv27_h16_z(p, p, p, p, 1, 64, 128, 16, 1, 0, None, None, 0, 0, 0, None) == -1
+    assert b"Z must be" in L.tm_last_error()
+    assert L.tm_op_conv27_h16_z(p, p, p, p, 1, 64, 128, 16, 1, 0, None, None, 0, 0, 9, None) == -1
+    assert b"Z must be" in L.tm_last_error()
+    assert L.tm_op_conv27_fused_z(p, p, p, p, p, p, p, 1, 64, 128, 16, 1, 1, 0, 9, None) == -1
+    assert b"Z must be" in L.tm_last_error()
+    assert L.tm_op_conv27_h16_z(p, p, p, p, 1, 64, 128, 16, 1, 0, None, None, 1, 0, 4, None) == -1
+    assert b"ups" in L.tm_last_error() and b"Z == 2" in L.tm_last_error()
+    assert L.tm_op_conv27_h16_z(p, p, p, None, 1, 64, 128, 16, 1, 0, p, p, 0, 1, 1, None) == -1
+    assert b"res_half" in L.tm_last_error() and b"Z == 2" in L.tm_last_error()
     # training attention core: Z = 2, S = 6 is a window of 18 tokens
     assert L.tm_op_window_attn_train(p, p, p, p, p, None, p, None, None, None, None, None, 1, 64, 2, 6, None) == -1
     assert b"18 tokens" in L.tm_last_error()

@@ -101,6 +101,53 @@ def conv27_fused(x, w, b, norm_w, scale, shift, per_image, dtype="bf16", waves=0
     return from_cb8(a2.float(), Cout)
 
 
+def conv27_h16_z(x, w, b, dtype="bf16", waves=0, res=None, out16=False):
+    """conv27_bf16 at any Z in 1 .. 8 (x NCDHW cuda, Z = x.shape[2]) through the Z-taking hook.  The output buffer is
+    prefilled with NaN: an element the kernel does not write (pad slots included) fails every comparison.  Returns
+    (fp32 NCDHW, the raw CB8 tensor as fp32)."""
+    N, Cin, Z, S, _ = x.shape
+    Cout = w.shape[0]
+    xc = to_cb8(x)
+    shp = (N, (Cout + 7) // 8, Z, S, S, 8)
+    yc = torch.full(shp, float("nan"), dtype=torch.float32, device=x.device) if not out16 else None
+    yh = torch.full(shp, float("nan"), dtype=H16[dtype][1], device=x.device) if out16 else None
+    rh = to_cb8_h16(res, dtype) if res is not None else None
+    wh, bh = w.contiguous().float(), b.contiguous().float()
+    _lib.check(_lib.lib().tm_op_conv27_h16_z(_lib.ptr(xc), C.c_void_p(wh.data_ptr()), C.c_void_p(bh.data_ptr()), _lib.ptr(yc),
+                                             N, Cin, Cout, S, H16[dtype][0], waves, _lib.ptr(rh), _lib.ptr(yh), 0, 0, Z,
+                                             _lib.current_stream_ptr()), "tm_op_conv27_h16_z")
+    yc = yh.float() if out16 else yc
+    return from_cb8(yc, Cout), yc
+
+
+def conv27_fused_z(x, w, b, norm_w, scale, shift, per_image, dtype="bf16", waves=0):
+    """conv27_fused at any Z in 1 .. 8 (Z = x.shape[2]); the 16-bit output is prefilled with NaN."""
+    N, Cin, Z, S, _ = x.shape
+    Cout = w.shape[0]
+    xc = to_cb8(x)
+    a2 = torch.full((N, Cout // 8, Z, S, S, 8), float("nan"), dtype=H16[dtype][1], device=x.device)
+    hs = [t.contiguous().float() for t in (w, b, norm_w, scale, shift)]
+    _lib.check(_lib.lib().tm_op_conv27_fused_z(_lib.ptr(xc), *[C.c_void_p(t.data_ptr()) for t in hs], _lib.ptr(a2),
+                                               N, Cin, Cout, S, per_image, H16[dtype][0], waves, Z, _lib.current_stream_ptr()),
+               "tm_op_conv27_fused_z")
+    return from_cb8(a2.float(), Cout)
+
+
+def conv_mfma_res(x, w, b, res=None, variant=0):
+    """fp32 3x3x3 pad-1 conv (zmode 0) with bias and an optional residual (NCDHW cuda, y's geometry) at any Z; the output is
+    prefilled with NaN.  Returns (fp32 NCDHW, the raw CB8 tensor)."""
+    N, Cin, Z, S, _ = x.shape
+    Cout = w.shape[0]
+    xc = to_cb8(x)
+    rc = to_cb8(res) if res is not None else None
+    yc = torch.full((N, (Cout + 7) // 8, Z, S, S, 8), float("nan"), dtype=torch.float32, device=x.device)
+    wh, bh = w.contiguous().float(), b.contiguous().float()
+    _lib.check(_lib.lib().tm_op_conv_mfma_res(_lib.ptr(xc), C.c_void_p(wh.data_ptr()), C.c_void_p(bh.data_ptr()), _lib.ptr(yc),
+                                              _lib.ptr(rc), 0, N, Cin, Cout, Z, S, 3, 0, 0, variant, _lib.current_stream_ptr()),
+               "tm_op_conv_mfma_res")
+    return from_cb8(yc, Cout), yc
+
+
 def conv1_bf16(x, w, b, gelu=False, dtype="bf16", waves=0, res=None, gate=None, out16=False):
     N, Cin, Z, S, _ = x.shape
     Cout = w.shape[0]
