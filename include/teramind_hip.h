@@ -365,6 +365,20 @@ int tm_op_prep_h16(const void* const* src_h16, const int* src_c, const int* coll
                    const void* mod_shift, long mod_stride, int per_image, int act, int dtype, int variant,
                    void* out_h16, void* raw_h16, int iters, float* elapsed_ms, void* stream);
 
+/* The fp32 block-input pass on its own, as tm_op_prep_h16 with fp32 CB8 DEVICE sources, out_cb8 and (optional) raw_cb8 of
+ * exactly ceil-8 channel blocks per source: concat of nsrc (1..3) sources with to_collage where collage[i] != 0, up2 = 1 nearest
+ * x2 (sources at S/2), LlamaRMSNorm over c_real channels (norm_w_dev: device fp32 [padded C], or null), modulation (mod 0 none;
+ * 1 per image: device fp32 rows [b][mod_stride], image = n / per_image; 2 per voxel: fp32 CB8 scale / shift tensors with patch
+ * stride mod_stride floats, of the output geometry or, mod_half != 0, of half its in-plane resolution, read at (z, y >> 1,
+ * x >> 1)), SiLU (act != 0).  variant: 0 = the form the model picks, 1 = the four-wave kernels (two reads of every source above
+ * 256 channels), 2 = the wide resident form, 16 waves per 64 voxels (one read; bit-identical to 1), which takes
+ * 33..160 channel blocks: TM_ERR_ARG with a tm_last_error() text, before any device call, where it does not apply.
+ * iters >= 1 launches; elapsed_ms (host, optional): mean time of launches 2..iters. */
+int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
+                   int p1, int p2, int up2, const void* norm_w_dev, int c_real, int mod, const void* mod_scale,
+                   const void* mod_shift, long mod_stride, int mod_half, int per_image, int act, int variant,
+                   void* out_cb8, void* raw_cb8, int iters, float* elapsed_ms, void* stream);
+
 /* Windowed gene-patch cross attention core (model/MBAblocks.py:551-601 between the q/k/v Linears and proj):
  * q, k, v fp32 CB8 [N, C, Z, S, S]; qw, kw: device fp32 [C] (q_norm / k_norm weights).
  * dtype TM_DTYPE_F32: fp32 MFMA kernels, out = fp32 CB8.  TM_DTYPE_BF16: inputs are rounded to bf16 first (what the

@@ -950,8 +950,24 @@ struct WinLds {
   static constexpr int FLOATS = 128 * PS + 32 * PS + 3 * 128 + 512;
 };
 
+// The sum of squares of one token's 8-channel block, one function for both prefetch depths: eight ROUNDED products added in
+// ascending order (what the shallow loop has always compiled to).  The empty asm pins each product: left to itself the compiler
+// fuses the unrolled deep form into multiply-add chains and the shallow one not, and the two statistics differ in the last bit.
+__device__ __forceinline__ float win_sumsq8(const f32x4& a0, const f32x4& a1) {
+  float p[8] = {a0[0] * a0[0], a0[1] * a0[1], a0[2] * a0[2], a0[3] * a0[3], a1[0] * a1[0], a1[1] * a1[1], a1[2] * a1[2], a1[3] * a1[3]};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(p[j]));
+  return p[0] + p[1] + p[2] + p[3] + p[4] + p[5] + p[6] + p[7];
+}
+
+// DEEP: more loads in flight in the three global-memory loops (one workgroup per CU, so nothing else hides a round trip): the
+// statistics pass issues 8 channel blocks' 16 loads before the first use, the Q.K^T fragments run 4 channel blocks ahead in a
+// register ring, the V staging 2 chunks ahead.  The order of every sum and of the MFMAs is that of the shallow form (!DEEP, kept
+// for A/B timing and the equality test: TM_WIN_PREFETCH=0), so the outputs are bit-identical.  C / 8 is a multiple of 8.
+template <bool DEEP>
 __global__ __launch_bounds__(256) void window_attn_mfma_kernel(WinArgs a) {
   constexpr int T = 128, PS = WinLds::PS;
+  constexpr int SU = DEEP ? 8 : 1, QD = DEEP ? 4 : 1, VD = DEEP ? 2 : 1;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* P = sm;                       // [T][PS]
   float* Vt = P + T * PS;              // [32][PS]
@@ -982,10 +998,12 @@ __global__ __launch_bounds__(256) void window_attn_mfma_kernel(WinArgs a) {
     const float* p = isq ? qb + tokoff[t] : kb + TM_KVOFF(tokoff[t]);
     const long pp = isq ? a.plane : kvp;
     float ss = 0.f;
-    for (int cb = 0; cb < C / 8; ++cb) {
-      const f32x4 a0 = *(const f32x4*)(p + (long)cb * pp), a1 = *(const f32x4*)(p + (long)cb * pp + 4);
-      ss += a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2] + a0[3] * a0[3] + a1[0] * a1[0] + a1[1] * a1[1] +
-            a1[2] * a1[2] + a1[3] * a1[3];
+    for (int cb = 0; cb < C / 8; cb += SU) {
+      f32x4 a0[SU], a1[SU];
+#pragma unroll
+      for (int u = 0; u < SU; ++u) { a0[u] = *(const f32x4*)(p + (long)(cb + u) * pp); a1[u] = *(const f32x4*)(p + (long)(cb + u) * pp + 4); }
+#pragma unroll
+      for (int u = 0; u < SU; ++u) ss += win_sumsq8(a0[u], a1[u]);
     }
     const float r = 1.0f / sqrtf(ss / (float)C + TM_EPS);
     if (isq) rq[t] = r; else rk[t] = r;
@@ -1002,27 +1020,35 @@ __global__ __launch_bounds__(256) void window_attn_mfma_kernel(WinArgs a) {
   const float* kp[4];
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) kp[ct] = kb + TM_KVOFF(tokoff[ct * 32 + i32]) + 4 * h;
-  // fragments of channel block cb+1 are in flight while block cb's 16 MFMAs issue (one workgroup per CU: nothing
-  // else would hide the L2 round trip)
-  f32x4 qn = *(const f32x4*)qp, kn[4];
+  // fragments of channel blocks cb+1 .. cb+QD are in flight while block cb's 16 MFMAs issue (one workgroup per CU: nothing
+  // else would hide the L2 round trip): a register ring of QD slots, slot d = blocks d, d + QD, ...
+  f32x4 qn[QD], kn[QD][4];
 #pragma unroll
-  for (int ct = 0; ct < 4; ++ct) kn[ct] = *(const f32x4*)kp[ct];
-  for (int cb = 0; cb < C / 8; ++cb) {
-    const f32x4 qf = qn;
-    const f32x4 wf = *(const f32x4*)(w2 + cb * 8 + 4 * h);
-    f32x4 kf[4];
+  for (int d = 0; d < QD; ++d) {
+    qn[d] = *(const f32x4*)(qp + (long)d * a.plane);
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) kf[ct] = kn[ct] * wf;
-    if (cb + 1 < C / 8) {
-      const long po = (long)(cb + 1) * a.plane, pk = (long)(cb + 1) * kvp;
-      qn = *(const f32x4*)(qp + po);
+    for (int ct = 0; ct < 4; ++ct) kn[d][ct] = *(const f32x4*)(kp[ct] + (long)d * kvp);
+  }
+  for (int cb0 = 0; cb0 < C / 8; cb0 += QD) {
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) kn[ct] = *(const f32x4*)(kp[ct] + pk);
+    for (int d = 0; d < QD; ++d) {
+      const int cb = cb0 + d;
+      const f32x4 qf = qn[d];
+      const f32x4 wf = *(const f32x4*)(w2 + cb * 8 + 4 * h);
+      f32x4 kf[4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) kf[ct] = kn[d][ct] * wf;
+      if (cb + QD < C / 8) {
+        const long po = (long)(cb + QD) * a.plane, pk = (long)(cb + QD) * kvp;
+        qn[d] = *(const f32x4*)(qp + po);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) kn[d][ct] = *(const f32x4*)(kp[ct] + pk);
+      }
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[kk], kf[ct][kk], acc[ct], 0, 0, 0);
     }
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-      for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(qf[kk], kf[ct][kk], acc[ct], 0, 0, 0);
   }
   // ---- scale, softmax over keys (columns = lanes of this 32-lane half x 4 column tiles) ----
   const float inv_c = 1.0f / (float)C;                   // (q*scale).k*scale, scale = C^-1/2 (MBAblocks.py:571-577)
@@ -1052,25 +1078,32 @@ __global__ __launch_bounds__(256) void window_attn_mfma_kernel(WinArgs a) {
   const float* vfrag = Vt + i32 * PS + 4 * h;                      // A operand: Vt[c_i][u0 + 4h ..]
   const int myoff = tokoff[wv * 32 + i32];
   // V chunk staging: thread owns items (u, cbi) = (tid & 127, tid >> 7) and (tid & 127, 2 + (tid >> 7)); the next
-  // chunk's two 32-byte pieces are loaded into registers before the current chunk's MFMAs
+  // VD chunks' two 32-byte pieces each are loaded into registers before the current chunk's MFMAs (C / 32 is even)
   const int su = tid & (T - 1), scb = tid >> 7;
   const float* vsrc = vb + TM_KVOFF(tokoff[su]) + (long)scb * kvp;
-  f32x4 vr[4];
-  vr[0] = *(const f32x4*)vsrc; vr[1] = *(const f32x4*)(vsrc + 4);
-  vr[2] = *(const f32x4*)(vsrc + 2 * kvp); vr[3] = *(const f32x4*)(vsrc + 2 * kvp + 4);
-  for (int c0 = 0; c0 < C; c0 += 32) {
+  f32x4 vr[VD][4];
+#pragma unroll
+  for (int d = 0; d < VD; ++d) {
+    const float* p = vsrc + (long)(4 * d) * kvp;
+    vr[d][0] = *(const f32x4*)p; vr[d][1] = *(const f32x4*)(p + 4);
+    vr[d][2] = *(const f32x4*)(p + 2 * kvp); vr[d][3] = *(const f32x4*)(p + 2 * kvp + 4);
+  }
+  for (int cg = 0; cg < C; cg += 32 * VD)
+#pragma unroll
+  for (int vd = 0; vd < VD; ++vd) {
+    const int c0 = cg + 32 * vd;
     __syncthreads();                                               // Vt free (and, first time, P complete)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {                         // transposed store [channel][token]
       float* d = Vt + ((scb + 2 * half) * 8) * PS + su;
-      const f32x4 v0 = vr[2 * half], v1 = vr[2 * half + 1];
+      const f32x4 v0 = vr[vd][2 * half], v1 = vr[vd][2 * half + 1];
       d[0 * PS] = v0[0]; d[1 * PS] = v0[1]; d[2 * PS] = v0[2]; d[3 * PS] = v0[3];
       d[4 * PS] = v1[0]; d[5 * PS] = v1[1]; d[6 * PS] = v1[2]; d[7 * PS] = v1[3];
     }
-    if (c0 + 32 < C) {
-      const float* p = vsrc + (long)((c0 + 32) / 8) * kvp;
-      vr[0] = *(const f32x4*)p; vr[1] = *(const f32x4*)(p + 4);
-      vr[2] = *(const f32x4*)(p + 2 * kvp); vr[3] = *(const f32x4*)(p + 2 * kvp + 4);
+    if (c0 + 32 * VD < C) {
+      const float* p = vsrc + (long)((c0 + 32 * VD) / 8) * kvp;
+      vr[vd][0] = *(const f32x4*)p; vr[vd][1] = *(const f32x4*)(p + 4);
+      vr[vd][2] = *(const f32x4*)(p + 2 * kvp); vr[vd][3] = *(const f32x4*)(p + 2 * kvp + 4);
     }
     __syncthreads();
     f32x16 oc;
@@ -1450,12 +1483,17 @@ hipError_t launch_window_attn(const TV& q, const TV& k, const TV& v, const float
   if (T == 128 && a.C <= 512) {
     static DevOnce attr_set;
     const size_t lds = (size_t)WinLds::FLOATS * sizeof(float);
+    // TM_WIN_PREFETCH=0: the shallow prefetch depths (A/B timing and the equality test only); read once
+    static const bool deep = !(getenv("TM_WIN_PREFETCH") && atoi(getenv("TM_WIN_PREFETCH")) == 0);
     if (attr_set.need()) {
-      hipError_t e = hipFuncSetAttribute((const void*)window_attn_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      hipError_t e = hipFuncSetAttribute((const void*)window_attn_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)window_attn_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
       if (e != hipSuccess) return e;
       attr_set.mark();
     }
-    hipLaunchKernelGGL(window_attn_mfma_kernel, dim3(q.N * 4), dim3(256), lds, s, a);
+    if (deep) hipLaunchKernelGGL(window_attn_mfma_kernel<true>, dim3(q.N * 4), dim3(256), lds, s, a);
+    else hipLaunchKernelGGL(window_attn_mfma_kernel<false>, dim3(q.N * 4), dim3(256), lds, s, a);
     return hipGetLastError();
   }
   if (T == 32) return launch_win<32>(a, q.N, s);

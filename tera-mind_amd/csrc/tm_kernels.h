@@ -182,9 +182,13 @@ hipError_t launch_prep_drop(const PrepLaunch& L, const DropRng& r, hipStream_t s
 // the keep mask of drop_keep8 as an fp32 CB8 tensor of 0 / 1 (pad channels 0)
 hipError_t launch_dropout_mask(float* mask, int N, int C, int Z, int S, unsigned long long key, uint32_t site, uint32_t thr,
                                hipStream_t s);
-// test / measurement knob (tm_op_prep_h16): 0 automatic, 1 prep_kernel, 2 / 3 the two forms of prep_h16_kernel; process-wide,
+// test / measurement knob (tm_op_prep_h16, tm_op_prep_f32): 0 automatic, 1 prep_kernel's four-wave forms, 2 / 3 the two forms of
+// prep_h16_kernel (16-bit calls), 2 the wide form of prep_kernel (fp32 calls, where it is also the automatic choice); process-wide,
 // set and reset around the op's own launches only
 void set_prep_variant(int v);
+// launch_prep takes the call in the wide resident form of prep_kernel (fp32 sources and fp32 out, 33..160 channel blocks)
+bool prep_wide_applies(const PrepLaunch& L);
+constexpr int PREP_WIDE_MAX_CB = 160;      // channel blocks (1280 channels) the wide form keeps resident
 
 // ---- generic direct conv (VALU) with strided accessors --------------------------------
 struct Acc5 {                        // address = n*sN + (c/8)*sCb + (c%8)*sC8 + z*sZ + y*sY + x*sX
@@ -217,11 +221,11 @@ hipError_t launch_to_cb8(const float* x, TV y, hipStream_t s);        // NCDHW -
 hipError_t launch_from_cb8(TV x, float* y, hipStream_t s);            // CB8 -> NCDHW
 
 // ---- time embedding --------------------------------------------------------------------
-// te[b][E] = W2 * silu(W1 * sinusoid(t) + b1) + b2 ; then ss[b][tot] = Wall * silu(te) + ball
+// te[b][E] = W2 * silu(W1 * sinusoid(t) + b1) + b2, te_act[b][E] = silu(te) ; then ss[b][tot] = Wall * te_act + ball
 hipError_t launch_time_embed(const int64_t* t, int b, int ch, int E, const float* w1,
-                             const float* b1, const float* w2, const float* b2, float* te,
+                             const float* b1, const float* w2, const float* b2, float* te, float* te_act,
                              hipStream_t s);
-hipError_t launch_emb_all(const float* te, int b, int E, const float* wall, const float* ball,
+hipError_t launch_emb_all(const float* te_act, int b, int E, const float* wall, const float* ball,
                           int tot, float* ss, hipStream_t s);
 
 // ---- gene-gene attention ---------------------------------------------------------------

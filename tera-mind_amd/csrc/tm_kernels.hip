@@ -780,12 +780,26 @@ __device__ __forceinline__ DropRng rng_of(const PrepDropArgs& a) { return a.r; }
 // sum-of-squares pass and the apply pass, so every source byte is read from HBM once.
 // DRAW (NSUB 1, fp32 out; args PrepDropArgs): the training dropout keep mask is drawn here (drop_keep8, one Philox pair per
 // channel block) instead of read from drop_mask.  Its own instantiations: the inference ones compile as without it.
-template <int NSUB, bool CACHED, bool DRAW = false, class Args = PrepArgs>
-__global__ __launch_bounds__(256) void prep_kernel(Args pa) {
+// WV > 4, the wide resident form (NSUB 1, CACHED, fp32 sources and fp32 out; launch_prep picks it for 33..160 channel blocks):
+// WV waves split the channel blocks of the 64 voxels, NCW blocks each, so that up to 1280 channels stay in registers and every
+// source byte is read once.  All of a wave's loads are issued before the first use, unconditionally (a block past the end re-reads
+// the wave's last real one, an invalid lane reads voxel 0).  The sum of squares keeps the four-wave form's association -- four
+// chains over the blocks r, r + 4, r + 8, ... in ascending order from 0.f, then c0 + c1 + c2 + c3: every wave leaves the 8-term sum
+// (sumsq8) of each of its blocks in LDS and waves 0..3 form the chains -- so the result is bit-identical to prep_kernel<1, false>.
+// sumsq8 is one function so that every form hands the compiler the same expression to contract; that it does contract it the
+// same way in the rolled loop, the cached loop and the store to LDS is held by tests/test_gpu_prep_wide.py (bit equality of the
+// forms), not by the language: a compiler that splits them shows there first.
+__device__ __forceinline__ float sumsq8(const f32x4& a0, const f32x4& a1) {
+  return a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2] + a0[3] * a0[3] + a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2] + a1[3] * a1[3];
+}
+template <int NSUB, bool CACHED, bool DRAW = false, class Args = PrepArgs, int WV = 4, int NCW = 8>
+__global__ __launch_bounds__(WV * 64) void prep_kernel(Args pa) {
+  constexpr bool WIDE = WV > 4;
+  static_assert(!WIDE || (NSUB == 1 && CACHED && !DRAW && WV * NCW >= 4), "the wide form is a cached NSUB 1 form");
   const PrepLaunch& L = pa.L;
   const DropRng R = rng_of(pa);
   __shared__ float red[4][NSUB][64];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, wv = WIDE ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   const int S = L.S, Z = L.Z;
   const long vpn = (long)Z * S * S;
   const long vidx = (long)blockIdx.x * 64 + lane;
@@ -853,7 +867,7 @@ __global__ __launch_bounds__(256) void prep_kernel(Args pa) {
       a0 = *(const f32x4*)p; a1 = *(const f32x4*)(p + 4);
     }
   };
-  constexpr int NC = CACHED ? 8 : 1;
+  constexpr int NC = CACHED ? NCW : 1;
   f32x4 c0[NC], c1[NC];            // CACHED only (NSUB == 1)
 
   float rstd[NSUB];
@@ -863,15 +877,35 @@ __global__ __launch_bounds__(256) void prep_kernel(Args pa) {
     float ssq[NSUB];
 #pragma unroll
     for (int sub = 0; sub < NSUB; ++sub) ssq[sub] = 0.f;
-    if (valid) {
+    if constexpr (WIDE) {
+      __shared__ float bsum[PREP_WIDE_MAX_CB][64];
+      const int glast = wv < cbtot ? cbtot - 1 - ((cbtot - 1 - wv) % WV) : 0;    // the wave's last real block
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        const int gb = min(wv + WV * i, glast);
+        const int k = (gb >= cb0) + (gb >= cb01);              // wave-uniform
+        const int cb = gb - (k == 0 ? 0 : (k == 1 ? cb0 : cb01));
+        const float* sp = k == 0 ? L.src[0].p : (k == 1 ? L.src[1].p : L.src[2].p);
+        const float* p = sp + (k == 0 ? soff[0][0] : (k == 1 ? soff[1][0] : soff[2][0])) +
+                         (long)cb * (k == 0 ? splane[0] : (k == 1 ? splane[1] : splane[2]));
+        c0[i] = *(const f32x4*)p; c1[i] = *(const f32x4*)(p + 4);
+      }
+      if (L.norm_w) {
+#pragma unroll
+        for (int i = 0; i < NC; ++i)
+          if (wv + WV * i < cbtot) bsum[wv + WV * i][lane] = sumsq8(c0[i], c1[i]);
+        __syncthreads();
+        if (wv < 4)
+          for (int gb = wv; gb < cbtot; gb += 4) ssq[0] += bsum[gb][lane];
+      }
+    } else if (valid) {
       if (CACHED) {
 #pragma unroll
         for (int i = 0; i < NC; ++i) {
           const int gb = wv + 4 * i;
           if (gb < cbtot) {
             load8(gb, 0, c0[i], c1[i]);
-            ssq[0] += c0[i][0] * c0[i][0] + c0[i][1] * c0[i][1] + c0[i][2] * c0[i][2] + c0[i][3] * c0[i][3] +
-                      c1[i][0] * c1[i][0] + c1[i][1] * c1[i][1] + c1[i][2] * c1[i][2] + c1[i][3] * c1[i][3];
+            ssq[0] += sumsq8(c0[i], c1[i]);
           }
         }
       } else {
@@ -880,15 +914,16 @@ __global__ __launch_bounds__(256) void prep_kernel(Args pa) {
           for (int sub = 0; sub < NSUB; ++sub) {
             f32x4 a0, a1;
             load8(gb, sub, a0, a1);
-            ssq[sub] += a0[0] * a0[0] + a0[1] * a0[1] + a0[2] * a0[2] + a0[3] * a0[3] +
-                        a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2] + a1[3] * a1[3];
+            ssq[sub] += sumsq8(a0, a1);
           }
         }
       }
     }
     if (L.norm_w) {
+      if (!WIDE || wv < 4) {
 #pragma unroll
-      for (int sub = 0; sub < NSUB; ++sub) red[wv][sub][lane] = ssq[sub];
+        for (int sub = 0; sub < NSUB; ++sub) red[wv][sub][lane] = ssq[sub];
+      }
       __syncthreads();
 #pragma unroll
       for (int sub = 0; sub < NSUB; ++sub) {
@@ -1007,7 +1042,7 @@ __global__ __launch_bounds__(256) void prep_kernel(Args pa) {
   if (CACHED) {
 #pragma unroll
     for (int i = 0; i < NC; ++i)
-      if (wv + 4 * i < cbtot) emit(wv + 4 * i, i);
+      if (wv + WV * i < cbtot) emit(wv + WV * i, i);
   } else {
     for (int gb = wv; gb < cbtot; gb += 4) emit(gb, 0);
   }
@@ -1357,7 +1392,8 @@ __global__ __launch_bounds__(256) void prep_down_h16_kernel(PrepArgs pa) {
 }
 
 // variant: 0 = automatic, 1 = prep_kernel (the generic form), 2 = prep_h16_kernel with one wave per 64 voxels, 3 = prep_h16_kernel
-// with the four waves of a workgroup splitting the channel blocks
+// with the four waves of a workgroup splitting the channel blocks.  fp32 calls (tm_op_prep_f32): 1 = the four-wave forms of
+// prep_kernel, 2 = its wide resident form
 static int g_prep_variant = 0;
 void set_prep_variant(int v) { g_prep_variant = v; }
 
@@ -1398,6 +1434,13 @@ hipError_t launch_prep_drop(const PrepLaunch& L, const DropRng& r, hipStream_t s
   return hipGetLastError();
 }
 
+// The wide resident form of prep_kernel takes the call: decided by the properties of the call only, never by N or the launch size
+bool prep_wide_applies(const PrepLaunch& L) {
+  int cbtot = 0;
+  for (int k = 0; k < L.nsrc; ++k) cbtot += L.src[k].Cb;
+  return !L.src_h && L.out && !L.out_h && !L.raw_h && !L.drop_mask && L.resample != RS_DOWN2 && cbtot > 32 && cbtot <= PREP_WIDE_MAX_CB;
+}
+
 hipError_t launch_prep(const PrepLaunch& L, hipStream_t s) {
   static const int env_form = getenv("TM_PREP_FORM") ? atoi(getenv("TM_PREP_FORM")) : 0;       // A/B timing only
   const int form = g_prep_variant ? g_prep_variant : env_form;
@@ -1419,6 +1462,14 @@ hipError_t launch_prep(const PrepLaunch& L, hipStream_t s) {
   const unsigned grid = (unsigned)((vox + 63) / 64);
   int cbtot = 0;
   for (int k = 0; k < L.nsrc; ++k) cbtot += L.src[k].Cb;
+  if (form != 1 && prep_wide_applies(L)) {
+    // 16 waves x <= 3 / 6 / 10 blocks.  Eight waves of twice the blocks were timed beside it (profiles/fp32_glue.txt section 4):
+    // equal at 48 and 93 blocks, 31.5 against 26.3 us at 157 blocks
+#define TM_PREP_WIDE(WV, NCW) hipLaunchKernelGGL((prep_kernel<1, true, false, PrepArgs, WV, NCW>), dim3(grid), dim3(WV * 64), 0, s, pa)
+    if (cbtot <= 48) TM_PREP_WIDE(16, 3); else if (cbtot <= 96) TM_PREP_WIDE(16, 6); else TM_PREP_WIDE(16, 10);
+#undef TM_PREP_WIDE
+    return hipGetLastError();
+  }
   if (L.resample == RS_DOWN2) hipLaunchKernelGGL((prep_kernel<4, false>), dim3(grid), dim3(256), 0, s, pa);
   else if (cbtot <= 32) hipLaunchKernelGGL((prep_kernel<1, true>), dim3(grid), dim3(256), 0, s, pa);
   else hipLaunchKernelGGL((prep_kernel<1, false>), dim3(grid), dim3(256), 0, s, pa);
@@ -1722,7 +1773,7 @@ hipError_t launch_from_cb8(TV x, float* y, hipStream_t s) {
 // ==========================================================================================
 __global__ __launch_bounds__(256) void time_embed_kernel(const int64_t* t, int ch, int E, const float* w1,
                                                          const float* b1, const float* w2, const float* b2,
-                                                         float* te) {
+                                                         float* te, float* te_act) {
   extern __shared__ float sm[];       // [ch] sinusoid, [E] hidden
   float* sinu = sm;
   float* hid = sm + ch;
@@ -1746,16 +1797,18 @@ __global__ __launch_bounds__(256) void time_embed_kernel(const int64_t* t, int c
     float acc = b2[o];
     for (int k = 0; k < E; ++k) acc = fmaf(w2[(long)o * E + k], hid[k], acc);
     te[(long)b * E + o] = acc;
+    te_act[(long)b * E + o] = silu_f(acc);      // what every emb_layer reads (emb_all_kernel)
   }
 }
 hipError_t launch_time_embed(const int64_t* t, int b, int ch, int E, const float* w1, const float* b1,
-                             const float* w2, const float* b2, float* te, hipStream_t s) {
-  hipLaunchKernelGGL(time_embed_kernel, dim3(b), dim3(256), (ch + E) * sizeof(float), s, t, ch, E, w1, b1, w2, b2, te);
+                             const float* w2, const float* b2, float* te, float* te_act, hipStream_t s) {
+  hipLaunchKernelGGL(time_embed_kernel, dim3(b), dim3(256), (ch + E) * sizeof(float), s, t, ch, E, w1, b1, w2, b2, te, te_act);
   return hipGetLastError();
 }
 
-// one wave per output row e; lanes split E; weight row kept in registers across images
-__global__ __launch_bounds__(256) void emb_all_kernel(const float* te, int b, int E, const float* wall,
+// one wave per output row e; lanes split E; weight row kept in registers across images.  te_act = SiLU(te), computed once by
+// time_embed_kernel (the same silu_f: the same bits as applying it here for every row)
+__global__ __launch_bounds__(256) void emb_all_kernel(const float* te_act, int b, int E, const float* wall,
                                                       const float* ball, int tot, float* ss) {
   const int lane = threadIdx.x & 63;
   const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1769,15 +1822,15 @@ __global__ __launch_bounds__(256) void emb_all_kernel(const float* te, int b, in
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 16; ++j)
-      if (j < per) acc = fmaf(w[j], silu_f(te[(long)i * E + j * 64 + lane]), acc);
+      if (j < per) acc = fmaf(w[j], te_act[(long)i * E + j * 64 + lane], acc);
     acc = wave_sum(acc);
     if (lane == 0) ss[(long)i * tot + e] = acc + bias;
   }
 }
-hipError_t launch_emb_all(const float* te, int b, int E, const float* wall, const float* ball, int tot,
+hipError_t launch_emb_all(const float* te_act, int b, int E, const float* wall, const float* ball, int tot,
                           float* ss, hipStream_t s) {
   if (E % 64 || E > 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(emb_all_kernel, dim3((tot + 3) / 4), dim3(256), 0, s, te, b, E, wall, ball, tot, ss);
+  hipLaunchKernelGGL(emb_all_kernel, dim3((tot + 3) / 4), dim3(256), 0, s, te_act, b, E, wall, ball, tot, ss);
   return hipGetLastError();
 }
 

@@ -1441,12 +1441,13 @@ static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* 
   const int ne_img = cx.p1 * cx.p2, nd_img = (cx.p1 - 1) * (cx.p2 - 1);
   const bool h16 = is_h16(c.dtype);
   // ---- time embedding + all emb_layers ----
-  float* te = cx.alloc_f((size_t)b * c.embed_ch);
+  float* te = cx.alloc_f((size_t)2 * b * c.embed_ch);       // te, then SiLU(te)
+  float* te_act = te + (size_t)b * c.embed_ch;
   float* ss = cx.alloc_f((size_t)b * m->emb_tot);
   cx.ss = ss;
   if (!cx.dry) {
-    cx.check(launch_time_embed(t, b, c.net_ch, c.embed_ch, m->te_w1, m->te_b1, m->te_w2, m->te_b2, te, cx.s));
-    cx.check(launch_emb_all(te, b, c.embed_ch, m->emb_w, m->emb_b, m->emb_tot, ss, cx.s));
+    cx.check(launch_time_embed(t, b, c.net_ch, c.embed_ch, m->te_w1, m->te_b1, m->te_w2, m->te_b2, te, te_act, cx.s));
+    cx.check(launch_emb_all(te_act, b, c.embed_ch, m->emb_w, m->emb_b, m->emb_tot, ss, cx.s));
   }
   // ---- RNA pyramid ----
   RnaOut Rloc;

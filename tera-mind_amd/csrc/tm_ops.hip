@@ -445,6 +445,56 @@ extern "C" int tm_op_prep_h16(const void* const* src_h16, const int* src_c, cons
   }
   return rc;
 }
+extern "C" int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
+                              int p1, int p2, int up2, const void* norm_w_dev, int c_real, int mod, const void* mod_scale,
+                              const void* mod_shift, long mod_stride, int mod_half, int per_image, int act, int variant,
+                              void* out_cb8, void* raw_cb8, int iters, float* elapsed_ms, void* stream) {
+  if (!src_cb8 || !src_c || !collage || !out_cb8 || nsrc < 1 || nsrc > 3 || iters < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (N < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "N, Z and S must be positive");
+  if (variant < 0 || variant > 2) return fail(TM_ERR_ARG, "variant: 0 automatic, 1 four-wave kernel, 2 wide form");
+  if (mod != MOD_NONE && (!mod_scale || !mod_shift)) return fail(TM_ERR_ARG, "modulation tensors missing");
+  if (mod_half && (mod != MOD_VOXEL || (S & 1))) return fail(TM_ERR_ARG, "mod_half takes a per-voxel modulation and an even S");
+  hipStream_t st = (hipStream_t)stream;
+  bool any_col = false;
+  for (int i = 0; i < nsrc; ++i) any_col = any_col || collage[i];
+  const int q = any_col ? (p1 - 1) * (p2 - 1) : 1;
+  if (any_col && (p1 < 2 || p2 < 2 || N % q)) return fail(TM_ERR_ARG, "collage needs N = b * (p1-1) * (p2-1)");
+  if (up2 < 0 || up2 > 1) return fail(TM_ERR_ARG, "up2: 0 same, 1 nearest x2");
+  if (up2 == 1 && (any_col || (S & 1))) return fail(TM_ERR_ARG, "up2 takes plain sources and an even S");
+  const int Ss = up2 == 1 ? S / 2 : S;
+  PrepLaunch P;
+  P.nsrc = nsrc;
+  int cbtot = 0;
+  for (int i = 0; i < nsrc; ++i) {
+    const int cb = (src_c[i] + 7) / 8;
+    P.src[i].p = (const float*)src_cb8[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
+    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
+    cbtot += cb;
+  }
+  P.resample = up2 == 1 ? RS_UP2 : RS_SAME; P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
+  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act; P.per_image = per_image > 0 ? per_image : 1;
+  P.mod = mod; P.mod_stride = mod_stride; P.mod_half = mod_half ? 1 : 0;
+  P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift;
+  P.out = (float*)out_cb8; P.out_nstride = (long)cbtot * Z * S * S * 8;
+  if (raw_cb8) { P.raw = (float*)raw_cb8; P.raw_nstride = P.out_nstride; }
+  if (variant == 2 && !prep_wide_applies(P))
+    return fail(TM_ERR_ARG, "the wide form takes 33..%d channel blocks (this call has %d)", PREP_WIDE_MAX_CB, cbtot);
+  DevTmp tmp;
+  hipEvent_t e0 = elapsed_ms ? tmp.event() : nullptr, e1 = elapsed_ms ? tmp.event() : nullptr;
+  if (tmp.err) return tmp.report();
+  set_prep_variant(variant);
+  hipError_t e = launch_prep(P, st);                                   // warm-up / the result
+  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e0, st);
+  for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_prep(P, st);
+  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e1, st);
+  set_prep_variant(0);
+  const int rc = finish(st, e, "prep (fp32)");
+  if (elapsed_ms) {
+    *elapsed_ms = 0.f;
+    if (rc == TM_OK && iters > 1) { (void)hipEventElapsedTime(elapsed_ms, e0, e1); *elapsed_ms /= (float)(iters - 1); }
+  }
+  return rc;
+}
 extern "C" int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_dev,
                                  const void* kw_dev, void* out, int N, int C, int Z, int S, int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
