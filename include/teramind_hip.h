@@ -283,16 +283,35 @@ int tm_op_from_cb8(const void* x_cb8, void* y_ncdhw, int N, int C, int Z, int H,
  *   3: 3x3x3 pad (1,1,1) of the nearest-x2 UPSAMPLED x (Upsample then Conv3d as in ResBlock(up=True), model/MBAblocks.py:254-258,
  *      blocks.py:362-371), Z == 2, computed on x itself with per-phase 2x2 in-plane weights: y is [N, Cout, Z, 2S, 2S].
  * up2: nearest x2 on (H, W) applied to the output (not with zmode 3).  w [Cout][Cin][kz][3][3] HOST fp32,
- * bias [Cout] HOST fp32; x, y CB8 DEVICE. */
+ * bias [Cout] HOST fp32; x, y CB8 DEVICE.
+ * tile_variant: 0 = the launcher's choice by launch size, 1 | 2 = 128- | 256-voxel workgroup tiles.  With ksize 1 also 3 = the
+ * 128-cout tile of the 1x1x1 kernel whatever the launch size (tm_conv1_form; an odd count of 64-cout tiles is refused with a
+ * HIP invalid-value error); with ksize 3 any other value means 1. */
 int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8,
                     int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
                     int tile_variant, void* stream);
 /* The same with the epilogue's residual (ksize 3, not zmode 3): y = res + conv + bias, res CB8 DEVICE in y's geometry, or with
  * res_half != 0 at half the in-plane resolution ([N][ceil(Cout/8)][Zout][S/2][S/2][8], read at (z, y >> 1, x >> 1): the
- * residual of a ResBlock(up=True)).  res_cb8 NULL: tm_op_conv_mfma. */
+ * residual of a ResBlock(up=True)).  res_cb8 NULL: tm_op_conv_mfma.  tile_variant as there. */
 int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                         int res_half, int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
                         int tile_variant, void* stream);
+
+/* The fp32 1x1x1 conv / Linear (conv1_mfma) in every form the model launches: y = res + gate_up * act(W x + b).
+ * x_cb8: DEVICE [N][x_cbtot][Z][S][S][8]; the conv reads the channel-block slice [x_cb0, x_cb0 + ceil(Cin/8)) of it in place
+ * (the patch stride stays that of the wide tensor).  w_host [Cout][Cin], bias_host [Cout]: HOST.  y_cb8: [N][ceil(Cout/8)][Z][S][S][8].
+ * res_cb8 (nullable): y's geometry; res_cb8 == y_cb8 is the in-place update x <- x + gate * Linear(.).  gate_cb8 (nullable):
+ * [N][gate_cbtot][Z][Sg][Sg][8], read from block gate_cb0 on; Sg = S, or S / 2 with gate_half != 0 (read at (z, y >> 1, x >> 1)).
+ * gelu != 0: act = tanh-GELU.  tile_variant: 0 = the launcher's choice, 1 | 2 = 128- | 256-voxel tiles, 3 = the 128-cout tile
+ * whatever the launch size.  *form_out (nullable) receives the kernel form launched (tm_conv1_form).
+ * TM_ERR_ARG before any device call: gate_half without a gate or with S not a power of two >= 2, a slice that runs past its
+ * tensor, tile_variant outside 0..3 or 3 with an odd count of 64-cout tiles. */
+int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                    const void* gate_cb8, int x_cbtot, int x_cb0, int gate_cbtot, int gate_cb0, int gate_half, int gelu,
+                    int tile_variant, int N, int Cin, int Cout, int Z, int S, int* form_out, void* stream);
+/* The form of the fp32 1x1x1 conv kernel a launch of `vox` voxels and `ntile` = ceil(Cout/64) cout tiles takes: 1 = 128 voxels
+ * x 64 couts per workgroup, 2 = 256 x 64, 3 = 256 x 128; 0 = refused (tile_variant 3 with an odd ntile).  Host only. */
+int tm_conv1_form(long vox, int ntile, int tile_variant);
 
 /* 16-bit variant of the 3x3x3 pad-1 conv (Z == 2): x fp32 CB8 is rounded to `dtype` (TM_DTYPE_BF16 | TM_DTYPE_F16, RNE) on
  * the device, w rounded on the host; fp32 accumulate, fp32 CB8 output.  waves: 0 = the launcher's choice, 4 | 8 = force
@@ -339,6 +358,13 @@ int tm_op_conv27_fused_z(const void* x_cb8, const void* w_host, const void* bias
 int tm_op_conv1_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8,
                      int N, int Cin, int Cout, int Z, int S, int gelu, int dtype, int waves, const void* res_h16,
                      const void* gate_h16, void* y_h16, void* stream);
+
+/* The same with the gate as a channel-block slice and / or at half resolution: gate_h16 is [N][gate_cbtot][Z][Sg][Sg][8], read
+ * from block gate_cb0 on; Sg = S, or S / 2 with gate_half != 0 (read at (z, y >> 1, x >> 1); S a power of two >= 2).
+ * tm_op_conv1_bf16 is this call with gate_half = 0, gate_cbtot = ceil(Cout/8), gate_cb0 = 0. */
+int tm_op_conv1_h16_gate(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8,
+                         int N, int Cin, int Cout, int Z, int S, int gelu, int dtype, int waves, const void* res_h16,
+                         const void* gate_h16, void* y_h16, int gate_half, int gate_cbtot, int gate_cb0, void* stream);
 
 /* The ResBlock skip conv as the 16-bit modes run it (model/MBAblocks.py:220-224,297 on x = th.cat((h, skip, rna), 1),
  * model/unet_ours.py:384,418, with to_collage :325-341 applied to the sources of the collage decoder): a 1x1x1 conv whose

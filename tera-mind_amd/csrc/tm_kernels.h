@@ -54,13 +54,15 @@ struct ConvLaunch {
   const TV* res = nullptr;   // optional residual (same geometry as y)
   const TV* gate = nullptr;  // optional gate: y = res + gate * (conv + bias)
   int flags = 0;
-  int tile_variant = 0;  // 0 auto, 1 = 128-voxel blocks, 2 = 256-voxel blocks
+  int tile_variant = 0;  // 0 auto, 1 = 128-voxel blocks, 2 = 256-voxel blocks; taps == 1 also 3 = the 128-cout tile (conv1_form)
   int gate_half = 0;     // taps == 1 only: `gate` lives at S/2 and is read at (z, y >> 1, x >> 1) (S a power of two)
   int res_half = 0;      // k x 3 x 3 only: `res` lives at S/2 and is read at (z, y >> 1, x >> 1): the residual of a ResBlock(up=True)
                          // is the nearest-x2 upsampled block input (model/MBAblocks.py:254-258,297)
   int zmode = ZM_PAD1;   // ignored for taps == 1
 };
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
+// which conv1_mfma instantiation a taps == 1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
+int conv1_form(long vox, int ntile, int tile_variant);
 
 // ---- bf16 3x3x3 conv (tm_conv_bf16.hip) --------------------------------------------------
 struct TVH {                        // bf16 CB8 tensor [N][Cb (even)][Z][H][W][8]; strides in elements

@@ -607,6 +607,18 @@ void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
   }
 }
 
+// The instantiation of conv1_mfma a 1x1x1 launch of `vox` voxels and `ntile` 64-cout tiles runs: 1 = <1, 2> (128 voxels x 64
+// couts per workgroup), 2 = <2, 2> (256 x 64), 3 = <2, 4> (256 x 128: pairs of cout tiles, so ntile must be even).
+// tile_variant 0 chooses by launch size: 256-voxel tiles from 512 workgroups of them, the 128-cout tile where those still make
+// 512; 1 and 2 force the voxel tile (2 keeps the size rule for the cout tile); 3 forces the 128-cout tile whatever the size
+// and is refused (0) on an odd ntile.
+int conv1_form(long vox, int ntile, int tile_variant) {
+  if (tile_variant == 3) return (ntile & 1) == 0 ? 3 : 0;
+  const int variant = tile_variant ? tile_variant : ((vox / 256) * ntile >= 512 ? 2 : 1);
+  if (variant == 2 && (ntile & 1) == 0 && (vox / 256) * (ntile / 2) >= 512) return 3;
+  return variant == 2 ? 2 : 1;
+}
+
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   ConvArgs a;
   a.x = L.x.p; a.x_nstride = L.x.nstride; a.x_plane = L.x.plane();
@@ -627,18 +639,18 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   if (L.w.taps == 1) {
     if (L.flags & EPI_UP2) return hipErrorInvalidValue;
     if (L.y.H != L.x.H || L.y.Z != L.x.Z) return hipErrorInvalidValue;
-    int variant = L.tile_variant ? L.tile_variant : ((vox / 256) * a.ntile >= 512 ? 2 : 1);
-    if (variant == 2 && (a.ntile & 1) == 0 && (vox / 256) * (a.ntile / 2) >= 512) {
+    const int form = conv1_form(vox, a.ntile, L.tile_variant);
+    if (form == 3) {
       const long mt = (vox + 255) / 256;                  // 128-cout x 256-voxel workgroups
       a.ntile /= 2;
       hipLaunchKernelGGL((conv1_mfma<2, 4>), dim3((unsigned)(mt * a.ntile)), dim3(256), 0, s, a);
-    } else if (variant == 2) {
+    } else if (form == 2) {
       const long mt = (vox + 255) / 256;
       hipLaunchKernelGGL((conv1_mfma<2, 2>), dim3((unsigned)(mt * a.ntile)), dim3(256), 0, s, a);
-    } else {
+    } else if (form == 1) {
       const long mt = (vox + 127) / 128;
       hipLaunchKernelGGL((conv1_mfma<1, 2>), dim3((unsigned)(mt * a.ntile)), dim3(256), 0, s, a);
-    }
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
   }
   // ---- k x 3 x 3 kernels ----

@@ -198,6 +198,50 @@ extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const 
   return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_mfma");
 }
 
+// power of two >= 2: what a half-resolution gate needs of S (read at (z, y >> 1, x >> 1))
+static bool half_gate_ok(int S) { return S >= 2 && (S & (S - 1)) == 0; }
+
+extern "C" int tm_conv1_form(long vox, int ntile, int tile_variant) { return conv1_form(vox, ntile, tile_variant); }
+
+extern "C" int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                               const void* gate_cb8, int x_cbtot, int x_cb0, int gate_cbtot, int gate_cb0, int gate_half, int gelu,
+                               int tile_variant, int N, int Cin, int Cout, int Z, int S, int* form_out, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || !y_cb8) return fail(TM_ERR_ARG, "null argument");
+  if (N < 1 || Cin < 1 || Cout < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "N, Cin, Cout, Z, S must be positive");
+  const int Cbi = (Cin + 7) / 8, Cob = (Cout + 7) / 8;
+  if (x_cb0 < 0 || x_cb0 + Cbi > x_cbtot)
+    return fail(TM_ERR_ARG, "x slice: blocks [%d, %d) run past the %d blocks of the tensor", x_cb0, x_cb0 + Cbi, x_cbtot);
+  if (gate_half && !gate_cb8) return fail(TM_ERR_ARG, "gate_half without a gate");
+  if (gate_half && !half_gate_ok(S)) return fail(TM_ERR_ARG, "gate_half: S must be a power of two >= 2 (got %d)", S);
+  if (gate_cb8 && (gate_cb0 < 0 || gate_cb0 + Cob > gate_cbtot))
+    return fail(TM_ERR_ARG, "gate slice: blocks [%d, %d) run past the %d blocks of the tensor", gate_cb0, gate_cb0 + Cob, gate_cbtot);
+  if (tile_variant < 0 || tile_variant > 3) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1, 2 or 3 (got %d)", tile_variant);
+  ConvW cw = conv_form(Cin, Cout, 1, ZM_PAD1, Z);
+  const int form = conv1_form((long)N * Z * S * S, cw.ntile, tile_variant);
+  if (!form) return fail(TM_ERR_ARG, "tile_variant 3 (128-cout tile) needs an even number of 64-cout tiles (got %d)", cw.ntile);
+  if (form_out) *form_out = form;
+  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, 1));
+  conv_pack_host((const float*)w_host, Cout, &Cin, 1, 1, pk.data());
+  DevTmp tmp;
+  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, x_cbtot * 8, Z, S, S).blocks(x_cb0, Cbi);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.tile_variant = tile_variant;
+  L.flags = gelu ? EPI_GELU : 0;
+  TV res = L.y, gate;
+  if (res_cb8) { res.p = (float*)const_cast<void*>(res_cb8); L.res = &res; }      // res_cb8 == y_cb8: x <- x + gate * Linear(.)
+  if (gate_cb8) {
+    const int Sg = gate_half ? S / 2 : S;
+    gate = view_cb8(const_cast<void*>(gate_cb8), N, gate_cbtot * 8, Z, Sg, Sg).blocks(gate_cb0, Cob);
+    L.gate = &gate;
+    L.gate_half = gate_half ? 1 : 0;
+  }
+  return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv1 (fp32)");
+}
+
 // The ConvLaunchH of the 16-bit 3x3x3 conv hooks: x N x Cin channels (blocks paired) on Z planes of S x S, y Cout channels at
 // So = S, or 2S in the upsampled-input form (Z == 2 only, as the half-resolution residual); fused: the norm epilogue writes the
 // 16-bit a2 at y's geometry.  Rejects the forms the kernels do not take, before any device call; the caller sets the pointers.
@@ -339,10 +383,21 @@ extern "C" int tm_op_conv27_time(int N, int Cin, int Cout, int S, int dtype, int
 extern "C" int tm_op_conv1_bf16(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                                 int Cout, int Z, int S, int gelu, int dtype, int waves, const void* res_h16, const void* gate_h16,
                                 void* y_h16, void* stream) {
+  return tm_op_conv1_h16_gate(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, gelu, dtype, waves, res_h16, gate_h16, y_h16, 0,
+                              (Cout + 7) / 8, 0, stream);
+}
+extern "C" int tm_op_conv1_h16_gate(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                    int Cout, int Z, int S, int gelu, int dtype, int waves, const void* res_h16,
+                                    const void* gate_h16, void* y_h16, int gate_half, int gate_cbtot, int gate_cb0, void* stream) {
   if (!x_cb8 || !w_host || !bias_host || (!y_cb8 && !y_h16)) return fail(TM_ERR_ARG, "null argument");
   if (!y_cb8) y_cb8 = y_h16;                              // geometry carrier only
   if (!is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_BF16 or TM_DTYPE_F16");
   if (waves != 0 && waves != 4 && waves != 8) return fail(TM_ERR_ARG, "waves must be 0 (auto), 4 or 8");
+  if (gate_half && !gate_h16) return fail(TM_ERR_ARG, "gate_half without a gate");
+  if (gate_half && !half_gate_ok(S)) return fail(TM_ERR_ARG, "gate_half: S must be a power of two >= 2 (got %d)", S);
+  if (gate_h16 && (gate_cb0 < 0 || gate_cb0 + (Cout + 7) / 8 > gate_cbtot))
+    return fail(TM_ERR_ARG, "gate slice: blocks [%d, %d) run past the %d blocks of the tensor", gate_cb0, gate_cb0 + (Cout + 7) / 8,
+                gate_cbtot);
   const bool f16 = dtype == TM_DTYPE_F16;
   hipStream_t st = (hipStream_t)stream;
   std::vector<uint16_t> pk(conv1_bf16_pack_elems(Cout, (Cin + 7) / 8));
@@ -355,9 +410,14 @@ extern "C" int tm_op_conv1_bf16(const void* x_cb8, const void* w_host, const voi
   L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
   L.Cout = Cout; L.flags = gelu ? EPI_GELU : 0; L.force_waves = waves;
   L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
-  TVH resh = as_h(L.y), gateh = as_h(L.y);
+  TVH resh = as_h(L.y), gateh;
   if (res_h16) { resh.p = (uint16_t*)const_cast<void*>(res_h16); L.res_h = &resh; }
-  if (gate_h16) { gateh.p = (uint16_t*)const_cast<void*>(gate_h16); L.gate_h = &gateh; }
+  if (gate_h16) {                                         // [N][gate_cbtot][Z][Sg][Sg][8], blocks from gate_cb0
+    const int Sg = gate_half ? S / 2 : S;
+    gateh = view_h16(const_cast<void*>(gate_h16), N, gate_cbtot * 8, Z, Sg, Sg).blocks(gate_cb0, L.y.Cb);
+    L.gate_h = &gateh;
+    L.gate_half = gate_half ? 1 : 0;
+  }
   if (y_h16) { L.y_h = (uint16_t*)y_h16; L.yh_nstride = L.y.nstride; }
   if (e == hipSuccess) e = (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st);
   return finish(st, e, "conv1 (16-bit)");
