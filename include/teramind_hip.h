@@ -297,6 +297,27 @@ int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const void* bias_
                         int res_half, int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
                         int tile_variant, void* stream);
 
+/* The fp32 3x3x3 pad-1 conv at Z == 2 in its pair form with the ResBlock mid-section fused into the epilogue (Cout == 64, the
+ * 128-voxel tile): out_layers[0] RMSNorm(C) * norm_w -> x * (1 + scale) + shift -> SiLU (model/MBAblocks.py:196-203,356-367),
+ * written as the fp32 CB8 tensor a2_out [N][8][2][S][S][8] (the second conv's input); the conv output itself is not stored.
+ * x CB8 DEVICE; w [64][Cin][27], bias [64], norm_w [64], scale / shift [ceil(N/per_image)][64] HOST fp32; patch n uses row
+ * n / per_image.  h1_out (nullable, DEVICE, a2's shape): conv + bias from a second, plain launch of the same tile.  a2_sep_out
+ * (nullable, needs h1_out): the separate norm pass (prep_kernel) applied to h1_out.  tile_variant: 0 = by launch size, 1 | 2 =
+ * the 64- | 128-voxel tile.  TM_ERR_ARG before any device call: Z != 2, Cout != 64, a residual (res_cb8 non-NULL), S outside
+ * {8, .., 128}, a launch that takes the 64-voxel tile, the pair form switched off. */
+int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
+                               const void* scale_host, const void* shift_host, const void* res_cb8, void* a2_out,
+                               void* h1_out, void* a2_sep_out, int N, int Cin, int Cout, int Z, int S, int per_image,
+                               int tile_variant, void* stream);
+
+/* The fp32 3x3x3 pad-1 conv of the nearest-x2 UPSAMPLED x at Z == 2 (ResBlock(up=True)'s first conv), computed on x itself in
+ * the pair form (conv3d_zpair_ups: per output phase three 2x2 in-plane products per plane pair).  x CB8 DEVICE
+ * [N][ceil(Cin/8)][2][S][S][8]; w [Cout][Cin][27], bias [Cout] HOST; y CB8 DEVICE [N][ceil(Cout/8)][2][2S][2S][8].
+ * tile_variant: 0 = by launch size, 1 | 2 = the 64- | 128-voxel tile.  TM_ERR_ARG before any device call: Z != 2, S outside
+ * {4, .., 64}.  tm_op_conv_mfma with zmode 3 is the z-skip form of the same conv. */
+int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                            int Cout, int Z, int S, int tile_variant, void* stream);
+
 /* The fp32 1x1x1 conv / Linear (conv1_mfma) in every form the model launches: y = res + gate_up * act(W x + b).
  * x_cb8: DEVICE [N][x_cbtot][Z][S][S][8]; the conv reads the channel-block slice [x_cb0, x_cb0 + ceil(Cin/8)) of it in place
  * (the patch stride stays that of the wide tensor).  w_host [Cout][Cin], bias_host [Cout]: HOST.  y_cb8: [N][ceil(Cout/8)][Z][S][S][8].

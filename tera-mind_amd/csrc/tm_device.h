@@ -125,6 +125,14 @@ struct ConvArgs {
   // Linear(SiLU(cond)) of a nearest-x2 upsampled RNA level, i.e. constant over 2 x 2 voxel blocks.  gate_ls = log2(S), 0 = off
   int gate_ls = 0;
   int res_ls = 0;                   // the same for the fp32 residual `res` (3x3x3 conv epilogue): = log2(S), 0 = off
+  // conv3d_zpair<0, TW, true> only: the ResBlock mid-section in the epilogue (zpair_norm_epilogue); `y` is then the activated
+  // input of the second conv and the conv output itself is not stored
+  const float* norm_w = nullptr;    // [64]
+  const float* mod_scale = nullptr; // [image][..], row stride mod_stride floats
+  const float* mod_shift = nullptr;
+  long mod_stride = 0;
+  int per_image = 1;                // patches per image (n -> modulation row)
+  float inv_c = 0.f;                // 1 / 64
 };
 
 // in-plane element offset of voxel (z, y, x) -> (z, y >> 1, x >> 1) of the half-resolution plane; ls = log2(S)
@@ -220,6 +228,66 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[W
       }
     }
   }
+}
+
+// Fused mid-section of a fp32 ResBlock with 64 output channels, run on one output plane of conv3d_zpair<0, *>:
+// out_layers' LlamaRMSNorm(dim=1) * w -> x (1 + scale) + shift -> SiLU (model/MBAblocks.py:21-43,196-203,356-367) applied to
+// conv + bias while it is still in the accumulators, written as the second conv's input.  eps, the modulation formula and the
+// SiLU form are prep_kernel's, and so is the ORDER of the sum of squares, so that a layer gives the same bits whether a launch
+// fuses or runs the separate pass (tests/test_gpu_conv_zpair_fused.py holds the two to equal bits):
+//   * per channel block b (8 channels) s8[b] = ((((((p0 + p1) + p2) + p3) + p4) + p5) + p6) + p7 with p_c = h_c * h_c ROUNDED
+//     (what sumsq8 compiles to in prep_kernel: v_pk_mul_f32 and seven adds; the products are pinned here so that none is
+//     contracted into an FMA);
+//   * the four chains of prep_kernel's four waves, red[r] = s8[r] + s8[r + 4], then ((red[0] + red[1]) + red[2]) + red[3].
+// Lane (i32, h) holds couts 32 ct + 8 g + 4 h + j of voxel i32 in o[ct][0][4 g + j]: block b = 4 ct + g has its channels 0..3 in
+// lane i32 and 4..7 in lane i32 + 32.  So lane h = 0 forms (p0 + p1) + p2) + p3 of every block and hands it across
+// (lane ^ 32), lane h = 1 continues the chain with its own four products and finishes the voxel's sum, which goes back across.
+// Every lane executes both halves; the half that is not its own is discarded.
+__device__ __forceinline__ void zpair_norm_epilogue(const ConvArgs& a, f32x16 (&o)[2][1], int h, int n, int ooff) {
+  float s8[8];
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 bv = *(const f32x4*)(a.bias + (ct * 4 + g) * 8 + 4 * h);
+      float p[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = o[ct][0][4 * g + j] + bv[j];
+        o[ct][0][4 * g + j] = v;
+        p[j] = v * v;
+        asm volatile("" : "+v"(p[j]));                           // a rounded product, as in prep_kernel: no FMA contraction
+      }
+      const float lo = ((p[0] + p[1]) + p[2]) + p[3];            // channels 0..3 of the block (lane h = 0)
+      const float lo_p = __shfl_xor(lo, 32, 64);
+      s8[ct * 4 + g] = (((lo_p + p[0]) + p[1]) + p[2]) + p[3];   // ... continued over channels 4..7 (lane h = 1)
+    }
+  float red[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) red[r] = s8[r] + s8[r + 4];
+  const float t1 = ((red[0] + red[1]) + red[2]) + red[3];
+  const float t0 = __shfl_xor(t1, 32, 64);
+  const float t = h ? t1 : t0;
+  if (ooff < 0) return;
+  const float rstd = 1.0f / sqrtf(t * a.inv_c + TM_EPS);
+  const long mo = (long)(n / a.per_image) * a.mod_stride;
+  float* yp = a.y + (long)n * a.y_nstride + ooff + 4 * h;
+#pragma unroll
+  for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int c0 = (ct * 4 + g) * 8 + 4 * h;
+      const f32x4 wn = *(const f32x4*)(a.norm_w + c0);
+      const f32x4 sc = *(const f32x4*)(a.mod_scale + mo + c0), sh = *(const f32x4*)(a.mod_shift + mo + c0);
+      f32x4 r;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float v = wn[j] * (o[ct][0][4 * g + j] * rstd);
+        v = v * (1.0f + sc[j]) + sh[j];
+        r[j] = silu_h16(v);
+      }
+      *(f32x4*)(yp + (long)(ct * 4 + g) * a.y_plane) = r;
+    }
 }
 
 }  // namespace tmk

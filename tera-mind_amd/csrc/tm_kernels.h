@@ -32,7 +32,8 @@ struct ConvW {
   const float* w = nullptr;     // device
   const float* bias = nullptr;  // device, [ntile*64]
   int Cout = 0, Cbi = 0, taps = 0, ntile = 0;
-  int zpair = 0;                // taps == 27 packed by conv_pack_zpair_host: ZM_PAD1 at Z == 2 runs the pair form (conv3d_zpair)
+  int zpair = 0;                // taps == 27 packed by conv_pack_zpair_host: ZM_PAD1 at Z == 2 runs the pair form (conv3d_zpair);
+                                // taps == 12 packed by conv_pack_zpair_ups_host: ZM_UPS runs conv3d_zpair_ups
 };
 size_t conv_pack_floats(int Cout, int Cbi, int taps);
 // host-side packing; seg_c[i] = real channels of concat segment i (each padded to x8).
@@ -42,6 +43,8 @@ size_t conv_pack_ups_floats(int Cout, int Cbi);          // phase weights of the
 void conv_pack_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
 bool conv_zpair_enabled();                               // false with TM_CONV_ZPAIR=0 (A/B timing): keep the 18-tap z-skip form
 void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
+// ZM_UPS in the pair form (conv3d_zpair_ups; ConvW.zpair with taps == 12): the z difference of the phase weights; the same size
+void conv_pack_zpair_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out);  // per-cin vector -> virtual order
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_UP2 = 2 };
@@ -59,8 +62,18 @@ struct ConvLaunch {
   int res_half = 0;      // k x 3 x 3 only: `res` lives at S/2 and is read at (z, y >> 1, x >> 1): the residual of a ResBlock(up=True)
                          // is the nearest-x2 upsampled block input (model/MBAblocks.py:254-258,297)
   int zmode = ZM_PAD1;   // ignored for taps == 1
+  // pair form (w.zpair), Cout == 64, the 128-voxel tile, no residual / gate / flags: fuse RMSNorm(C) * norm_w -> x (1 + scale) +
+  // shift -> SiLU into the epilogue and write `a2` (the next conv's input) instead of y; y carries the geometry only
+  int fuse_norm = 0;
+  const float *norm_w = nullptr, *mod_scale = nullptr, *mod_shift = nullptr;
+  float inv_c = 0.f;
+  long mod_stride = 0;
+  int per_image = 1;
+  TV a2;
 };
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
+int conv_zpair_half(long ovox, int ntile, int S, int tile_variant);   // 1: a pair-form launch takes the 64-voxel tile; no device call
+bool conv_fuse_mid_enabled();                            // false with TM_CONV_FUSE_MID=0 (A/B timing): separate mid-block norm pass
 // which conv1_mfma instantiation a taps == 1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
 int conv1_form(long vox, int ntile, int tile_variant);
 

@@ -212,6 +212,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
 // One workgroup owns an in-plane tile of MV voxels, BOTH output planes and 64 couts.  HALF = 0: 128 voxels, wave = 32 voxels x
 // 64 couts (3 x 2 accumulators); HALF = 1: 64 voxels, wave = 32 voxels x 32 couts (small launches).  Every output element
 // sees the same order in both -- cin block outer, then product, tap, k -- so the two tiles give identical bits.
+// FUSE (HALF = 0, 64 couts, one cout tile): the wave holds every channel of its 32 voxels, so the ResBlock mid-section (RMSNorm
+// over channels -> modulate -> SiLU, zpair_norm_epilogue) runs on each output plane in place of the plain epilogue and the
+// second conv's input is written instead of the conv output.  The K loop is the same code; layers that do not fuse run <.., false>.
 typedef int rsrc_words __attribute__((ext_vector_type(4)));     // a buffer descriptor as four SGPRs of an asm statement
 
 template <int HALF, int TW>
@@ -227,8 +230,9 @@ struct ZPGeo {
   static constexpr int LDS_BYTES = (WFLOATS + 3 * XV * 8) * 4;  // weights + the planes X0 + X1, X1, X0
 };
 
-template <int HALF, int TW>
+template <int HALF, int TW, bool FUSE = false>
 __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
+  static_assert(!FUSE || HALF == 0, "the fused mid-section needs every cout of a voxel in one wave");
   using G = ZPGeo<HALF, TW>;
   constexpr int NC = HALF ? 1 : 2;                               // 32-cout sub-tiles per wave
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -403,10 +407,182 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   const int nte = HALF ? 2 * nt + ct0 : nt;                      // conv_epilogue counts cout blocks in units of its own tile
 #pragma unroll
   for (int ct = 0; ct < NC; ++ct) o[ct][0] = acc[0][ct] + acc[1][ct];
-  conv_epilogue<1, NC>(a, o, nte, h, on, ooff0, 2 * S);
+  if constexpr (FUSE) zpair_norm_epilogue(a, o, h, on[0], ooff0[0]);
+  else conv_epilogue<1, NC>(a, o, nte, h, on, ooff0, 2 * S);
 #pragma unroll
   for (int ct = 0; ct < NC; ++ct) o[ct][0] = acc[0][ct] + acc[2][ct];
-  conv_epilogue<1, NC>(a, o, nte, h, on, ooff1, 2 * S);
+  if constexpr (FUSE) zpair_norm_epilogue(a, o, h, on[0], ooff1[0]);
+  else conv_epilogue<1, NC>(a, o, nte, h, on, ooff1, 2 * S);
+}
+
+// ---- pair form of the upsampled-input conv (fp32, Z == 2): ResBlock(up=True)'s first conv ----
+// The UPS form of conv3d_mfma runs, per output phase (py, px), a 2 x 2 in-plane window on each of the two z taps of each output
+// plane: four in-plane products per plane pair, 16 tap-products.  The pair identity above is linear in the weights, so it
+// commutes with the pre-summing of the phase weights: with V0, V1, V2 the kz slices of the PHASE weights (conv_pack_ups_host's
+// sums) the kernel computes P1 = V1 * (X0 + X1), P2 = (V2 - V1) * X1, P3 = (V0 - V1) * X0 on the low-resolution planes, 12
+// tap-products per plane pair, and stores Y0 = P1 + P2, Y1 = P1 + P3 at (2 y + py, 2 x + px) of the two output planes.
+// Weights: conv_pack_zpair_ups_host, per (phase, cout tile, cin block) 12 taps x 512 floats in the order the kernel consumes
+// them (product, wy, wx) -- the same size as the z-skip UPS pack.  Staging of X is conv3d_zpair's (the two planes added in
+// registers, three LDS planes).  The weights come by the same LDS-DMA pieces, but a block's 12 taps are only 24 KiB, so the ring
+// is two whole-block slots and a cin block costs two barriers, not four:
+//   vmcnt(0) | B0 | X(cb) -> LDS | B1 | 12 taps from slot cb & 1, with X(cb + 1) -> registers and the six pieces each wave owns of
+//   W(cb + 1) -> slot (cb + 1) & 1 behind the first six taps
+// Slot (cb + 1) & 1 was last read in block cb - 1, which every wave left before B0; a wave's own pieces of W(cb) are retired by
+// its vmcnt(0) in front of B0 and everybody's are visible behind it.  LDS: 2 x 24 576 B of weights + 3 X planes (at most 19 584 B)
+// = 68 736 B at most: two workgroups per CU.  Tiles, wave layout and accumulation order per output element (cin block, product,
+// tap, k) are conv3d_zpair's, so HALF = 0 and 1 give identical bits.
+template <int HALF, int TW>
+__global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
+  using G = ZPGeo<HALF, TW>;
+  constexpr int NC = HALF ? 1 : 2;
+  constexpr int WSLOT = 12 * 512;                                // floats of one (phase, cout tile, cin block)
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* lw = lds;                                               // [2][12][512]
+  float* lx = lds + 2 * WSLOT;                                   // [3][XV][8]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+
+  const int S = a.S;                                             // the LOW-resolution plane; the output plane is 2 S
+  const int tiles_c = S / TW, tiles_r = S / G::TR;
+  const int tiles = tiles_c * tiles_r;
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int nt = bid % a.ntile;
+  int mt_ = bid / a.ntile;
+  const int py = (mt_ >> 1) & 1, px = mt_ & 1;                   // the four phases of a tile are neighbours in the grid
+  mt_ >>= 2;
+  const int pg = mt_ / tiles;
+  mt_ -= pg * tiles;
+  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+
+  long xoff[G::PX];
+#pragma unroll
+  for (int k = 0; k < G::PX; ++k) {
+    const int i = tid + k * 256;
+    long off = -1;
+    if (i < G::XPIECES) {
+      const int half = i & 1;
+      int v = i >> 1;
+      const int hc = v % G::HC; v /= G::HC;
+      const int hr = v % G::HR;
+      const int ps = v / G::HR;
+      const int n = pg * G::NPB + ps;
+      const int y = tr * G::TR + hr - 1, x = tc * TW + hc - 1;
+      if (n < a.N && y >= 0 && y < S && x >= 0 && x < S) off = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
+    }
+    xoff[k] = off;
+  }
+  const long zplane = (long)S * S * 8;
+
+  const int vt = HALF ? (wv & 1) : wv;
+  const int ct0 = HALF ? (wv >> 1) : 0;
+  int xb, on[1], ooff0[1], ooff1[1];
+  {
+    const int v = vt * 32 + i32;
+    const int ps = v / (G::TR * TW);
+    const int rem = v - ps * (G::TR * TW);
+    const int r = rem / TW, c = rem - r * TW;
+    xb = ((ps * G::HR + r + py) * G::HC + c + px) * 8 + 4 * h;   // the phase's window starts at (y + py - 1, x + px - 1)
+    const int n = pg * G::NPB + ps;
+    on[0] = n;
+    const int y = tr * G::TR + r, x = tc * TW + c;
+    if (n < a.N) { ooff0[0] = ((2 * y + py) * 2 * S + 2 * x + px) * 8; ooff1[0] = ooff0[0] + 4 * S * S * 8; }
+    else { ooff0[0] = -1; ooff1[0] = -1; }
+  }
+  const int wb = ct0 * 256 + i32 * 8 + 4 * h;
+
+  f32x16 acc[3][NC];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int ct = 0; ct < NC; ++ct)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.f;
+
+  const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
+  const unsigned long wbase = (unsigned long)(a.w + ((long)(py * 2 + px) * a.ntile + nt) * a.Cbi * WSLOT);
+  const rsrc_words wrs = {(int)(unsigned)wbase, (int)((wbase >> 32) & 0xffff), a.Cbi * WSLOT * 4, 0x00020000};
+  const int wvo = lane * 16;
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);
+  // piece k (0..5) of this wave: 256 floats at j = 4 k + wave of the block's 24
+  auto issue_piece = [&](int cb, int k) __attribute__((always_inline)) {
+    const int j = k * 4 + wvu;
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(lw_lds + (unsigned)((cb & 1) * WSLOT + j * 256) * 4u), "v"(wvo), "s"(wrs), "s"((cb * WSLOT + j * 256) * 4)
+                 : "memory");
+  };
+
+  f32x4 xr[2][G::PX];
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  auto load_x = [&](int cb) {
+    const float* xp = a.x + (long)cb * a.x_plane;
+#pragma unroll
+    for (int k = 0; k < G::PX; ++k) {
+      xr[0][k] = xoff[k] >= 0 ? *(const f32x4*)(xp + xoff[k]) : zero4;
+      xr[1][k] = xoff[k] >= 0 ? *(const f32x4*)(xp + xoff[k] + zplane) : zero4;
+    }
+  };
+
+  load_x(0);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) issue_piece(0, k);
+  auto stage = [&](int cb, auto more_c) __attribute__((always_inline)) {
+    constexpr bool more = decltype(more_c)::value;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // X(cb) in registers; this wave's pieces of W(cb) landed
+    __builtin_amdgcn_s_barrier();                                // B0: every wave is through block cb - 1
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < G::PX; ++k)
+      if (tid + k * 256 < G::XPIECES) {
+        float* d = lx + (tid + k * 256) * 4;
+        *(f32x4*)(d) = xr[0][k] + xr[1][k];
+        *(f32x4*)(d + G::XV * 8) = xr[1][k];
+        *(f32x4*)(d + 2 * G::XV * 8) = xr[0][k];
+      }
+    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0) only
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                // B1
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) load_x(cb + 1);
+    const float* lwc = lw + (cb & 1) * WSLOT;
+
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+      for (int ky = 0; ky < 2; ++ky) {
+#pragma unroll
+        for (int kx = 0; kx < 2; ++kx) {
+          const int tap = p * 4 + ky * 2 + kx;
+          f32x4 wf[NC];
+#pragma unroll
+          for (int ct = 0; ct < NC; ++ct) wf[ct] = *(const f32x4*)(lwc + tap * 512 + ct * 256 + wb);
+          const f32x4 xf = *(const f32x4*)(lx + p * G::XV * 8 + (ky * G::HC + kx) * 8 + xb);
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+            for (int ct = 0; ct < NC; ++ct)
+              acc[p][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[ct][kk], xf[kk], acc[p][ct], 0, 0, 0);
+          if (more && tap < 6) issue_piece(cb + 1, tap);         // one piece of W(cb + 1) behind each of the first six taps
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+  for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
+  stage(a.Cbi - 1, std::false_type{});
+  f32x16 o[NC][1];
+  const int nte = HALF ? 2 * nt + ct0 : nt;
+#pragma unroll
+  for (int ct = 0; ct < NC; ++ct) o[ct][0] = acc[0][ct] + acc[1][ct];
+  conv_epilogue<1, NC>(a, o, nte, h, on, ooff0, 0);
+#pragma unroll
+  for (int ct = 0; ct < NC; ++ct) o[ct][0] = acc[0][ct] + acc[2][ct];
+  conv_epilogue<1, NC>(a, o, nte, h, on, ooff1, 0);
 }
 
 // ---- 1x1x1 conv / Linear over voxels (flat voxel tiles, KC channel blocks per stage) ----
@@ -597,6 +773,36 @@ void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const in
   free(weff);
 }
 
+// Pair-form phase weights (conv3d_zpair_ups): the phase sums of conv_pack_ups_host first, then the z difference of THOSE --
+// per phase V1, V2 - V1, V0 - V1 (four window taps each), all in fp32.  out: [phase = 2 py + px][conv_pack_host layout with 12
+// taps (product, wy, wx)]: conv_pack_ups_floats floats, as the z-skip pack.
+void conv_pack_zpair_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
+  int Cin = 0, Cbi = 0;
+  for (int s = 0; s < nseg; ++s) { Cin += seg_c[s]; Cbi += (seg_c[s] + 7) / 8; }
+  static const int G0[2][2][2] = {{{0, 0}, {1, 2}}, {{0, 1}, {2, 2}}};       // [phase bit][window pos] -> tap range [lo, hi]
+  const size_t per = conv_pack_floats(Cout, Cbi, 12);
+  float* weff = (float*)malloc((size_t)Cout * Cin * 12 * sizeof(float));
+  for (int py = 0; py < 2; ++py)
+    for (int px = 0; px < 2; ++px) {
+      for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
+        for (int wy = 0; wy < 2; ++wy)
+          for (int wx = 0; wx < 2; ++wx) {
+            float v[3];
+            for (int kz = 0; kz < 3; ++kz) {
+              float acc = 0.f;
+              for (int ky = G0[py][wy][0]; ky <= G0[py][wy][1]; ++ky)
+                for (int kx = G0[px][wx][0]; kx <= G0[px][wx][1]; ++kx) acc += w[i * 27 + kz * 9 + ky * 3 + kx];
+              v[kz] = acc;
+            }
+            weff[i * 12 + wy * 2 + wx] = v[1];
+            weff[i * 12 + 4 + wy * 2 + wx] = v[2] - v[1];
+            weff[i * 12 + 8 + wy * 2 + wx] = v[0] - v[1];
+          }
+      conv_pack_host(weff, Cout, seg_c, nseg, 12, out + (size_t)(py * 2 + px) * per);
+    }
+  free(weff);
+}
+
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
   int ci0 = 0, cb0 = 0;
   for (int s = 0; s < nseg; ++s) {
@@ -619,6 +825,20 @@ int conv1_form(long vox, int ntile, int tile_variant) {
   return variant == 2 ? 2 : 1;
 }
 
+// The tile of a pair-form launch: 1 = the 64-voxel tile (conv3d_zpair<1, *>), 0 = the 128-voxel one.  ovox = output voxels
+// (N * 2 * S * S); the one statement of the rule, for the launcher and for whoever must know the tile beforehand (the fused
+// mid-section exists in the 128-voxel tile only).  No device call.
+int conv_zpair_half(long ovox, int ntile, int S, int tile_variant) {
+  if (S == 4) return 1;
+  const int variant = tile_variant ? tile_variant : ((ovox / 256) * ntile >= 512 ? 2 : 1);
+  return variant == 2 ? 0 : 1;
+}
+// TM_CONV_FUSE_MID=0 (read once): fp32 ResBlocks keep the separate mid-block norm pass.  A/B timing in separate processes only.
+bool conv_fuse_mid_enabled() {
+  static const bool off = getenv("TM_CONV_FUSE_MID") && atoi(getenv("TM_CONV_FUSE_MID")) == 0;
+  return !off;
+}
+
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   ConvArgs a;
   a.x = L.x.p; a.x_nstride = L.x.nstride; a.x_plane = L.x.plane();
@@ -634,6 +854,17 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   }
   a.N = L.x.N; a.S = L.x.H; a.Z = L.x.Z; a.Cbi = L.w.Cbi; a.ntile = L.w.ntile; a.flags = L.flags;
   if (L.x.Cb != L.w.Cbi || L.x.H != L.x.W) return hipErrorInvalidValue;
+  if (L.fuse_norm) {             // the pair form's 128-voxel tile at 64 couts only; everything else is refused before any device call
+    if (!L.w.zpair || L.w.taps != 27 || L.zmode != ZM_PAD1 || L.x.Z != 2 || L.w.Cout != 64 || L.w.ntile != 1 || L.res || L.gate ||
+        L.flags || !L.norm_w || !L.mod_scale || !L.mod_shift || L.per_image < 1)
+      return hipErrorInvalidValue;
+    if (conv_zpair_half((long)L.x.N * 2 * L.x.H * L.x.H, 1, L.x.H, L.tile_variant)) return hipErrorInvalidValue;
+    if (!L.a2.p || L.a2.Cb != 8 || L.a2.N != L.x.N || L.a2.Z != 2 || L.a2.H != L.x.H || L.a2.W != L.x.H) return hipErrorInvalidValue;
+    if (L.y.Cb != 8 || L.y.Z != 2 || L.y.H != L.x.H) return hipErrorInvalidValue;       // y carries the geometry only
+    a.y = L.a2.p; a.y_nstride = L.a2.nstride; a.y_plane = L.a2.plane();
+    a.norm_w = L.norm_w; a.mod_scale = L.mod_scale; a.mod_shift = L.mod_shift; a.mod_stride = L.mod_stride;
+    a.per_image = L.per_image; a.inv_c = L.inv_c;
+  }
   if (L.y.Cb > L.w.ntile * 8 || L.y.N != L.x.N) return hipErrorInvalidValue;
   const long vox = (long)a.N * a.Z * a.S * a.S;
   if (L.w.taps == 1) {
@@ -702,6 +933,29 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     hipLaunchKernelGGL((conv3d_mfma<2, WM, TW, true>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
   } while (0)
     const int variant = L.tile_variant ? L.tile_variant : ((ovox / 256) * 4 * a.ntile >= 512 ? 2 : 1);
+    if (L.w.zpair) {                           // packed by conv_pack_zpair_ups_host: the pair form, the tile by the same rule
+#define TM_LAUNCHZU(HALF, TW)                                                                    \
+  do {                                                                                          \
+    using G = ZPGeo<HALF, TW>;                                                                  \
+    constexpr int LDSB = (2 * 12 * 512 + 3 * G::XV * 8) * 4;                                    \
+    static DevOnce attr_once;                                                                   \
+    if (attr_once.need()) {                                                                     \
+      hipError_t e = hipFuncSetAttribute((const void*)conv3d_zpair_ups<HALF, TW>,               \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);     \
+      if (e != hipSuccess) return e;                                                            \
+      attr_once.mark();                                                                         \
+    }                                                                                           \
+    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
+    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
+    const long grid = pgs * tiles * 4 * a.ntile;                                                \
+    hipLaunchKernelGGL((conv3d_zpair_ups<HALF, TW>), dim3((unsigned)grid), dim3(256), LDSB, s, a); \
+  } while (0)
+      if (S == 4) TM_LAUNCHZU(1, 4);
+      else if (variant == 2) { if (S >= 32) TM_LAUNCHZU(0, 32); else if (S == 16) TM_LAUNCHZU(0, 16); else TM_LAUNCHZU(0, 8); }
+      else { if (S >= 32) TM_LAUNCHZU(1, 32); else if (S == 16) TM_LAUNCHZU(1, 16); else TM_LAUNCHZU(1, 8); }
+#undef TM_LAUNCHZU
+      return hipGetLastError();
+    }
     if (S < 8) { if (S != 4) return hipErrorInvalidValue; TM_LAUNCHU(1, 4); }
     else if (variant == 2) { if (S >= 32) TM_LAUNCHU(2, 32); else if (S == 16) TM_LAUNCHU(2, 16); else TM_LAUNCHU(2, 8); }
     else { if (S >= 32) TM_LAUNCHU(1, 32); else if (S == 16) TM_LAUNCHU(1, 16); else TM_LAUNCHU(1, 8); }
@@ -709,14 +963,15 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     return hipGetLastError();
   }
   int variant = L.tile_variant ? L.tile_variant : ((ovox / 256) * a.ntile >= 512 ? 2 : 1);
+  if (L.fuse_norm && !L.w.zpair) return hipErrorInvalidValue;
   if (L.w.zpair) {                             // the form is the layer's (fixed at pack time); the tile follows the launch size
     if (L.zmode != ZM_PAD1 || nzi != 2) return hipErrorInvalidValue;
-#define TM_LAUNCHZ(HALF, TW)                                                                     \
+#define TM_LAUNCHZ(HALF, TW, FUSE)                                                                \
   do {                                                                                          \
     using G = ZPGeo<HALF, TW>;                                                                  \
     static DevOnce attr_once;                                                                   \
     if (attr_once.need()) {                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)conv3d_zpair<HALF, TW>,                   \
+      hipError_t e = hipFuncSetAttribute((const void*)conv3d_zpair<HALF, TW, FUSE>,             \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
       if (e != hipSuccess) return e;                                                            \
       attr_once.mark();                                                                         \
@@ -724,11 +979,13 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     const long tiles = (long)(S / TW) * (S / G::TR);                                            \
     const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
     const long grid = pgs * tiles * a.ntile;                                                    \
-    hipLaunchKernelGGL((conv3d_zpair<HALF, TW>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
+    hipLaunchKernelGGL((conv3d_zpair<HALF, TW, FUSE>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
   } while (0)
-    if (S == 4) TM_LAUNCHZ(1, 4);              // 4 patches per workgroup (8 would not leave LDS for two workgroups per CU)
-    else if (variant == 2) { if (S >= 32) TM_LAUNCHZ(0, 32); else if (S == 16) TM_LAUNCHZ(0, 16); else TM_LAUNCHZ(0, 8); }
-    else { if (S >= 32) TM_LAUNCHZ(1, 32); else if (S == 16) TM_LAUNCHZ(1, 16); else TM_LAUNCHZ(1, 8); }
+    if (L.fuse_norm) {                         // the 128-voxel tile: checked above (conv_zpair_half)
+      if (S >= 32) TM_LAUNCHZ(0, 32, true); else if (S == 16) TM_LAUNCHZ(0, 16, true); else TM_LAUNCHZ(0, 8, true);
+    } else if (S == 4) TM_LAUNCHZ(1, 4, false);  // 4 patches per workgroup (8 would not leave LDS for two workgroups per CU)
+    else if (variant == 2) { if (S >= 32) TM_LAUNCHZ(0, 32, false); else if (S == 16) TM_LAUNCHZ(0, 16, false); else TM_LAUNCHZ(0, 8, false); }
+    else { if (S >= 32) TM_LAUNCHZ(1, 32, false); else if (S == 16) TM_LAUNCHZ(1, 16, false); else TM_LAUNCHZ(1, 8, false); }
 #undef TM_LAUNCHZ
     return hipGetLastError();
   }

@@ -51,6 +51,9 @@ struct ResW {
   const uint16_t* c1uh = nullptr;                  // up blocks: in_layers' conv as phase weights of the upsampled-input form
   const uint16_t* skiph = nullptr;
   int emb_off = 0;
+  // fp32: out_layers' norm -> modulate -> SiLU runs in c1's epilogue (conv3d_zpair<0, *, true>) wherever the launch takes the
+  // 128-voxel tile.  Decided once, where c1 is packed: pair form, 64 output channels, TM_CONV_FUSE_MID not 0.
+  bool fuse_mid = false;
 };
 struct AttnW {
   std::string pfx;
@@ -581,12 +584,14 @@ extern "C" int tm_model_finalize(tm_model* m) {
       } else {
         pack_conv(m, pk, fx, r.c1, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg, 27, m->z == 1,
                   m->zpair);
+        r.fuse_mid = r.c1.zpair && r.cout == 64 && conv_fuse_mid_enabled();
         if (r.up && m->z == 2) {                             // phase weights (conv3d_mfma UPS form) + their own copy of the bias
           r.c1u = r.c1;
           r.c1u.taps = 12;
-          r.c1u.zpair = 0;
+          r.c1u.zpair = m->zpair ? 1 : 0;                    // the pair form of the phase weights (conv3d_zpair_ups), under the same switch
           const size_t off = pk.reserve(conv_pack_ups_floats(r.cout, r.cbi));
-          conv_pack_ups_host(P(m, r.pfx + ".in_layers.2.weight").data(), r.cout, r.seg.data(), (int)r.seg.size(), pk.buf.data() + off);
+          (m->zpair ? conv_pack_zpair_ups_host : conv_pack_ups_host)(P(m, r.pfx + ".in_layers.2.weight").data(), r.cout, r.seg.data(),
+                                                                    (int)r.seg.size(), pk.buf.data() + off);
           fx.push_back({&r.c1u.w, off});
           const size_t boff = pk.reserve((size_t)r.c1u.ntile * 64);
           const std::vector<float>& b = P(m, r.pfx + ".in_layers.2.bias");
@@ -768,13 +773,19 @@ static void dump_tv(Ctx& cx, const std::string& name, const TV& t_in) {
   if (f32copy) (void)hipFree(f32copy);
 }
 
+// fuse_rw (with y = the second conv's input A2): the fused mid-section of ResBlock *fuse_rw in this conv's epilogue
 static void run_conv(Ctx& cx, const TV& x, const ConvW& w, TV y, const TV* res, const TV* gate, int flags,
-                     int cin_real = 0, int zmode = ZM_PAD1, bool gate_half = false, bool res_half = false) {
+                     int cin_real = 0, int zmode = ZM_PAD1, bool gate_half = false, bool res_half = false,
+                     const ResW* fuse_rw = nullptr, int per_image = 1) {
   if (cx.dry) return;
   ConvLaunch L;
   L.x = x; L.w = w; L.y = y; L.res = res; L.gate = gate; L.flags = flags; L.zmode = zmode; L.gate_half = gate_half ? 1 : 0;
   L.res_half = res_half ? 1 : 0;
   tm_model* m = cx.m;
+  if (fuse_rw) {
+    L.fuse_norm = 1; L.a2 = y; L.norm_w = fuse_rw->n2; L.inv_c = 1.0f / (float)fuse_rw->cout; L.per_image = per_image;
+    L.mod_scale = cx.ss + fuse_rw->emb_off; L.mod_shift = cx.ss + fuse_rw->emb_off + fuse_rw->cout; L.mod_stride = m->emb_tot;
+  }
   const bool prof = m->prof_on && (w.taps == 27 || (m->z == 1 && w.taps == 9)) && zmode == ZM_PAD1;
   if (prof) {
     if (m->prof_used == m->prof_ev.size()) {
@@ -975,7 +986,8 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
   if (mode == RS_UP2 && w.c1u.w && !no_ups && src.size() == 1 && !src[0].collage && !w.has_skip && !(S_out & (S_out - 1))) {
     // ResBlock(up=True) (MBAblocks.py:254-261,297): h = Upsample(x) feeds in_layers, x = Upsample(x) is the residual.  Nothing
     // is upsampled here: norm and SiLU act per voxel, so they run on the low-resolution x (a quarter of the bytes); the first
-    // conv is the upsampled-input form of conv3d_mfma (per-phase 2 x 2 in-plane weights, 8 instead of 18 taps); the second
+    // conv is the upsampled-input form (per-phase 2 x 2 in-plane weights: conv3d_zpair_ups, 12 tap-products per plane pair, or
+    // with TM_CONV_ZPAIR=0 the z-skip form of conv3d_mfma, 8 instead of 18 taps per plane); the second
     // conv's epilogue reads the residual at (z, y >> 1, x >> 1) of x itself.
     const int S_in = S_out / 2;
     TV A = cx.tensor(N, w.cbi * 8, Z, S_in);
@@ -1024,9 +1036,16 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
     cx.check(launch_prep(P, cx.s));
   }
   A2 = cx.tensor(N, w.cout, Z, S_out);
-  H1 = cx.tensor(N, w.cout, Z, S_out);
-  run_conv(cx, A, w.c1, H1, nullptr, nullptr, 0, w.cin);
-  if (!cx.dry) {
+  // 64 output channels in the pair form's 128-voxel tile: a wave holds every channel of its voxels, so out_layers' norm ->
+  // modulate -> SiLU runs in c1's epilogue and H1 is never written (nor allocated: the dry pass takes the same branch)
+  const bool fuse_mid = w.fuse_mid && Z == 2 && !conv_zpair_half((long)N * Z * S_out * S_out, 1, S_out, 0);
+  if (fuse_mid) {
+    run_conv(cx, A, w.c1, A2, nullptr, nullptr, 0, w.cin, ZM_PAD1, false, false, &w, per_image);
+  } else {
+    H1 = cx.tensor(N, w.cout, Z, S_out);
+    run_conv(cx, A, w.c1, H1, nullptr, nullptr, 0, w.cin);
+  }
+  if (!cx.dry && !fuse_mid) {
     PrepLaunch P;
     P.nsrc = 1;
     P.src[0].p = H1.p; P.src[0].nstride = H1.nstride; P.src[0].Cb = H1.Cb;

@@ -198,6 +198,83 @@ extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const 
   return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_mfma");
 }
 
+// The fp32 pair-form conv with the ResBlock mid-section in its epilogue (conv3d_zpair<0, *, true>), alone.  The forms the kernel
+// does not take are refused here, before any device call, with the launcher's own rule for the tile (conv_zpair_half).
+extern "C" int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
+                                          const void* scale_host, const void* shift_host, const void* res_cb8, void* a2_out,
+                                          void* h1_out, void* a2_sep_out, int N, int Cin, int Cout, int Z, int S, int per_image,
+                                          int tile_variant, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || !norm_w_host || !scale_host || !shift_host || !a2_out) return fail(TM_ERR_ARG, "null argument");
+  if (N < 1 || Cin < 1 || per_image < 1) return fail(TM_ERR_ARG, "N, Cin, per_image must be positive");
+  if (Z != 2) return fail(TM_ERR_ARG, "the pair form exists at Z == 2 only (got Z = %d)", Z);
+  if (Cout != 64) return fail(TM_ERR_ARG, "the fused mid-section needs Cout == 64: one wave holds every channel (got %d)", Cout);
+  if (res_cb8) return fail(TM_ERR_ARG, "the fused mid-section takes no residual");
+  if (S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return fail(TM_ERR_ARG, "S must be 8, 16, 32, 64 or 128 (got %d)", S);
+  if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
+  if (conv_zpair_half((long)N * Z * S * S, 1, S, tile_variant))
+    return fail(TM_ERR_ARG, "the fused mid-section exists in the 128-voxel tile only; this launch takes the 64-voxel one");
+  if (a2_sep_out && !h1_out) return fail(TM_ERR_ARG, "a2_sep_out needs h1_out");
+  ConvW cw = conv_form(Cin, Cout, 3, ZM_PAD1, Z);
+  if (!cw.zpair) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
+  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, 27));
+  conv_pack_zpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
+  DevTmp tmp;
+  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  const int nimg = (N + per_image - 1) / per_image;
+  const float* nw = tmp.alloc((size_t)Cout, (const float*)norm_w_host);
+  const float* sc = tmp.alloc((size_t)nimg * Cout, (const float*)scale_host);
+  const float* sh = tmp.alloc((size_t)nimg * Cout, (const float*)shift_host);
+  if (tmp.err) return tmp.report();
+  hipStream_t st = (hipStream_t)stream;
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.w = cw;
+  L.tile_variant = tile_variant;
+  L.y = view_cb8(a2_out, N, Cout, Z, S, S);
+  L.fuse_norm = 1; L.a2 = L.y; L.norm_w = nw; L.mod_scale = sc; L.mod_shift = sh; L.mod_stride = Cout; L.per_image = per_image;
+  L.inv_c = 1.0f / (float)Cout;
+  hipError_t e = launch_conv_mfma(L, st);
+  if (e == hipSuccess && h1_out) {                      // the same conv, plain epilogue, then (a2_sep_out) the separate pass on it
+    ConvLaunch U = L;
+    U.fuse_norm = 0; U.y = view_cb8(h1_out, N, Cout, Z, S, S);
+    e = launch_conv_mfma(U, st);
+    if (e == hipSuccess && a2_sep_out) {
+      PrepLaunch P;
+      prep_single_src(P, U.y);
+      P.N = N; P.Z = Z; P.S = S; P.norm_w = nw; P.inv_c = L.inv_c; P.act = 1; P.per_image = per_image;
+      P.mod = MOD_IMAGE; P.mod_scale = sc; P.mod_shift = sh; P.mod_stride = Cout;
+      P.out = (float*)a2_sep_out; P.out_nstride = U.y.nstride;
+      e = launch_prep(P, st);
+    }
+  }
+  return finish(st, e, "conv_zpair_fused (fp32)");
+}
+
+// The pair form of the upsampled-input conv (conv3d_zpair_ups), alone: y [N][ceil(Cout/8)][2][2S][2S][8] = conv3d(pad 1) of the
+// nearest-x2 upsampled x, computed on x.  tm_op_conv_mfma with zmode 3 stays the z-skip form of the same conv.
+extern "C" int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                       int Cout, int Z, int S, int tile_variant, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || !y_cb8) return fail(TM_ERR_ARG, "null argument");
+  if (N < 1 || Cin < 1 || Cout < 1) return fail(TM_ERR_ARG, "N, Cin, Cout must be positive");
+  if (Z != 2) return fail(TM_ERR_ARG, "the pair form exists at Z == 2 only (got Z = %d)", Z);
+  if (S != 4 && S != 8 && S != 16 && S != 32 && S != 64) return fail(TM_ERR_ARG, "S must be 4, 8, 16, 32 or 64 (got %d)", S);
+  if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
+  ConvW cw = conv_form(Cin, Cout, 3, ZM_UPS, Z);
+  cw.zpair = 1;
+  std::vector<float> pk(conv_pack_ups_floats(Cout, cw.Cbi));
+  conv_pack_zpair_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
+  DevTmp tmp;
+  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, Z, 2 * S, 2 * S);
+  L.tile_variant = tile_variant;
+  L.zmode = ZM_UPS;
+  return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_ups_pair (fp32)");
+}
+
 // power of two >= 2: what a half-resolution gate needs of S (read at (z, y >> 1, x >> 1))
 static bool half_gate_ok(int S) { return S >= 2 && (S & (S - 1)) == 0; }
 
