@@ -318,6 +318,19 @@ int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host, const void
 int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                             int Cout, int Z, int S, int tile_variant, void* stream);
 
+/* The fp32 3x3x3 pad-1 conv at Z == 2 in its x-pair form (conv3d_xpair: the pair form in z composed with Winograd F(2,3) along
+ * x, 36 tap-products per four outputs).  x CB8 DEVICE [N][ceil(Cin/8)][2][S][S][8]; w [Cout][Cin][27], bias [Cout] HOST; y CB8
+ * DEVICE; res_cb8 (nullable): y's geometry, or S / 2 in-plane with res_half != 0 (read at (z, y >> 1, x >> 1)).  tile_variant:
+ * 0 = by launch size, 1 | 2 = the 64- | 128-voxel tile.  Returns the tile launched (1 | 2) on success.  TM_ERR_ARG before any
+ * device call: Z != 2, S outside {8, .., 128}, the form switched off (TM_CONV_XPAIR=0).  tm_op_conv_mfma with zmode 0 stays
+ * the pair form of the same conv. */
+int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                         int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream);
+/* Timing hook (tools/bench_conv_xpair.py): that conv packed once for `form` (0 = the pair form, 1 = the x-pair form), then
+ * `iters` launches, each between two events of its own: ms_out[i] (HOST) = the time of launch i. */
+int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                             int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream);
+
 /* The fp32 1x1x1 conv / Linear (conv1_mfma) in every form the model launches: y = res + gate_up * act(W x + b).
  * x_cb8: DEVICE [N][x_cbtot][Z][S][S][8]; the conv reads the channel-block slice [x_cb0, x_cb0 + ceil(Cin/8)) of it in place
  * (the patch stride stays that of the wide tensor).  w_host [Cout][Cin], bias_host [Cout]: HOST.  y_cb8: [N][ceil(Cout/8)][Z][S][S][8].

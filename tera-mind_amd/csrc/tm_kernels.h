@@ -34,6 +34,8 @@ struct ConvW {
   int Cout = 0, Cbi = 0, taps = 0, ntile = 0;
   int zpair = 0;                // taps == 27 packed by conv_pack_zpair_host: ZM_PAD1 at Z == 2 runs the pair form (conv3d_zpair);
                                 // taps == 12 packed by conv_pack_zpair_ups_host: ZM_UPS runs conv3d_zpair_ups
+  int xpair = 0;                // taps == 36 packed by conv_pack_xpair_host: ZM_PAD1 at Z == 2, S >= 8 runs conv3d_xpair (the pair
+                                // form in z with Winograd F(2,3) along x); every other launch of such weights is refused
 };
 size_t conv_pack_floats(int Cout, int Cbi, int taps);
 // host-side packing; seg_c[i] = real channels of concat segment i (each padded to x8).
@@ -43,6 +45,9 @@ size_t conv_pack_ups_floats(int Cout, int Cbi);          // phase weights of the
 void conv_pack_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
 bool conv_zpair_enabled();                               // false with TM_CONV_ZPAIR=0 (A/B timing): keep the 18-tap z-skip form
 void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
+bool conv_xpair_enabled();                               // false with TM_CONV_XPAIR=0 (A/B timing): keep the pair form everywhere
+// ConvW.xpair, taps == 36: per (product, ky) the four F(2,3) filter transforms of the pair-form weights; 4/3 of the 27-tap pack
+void conv_pack_xpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
 // ZM_UPS in the pair form (conv3d_zpair_ups; ConvW.zpair with taps == 12): the z difference of the phase weights; the same size
 void conv_pack_zpair_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out);  // per-cin vector -> virtual order
@@ -73,7 +78,8 @@ struct ConvLaunch {
 };
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
 int conv_zpair_half(long ovox, int ntile, int S, int tile_variant);   // 1: a pair-form launch takes the 64-voxel tile; no device call
-bool conv_fuse_mid_enabled();                            // false with TM_CONV_FUSE_MID=0 (A/B timing): separate mid-block norm pass
+int conv_xpair_half(long ovox, int ntile, int tile_variant);          // the same rule for an x-pair launch (conv3d_xpair); no device call
+bool conv_fuse_mid_enabled();                           // false with TM_CONV_FUSE_MID=0 (A/B timing): separate mid-block norm pass
 // which conv1_mfma instantiation a taps == 1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
 int conv1_form(long vox, int ntile, int tile_variant);
 

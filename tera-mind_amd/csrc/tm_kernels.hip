@@ -585,6 +585,279 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
   conv_epilogue<1, NC>(a, o, nte, h, on, ooff1, 0);
 }
 
+// ---- x-pair form of the 3x3x3 pad-1 conv at Z == 2 (fp32): the pair form in z composed with Winograd F(2,3) along x ----
+// The 1-D identity F(2,3) gives two neighbouring outputs of a 3-tap filter g with four products instead of six: with d0..d3 the
+// inputs at columns 2j - 1 .. 2j + 2,
+//   T0 = d0 - d2   T1 = d1 + d2   T2 = d2 - d1   T3 = d1 - d3          (formed while staging)
+//   U0 = g0   U1 = (g0 + g1 + g2) / 2   U2 = (g0 - g1 + g2) / 2   U3 = g2   (formed at pack time, conv_pack_xpair_host)
+//   out[2j] = U0 T0 + U1 T1 + U2 T2        out[2j + 1] = U1 T1 - U2 T2 - U3 T3.
+// It is linear in the weights, so it applies to each of the three z products of the pair form (V = W1, W2 - W1, W0 - W1 on
+// Xs = X0 + X1, X1, X0): per (product, ky) four transform positions per x-pair replace three taps per voxel, 36 tap-products
+// per four outputs (9 per output against the pair form's 13.5).  A_q(p) = sum over cin, ky of U_q(p)[ky] T_q(p)[y + ky - 1][j]
+// is accumulated on the MFMA exactly as a tap is; the epilogue forms, per product, even = (A0 + A1) + A2 and odd = (A1 - A2) -
+// A3, then Y0 = P(1) + P(2), Y1 = P(1) + P(3) per column parity and runs the common epilogue on each (plane, parity).
+// One workgroup (256 threads) owns MP x-pairs (2 MP in-plane voxels), both output planes and 64 couts.  HALF = 0: 64 pairs, a wave
+// owns 32 x-pairs x 32 couts with all four q (3 x 4 accumulators; waves 0/1 and 2/3 are the two pair tiles, wave & 1 the cout
+// half).  HALF = 1 (small launches, which do not fill the chip: the time is a wave's own work): 32 pairs, and the four waves
+// split a 32-pair x 32-cout tile by q -- waves 0/1 accumulate A0, A1, waves 2/3 A2, A3 (3 x 2 accumulators, half the MFMAs per
+// wave); after the K loop the q halves swap the one tile per product the other needs through LDS (A1 one way, A2 the other),
+// then waves 0/1 finish the even columns and waves 2/3 the odd ones.  Every output sees one order of sums in both -- cin
+// block, product, ky, k inside an accumulator, then the fixed output transform -- so the two tiles give identical bits.
+// LDS: per product four q-planes of XP = NPB x HR x TW/2 pair positions (no x halo: the transform consumed it), fragment
+// addresses contiguous in the pair index; weights are a ring of two PRODUCT slots (12 taps x 512 floats, the (ky, q) of one
+// product) filled by LDS-DMA as in conv3d_zpair_ups: product n = 3 cb + p reads slot n & 1, the pieces of product n + 1 go out
+// behind its first taps into the slot every wave left at the barrier in front of product n, and a wave retires its own with the
+// vmcnt(0) in front of the next product's barrier.  A cin block costs four barriers:
+//   vmcnt(0) | B0 | T(cb) -> LDS | B1 | P1, X(cb + 1) -> registers | vmcnt(0) | B2 | P2 | vmcnt(0) | B3 | P3
+// HALF = 0: 2 x 24 576 B + 3 x 4 x 80 x 32 B = 79 872 B: two workgroups per CU.
+template <int HALF, int TW>
+struct XPGeo {
+  static constexpr int NW = 4;                                   // waves per workgroup
+  static constexpr int NQ = HALF ? 2 : 4;                        // transform positions q a wave accumulates
+  static constexpr int MP = HALF ? 32 : 64;                      // x-pairs per workgroup
+  static constexpr int PWD = TW / 2;                             // pairs per tile row
+  static constexpr int TR = (MP / PWD < TW) ? (MP / PWD) : TW;   // tile rows
+  static constexpr int NPB = MP / (TR * PWD);                    // patches per workgroup
+  static constexpr int HR = TR + 2;
+  static constexpr int XP = NPB * HR * PWD;                      // pair positions of one q-plane (y halo only)
+  static constexpr int XITEMS = XP * 2;                          // staging items: (position, half block), one per thread
+  static constexpr int WSLOT = 12 * 512;                         // floats of one product of a (cout tile, cin block)
+  static constexpr int KP = 24 / NW;                             // LDS-DMA pieces (256 floats) of a slot per wave
+  static constexpr int LDS_BYTES = (2 * WSLOT + 12 * XP * 8) * 4;
+};
+
+template <int HALF, int TW>
+__global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
+  using G = XPGeo<HALF, TW>;
+  static_assert(G::XITEMS <= 64 * G::NW, "one staging item per thread");
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* lw = lds;                                               // [2][12][512]: the LDS-DMA destinations stay below 64 KiB
+  // the X planes [3 products][4 q][XP][8] follow at float 2 * WSLOT, up to byte 79 872 (addressed through xw / xb below)
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+
+  const int S = a.S;
+  const int tiles_c = S / TW, tiles_r = S / G::TR;
+  const int tiles = tiles_c * tiles_r;
+  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
+  const int nt = bid % a.ntile;
+  int mt_ = bid / a.ntile;
+  const int pg = mt_ / tiles;
+  mt_ -= pg * tiles;
+  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+
+  // ---- staging descriptor: this thread's (row, x-pair, half block); xoff addresses column 2j of plane 0 ----
+  long xoff = -1;
+  bool okl = false, okr = false;                                 // columns 2j - 1 and 2j + 2 lie inside the plane
+  if (tid < G::XITEMS) {
+    const int half = tid & 1;
+    int v = tid >> 1;
+    const int j = v % G::PWD; v /= G::PWD;
+    const int hr = v % G::HR;
+    const int ps = v / G::HR;
+    const int n = pg * G::NPB + ps;
+    const int y = tr * G::TR + hr - 1, x = tc * TW + 2 * j;
+    if (n < a.N && y >= 0 && y < S) {
+      xoff = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
+      okl = x > 0;
+      okr = x + 2 < S;
+    }
+  }
+  const long zplane = (long)S * S * 8;
+  int xw = 2 * G::WSLOT + tid * 4;                               // this item's slot of a q-plane (base hidden as xb's below)
+  asm volatile("" : "+v"(xw));
+
+  // ---- per-lane fragment addresses ----
+  const int pt = HALF ? 0 : (wv >> 1);                           // 32-pair tile of this wave
+  const int ch = wv & 1;                                         // its 32-cout half
+  const int q0 = HALF ? (wv >> 1) * 2 : 0;                       // its first q
+  int xb, on[1], ooff0;                                          // ooff0: the even column of plane 0 (or -1)
+  {
+    const int v = pt * 32 + i32;
+    const int ps = v / (G::TR * G::PWD);
+    const int rem = v - ps * (G::TR * G::PWD);
+    const int r = rem / G::PWD, j = rem - r * G::PWD;
+    // lx's offset is part of the lane's base and hidden from the compiler, so that the (product, q, ky) of a fragment is a
+    // 16-bit ds_read offset of ONE register (folded into the constant it would pass 64 KiB and take a register per plane)
+    xb = 2 * G::WSLOT + q0 * G::XP * 8 + ((ps * G::HR + r) * G::PWD + j) * 8 + 4 * h;
+    asm volatile("" : "+v"(xb));
+    const int n = pg * G::NPB + ps;
+    on[0] = n;
+    const int y = tr * G::TR + r, x = tc * TW + 2 * j;
+    ooff0 = n < a.N ? (y * S + x) * 8 : -1;
+  }
+  const int wb = q0 * 512 + ch * 256 + i32 * 8 + 4 * h;
+
+  f32x16 acc[3][G::NQ];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int q = 0; q < G::NQ; ++q)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[p][q][r] = 0.f;
+
+  const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
+  const unsigned long wbase = (unsigned long)(a.w + (long)nt * a.Cbi * 3 * G::WSLOT);
+  const rsrc_words wrs = {__builtin_amdgcn_readfirstlane((int)(unsigned)wbase),
+                          __builtin_amdgcn_readfirstlane((int)((wbase >> 32) & 0xffff)), a.Cbi * 3 * G::WSLOT * 4, 0x00020000};
+  const int wvo = lane * 16;
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);
+  // piece k (0 .. KP - 1) of this wave of product n: 256 floats at j = NW k + wave of the product's 24
+  auto issue_piece = [&](int n, int k) __attribute__((always_inline)) {
+    const int j = k * G::NW + wvu;
+    unsigned keep;
+    // (s_nop 4: the source offset may come straight from the SALU, five wait states ahead of a VMEM read of it)
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(lw_lds + (unsigned)((n & 1) * G::WSLOT + j * 256) * 4u), "v"(wvo), "s"(wrs), "s"((n * G::WSLOT + j * 256) * 4)
+                 : "memory");
+  };
+
+  f32x4 xr[2][4];                                                // [plane][column 2j - 1 .. 2j + 2]
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  auto load_x = [&](int cb) {
+    const float* xp = a.x + (long)cb * a.x_plane;
+#pragma unroll
+    for (int z = 0; z < 2; ++z) {
+      const float* b = xp + xoff + z * zplane;
+      xr[z][0] = okl ? *(const f32x4*)(b - 8) : zero4;
+      xr[z][1] = xoff >= 0 ? *(const f32x4*)(b) : zero4;
+      xr[z][2] = xoff >= 0 ? *(const f32x4*)(b + 8) : zero4;
+      xr[z][3] = okr ? *(const f32x4*)(b + 16) : zero4;
+    }
+  };
+  // the four transform planes of one product from its four columns
+  auto put_t = [&](int p, const f32x4& d0, const f32x4& d1, const f32x4& d2, const f32x4& d3) __attribute__((always_inline)) {
+    float* d = lds + xw + p * 4 * G::XP * 8;
+    *(f32x4*)(d) = d0 - d2;
+    *(f32x4*)(d + G::XP * 8) = d1 + d2;
+    *(f32x4*)(d + 2 * G::XP * 8) = d2 - d1;
+    *(f32x4*)(d + 3 * G::XP * 8) = d1 - d3;
+  };
+
+  load_x(0);
+#pragma unroll
+  for (int k = 0; k < G::KP; ++k) issue_piece(0, k);
+  // one cin block; MORE = another block follows (the last block is its own instantiation: no branch around a piece)
+  auto stage = [&](int cb, auto more_c) __attribute__((always_inline)) {
+    constexpr bool more = decltype(more_c)::value;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // X(cb) in registers; this wave's pieces of product 3 cb landed
+    __builtin_amdgcn_s_barrier();                                // B0: every wave is through block cb - 1: lx and the other slot are free
+    asm volatile("" ::: "memory");
+    if (tid < G::XITEMS) {
+      put_t(2, xr[0][0], xr[0][1], xr[0][2], xr[0][3]);         // X0 first: its registers then take X0 + X1 (no temporaries)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xr[0][c] = xr[0][c] + xr[1][c];
+      put_t(0, xr[0][0], xr[0][1], xr[0][2], xr[0][3]);
+      put_t(1, xr[1][0], xr[1][1], xr[1][2], xr[1][3]);
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0) only
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                // B1
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) load_x(cb + 1);
+
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      const int n = cb * 3 + p;
+      if (p > 0) {                                               // B2, B3: this wave's pieces of product n landed, everybody's are visible
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // behind the barrier, and the slot of product n - 1 is free
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const float* lwc = lw + (n & 1) * G::WSLOT + wb;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int q = 0; q < G::NQ; ++q) {                        // (q counts from the wave's q0: in both bases)
+          const int tap = ky * 4 + q;
+          const f32x4 wf = *(const f32x4*)(lwc + tap * 512);
+          const f32x4 xf = *(const f32x4*)(lds + xb + ((p * 4 + q) * G::XP + ky * G::PWD) * 8);
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[kk], xf[kk], acc[p][q], 0, 0, 0);
+          if (ky * G::NQ + q < G::KP && (p < 2 || more)) issue_piece(n + 1, ky * G::NQ + q);   // a piece of product n + 1 behind each of the first six taps
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+  for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
+  stage(a.Cbi - 1, std::false_type{});
+  // output transform per product, then the plane sums: one epilogue per (plane, column parity) with that parity's offsets
+  // (in place: tile 0 of a product becomes its even column, tile 1 its odd one, so the other two die before the first store)
+  const int nte = 2 * nt + ch;                                   // conv_epilogue counts cout blocks in units of its own tile
+  if constexpr (HALF) {
+    // the q halves swap through LDS (free behind the barrier: nothing of the K loop is read or in flight any more): waves 0/1
+    // hand A1(p) over and take A2(p), waves 2/3 the reverse; a tile is [16 registers / 4][64 lanes] float4
+    const int qh = __builtin_amdgcn_readfirstlane(wv >> 1);
+    __syncthreads();
+    auto hand_over = [&](const f32x16& t, int p) __attribute__((always_inline)) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 v = {t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]};
+        *(f32x4*)(lds + ((wv * 3 + p) * 4 + i) * 256 + lane * 4) = v;
+      }
+    };
+    if (qh) {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) hand_over(acc[p][0], p);
+    } else {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) hand_over(acc[p][1], p);
+    }
+    __syncthreads();
+    f32x16 got[3];
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const f32x4 v = *(const f32x4*)(lds + (((wv ^ 2) * 3 + p) * 4 + i) * 256 + lane * 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) got[p][4 * i + e] = v[e];
+      }
+    // waves 0/1: even = (A0 + A1) + A2; waves 2/3 (holding A2, A3): odd = (A1 - A2) - A3
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      acc[p][0] = qh ? (got[p] - acc[p][0]) - acc[p][1] : (acc[p][0] + acc[p][1]) + got[p];
+      asm volatile("" : "+v"(acc[p][0]));
+    }
+#pragma unroll
+    for (int z = 0; z < 2; ++z) {
+      f32x16 o[1][1];
+      o[0][0] = acc[0][0] + acc[1 + z][0];
+      asm volatile("" : "+v"(o[0][0]));
+      const int ooff[1] = {ooff0 >= 0 ? ooff0 + (z * S * S + qh) * 8 : -1};
+      __builtin_amdgcn_sched_barrier(0);
+      conv_epilogue<1, 1>(a, o, nte, h, on, ooff, 2 * S);
+    }
+  } else {
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      const f32x16 ev = (acc[p][0] + acc[p][1]) + acc[p][2];
+      acc[p][1] = (acc[p][1] - acc[p][2]) - acc[p][3];
+      acc[p][0] = ev;
+      asm volatile("" : "+v"(acc[p][0]), "+v"(acc[p][1]));       // formed HERE, not sunk into the guarded stores below
+    }
+#pragma unroll
+    for (int z = 0; z < 2; ++z)
+#pragma unroll
+      for (int par = 0; par < 2; ++par) {
+        f32x16 o[1][1];
+        o[0][0] = acc[0][par] + acc[1 + z][par];
+        asm volatile("" : "+v"(o[0][0]));
+        const int ooff[1] = {ooff0 >= 0 ? ooff0 + (z * S * S + par) * 8 : -1};
+        __builtin_amdgcn_sched_barrier(0);
+        conv_epilogue<1, 1>(a, o, nte, h, on, ooff, 2 * S);
+      }
+  }
+}
+
 // ---- 1x1x1 conv / Linear over voxels (flat voxel tiles, KC channel blocks per stage) ----
 // Replaces the skip_connection Conv3d(k=1) (model/MBAblocks.py:220-224) and every nn.Linear
 // of AttnBlock / Attention / Mlp applied to '(z h w) c' tokens (model/MBAblocks.py:465,
@@ -773,6 +1046,40 @@ void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const in
   free(weff);
 }
 
+// x-pair weights (conv3d_xpair): the z differences of conv_pack_zpair_host first, then per (product, ky) the F(2,3) filter
+// transform of the three kx taps g0, g1, g2 of THOSE -- U0 = g0, U1 = ((g0 + g1) + g2) * 0.5, U2 = ((g0 - g1) + g2) * 0.5,
+// U3 = g2, all in fp32 -- in the order the kernel consumes them (product, ky, q): 36 taps, 4/3 of the 27-tap pack.
+// TM_CONV_XPAIR=0 (read once, at pack time) keeps the pair form everywhere: A/B timing in separate processes only.
+bool conv_xpair_enabled() {
+  static const bool off = getenv("TM_CONV_XPAIR") && atoi(getenv("TM_CONV_XPAIR")) == 0;
+  return !off;
+}
+void conv_pack_xpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
+  int Cin = 0;
+  for (int s = 0; s < nseg; ++s) Cin += seg_c[s];
+  float* weff = (float*)malloc((size_t)Cout * Cin * 36 * sizeof(float));
+  for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
+    for (int ky = 0; ky < 3; ++ky) {
+      float g[3][3];                                             // [product][kx]
+      for (int kx = 0; kx < 3; ++kx) {
+        const int t = ky * 3 + kx;
+        const float w0 = w[i * 27 + t], w1 = w[i * 27 + 9 + t], w2 = w[i * 27 + 18 + t];
+        g[0][kx] = w1;
+        g[1][kx] = w2 - w1;
+        g[2][kx] = w0 - w1;
+      }
+      for (int p = 0; p < 3; ++p) {
+        float* u = weff + i * 36 + p * 12 + ky * 4;
+        u[0] = g[p][0];
+        u[1] = ((g[p][0] + g[p][1]) + g[p][2]) * 0.5f;
+        u[2] = ((g[p][0] - g[p][1]) + g[p][2]) * 0.5f;
+        u[3] = g[p][2];
+      }
+    }
+  conv_pack_host(weff, Cout, seg_c, nseg, 36, out);
+  free(weff);
+}
+
 // Pair-form phase weights (conv3d_zpair_ups): the phase sums of conv_pack_ups_host first, then the z difference of THOSE --
 // per phase V1, V2 - V1, V0 - V1 (four window taps each), all in fp32.  out: [phase = 2 py + px][conv_pack_host layout with 12
 // taps (product, wy, wx)]: conv_pack_ups_floats floats, as the z-skip pack.
@@ -830,6 +1137,12 @@ int conv1_form(long vox, int ntile, int tile_variant) {
 // mid-section exists in the 128-voxel tile only).  No device call.
 int conv_zpair_half(long ovox, int ntile, int S, int tile_variant) {
   if (S == 4) return 1;
+  const int variant = tile_variant ? tile_variant : ((ovox / 256) * ntile >= 512 ? 2 : 1);
+  return variant == 2 ? 0 : 1;
+}
+// The tile of an x-pair launch by the same launch-size rule: 1 = the 64-voxel tile (conv3d_xpair<1, *>), 0 = the
+// 128-voxel one.  No device call.
+int conv_xpair_half(long ovox, int ntile, int tile_variant) {
   const int variant = tile_variant ? tile_variant : ((ovox / 256) * ntile >= 512 ? 2 : 1);
   return variant == 2 ? 0 : 1;
 }
@@ -891,6 +1204,11 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   if (L.zmode == ZM_PAD1 && L.w.taps == 9) {   // 3x3x3 pad 1 on ONE plane: only the centre z slice meets data (packed as 9 taps)
     if (L.x.Z != 1 || L.y.Z != 1) return hipErrorInvalidValue;
     nzi = 1;
+  } else if (L.zmode == ZM_PAD1 && L.w.xpair) {  // 3x3x3 pad 1 over two planes, packed by conv_pack_xpair_host: conv3d_xpair only
+    if (L.w.taps != 36 || L.x.Z != 2 || L.y.Z != 2 || L.x.H < 8 || (L.flags & EPI_UP2) || L.fuse_norm) return hipErrorInvalidValue;
+    nzi = 2;
+  } else if (L.w.xpair) {
+    return hipErrorInvalidValue;
   } else if (L.zmode == ZM_PAD1) {             // 3x3x3 pad 1
     if (L.w.taps != 27 || L.y.Z != L.x.Z) return hipErrorInvalidValue;
     if (L.x.Z == 2) nzi = 2;                   // z-skip form, or the pair form when the weights were packed for it
@@ -960,6 +1278,27 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     else if (variant == 2) { if (S >= 32) TM_LAUNCHU(2, 32); else if (S == 16) TM_LAUNCHU(2, 16); else TM_LAUNCHU(2, 8); }
     else { if (S >= 32) TM_LAUNCHU(1, 32); else if (S == 16) TM_LAUNCHU(1, 16); else TM_LAUNCHU(1, 8); }
 #undef TM_LAUNCHU
+    return hipGetLastError();
+  }
+  if (L.w.xpair) {                             // the form is the layer's (fixed at pack time); the tile follows the launch size
+#define TM_LAUNCHX(HALF, TW)                                                                     \
+  do {                                                                                          \
+    using G = XPGeo<HALF, TW>;                                                                  \
+    static DevOnce attr_once;                                                                   \
+    if (attr_once.need()) {                                                                     \
+      hipError_t e = hipFuncSetAttribute((const void*)conv3d_xpair<HALF, TW>,                   \
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
+      if (e != hipSuccess) return e;                                                            \
+      attr_once.mark();                                                                         \
+    }                                                                                           \
+    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
+    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
+    const long grid = pgs * tiles * a.ntile;                                                    \
+    hipLaunchKernelGGL((conv3d_xpair<HALF, TW>), dim3((unsigned)grid), dim3(64 * G::NW), G::LDS_BYTES, s, a); \
+  } while (0)
+    if (conv_xpair_half(ovox, a.ntile, L.tile_variant)) { if (S >= 16) TM_LAUNCHX(1, 16); else TM_LAUNCHX(1, 8); }
+    else { if (S >= 16) TM_LAUNCHX(0, 16); else TM_LAUNCHX(0, 8); }
+#undef TM_LAUNCHX
     return hipGetLastError();
   }
   int variant = L.tile_variant ? L.tile_variant : ((ovox / 256) * a.ntile >= 512 ? 2 : 1);

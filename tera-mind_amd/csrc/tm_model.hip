@@ -54,6 +54,9 @@ struct ResW {
   // fp32: out_layers' norm -> modulate -> SiLU runs in c1's epilogue (conv3d_zpair<0, *, true>) wherever the launch takes the
   // 128-voxel tile.  Decided once, where c1 is packed: pair form, 64 output channels, TM_CONV_FUSE_MID not 0.
   bool fuse_mid = false;
+  // a decoder block of the deepest level (its launches are the smallest of the step: the interior patches at patch / 8): its
+  // convs stay on the pair form, whose 64-voxel tile is the faster there (profiles/fp32_xpair.txt).  A role, fixed at pack time.
+  bool dec_deep = false;
 };
 struct AttnW {
   std::string pfx;
@@ -79,6 +82,9 @@ struct tm_model {
   tm_config cfg;
   int z = 0, gn = 0, D = 0, L = 4;
   bool zpair = false;            // fp32, z == 2: the ResBlock 3x3x3 convs are packed for and run in the pair form (conv3d_zpair)
+  // ... and, of those, the ones tm_model_finalize moves on to the x-pair form (conv3d_xpair): every level's plane is at least
+  // 8 x 8 (patch size 64 or 128; a 4 x 4 plane has no x-pair tile), TM_CONV_XPAIR not 0.  Fixed at pack time, never by N.
+  bool xpair = false;
   int rw[4];                          // rna pyramid widths
   std::vector<std::pair<std::string, std::vector<int64_t>>> spec;
   std::map<std::string, HostParam> host;
@@ -109,6 +115,7 @@ struct tm_model {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   size_t prof_used = 0;
   double prof_nominal = 0, prof_bytes = 0;
+  double prof_xpair = 0;              // the part of prof_nominal launched in the x-pair form (18 of the nominal 54 tap-products)
   struct ProfTag { int cin, cout, S, N; double nominal; };
   std::vector<ProfTag> prof_tag;     // per counted launch (TM_PROF_LAYERS)
 };
@@ -252,6 +259,7 @@ static int build_graph(tm_model* m) {
       DecEntry e; e.lvl = lvl;
       spec_res(s, p + ".0", ch + skip + rd, cout, E);
       e.ops.push_back({0, add_res(m, p + ".0", {ch, skip, rd}, cout), RS_SAME});
+      m->res.back().dec_deep = lvl == L - 1;
       ch = cout;
       int nxt = 1;
       if (res == c.attn_res) {
@@ -315,6 +323,7 @@ extern "C" int tm_model_create(const tm_config* cfg, tm_model** out) {
   m->cfg = *cfg;
   m->z = (cfg->rna_slc + 1) / 2;
   m->zpair = m->z == 2 && !is_h16(cfg->dtype) && conv_zpair_enabled();
+  m->xpair = m->zpair && conv_xpair_enabled() && (cfg->patch_size >> 3) >= 8;   // the deepest of the four levels: patch / 8
   m->gn = cfg->patch_size / 16;
   m->D = m->gn * m->gn * cfg->rna_slc;
   m->gene_mfma = m->D == 64 && cfg->rna_num <= 232 && cfg->rna_num != 81;
@@ -373,7 +382,7 @@ static const std::vector<float>& P(tm_model* m, const std::string& k) { return m
 
 static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, const std::string& wkey,
                       const std::string& bkey, int Cout, const std::vector<int>& seg, int taps, bool centre_slice = false,
-                      bool zpair = false) {
+                      bool zpair = false, bool xpair = false) {
   int cbi = 0, cin = 0;
   for (int c : seg) { cbi += (c + 7) / 8; cin += c; }
   // centre_slice: a 3x3x3 pad-1 conv applied to ONE plane (z_size 1, rna_slc 1) only ever multiplies its kz = 1 slice
@@ -389,9 +398,13 @@ static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, 
   }
   cw.Cout = Cout; cw.Cbi = cbi; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
   // zpair: a 3x3x3 pad-1 conv over TWO planes (z_size 2) packed for the pair form (three in-plane products per plane pair)
-  cw.zpair = (zpair && taps == 27) ? 1 : 0;
+  // xpair: the same conv packed for the x-pair form instead (36 transformed taps; conv3d_xpair)
+  cw.xpair = (zpair && xpair && taps == 27) ? 1 : 0;
+  cw.zpair = (zpair && taps == 27 && !cw.xpair) ? 1 : 0;
+  if (cw.xpair) cw.taps = taps = 36;
   size_t off = pk.reserve(conv_pack_floats(Cout, cbi, taps));
-  if (cw.zpair) conv_pack_zpair_host(wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
+  if (cw.xpair) conv_pack_xpair_host(wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
+  else if (cw.zpair) conv_pack_zpair_host(wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
   else conv_pack_host(wsrc, Cout, seg.data(), (int)seg.size(), taps, pk.buf.data() + off);
   fx.push_back({&cw.w, off});
   size_t boff = pk.reserve((size_t)cw.ntile * 64);
@@ -582,12 +595,18 @@ extern "C" int tm_model_finalize(tm_model* m) {
           fxh.push_back({&r.c1uh, off});
         }
       } else {
+        // c1 of a 64-channel block: the pair form fuses the mid norm into its epilogue, an x-pair wave holds 32 of the 64 channels
+        // and leaves the norm to the separate pass.  Measured per step (profiles/fp32_xpair.txt), x-pair + separate pass is the
+        // faster by 0.58 ms over the six launches, so these layers move too; TM_CONV_XPAIR_MID=0 keeps them fused (A/B timing)
+        static const bool xmid = !(getenv("TM_CONV_XPAIR_MID") && atoi(getenv("TM_CONV_XPAIR_MID")) == 0);
+        const bool fuses = m->zpair && r.cout == 64 && conv_fuse_mid_enabled();
         pack_conv(m, pk, fx, r.c1, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg, 27, m->z == 1,
-                  m->zpair);
+                  m->zpair, m->xpair && !r.dec_deep && (!fuses || xmid));
         r.fuse_mid = r.c1.zpair && r.cout == 64 && conv_fuse_mid_enabled();
         if (r.up && m->z == 2) {                             // phase weights (conv3d_mfma UPS form) + their own copy of the bias
           r.c1u = r.c1;
           r.c1u.taps = 12;
+          r.c1u.xpair = 0;
           r.c1u.zpair = m->zpair ? 1 : 0;                    // the pair form of the phase weights (conv3d_zpair_ups), under the same switch
           const size_t off = pk.reserve(conv_pack_ups_floats(r.cout, r.cbi));
           (m->zpair ? conv_pack_zpair_ups_host : conv_pack_ups_host)(P(m, r.pfx + ".in_layers.2.weight").data(), r.cout, r.seg.data(),
@@ -599,7 +618,7 @@ extern "C" int tm_model_finalize(tm_model* m) {
           fx.push_back({&r.c1u.bias, boff});
         }
         pack_conv(m, pk, fx, r.c2, r.pfx + ".out_layers.3.weight", r.pfx + ".out_layers.3.bias", r.cout, {r.cout}, 27, m->z == 1,
-                  m->zpair);
+                  m->zpair, m->xpair && !r.dec_deep);
       }
       if (r.has_skip) {
         if (bf16) pack_linear_stack_h(m, pk, fx, fxh, r.skip, &r.skiph, {r.pfx + ".skip_connection"}, r.cout, r.seg);
@@ -675,10 +694,13 @@ extern "C" int tm_profile_collect(tm_model* m, tm_prof_stats* out) {
   // Z == 2: the pair form issues 27 taps per plane PAIR (27 of the nominal 54), the z-skip form 18 of 27 per plane; Z == 1: the
   // centre slice only (9); Z >= 3: all 27 (zero planes staged)
   // (the 16-bit conv never stages z-padding planes: (3Z - 2) / 3Z of the taps for any Z)
-  out->executed_flops = m->prof_nominal * (is_h16(m->cfg.dtype) ? (3.0 * m->z - 2.0) / (3.0 * m->z)
-                                           : (m->z == 2 ? (m->zpair ? 27.0 / 54.0 : 18.0 / 27.0) : (m->z == 1 ? 9.0 / 27.0 : 1.0)));
+  // per layer: a launch in the x-pair form issues 36 tap-products per FOUR outputs, 18 of the nominal 54
+  out->executed_flops = (m->prof_nominal - m->prof_xpair) *
+                            (is_h16(m->cfg.dtype) ? (3.0 * m->z - 2.0) / (3.0 * m->z)
+                                                  : (m->z == 2 ? (m->zpair ? 27.0 / 54.0 : 18.0 / 27.0) : (m->z == 1 ? 9.0 / 27.0 : 1.0))) +
+                        m->prof_xpair * (18.0 / 54.0);
   out->alg_bytes = m->prof_bytes;
-  m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0;
+  m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0; m->prof_xpair = 0;
   return TM_OK;
 }
 
@@ -786,7 +808,7 @@ static void run_conv(Ctx& cx, const TV& x, const ConvW& w, TV y, const TV* res, 
     L.fuse_norm = 1; L.a2 = y; L.norm_w = fuse_rw->n2; L.inv_c = 1.0f / (float)fuse_rw->cout; L.per_image = per_image;
     L.mod_scale = cx.ss + fuse_rw->emb_off; L.mod_shift = cx.ss + fuse_rw->emb_off + fuse_rw->cout; L.mod_stride = m->emb_tot;
   }
-  const bool prof = m->prof_on && (w.taps == 27 || (m->z == 1 && w.taps == 9)) && zmode == ZM_PAD1;
+  const bool prof = m->prof_on && (w.taps == 27 || w.xpair || (m->z == 1 && w.taps == 9)) && zmode == ZM_PAD1;
   if (prof) {
     if (m->prof_used == m->prof_ev.size()) {
       hipEvent_t a, b;
@@ -801,8 +823,9 @@ static void run_conv(Ctx& cx, const TV& x, const ConvW& w, TV y, const TV* res, 
     m->prof_used++;
     const double vox = (double)x.N * x.Z * x.H * x.W;
     m->prof_nominal += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
+    if (w.xpair) m->prof_xpair += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
     m->prof_tag.push_back({cin_real ? cin_real : x.C, w.Cout, x.H, x.N, 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox});
-    m->prof_bytes += 4.0 * (vox * x.Cb * 8 + (double)w.ntile * w.Cbi * 27 * 512 + vox * y.Cb * 8);
+    m->prof_bytes += 4.0 * (vox * x.Cb * 8 + (double)w.ntile * w.Cbi * w.taps * 512 + vox * y.Cb * 8);
   }
 }
 

@@ -275,6 +275,78 @@ extern "C" int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, co
   return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_ups_pair (fp32)");
 }
 
+// The x-pair form of the fp32 3x3x3 pad-1 conv at Z == 2 (conv3d_xpair), alone.  Returns the tile it launched (1 = the 64-voxel
+// tile, 2 = the 128-voxel one) or a negative error; what the kernel does not take is refused here, before any device call.
+static int xpair_args(const void* x, const void* w, const void* b, const void* y, int N, int Cin, int Cout, int Z, int S,
+                      int tile_variant) {
+  if (!x || !w || !b || !y) return fail(TM_ERR_ARG, "null argument");
+  if (N < 1 || Cin < 1 || Cout < 1) return fail(TM_ERR_ARG, "N, Cin, Cout must be positive");
+  if (Z != 2) return fail(TM_ERR_ARG, "the x-pair form exists at Z == 2 only (got Z = %d)", Z);
+  if (S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return fail(TM_ERR_ARG, "S must be 8, 16, 32, 64 or 128 (got %d)", S);
+  if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
+  if (!conv_xpair_enabled()) return fail(TM_ERR_ARG, "the x-pair form is switched off (TM_CONV_XPAIR=0)");
+  return TM_OK;
+}
+static ConvW xpair_form(int Cin, int Cout) {
+  ConvW cw;
+  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.ntile = (Cout + 63) / 64; cw.taps = 36; cw.xpair = 1;
+  return cw;
+}
+extern "C" int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                                    int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream) {
+  if (const int rc = xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
+  if (res_half && !res_cb8) return fail(TM_ERR_ARG, "res_half needs a residual");
+  ConvW cw = xpair_form(Cin, Cout);
+  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, 36));
+  conv_pack_xpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
+  DevTmp tmp;
+  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (tmp.err) return tmp.report();
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.tile_variant = tile_variant;
+  TV res;
+  if (res_cb8) {
+    res = view_cb8(const_cast<void*>(res_cb8), N, Cout, Z, res_half ? S / 2 : S, res_half ? S / 2 : S);
+    L.res = &res;
+    L.res_half = res_half ? 1 : 0;
+  }
+  const int rc = finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_xpair (fp32)");
+  return rc ? rc : (conv_xpair_half((long)N * Z * S * S, cw.ntile, tile_variant) ? 1 : 2);
+}
+
+// Timing hook (tools/bench_conv_xpair.py): the 3x3x3 pad-1 conv at Z == 2 packed once for `form` (0 = the pair form, 1 = the
+// x-pair form), then `iters` launches, each between two events of its own; ms_out[i] (host) = the time of launch i.
+extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                        int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream) {
+  if (const int rc = xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant)) return rc;
+  if ((form != 0 && form != 1) || iters < 1 || !ms_out) return fail(TM_ERR_ARG, "form must be 0 or 1, iters >= 1, ms_out non-null");
+  ConvW cw = form ? xpair_form(Cin, Cout) : conv_form(Cin, Cout, 3, ZM_PAD1, 2);
+  if (!form && !cw.zpair) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
+  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, cw.taps));
+  (form ? conv_pack_xpair_host : conv_pack_zpair_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
+  DevTmp tmp;
+  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  hipEvent_t e0 = tmp.event(), e1 = tmp.event();
+  if (tmp.err) return tmp.report();
+  hipStream_t st = (hipStream_t)stream;
+  ConvLaunch L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, 2, S, S);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, 2, S, S);
+  L.tile_variant = tile_variant;
+  for (int i = 0; i < iters; ++i) {
+    HIP_TRY(hipEventRecord(e0, st));
+    HIP_TRY(launch_conv_mfma(L, st));
+    HIP_TRY(hipEventRecord(e1, st));
+    HIP_TRY(hipEventSynchronize(e1));
+    HIP_TRY(hipEventElapsedTime(ms_out + i, e0, e1));
+  }
+  return finish(st, hipSuccess, "conv_pad1_time (fp32)");
+}
+
 // power of two >= 2: what a half-resolution gate needs of S (read at (z, y >> 1, x >> 1))
 static bool half_gate_ok(int S) { return S >= 2 && (S & (S - 1)) == 0; }
 

@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""Op-level timing of the fp32 3x3x3 pad-1 conv at Z = 2 in its two forms, the pair form (conv3d_zpair) against the x-pair form
+(conv3d_xpair), at the governing geometries of the fp32 step.  Per geometry ROUNDS rounds of CHUNK launches of each form,
+interleaved (pair, x-pair, pair, ..), every launch between two events of its own (tm_op_conv_pad1_time_f32); the first launch
+of a chunk is dropped.  Prints one JSON line per geometry: median, 10th and 90th percentile in microseconds of each form, and
+whether the x-pair median is below the pair form's by more than the larger of the two p90 - p10 spreads.
+
+    python3 tools/bench_conv_xpair.py [--rounds 5] [--chunk 21] [--tile 0]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import teramind_amd  # noqa: E402,F401
+from teramind_amd import _lib  # noqa: E402
+
+# (N, Cin, Cout, S): the four encoder / decoder levels of configs[1] at b = 32, P = 1 and the widest decoder concat
+GEOMETRIES = [(128, 96, 64, 64), (128, 128, 128, 32), (128, 256, 256, 16), (128, 512, 512, 8), (32, 1253, 512, 8)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--chunk", type=int, default=21)
+    ap.add_argument("--tile", type=int, default=0)
+    ap.add_argument("--geometry", type=int, default=-1, help="index into GEOMETRIES (default: all)")
+    a = ap.parse_args()
+    L = _lib.lib()
+    geos = GEOMETRIES if a.geometry < 0 else [GEOMETRIES[a.geometry]]
+    for (N, Cin, Cout, S) in geos:
+        g = torch.Generator(device="cuda").manual_seed(N + Cin + Cout + S)
+        x = torch.randn((N, (Cin + 7) // 8, 2, S, S, 8), device="cuda", generator=g)
+        y = torch.empty((N, (Cout + 7) // 8, 2, S, S, 8), device="cuda")
+        w = (torch.randn((Cout, Cin, 27)) / (27 * Cin) ** 0.5).contiguous()
+        b = torch.randn((Cout,))
+        ms = (C.c_float * a.chunk)()
+        t = {0: [], 1: []}
+        for _ in range(a.rounds):
+            for form in (0, 1):
+                rc = L.tm_op_conv_pad1_time_f32(_lib.ptr(x), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), _lib.ptr(y), N, Cin,
+                                                Cout, S, form, a.tile, a.chunk, ms, _lib.current_stream_ptr())
+                _lib.check(rc, "tm_op_conv_pad1_time_f32")
+                t[form] += [1e3 * v for v in list(ms)[1:]]
+        q = {f: [float(np.percentile(t[f], p)) for p in (50, 10, 90)] for f in t}
+        spread = max(q[0][2] - q[0][1], q[1][2] - q[1][1])
+        print(json.dumps({"N": N, "Cin": Cin, "Cout": Cout, "S": S, "launches": len(t[0]),
+                          "pair_us": [round(v, 1) for v in q[0]], "xpair_us": [round(v, 1) for v in q[1]],
+                          "ratio": round(q[1][0] / q[0][0], 4), "spread_us": round(spread, 1),
+                          "wins": bool(q[0][0] - q[1][0] > spread)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
