@@ -2164,7 +2164,7 @@ void conv_bf16_pack_host(const float* w, int Cout, const int* seg_c, int nseg, u
   }
 }
 
-// Phase weights of the upsampled-input conv (HGeo UPS; the fp32 twin is conv_pack_ups_host): per output phase (py, px) the
+// Phase weights of the upsampled-input conv (HGeo UPS; the fp32 twin is the CF_ZSKIP_UPS pack of conv_pack_host): per output phase (py, px) the
 // 3 x 3 in-plane taps collapse onto a 2 x 2 window of the low-resolution input -- rows: py = 0: {ky 0} | {ky 1, 2};
 // py = 1: {ky 0, 1} | {ky 2}; columns alike; the sums are formed in fp32 and rounded once.
 // out: [phase = 2 py + px][n-tile][pair][kz 3][4 taps (wy, wx)][TN][2][8]

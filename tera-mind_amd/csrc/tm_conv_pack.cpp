@@ -1,0 +1,157 @@
+// The forms of the fp32 MFMA conv (ConvForm, tm_kernels.h): which form a layer runs in, and the host packers of each.  Host only.
+#include "tm_kernels.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+namespace tmk {
+
+int conv_form_taps(int form) {
+  switch (form) {
+    case CF_1X1: return 1;
+    case CF_INPLANE: return 9;
+    case CF_ZSKIP_UPS: case CF_PAIR_UPS: return 12;
+    case CF_XPAIR: return 36;
+    default: return 27;
+  }
+}
+static bool form_ups(int form) { return form == CF_ZSKIP_UPS || form == CF_PAIR_UPS; }
+size_t conv_pack_floats(int form, int Cout, int Cbi) {
+  return (size_t)(form_ups(form) ? 4 : 1) * ((Cout + 63) / 64) * Cbi * conv_form_taps(form) * 512;
+}
+ConvW conv_w(int form, int Cout, int Cbi) {
+  ConvW cw;
+  cw.form = form; cw.Cout = Cout; cw.Cbi = Cbi; cw.taps = conv_form_taps(form); cw.ntile = (Cout + 63) / 64;
+  return cw;
+}
+
+static bool switch_on(const char* name) {        // an A/B switch: on unless the variable is set to 0
+  const char* v = getenv(name);
+  return !(v && atoi(v) == 0);
+}
+int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse_mid) {
+  static const bool zpair_on = switch_on("TM_CONV_ZPAIR"), xpair_on = switch_on("TM_CONV_XPAIR"),
+                    xmid_on = switch_on("TM_CONV_XPAIR_MID"), fuse_on = switch_on("TM_CONV_FUSE_MID");
+  if (fuse_mid) *fuse_mid = false;
+  if (ksize == 1) return CF_1X1;
+  if (zmode == ZM_INPLANE) return CF_INPLANE;
+  if (zmode == ZM_VALID) return CF_PLANES3;
+  const bool pair = Z == 2 && zpair_on;
+  if (zmode == ZM_UPS) return ((role & ROLE_OP_PAIR_UPS) || ((role & ROLE_RES) && pair)) ? CF_PAIR_UPS : CF_ZSKIP_UPS;
+  if (Z != 2) return (Z == 1 && (role & ROLE_RES)) ? CF_INPLANE : CF_PLANES3;
+  if ((role & ROLE_OP_XPAIR) && xpair_on) return CF_XPAIR;
+  if (!pair) return CF_ZSKIP;
+  // c1 of a 64-channel block: the pair form fuses the mid norm into its epilogue, an x-pair wave holds 32 of the 64 channels and
+  // leaves the norm to the separate pass.  Measured per step (profiles/fp32_xpair.txt), x-pair + separate pass is the faster by
+  // 0.58 ms over the six launches, so these layers move too; TM_CONV_XPAIR_MID=0 keeps them fused
+  const bool fuses = (role & ROLE_C1_64) && fuse_on;
+  const bool xp = (role & ROLE_RES) && !(role & ROLE_DEEP) && xpair_on && deep8 && (!fuses || xmid_on);
+  if (fuse_mid) *fuse_mid = fuses && !xp;
+  return xp ? CF_XPAIR : CF_PAIR;
+}
+
+// ---- packers ----
+static void seg_counts(const int* seg_c, int nseg, int& Cin, int& Cbi) {
+  Cin = Cbi = 0;
+  for (int s = 0; s < nseg; ++s) { Cin += seg_c[s]; Cbi += (seg_c[s] + 7) / 8; }
+}
+// w [Cout][Cin][taps] -> [n_tile][cblk][tap][64 cout][8 cin], pad slots zero
+static void pack_taps(const float* w, int Cout, const int* seg_c, int nseg, int taps, float* out) {
+  int Cin, Cbi;
+  seg_counts(seg_c, nseg, Cin, Cbi);
+  memset(out, 0, (size_t)((Cout + 63) / 64) * Cbi * taps * 512 * sizeof(float));
+  int ci0 = 0, cb0 = 0;
+  for (int s = 0; s < nseg; ++s) {
+    for (int c = 0; c < seg_c[s]; ++c) {
+      const int ci = ci0 + c;
+      const int cb = cb0 + c / 8, c8 = c % 8;
+      for (int co = 0; co < Cout; ++co) {
+        const int nt = co / 64, col = co % 64;
+        const float* src = w + ((size_t)co * Cin + ci) * taps;
+        float* dst = out + (((size_t)nt * Cbi + cb) * taps) * 512 + (size_t)col * 8 + c8;
+        for (int t = 0; t < taps; ++t) dst[(size_t)t * 512] = src[t];
+      }
+    }
+    ci0 += seg_c[s];
+    cb0 += (seg_c[s] + 7) / 8;
+  }
+}
+
+// The three weight transforms, each over n = Cout * Cin filters and all in fp32.
+// Phase sums of the upsampled-input conv: for output phase (py, px) the 3 x 3 in-plane taps collapse onto a 2 x 2 window of the
+// low-resolution input -- rows: py = 0: {ky 0} | {ky 1, 2}; py = 1: {ky 0, 1} | {ky 2}; columns alike.  [n][27] -> [n][kz][wy][wx]
+static std::vector<float> phase_sums(const float* w, size_t n, int py, int px) {
+  static const int G0[2][2][2] = {{{0, 0}, {1, 2}}, {{0, 1}, {2, 2}}};       // [phase bit][window pos] -> tap range [lo, hi]
+  std::vector<float> o(n * 12);
+  for (size_t i = 0; i < n; ++i)
+    for (int kz = 0; kz < 3; ++kz)
+      for (int wy = 0; wy < 2; ++wy)
+        for (int wx = 0; wx < 2; ++wx) {
+          float acc = 0.f;
+          for (int ky = G0[py][wy][0]; ky <= G0[py][wy][1]; ++ky)
+            for (int kx = G0[px][wx][0]; kx <= G0[px][wx][1]; ++kx) acc += w[i * 27 + kz * 9 + ky * 3 + kx];
+          o[i * 12 + kz * 4 + wy * 2 + wx] = acc;
+        }
+  return o;
+}
+// z difference of the pair forms: the kz slices V0, V1, V2 of k in-plane taps each -> V1, V2 - V1, V0 - V1, the order the
+// kernels consume the three products in.  [n][3][k] -> [n][3][k]
+static std::vector<float> z_diff(const float* w, size_t n, int k) {
+  std::vector<float> o(n * 3 * k);
+  for (size_t i = 0; i < n; ++i)
+    for (int t = 0; t < k; ++t) {
+      const float w0 = w[i * 3 * k + t], w1 = w[i * 3 * k + k + t], w2 = w[i * 3 * k + 2 * k + t];
+      o[i * 3 * k + t] = w1;
+      o[i * 3 * k + k + t] = w2 - w1;
+      o[i * 3 * k + 2 * k + t] = w0 - w1;
+    }
+  return o;
+}
+// F(2,3) filter transform of the three kx taps g0, g1, g2 of every (product, ky) row: U0 = g0, U1 = ((g0 + g1) + g2) / 2,
+// U2 = ((g0 - g1) + g2) / 2, U3 = g2.  [n][9 rows][3] -> [n][9 rows][4]
+static std::vector<float> f23_rows(const float* w, size_t n) {
+  std::vector<float> o(n * 36);
+  for (size_t r = 0; r < n * 9; ++r) {
+    const float* g = w + r * 3;
+    float* u = o.data() + r * 4;
+    u[0] = g[0];
+    u[1] = ((g[0] + g[1]) + g[2]) * 0.5f;
+    u[2] = ((g[0] - g[1]) + g[2]) * 0.5f;
+    u[3] = g[2];
+  }
+  return o;
+}
+
+void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int nseg, float* out) {
+  int Cin, Cbi;
+  seg_counts(seg_c, nseg, Cin, Cbi);
+  const size_t n = (size_t)Cout * Cin;
+  if (form == CF_PAIR) {
+    pack_taps(z_diff(w, n, 9).data(), Cout, seg_c, nseg, 27, out);
+  } else if (form == CF_XPAIR) {
+    pack_taps(f23_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, 36, out);
+  } else if (form_ups(form)) {               // [phase = 2 py + px][the 12-tap pack of that phase's weights]
+    const size_t per = conv_pack_floats(form, Cout, Cbi) / 4;
+    for (int ph = 0; ph < 4; ++ph) {
+      std::vector<float> v = phase_sums(w, n, ph >> 1, ph & 1);
+      if (form == CF_PAIR_UPS) v = z_diff(v.data(), n, 4);
+      pack_taps(v.data(), Cout, seg_c, nseg, 12, out + ph * per);
+    }
+  } else {
+    pack_taps(w, Cout, seg_c, nseg, conv_form_taps(form), out);
+  }
+}
+
+void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
+  int ci0 = 0, cb0 = 0;
+  for (int s = 0; s < nseg; ++s) {
+    const int nb = (seg_c[s] + 7) / 8;
+    for (int c = 0; c < nb * 8; ++c) out[cb0 * 8 + c] = (c < seg_c[s]) ? v[ci0 + c] : 0.f;
+    ci0 += seg_c[s];
+    cb0 += nb;
+  }
+}
+
+}  // namespace tmk

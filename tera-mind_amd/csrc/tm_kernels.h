@@ -25,36 +25,49 @@ struct TV {
   }
 };
 
-// ---- packed conv weights for the MFMA implicit-GEMM kernel ---------------------------
+// ---- packed conv weights for the MFMA implicit-GEMM kernels ----------------------------
 // layout: [n_tile][cblk][tap][64 cout][8 cin] fp32, cout padded to a multiple of 64,
 // cin padded per concat segment to multiples of 8 ("virtual" cin order).
+// The form of a conv: which kernel reads the pack, hence its tap count and layout.  Decided by conv_pick_form and nowhere else.
+enum ConvForm {
+  CF_1X1 = 0,        // 1x1x1 conv / Linear (conv1_mfma), 1 tap
+  CF_INPLANE,        // 9 in-plane taps on one plane: 1x3x3, or the centre slice of a 3x3x3 pad-1 conv at Z == 1 (conv3d_mfma<1>)
+  CF_PLANES3,        // 27 taps over three staged planes: pad 1 (any Z but 2) or valid in z, by ConvLaunch.zmode (conv3d_mfma<3>)
+  CF_ZSKIP,          // the same 27-tap pack at Z == 2: 18 of the 27 taps per output plane (conv3d_mfma<2>)
+  CF_ZSKIP_UPS,      // z-skip of the nearest-x2 upsampled input: 4 phases x 12 phase-sum taps (conv3d_mfma<2, .., true>)
+  CF_PAIR,           // pair form at Z == 2: W1, W2 - W1, W0 - W1, 27 taps (conv3d_zpair)
+  CF_PAIR_UPS,       // pair form of the upsampled input: the z difference of the phase sums, 4 x 12 taps (conv3d_zpair_ups)
+  CF_XPAIR,          // pair form in z with Winograd F(2,3) along x: 36 transformed taps (conv3d_xpair)
+};
 struct ConvW {
   const float* w = nullptr;     // device
   const float* bias = nullptr;  // device, [ntile*64]
-  int Cout = 0, Cbi = 0, taps = 0, ntile = 0;
-  int zpair = 0;                // taps == 27 packed by conv_pack_zpair_host: ZM_PAD1 at Z == 2 runs the pair form (conv3d_zpair);
-                                // taps == 12 packed by conv_pack_zpair_ups_host: ZM_UPS runs conv3d_zpair_ups
-  int xpair = 0;                // taps == 36 packed by conv_pack_xpair_host: ZM_PAD1 at Z == 2, S >= 8 runs conv3d_xpair (the pair
-                                // form in z with Winograd F(2,3) along x); every other launch of such weights is refused
+  int Cout = 0, Cbi = 0, taps = 0, ntile = 0;     // taps = conv_form_taps(form): set by conv_w only
+  int form = CF_1X1;
 };
-size_t conv_pack_floats(int Cout, int Cbi, int taps);
-// host-side packing; seg_c[i] = real channels of concat segment i (each padded to x8).
-void conv_pack_host(const float* w /*[Cout][Cin][taps]*/, int Cout, const int* seg_c, int nseg,
-                    int taps, float* out);
-size_t conv_pack_ups_floats(int Cout, int Cbi);          // phase weights of the upsampled-input conv (ZM_UPS), taps = 12
-void conv_pack_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
-bool conv_zpair_enabled();                               // false with TM_CONV_ZPAIR=0 (A/B timing): keep the 18-tap z-skip form
-void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
-bool conv_xpair_enabled();                               // false with TM_CONV_XPAIR=0 (A/B timing): keep the pair form everywhere
-// ConvW.xpair, taps == 36: per (product, ky) the four F(2,3) filter transforms of the pair-form weights; 4/3 of the 27-tap pack
-void conv_pack_xpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
-// ZM_UPS in the pair form (conv3d_zpair_ups; ConvW.zpair with taps == 12): the z difference of the phase weights; the same size
-void conv_pack_zpair_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out);
+int conv_form_taps(int form);                            // taps per (cout tile, cin block) of the pack: 1 / 9 / 27 / 12 / 36
+size_t conv_pack_floats(int form, int Cout, int Cbi);    // floats of the whole pack (the upsampled forms hold four phases)
+ConvW conv_w(int form, int Cout, int Cbi);               // the weight geometry of a form; w / bias are left for the caller
+// Which form a conv runs in, from what its caller knows: the kernel size (1 or 3), the z semantics (ZM_*), the input planes Z,
+// whether the model's deepest plane is at least 8 x 8 (the x-pair kernel has no 4 x 4 tile) and the role of the layer.  The one
+// reader of the A/B switches TM_CONV_ZPAIR, TM_CONV_XPAIR, TM_CONV_XPAIR_MID and TM_CONV_FUSE_MID (each read once; =0 switches
+// the form off, for timing in separate processes only).  *fuse_mid (nullable): the layer runs the ResBlock mid-section in its
+// epilogue wherever a launch takes the 128-voxel tile.
+enum { ROLE_OP = 0,             // single-operator hooks and the training tape: pair form at Z == 2, never x-pair
+       ROLE_RES = 1,            // a ResBlock 3x3x3 conv of the executor: centre slice at Z == 1, x-pair at Z == 2
+       ROLE_DEEP = 2,           // + a decoder block of the deepest level: stays on the pair form (profiles/fp32_xpair.txt)
+       ROLE_C1_64 = 4,          // + the first conv of a 64-channel block: pair form with the fused mid-section, or x-pair
+       ROLE_OP_XPAIR = 8,       // the hooks of the x-pair form: under TM_CONV_XPAIR alone
+       ROLE_OP_PAIR_UPS = 16 }; // the hook of the upsampled pair form: under no switch
+int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse_mid = nullptr);
+// host-side packing (tm_conv_pack.cpp); w [Cout][Cin][9 (CF_INPLANE) | 1 (CF_1X1) | 27], seg_c[i] = real channels of concat
+// segment i (each padded to x8)
+void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int nseg, float* out);
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out);  // per-cin vector -> virtual order
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_UP2 = 2 };
 enum { ZM_PAD1 = 0, ZM_INPLANE = 1, ZM_VALID = 2,    // z structure of a k x 3 x 3 conv (see conv3d_mfma)
-       ZM_UPS = 3 };                                   // 3x3x3 pad 1 of nearest-x2 upsampled x, computed on x (conv_pack_ups_host weights)
+       ZM_UPS = 3 };                                   // 3x3x3 pad 1 of nearest-x2 upsampled x, computed on x (phase weights)
 struct ConvLaunch {
   TV x;                  // activated input, Cb == w.Cbi
   ConvW w;
@@ -62,12 +75,12 @@ struct ConvLaunch {
   const TV* res = nullptr;   // optional residual (same geometry as y)
   const TV* gate = nullptr;  // optional gate: y = res + gate * (conv + bias)
   int flags = 0;
-  int tile_variant = 0;  // 0 auto, 1 = 128-voxel blocks, 2 = 256-voxel blocks; taps == 1 also 3 = the 128-cout tile (conv1_form)
-  int gate_half = 0;     // taps == 1 only: `gate` lives at S/2 and is read at (z, y >> 1, x >> 1) (S a power of two)
+  int tile_variant = 0;  // 0 auto, 1 = 128-voxel blocks, 2 = 256-voxel blocks; CF_1X1 also 3 = the 128-cout tile (conv1_form)
+  int gate_half = 0;     // CF_1X1 only: `gate` lives at S/2 and is read at (z, y >> 1, x >> 1) (S a power of two)
   int res_half = 0;      // k x 3 x 3 only: `res` lives at S/2 and is read at (z, y >> 1, x >> 1): the residual of a ResBlock(up=True)
                          // is the nearest-x2 upsampled block input (model/MBAblocks.py:254-258,297)
-  int zmode = ZM_PAD1;   // ignored for taps == 1
-  // pair form (w.zpair), Cout == 64, the 128-voxel tile, no residual / gate / flags: fuse RMSNorm(C) * norm_w -> x (1 + scale) +
+  int zmode = ZM_PAD1;   // the caller's statement of the z semantics; must agree with w.form (ignored for CF_1X1)
+  // CF_PAIR, Cout == 64, the 128-voxel tile, no residual / gate / flags: fuse RMSNorm(C) * norm_w -> x (1 + scale) +
   // shift -> SiLU into the epilogue and write `a2` (the next conv's input) instead of y; y carries the geometry only
   int fuse_norm = 0;
   const float *norm_w = nullptr, *mod_scale = nullptr, *mod_shift = nullptr;
@@ -77,10 +90,12 @@ struct ConvLaunch {
   TV a2;
 };
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
-int conv_zpair_half(long ovox, int ntile, int S, int tile_variant);   // 1: a pair-form launch takes the 64-voxel tile; no device call
-int conv_xpair_half(long ovox, int ntile, int tile_variant);          // the same rule for an x-pair launch (conv3d_xpair); no device call
-bool conv_fuse_mid_enabled();                           // false with TM_CONV_FUSE_MID=0 (A/B timing): separate mid-block norm pass
-// which conv1_mfma instantiation a taps == 1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
+// The tile of a k x 3 x 3 launch of `ovox` output voxels (N * Z * S * S of the launched plane): 2 = the large tile (256 voxels; 128
+// in the pair and x-pair forms), 1 = the small one.  tile_variant 0 chooses by launch size (conv_fills_chip), 1 / 2 force it; a 4 x 4
+// plane has the small tile only.  The one statement of the rule, for the launcher and for whoever must know the tile beforehand
+// (the fused mid-section exists in the large tile only).  No device call.
+int conv_tile(int form, long ovox, int ntile, int S, int tile_variant);
+// which conv1_mfma instantiation a CF_1X1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
 int conv1_form(long vox, int ntile, int tile_variant);
 
 // ---- bf16 3x3x3 conv (tm_conv_bf16.hip) --------------------------------------------------
@@ -302,8 +317,8 @@ hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin,
                                   hipStream_t s);
 int conv_wgrad_chunks(int N, int Z, int S, int Cin, int Cout, int* per_out);
 size_t conv_wgrad_scratch_floats(int N, int Z, int S, int Cin, int Cout, int taps);
-// device twin of conv_pack_host / conv_pack_zpair_host (pair); role 1: the data-gradient filter (flipped, cin <-> cout)
-hipError_t launch_conv_pack(const float* w, float* out, int Cout, int Cin, int taps, int role, int pair, hipStream_t s);
+// device twin of conv_pack_host for CF_1X1, CF_PLANES3, CF_ZSKIP and CF_PAIR; role 1: the data-gradient filter (flipped, cin <-> cout)
+hipError_t launch_conv_pack(const float* w, float* out, int Cout, int Cin, int form, int role, hipStream_t s);
 // AttnBlock pieces (model/MBAblocks.py:428-614)
 hipError_t launch_ew(int op, const float* a, const float* b, const float* c, float* o1, float* o2, long n, hipStream_t s);
 hipError_t launch_modnorm_bwd(const TV& x, const float* g, const float* w, const float* scale, float* dx, float* dscale, float* dshift,

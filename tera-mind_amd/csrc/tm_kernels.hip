@@ -11,7 +11,7 @@
 //   (gene-gene and windowed attention kernels: tm_attn.hip)
 //   time_embed / emb_all       timestep embedding MLP and all ResBlock emb_layers at once
 //   (sampler_step / pad_patchify live in tm_sampler.hip: built with -ffp-contract=off)
-#include "tm_device.h"
+#include "tm_conv_pair.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -30,11 +30,12 @@ namespace tmk {
 //            in_layers, model/MBAblocks.py:254-258, blocks.py:362-371), computed on the LOW-resolution tensor: output voxel
 //            (2y + py, 2x + px) sees only the 2 x 2 low-resolution voxels (y + py - 1 .. y + py, x + px - 1 .. x + px), so
 //            each of the four phases (py, px) is a conv with 2 x 2 in-plane taps whose weights are the sums of the 3 x 3
-//            taps that land on the same source voxel (packed per phase by conv_pack_ups_host): 8 instead of 18 taps per
+//            taps that land on the same source voxel (packed per phase by conv_pack_host, CF_ZSKIP_UPS): 8 instead of 18 taps per
 //            output plane and a quarter of the input bytes; the zero padding of the upsampled tensor maps onto the zero
 //            halo of the low-resolution tile.  Same sums, different association (weights are added before the products).
 template <int NZI, int WM, int TW, bool UPS = false>
 struct C3Geo {
+  static constexpr int TW_ = TW;
   static constexpr int MV = 4 * WM * 32;                         // voxels per workgroup
   static constexpr int TR = (MV / TW < TW) ? (MV / TW) : TW;     // tile rows (<= plane size S == TW or 2*TW)
   static constexpr int NPB = MV / (TR * TW);                     // patches per workgroup
@@ -68,18 +69,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
   const int i32 = lane & 31, h = lane >> 5;
 
   const int S = a.S;
-  const int tiles_c = S / TW, tiles_r = S / G::TR;
-  const int tiles = tiles_c * tiles_r;
-  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int nt = bid % a.ntile;
-  int mt_ = bid / a.ntile;
-  int py = 0, px = 0;                                            // UPS: output phase of this workgroup (the four phases of a
-  if (UPS) { py = (mt_ >> 1) & 1; px = mt_ & 1; mt_ >>= 2; }     // tile are neighbours in the grid: they share the input halo)
-  const int pg = mt_ / (a.Z * tiles);                            // a.Z = OUTPUT planes
-  mt_ -= pg * a.Z * tiles;
-  const int zo = mt_ / tiles;
-  mt_ -= zo * tiles;
-  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+  const ConvTile t = conv_tile_of<TW, G::TR, UPS, true>(a);       // UPS: with the output phase of this workgroup
+  const int nt = t.nt, pg = t.pg, zo = t.zo, tr = t.tr, tc = t.tc, py = t.py, px = t.px;
 
   // ---- per-thread staging descriptors (constant over the K loop) ----
   long xoff[G::PX];
@@ -129,12 +120,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
   const int wb = i32 * 8 + 4 * h;
 
   f32x16 acc[2][WM];
-#pragma unroll
-  for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-    for (int mt = 0; mt < WM; ++mt)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[ct][mt][r] = 0.f;
+  clear_acc(acc);
 
   f32x4 xr[KB][G::PX], wr[KB][G::PW];
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -207,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
 // the z-skip form above (36 taps per plane pair).  Three are enough:
 //   P1 = W1 * (X0 + X1)    P2 = (W2 - W1) * X1    P3 = (W0 - W1) * X0        Y0 = P1 + P2    Y1 = P1 + P3
 // (27 taps per plane pair, a quarter fewer MFMAs).  The weight slices are differenced once at pack time
-// (conv_pack_zpair_host: W1, W2 - W1, W0 - W1, nine taps each), the two planes are added while staging.  Products and
+// (conv_pack_host, CF_PAIR: W1, W2 - W1, W0 - W1, nine taps each), the two planes are added while staging.  Products and
 // accumulation are fp32 as everywhere; the z association differs from F.conv3d's, like the in-plane association of UPS.
 // One workgroup owns an in-plane tile of MV voxels, BOTH output planes and 64 couts.  HALF = 0: 128 voxels, wave = 32 voxels x
 // 64 couts (3 x 2 accumulators); HALF = 1: 64 voxels, wave = 32 voxels x 32 couts (small launches).  Every output element
@@ -215,10 +201,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
 // FUSE (HALF = 0, 64 couts, one cout tile): the wave holds every channel of its 32 voxels, so the ResBlock mid-section (RMSNorm
 // over channels -> modulate -> SiLU, zpair_norm_epilogue) runs on each output plane in place of the plain epilogue and the
 // second conv's input is written instead of the conv output.  The K loop is the same code; layers that do not fuse run <.., false>.
-typedef int rsrc_words __attribute__((ext_vector_type(4)));     // a buffer descriptor as four SGPRs of an asm statement
-
 template <int HALF, int TW>
 struct ZPGeo {
+  static constexpr int TW_ = TW;
   static constexpr int MV = HALF ? 64 : 128;                     // in-plane voxels per workgroup (2 MV outputs)
   static constexpr int TR = (MV / TW < TW) ? (MV / TW) : TW;     // tile rows
   static constexpr int NPB = MV / (TR * TW);                     // patches per workgroup
@@ -244,14 +229,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   const int i32 = lane & 31, h = lane >> 5;
 
   const int S = a.S;
-  const int tiles_c = S / TW, tiles_r = S / G::TR;
-  const int tiles = tiles_c * tiles_r;
-  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int nt = bid % a.ntile;
-  int mt_ = bid / a.ntile;
-  const int pg = mt_ / tiles;
-  mt_ -= pg * tiles;
-  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+  const ConvTile t = conv_tile_of<TW, G::TR, false, false>(a);
+  const int nt = t.nt, pg = t.pg, tr = t.tr, tc = t.tc;
 
   // ---- per-thread staging descriptors: the z = 0 piece of a halo position (the z = 1 piece is one plane further) ----
   long xoff[G::PX];
@@ -278,14 +257,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   const int ct0 = HALF ? (wv >> 1) : 0;                          // its first 32-cout sub-tile
   int xb, on[1], ooff0[1], ooff1[1];
   {
-    const int v = vt * 32 + i32;
-    const int ps = v / (G::TR * TW);
-    const int rem = v - ps * (G::TR * TW);
-    const int r = rem / TW, c = rem - r * TW;
-    xb = ((ps * G::HR + r) * G::HC + c) * 8 + 4 * h;
-    const int n = pg * G::NPB + ps;
+    const ConvLane l = conv_lane_of<G::TR, TW, G::HR, G::HC>(vt * 32 + i32, h, 0, 0);
+    xb = l.xb;
+    const int n = pg * G::NPB + l.ps;
     on[0] = n;
-    const int y = tr * G::TR + r, x = tc * TW + c;
+    const int y = tr * G::TR + l.r, x = tc * TW + l.c;
     if (n < a.N) {
       if (a.flags & EPI_UP2) { ooff0[0] = (2 * y * 2 * S + 2 * x) * 8; ooff1[0] = ooff0[0] + 4 * S * S * 8; }
       else { ooff0[0] = (y * S + x) * 8; ooff1[0] = ooff0[0] + S * S * 8; }
@@ -294,12 +270,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   const int wb = ct0 * 256 + i32 * 8 + 4 * h;
 
   f32x16 acc[3][NC];
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int ct = 0; ct < NC; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.f;
+  clear_acc(acc);
 
   // ---- weights: global -> LDS by LDS-DMA (`buffer_load_dwordx4 ... offen lds`), no staging registers ----
   // The packed weights of a (cout tile, cin block) ARE the LDS image, product by product, so lw is a ring of three 9-tap slots
@@ -311,20 +282,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   // The pieces are inline asm (M0 = LDS address of the piece, set in the statement that uses it): hipcc does not count them,
   // so it neither drains them at a barrier nor waits for them in front of the fragment reads of the other slots.
   const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
-  const unsigned long wbase = (unsigned long)(a.w + (long)nt * a.Cbi * G::WFLOATS);
-  const rsrc_words wrs = {(int)(unsigned)wbase, (int)((wbase >> 32) & 0xffff), a.Cbi * G::WFLOATS * 4, 0x00020000};
+  const rsrc_words wrs = weight_rsrc<false>(a.w + (long)nt * a.Cbi * G::WFLOATS, a.Cbi * G::WFLOATS * 4);
   const int wvo = lane * 16;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
-  auto issue_piece = [&](int cb, int p, int k) __attribute__((always_inline)) {
-    const int j = k * 4 + wvu;                                   // piece of the slot: 256 floats
-    if (k < 4 || j < 18) {
-      unsigned keep;
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep)
-                   : "s"(lw_lds + (unsigned)(p * 9 * 512 + j * 256) * 4u), "v"(wvo), "s"(wrs),
-                     "s"(((cb * 27 + p * 9) * 512 + j * 256) * 4)
-                   : "memory");
-    }
+  auto issue_piece = [&](int cb, int p, int k) __attribute__((always_inline)) {   // piece k of this wave of slot p's 18
+    lds_dma_piece<0, 18>(lw_lds, p * 9 * 512, (cb * 27 + p * 9) * 512, k, wvu, wvo, wrs);
   };
 
   f32x4 xr[2][G::PX];
@@ -418,10 +380,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
 // ---- pair form of the upsampled-input conv (fp32, Z == 2): ResBlock(up=True)'s first conv ----
 // The UPS form of conv3d_mfma runs, per output phase (py, px), a 2 x 2 in-plane window on each of the two z taps of each output
 // plane: four in-plane products per plane pair, 16 tap-products.  The pair identity above is linear in the weights, so it
-// commutes with the pre-summing of the phase weights: with V0, V1, V2 the kz slices of the PHASE weights (conv_pack_ups_host's
+// commutes with the pre-summing of the phase weights: with V0, V1, V2 the kz slices of the PHASE weights (the CF_ZSKIP_UPS pack's
 // sums) the kernel computes P1 = V1 * (X0 + X1), P2 = (V2 - V1) * X1, P3 = (V0 - V1) * X0 on the low-resolution planes, 12
 // tap-products per plane pair, and stores Y0 = P1 + P2, Y1 = P1 + P3 at (2 y + py, 2 x + px) of the two output planes.
-// Weights: conv_pack_zpair_ups_host, per (phase, cout tile, cin block) 12 taps x 512 floats in the order the kernel consumes
+// Weights: conv_pack_host (CF_PAIR_UPS), per (phase, cout tile, cin block) 12 taps x 512 floats in the order the kernel consumes
 // them (product, wy, wx) -- the same size as the z-skip UPS pack.  Staging of X is conv3d_zpair's (the two planes added in
 // registers, three LDS planes).  The weights come by the same LDS-DMA pieces, but a block's 12 taps are only 24 KiB, so the ring
 // is two whole-block slots and a cin block costs two barriers, not four:
@@ -432,10 +394,16 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
 // = 68 736 B at most: two workgroups per CU.  Tiles, wave layout and accumulation order per output element (cin block, product,
 // tap, k) are conv3d_zpair's, so HALF = 0 and 1 give identical bits.
 template <int HALF, int TW>
+struct ZPUGeo : ZPGeo<HALF, TW> {
+  static constexpr int WSLOT = 12 * 512;                         // floats of one (phase, cout tile, cin block)
+  static constexpr int LDS_BYTES = (2 * WSLOT + 3 * ZPGeo<HALF, TW>::XV * 8) * 4;   // the two-slot ring + the planes X0 + X1, X1, X0
+};
+
+template <int HALF, int TW>
 __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
-  using G = ZPGeo<HALF, TW>;
+  using G = ZPUGeo<HALF, TW>;
   constexpr int NC = HALF ? 1 : 2;
-  constexpr int WSLOT = 12 * 512;                                // floats of one (phase, cout tile, cin block)
+  constexpr int WSLOT = G::WSLOT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* lw = lds;                                               // [2][12][512]
   float* lx = lds + 2 * WSLOT;                                   // [3][XV][8]
@@ -445,16 +413,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
   const int i32 = lane & 31, h = lane >> 5;
 
   const int S = a.S;                                             // the LOW-resolution plane; the output plane is 2 S
-  const int tiles_c = S / TW, tiles_r = S / G::TR;
-  const int tiles = tiles_c * tiles_r;
-  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int nt = bid % a.ntile;
-  int mt_ = bid / a.ntile;
-  const int py = (mt_ >> 1) & 1, px = mt_ & 1;                   // the four phases of a tile are neighbours in the grid
-  mt_ >>= 2;
-  const int pg = mt_ / tiles;
-  mt_ -= pg * tiles;
-  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+  const ConvTile t = conv_tile_of<TW, G::TR, true, false>(a);
+  const int nt = t.nt, pg = t.pg, tr = t.tr, tc = t.tc, py = t.py, px = t.px;
 
   long xoff[G::PX];
 #pragma unroll
@@ -479,40 +439,26 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
   const int ct0 = HALF ? (wv >> 1) : 0;
   int xb, on[1], ooff0[1], ooff1[1];
   {
-    const int v = vt * 32 + i32;
-    const int ps = v / (G::TR * TW);
-    const int rem = v - ps * (G::TR * TW);
-    const int r = rem / TW, c = rem - r * TW;
-    xb = ((ps * G::HR + r + py) * G::HC + c + px) * 8 + 4 * h;   // the phase's window starts at (y + py - 1, x + px - 1)
-    const int n = pg * G::NPB + ps;
+    const ConvLane l = conv_lane_of<G::TR, TW, G::HR, G::HC>(vt * 32 + i32, h, py, px);   // the phase's window starts at
+    xb = l.xb;                                                                            // (y + py - 1, x + px - 1)
+    const int n = pg * G::NPB + l.ps;
     on[0] = n;
-    const int y = tr * G::TR + r, x = tc * TW + c;
+    const int y = tr * G::TR + l.r, x = tc * TW + l.c;
     if (n < a.N) { ooff0[0] = ((2 * y + py) * 2 * S + 2 * x + px) * 8; ooff1[0] = ooff0[0] + 4 * S * S * 8; }
     else { ooff0[0] = -1; ooff1[0] = -1; }
   }
   const int wb = ct0 * 256 + i32 * 8 + 4 * h;
 
   f32x16 acc[3][NC];
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int ct = 0; ct < NC; ++ct)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.f;
+  clear_acc(acc);
 
   const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
-  const unsigned long wbase = (unsigned long)(a.w + ((long)(py * 2 + px) * a.ntile + nt) * a.Cbi * WSLOT);
-  const rsrc_words wrs = {(int)(unsigned)wbase, (int)((wbase >> 32) & 0xffff), a.Cbi * WSLOT * 4, 0x00020000};
+  const rsrc_words wrs = weight_rsrc<false>(a.w + ((long)(py * 2 + px) * a.ntile + nt) * a.Cbi * WSLOT, a.Cbi * WSLOT * 4);
   const int wvo = lane * 16;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
   // piece k (0..5) of this wave: 256 floats at j = 4 k + wave of the block's 24
   auto issue_piece = [&](int cb, int k) __attribute__((always_inline)) {
-    const int j = k * 4 + wvu;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lw_lds + (unsigned)((cb & 1) * WSLOT + j * 256) * 4u), "v"(wvo), "s"(wrs), "s"((cb * WSLOT + j * 256) * 4)
-                 : "memory");
+    lds_dma_piece<0, 24>(lw_lds, (cb & 1) * WSLOT, cb * WSLOT, k, wvu, wvo, wrs);
   };
 
   f32x4 xr[2][G::PX];
@@ -589,7 +535,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
 // The 1-D identity F(2,3) gives two neighbouring outputs of a 3-tap filter g with four products instead of six: with d0..d3 the
 // inputs at columns 2j - 1 .. 2j + 2,
 //   T0 = d0 - d2   T1 = d1 + d2   T2 = d2 - d1   T3 = d1 - d3          (formed while staging)
-//   U0 = g0   U1 = (g0 + g1 + g2) / 2   U2 = (g0 - g1 + g2) / 2   U3 = g2   (formed at pack time, conv_pack_xpair_host)
+//   U0 = g0   U1 = (g0 + g1 + g2) / 2   U2 = (g0 - g1 + g2) / 2   U3 = g2   (formed at pack time, conv_pack_host, CF_XPAIR)
 //   out[2j] = U0 T0 + U1 T1 + U2 T2        out[2j + 1] = U1 T1 - U2 T2 - U3 T3.
 // It is linear in the weights, so it applies to each of the three z products of the pair form (V = W1, W2 - W1, W0 - W1 on
 // Xs = X0 + X1, X1, X0): per (product, ky) four transform positions per x-pair replace three taps per voxel, 36 tap-products
@@ -612,6 +558,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
 // HALF = 0: 2 x 24 576 B + 3 x 4 x 80 x 32 B = 79 872 B: two workgroups per CU.
 template <int HALF, int TW>
 struct XPGeo {
+  static constexpr int TW_ = TW;
   static constexpr int NW = 4;                                   // waves per workgroup
   static constexpr int NQ = HALF ? 2 : 4;                        // transform positions q a wave accumulates
   static constexpr int MP = HALF ? 32 : 64;                      // x-pairs per workgroup
@@ -639,14 +586,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
   const int i32 = lane & 31, h = lane >> 5;
 
   const int S = a.S;
-  const int tiles_c = S / TW, tiles_r = S / G::TR;
-  const int tiles = tiles_c * tiles_r;
-  const int bid = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int nt = bid % a.ntile;
-  int mt_ = bid / a.ntile;
-  const int pg = mt_ / tiles;
-  mt_ -= pg * tiles;
-  const int tr = mt_ / tiles_c, tc = mt_ - tr * tiles_c;
+  const ConvTile t = conv_tile_of<TW, G::TR, false, false>(a);
+  const int nt = t.nt, pg = t.pg, tr = t.tr, tc = t.tc;
 
   // ---- staging descriptor: this thread's (row, x-pair, half block); xoff addresses column 2j of plane 0 ----
   long xoff = -1;
@@ -675,44 +616,29 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
   const int q0 = HALF ? (wv >> 1) * 2 : 0;                       // its first q
   int xb, on[1], ooff0;                                          // ooff0: the even column of plane 0 (or -1)
   {
-    const int v = pt * 32 + i32;
-    const int ps = v / (G::TR * G::PWD);
-    const int rem = v - ps * (G::TR * G::PWD);
-    const int r = rem / G::PWD, j = rem - r * G::PWD;
+    const ConvLane l = conv_lane_of<G::TR, G::PWD, G::HR, G::PWD>(pt * 32 + i32, h, 0, 0);
     // lx's offset is part of the lane's base and hidden from the compiler, so that the (product, q, ky) of a fragment is a
     // 16-bit ds_read offset of ONE register (folded into the constant it would pass 64 KiB and take a register per plane)
-    xb = 2 * G::WSLOT + q0 * G::XP * 8 + ((ps * G::HR + r) * G::PWD + j) * 8 + 4 * h;
+    xb = 2 * G::WSLOT + q0 * G::XP * 8 + l.xb;
     asm volatile("" : "+v"(xb));
-    const int n = pg * G::NPB + ps;
+    const int n = pg * G::NPB + l.ps;
     on[0] = n;
-    const int y = tr * G::TR + r, x = tc * TW + 2 * j;
+    const int y = tr * G::TR + l.r, x = tc * TW + 2 * l.c;
     ooff0 = n < a.N ? (y * S + x) * 8 : -1;
   }
   const int wb = q0 * 512 + ch * 256 + i32 * 8 + 4 * h;
 
   f32x16 acc[3][G::NQ];
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int q = 0; q < G::NQ; ++q)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[p][q][r] = 0.f;
+  clear_acc(acc);
 
   const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
-  const unsigned long wbase = (unsigned long)(a.w + (long)nt * a.Cbi * 3 * G::WSLOT);
-  const rsrc_words wrs = {__builtin_amdgcn_readfirstlane((int)(unsigned)wbase),
-                          __builtin_amdgcn_readfirstlane((int)((wbase >> 32) & 0xffff)), a.Cbi * 3 * G::WSLOT * 4, 0x00020000};
+  const rsrc_words wrs = weight_rsrc<true>(a.w + (long)nt * a.Cbi * 3 * G::WSLOT, a.Cbi * 3 * G::WSLOT * 4);
   const int wvo = lane * 16;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
   // piece k (0 .. KP - 1) of this wave of product n: 256 floats at j = NW k + wave of the product's 24
+  // (s_nop 4: the source offset may come straight from the SALU, five wait states ahead of a VMEM read of it)
   auto issue_piece = [&](int n, int k) __attribute__((always_inline)) {
-    const int j = k * G::NW + wvu;
-    unsigned keep;
-    // (s_nop 4: the source offset may come straight from the SALU, five wait states ahead of a VMEM read of it)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 4\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "s"(lw_lds + (unsigned)((n & 1) * G::WSLOT + j * 256) * 4u), "v"(wvo), "s"(wrs), "s"((n * G::WSLOT + j * 256) * 4)
-                 : "memory");
+    lds_dma_piece<4, 4 * G::KP>(lw_lds, (n & 1) * G::WSLOT, n * G::WSLOT, k, wvu, wvo, wrs);
   };
 
   f32x4 xr[2][4];                                                // [plane][column 2j - 1 .. 2j + 2]
@@ -970,155 +896,10 @@ __global__ __launch_bounds__(256, 2) void conv1_mfma(ConvArgs a) {
   conv_epilogue<WM, WN>(a, acc, nt, h, on, ooff, 0);
 }
 
-size_t conv_pack_floats(int Cout, int Cbi, int taps) {
-  const int ntile = (Cout + 63) / 64;
-  return (size_t)ntile * Cbi * taps * 512;
-}
-
-void conv_pack_host(const float* w, int Cout, const int* seg_c, int nseg, int taps, float* out) {
-  int Cin = 0, Cbi = 0;
-  for (int s = 0; s < nseg; ++s) { Cin += seg_c[s]; Cbi += (seg_c[s] + 7) / 8; }
-  const int ntile = (Cout + 63) / 64;
-  memset(out, 0, conv_pack_floats(Cout, Cbi, taps) * sizeof(float));
-  int ci0 = 0, cb0 = 0;
-  for (int s = 0; s < nseg; ++s) {
-    for (int c = 0; c < seg_c[s]; ++c) {
-      const int ci = ci0 + c;
-      const int cb = cb0 + c / 8, c8 = c % 8;
-      for (int co = 0; co < Cout; ++co) {
-        const int nt = co / 64, col = co % 64;
-        const float* src = w + ((size_t)co * Cin + ci) * taps;
-        float* dst = out + (((size_t)nt * Cbi + cb) * taps) * 512 + (size_t)col * 8 + c8;
-        for (int t = 0; t < taps; ++t) dst[(size_t)t * 512] = src[t];
-      }
-    }
-    ci0 += seg_c[s];
-    cb0 += (seg_c[s] + 7) / 8;
-  }
-  (void)ntile;
-}
-
-// Phase weights of the upsampled-input conv (C3Geo, UPS): for output phase (py, px) the 3 x 3 in-plane taps collapse onto a
-// 2 x 2 window of the low-resolution input -- rows: py = 0: {ky 0} | {ky 1, 2}; py = 1: {ky 0, 1} | {ky 2}; columns alike.
-// out: [phase = 2 py + px][conv_pack_host layout with 12 taps (kz, ky', kx')]
-size_t conv_pack_ups_floats(int Cout, int Cbi) { return 4 * conv_pack_floats(Cout, Cbi, 12); }
-void conv_pack_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
-  int Cin = 0, Cbi = 0;
-  for (int s = 0; s < nseg; ++s) { Cin += seg_c[s]; Cbi += (seg_c[s] + 7) / 8; }
-  static const int G0[2][2][2] = {{{0, 0}, {1, 2}}, {{0, 1}, {2, 2}}};       // [phase bit][window pos] -> tap range [lo, hi]
-  const size_t per = conv_pack_floats(Cout, Cbi, 12);
-  float* weff = (float*)malloc((size_t)Cout * Cin * 12 * sizeof(float));
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
-        for (int kz = 0; kz < 3; ++kz)
-          for (int wy = 0; wy < 2; ++wy)
-            for (int wx = 0; wx < 2; ++wx) {
-              float acc = 0.f;
-              for (int ky = G0[py][wy][0]; ky <= G0[py][wy][1]; ++ky)
-                for (int kx = G0[px][wx][0]; kx <= G0[px][wx][1]; ++kx) acc += w[i * 27 + kz * 9 + ky * 3 + kx];
-              weff[i * 12 + kz * 4 + wy * 2 + wx] = acc;
-            }
-      conv_pack_host(weff, Cout, seg_c, nseg, 12, out + (size_t)(py * 2 + px) * per);
-    }
-  free(weff);
-}
-
-// Pair-form weights (conv3d_zpair): per (cout tile, cin block) the 27 taps in the order the kernel consumes them -- W1, W2 - W1,
-// W0 - W1 (kz slices, nine in-plane taps each), differences in fp32.  Same size as the plain 27-tap pack.
-// TM_CONV_ZPAIR=0 (read once, at pack time) keeps the 18-tap z-skip form: A/B timing in separate processes only.
-bool conv_zpair_enabled() {
-  static const bool off = getenv("TM_CONV_ZPAIR") && atoi(getenv("TM_CONV_ZPAIR")) == 0;
-  return !off;
-}
-void conv_pack_zpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
-  int Cin = 0;
-  for (int s = 0; s < nseg; ++s) Cin += seg_c[s];
-  float* weff = (float*)malloc((size_t)Cout * Cin * 27 * sizeof(float));
-  for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
-    for (int t = 0; t < 9; ++t) {
-      const float w0 = w[i * 27 + t], w1 = w[i * 27 + 9 + t], w2 = w[i * 27 + 18 + t];
-      weff[i * 27 + t] = w1;
-      weff[i * 27 + 9 + t] = w2 - w1;
-      weff[i * 27 + 18 + t] = w0 - w1;
-    }
-  conv_pack_host(weff, Cout, seg_c, nseg, 27, out);
-  free(weff);
-}
-
-// x-pair weights (conv3d_xpair): the z differences of conv_pack_zpair_host first, then per (product, ky) the F(2,3) filter
-// transform of the three kx taps g0, g1, g2 of THOSE -- U0 = g0, U1 = ((g0 + g1) + g2) * 0.5, U2 = ((g0 - g1) + g2) * 0.5,
-// U3 = g2, all in fp32 -- in the order the kernel consumes them (product, ky, q): 36 taps, 4/3 of the 27-tap pack.
-// TM_CONV_XPAIR=0 (read once, at pack time) keeps the pair form everywhere: A/B timing in separate processes only.
-bool conv_xpair_enabled() {
-  static const bool off = getenv("TM_CONV_XPAIR") && atoi(getenv("TM_CONV_XPAIR")) == 0;
-  return !off;
-}
-void conv_pack_xpair_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
-  int Cin = 0;
-  for (int s = 0; s < nseg; ++s) Cin += seg_c[s];
-  float* weff = (float*)malloc((size_t)Cout * Cin * 36 * sizeof(float));
-  for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
-    for (int ky = 0; ky < 3; ++ky) {
-      float g[3][3];                                             // [product][kx]
-      for (int kx = 0; kx < 3; ++kx) {
-        const int t = ky * 3 + kx;
-        const float w0 = w[i * 27 + t], w1 = w[i * 27 + 9 + t], w2 = w[i * 27 + 18 + t];
-        g[0][kx] = w1;
-        g[1][kx] = w2 - w1;
-        g[2][kx] = w0 - w1;
-      }
-      for (int p = 0; p < 3; ++p) {
-        float* u = weff + i * 36 + p * 12 + ky * 4;
-        u[0] = g[p][0];
-        u[1] = ((g[p][0] + g[p][1]) + g[p][2]) * 0.5f;
-        u[2] = ((g[p][0] - g[p][1]) + g[p][2]) * 0.5f;
-        u[3] = g[p][2];
-      }
-    }
-  conv_pack_host(weff, Cout, seg_c, nseg, 36, out);
-  free(weff);
-}
-
-// Pair-form phase weights (conv3d_zpair_ups): the phase sums of conv_pack_ups_host first, then the z difference of THOSE --
-// per phase V1, V2 - V1, V0 - V1 (four window taps each), all in fp32.  out: [phase = 2 py + px][conv_pack_host layout with 12
-// taps (product, wy, wx)]: conv_pack_ups_floats floats, as the z-skip pack.
-void conv_pack_zpair_ups_host(const float* w /*[Cout][Cin][27]*/, int Cout, const int* seg_c, int nseg, float* out) {
-  int Cin = 0, Cbi = 0;
-  for (int s = 0; s < nseg; ++s) { Cin += seg_c[s]; Cbi += (seg_c[s] + 7) / 8; }
-  static const int G0[2][2][2] = {{{0, 0}, {1, 2}}, {{0, 1}, {2, 2}}};       // [phase bit][window pos] -> tap range [lo, hi]
-  const size_t per = conv_pack_floats(Cout, Cbi, 12);
-  float* weff = (float*)malloc((size_t)Cout * Cin * 12 * sizeof(float));
-  for (int py = 0; py < 2; ++py)
-    for (int px = 0; px < 2; ++px) {
-      for (size_t i = 0; i < (size_t)Cout * Cin; ++i)
-        for (int wy = 0; wy < 2; ++wy)
-          for (int wx = 0; wx < 2; ++wx) {
-            float v[3];
-            for (int kz = 0; kz < 3; ++kz) {
-              float acc = 0.f;
-              for (int ky = G0[py][wy][0]; ky <= G0[py][wy][1]; ++ky)
-                for (int kx = G0[px][wx][0]; kx <= G0[px][wx][1]; ++kx) acc += w[i * 27 + kz * 9 + ky * 3 + kx];
-              v[kz] = acc;
-            }
-            weff[i * 12 + wy * 2 + wx] = v[1];
-            weff[i * 12 + 4 + wy * 2 + wx] = v[2] - v[1];
-            weff[i * 12 + 8 + wy * 2 + wx] = v[0] - v[1];
-          }
-      conv_pack_host(weff, Cout, seg_c, nseg, 12, out + (size_t)(py * 2 + px) * per);
-    }
-  free(weff);
-}
-
-void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
-  int ci0 = 0, cb0 = 0;
-  for (int s = 0; s < nseg; ++s) {
-    const int nb = (seg_c[s] + 7) / 8;
-    for (int c = 0; c < nb * 8; ++c) out[cb0 * 8 + c] = (c < seg_c[s]) ? v[ci0 + c] : 0.f;
-    ci0 += seg_c[s];
-    cb0 += nb;
-  }
-}
+// ---- launch-size rule and launcher of the MFMA convs ----
+// A launch of `vox` voxels and `tiles` tile columns (cout tiles, x 4 phases for the upsampled forms) takes its large tile where
+// 256-voxel workgroups of it still make 512: below that, smaller workgroups fill more CUs.
+static bool conv_fills_chip(long vox, long tiles) { return (vox / 256) * tiles >= 512; }
 
 // The instantiation of conv1_mfma a 1x1x1 launch of `vox` voxels and `ntile` 64-cout tiles runs: 1 = <1, 2> (128 voxels x 64
 // couts per workgroup), 2 = <2, 2> (256 x 64), 3 = <2, 4> (256 x 128: pairs of cout tiles, so ntile must be even).
@@ -1127,29 +908,50 @@ void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
 // and is refused (0) on an odd ntile.
 int conv1_form(long vox, int ntile, int tile_variant) {
   if (tile_variant == 3) return (ntile & 1) == 0 ? 3 : 0;
-  const int variant = tile_variant ? tile_variant : ((vox / 256) * ntile >= 512 ? 2 : 1);
-  if (variant == 2 && (ntile & 1) == 0 && (vox / 256) * (ntile / 2) >= 512) return 3;
+  const int variant = tile_variant ? tile_variant : (conv_fills_chip(vox, ntile) ? 2 : 1);
+  if (variant == 2 && (ntile & 1) == 0 && conv_fills_chip(vox, ntile / 2)) return 3;
   return variant == 2 ? 2 : 1;
 }
 
-// The tile of a pair-form launch: 1 = the 64-voxel tile (conv3d_zpair<1, *>), 0 = the 128-voxel one.  ovox = output voxels
-// (N * 2 * S * S); the one statement of the rule, for the launcher and for whoever must know the tile beforehand (the fused
-// mid-section exists in the 128-voxel tile only).  No device call.
-int conv_zpair_half(long ovox, int ntile, int S, int tile_variant) {
-  if (S == 4) return 1;
-  const int variant = tile_variant ? tile_variant : ((ovox / 256) * ntile >= 512 ? 2 : 1);
-  return variant == 2 ? 0 : 1;
+int conv_tile(int form, long ovox, int ntile, int S, int tile_variant) {
+  if (S == 4) return 1;                        // 4 x 4 planes: several patches per workgroup of the small tile
+  const long tiles = (form == CF_ZSKIP_UPS || form == CF_PAIR_UPS) ? 4L * ntile : ntile;
+  const int variant = tile_variant ? tile_variant : (conv_fills_chip(ovox, tiles) ? 2 : 1);
+  return variant == 2 ? 2 : 1;
 }
-// The tile of an x-pair launch by the same launch-size rule: 1 = the 64-voxel tile (conv3d_xpair<1, *>), 0 = the
-// 128-voxel one.  No device call.
-int conv_xpair_half(long ovox, int ntile, int tile_variant) {
-  const int variant = tile_variant ? tile_variant : ((ovox / 256) * ntile >= 512 ? 2 : 1);
-  return variant == 2 ? 0 : 1;
+
+// One k x 3 x 3 launch: KERN over the tiles of geometry G (TW x TR voxels of NPB patches, LDS_BYTES of dynamic LDS), `factor`
+// workgroups per (patch group, tile, cout tile): output planes and / or the four phases.
+template <void (*KERN)(ConvArgs), class G, int BLOCK = 256>
+static hipError_t launch_tiled(const ConvArgs& a, long factor, hipStream_t s) {
+  static DevOnce attr_once;
+  if (attr_once.need()) {
+    hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES);
+    if (e != hipSuccess) return e;
+    attr_once.mark();
+  }
+  const long tiles = (long)(a.S / G::TW_) * (a.S / G::TR);
+  const long pgs = (a.N + G::NPB - 1) / G::NPB;
+  hipLaunchKernelGGL(KERN, dim3((unsigned)(pgs * tiles * factor * a.ntile)), dim3(BLOCK), G::LDS_BYTES, s, a);
+  return hipGetLastError();
 }
-// TM_CONV_FUSE_MID=0 (read once): fp32 ResBlocks keep the separate mid-block norm pass.  A/B timing in separate processes only.
-bool conv_fuse_mid_enabled() {
-  static const bool off = getenv("TM_CONV_FUSE_MID") && atoi(getenv("TM_CONV_FUSE_MID")) == 0;
-  return !off;
+// f(TW) with the tile width of a plane of S = 8 .. 128 as a compile-time constant
+template <int MAXTW, class F>
+static hipError_t with_tile_width(int S, F f) {
+  if constexpr (MAXTW >= 32)
+    if (S >= 32) return f(std::integral_constant<int, 32>{});
+  if (S >= 16) return f(std::integral_constant<int, 16>{});
+  return f(std::integral_constant<int, 8>{});
+}
+template <int NZI, bool UPS>
+static hipError_t launch_c3(const ConvArgs& a, bool large, hipStream_t s) {
+  const long factor = UPS ? 4L * a.Z : a.Z;
+  if (a.S == 4) return launch_tiled<conv3d_mfma<NZI, 1, 4, UPS>, C3Geo<NZI, 1, 4, UPS>>(a, factor, s);
+  return with_tile_width<32>(a.S, [&](auto tw) {
+    constexpr int TW = decltype(tw)::value;
+    return large ? launch_tiled<conv3d_mfma<NZI, 2, TW, UPS>, C3Geo<NZI, 2, TW, UPS>>(a, factor, s)
+                 : launch_tiled<conv3d_mfma<NZI, 1, TW, UPS>, C3Geo<NZI, 1, TW, UPS>>(a, factor, s);
+  });
 }
 
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
@@ -1159,19 +961,21 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   a.y = L.y.p; a.y_nstride = L.y.nstride; a.y_plane = L.y.plane(); a.Cob = L.y.Cb;
   a.res = L.res ? L.res->p : nullptr; a.res_nstride = L.res ? L.res->nstride : 0;
   a.gate = L.gate ? L.gate->p : nullptr; a.gate_nstride = L.gate ? L.gate->nstride : 0;
+  const int form = L.w.form;
+  if (L.w.taps != conv_form_taps(form)) return hipErrorInvalidValue;
   if (L.gate_half) {
     int ls = 0;
     while ((1 << ls) < L.y.H) ++ls;
-    if (!L.gate || L.w.taps != 1 || (1 << ls) != L.y.H || L.y.H != L.y.W || ls < 1) return hipErrorInvalidValue;
+    if (!L.gate || form != CF_1X1 || (1 << ls) != L.y.H || L.y.H != L.y.W || ls < 1) return hipErrorInvalidValue;
     a.gate_ls = ls;
   }
   a.N = L.x.N; a.S = L.x.H; a.Z = L.x.Z; a.Cbi = L.w.Cbi; a.ntile = L.w.ntile; a.flags = L.flags;
   if (L.x.Cb != L.w.Cbi || L.x.H != L.x.W) return hipErrorInvalidValue;
   if (L.fuse_norm) {             // the pair form's 128-voxel tile at 64 couts only; everything else is refused before any device call
-    if (!L.w.zpair || L.w.taps != 27 || L.zmode != ZM_PAD1 || L.x.Z != 2 || L.w.Cout != 64 || L.w.ntile != 1 || L.res || L.gate ||
-        L.flags || !L.norm_w || !L.mod_scale || !L.mod_shift || L.per_image < 1)
+    if (form != CF_PAIR || L.zmode != ZM_PAD1 || L.x.Z != 2 || L.w.Cout != 64 || L.w.ntile != 1 || L.res || L.gate || L.flags ||
+        !L.norm_w || !L.mod_scale || !L.mod_shift || L.per_image < 1)
       return hipErrorInvalidValue;
-    if (conv_zpair_half((long)L.x.N * 2 * L.x.H * L.x.H, 1, L.x.H, L.tile_variant)) return hipErrorInvalidValue;
+    if (conv_tile(form, (long)L.x.N * 2 * L.x.H * L.x.H, 1, L.x.H, L.tile_variant) != 2) return hipErrorInvalidValue;
     if (!L.a2.p || L.a2.Cb != 8 || L.a2.N != L.x.N || L.a2.Z != 2 || L.a2.H != L.x.H || L.a2.W != L.x.H) return hipErrorInvalidValue;
     if (L.y.Cb != 8 || L.y.Z != 2 || L.y.H != L.x.H) return hipErrorInvalidValue;       // y carries the geometry only
     a.y = L.a2.p; a.y_nstride = L.a2.nstride; a.y_plane = L.a2.plane();
@@ -1180,193 +984,84 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
   }
   if (L.y.Cb > L.w.ntile * 8 || L.y.N != L.x.N) return hipErrorInvalidValue;
   const long vox = (long)a.N * a.Z * a.S * a.S;
-  if (L.w.taps == 1) {
+  if (form == CF_1X1) {
     if (L.flags & EPI_UP2) return hipErrorInvalidValue;
     if (L.y.H != L.x.H || L.y.Z != L.x.Z) return hipErrorInvalidValue;
-    const int form = conv1_form(vox, a.ntile, L.tile_variant);
-    if (form == 3) {
+    const int form1 = conv1_form(vox, a.ntile, L.tile_variant);
+    if (form1 == 3) {
       const long mt = (vox + 255) / 256;                  // 128-cout x 256-voxel workgroups
       a.ntile /= 2;
       hipLaunchKernelGGL((conv1_mfma<2, 4>), dim3((unsigned)(mt * a.ntile)), dim3(256), 0, s, a);
-    } else if (form == 2) {
+    } else if (form1 == 2) {
       const long mt = (vox + 255) / 256;
       hipLaunchKernelGGL((conv1_mfma<2, 2>), dim3((unsigned)(mt * a.ntile)), dim3(256), 0, s, a);
-    } else if (form == 1) {
+    } else if (form1 == 1) {
       const long mt = (vox + 127) / 128;
       hipLaunchKernelGGL((conv1_mfma<1, 2>), dim3((unsigned)(mt * a.ntile)), dim3(256), 0, s, a);
     } else return hipErrorInvalidValue;
     return hipGetLastError();
   }
-  // ---- k x 3 x 3 kernels ----
+  // ---- k x 3 x 3 kernels: what each form takes; zmode is the caller's statement and must agree with the form ----
   const int S = a.S;
-  int nzi;
+  const bool z2 = L.x.Z == 2 && L.y.Z == 2, up2 = (L.flags & EPI_UP2) != 0;
   a.Zin = L.x.Z; a.zoff = 0;
-  if (L.zmode == ZM_PAD1 && L.w.taps == 9) {   // 3x3x3 pad 1 on ONE plane: only the centre z slice meets data (packed as 9 taps)
-    if (L.x.Z != 1 || L.y.Z != 1) return hipErrorInvalidValue;
-    nzi = 1;
-  } else if (L.zmode == ZM_PAD1 && L.w.xpair) {  // 3x3x3 pad 1 over two planes, packed by conv_pack_xpair_host: conv3d_xpair only
-    if (L.w.taps != 36 || L.x.Z != 2 || L.y.Z != 2 || L.x.H < 8 || (L.flags & EPI_UP2) || L.fuse_norm) return hipErrorInvalidValue;
-    nzi = 2;
-  } else if (L.w.xpair) {
-    return hipErrorInvalidValue;
-  } else if (L.zmode == ZM_PAD1) {             // 3x3x3 pad 1
-    if (L.w.taps != 27 || L.y.Z != L.x.Z) return hipErrorInvalidValue;
-    if (L.x.Z == 2) nzi = 2;                   // z-skip form, or the pair form when the weights were packed for it
-    else if (L.w.zpair) return hipErrorInvalidValue;
-    else { nzi = 3; a.zoff = -1; }
-  } else if (L.zmode == ZM_INPLANE) {  // 1x3x3
-    if (L.w.taps != 9 || L.y.Z != L.x.Z) return hipErrorInvalidValue;
-    nzi = 1;
-  } else if (L.zmode == ZM_VALID) {    // 3x3x3 valid in z
-    if (L.w.taps != 27 || L.y.Z != L.x.Z - 2) return hipErrorInvalidValue;
-    nzi = 3;
-  } else if (L.zmode == ZM_UPS) {      // 3x3x3 pad 1 of the nearest-x2 upsampled x, on the low-resolution x (phase weights)
-    if (L.w.taps != 12 || L.x.Z != 2 || L.y.Z != 2 || (L.flags & EPI_UP2) || L.res || L.gate) return hipErrorInvalidValue;
-    nzi = 2;
-  } else return hipErrorInvalidValue;
+  switch (form) {
+    case CF_INPLANE:               // 1x3x3 at any Z, or 3x3x3 pad 1 on ONE plane: only the centre z slice meets data
+      if (L.zmode == ZM_PAD1 ? (L.x.Z != 1 || L.y.Z != 1) : (L.zmode != ZM_INPLANE || L.y.Z != L.x.Z)) return hipErrorInvalidValue;
+      break;
+    case CF_PLANES3:               // 3x3x3 valid in z, or pad 1 (planes outside [0, Zin) zero) at any Z but the 2 of CF_ZSKIP
+      if (L.zmode == ZM_PAD1 ? (L.y.Z != L.x.Z || L.x.Z == 2) : (L.zmode != ZM_VALID || L.y.Z != L.x.Z - 2)) return hipErrorInvalidValue;
+      if (L.zmode == ZM_PAD1) a.zoff = -1;
+      break;
+    case CF_ZSKIP: case CF_PAIR:   // 3x3x3 pad 1 over two planes
+      if (L.zmode != ZM_PAD1 || !z2) return hipErrorInvalidValue;
+      break;
+    case CF_XPAIR:                 // ... with Winograd along x: planes of at least 8 x 8, plain epilogue
+      if (L.zmode != ZM_PAD1 || !z2 || L.x.H < 8 || up2) return hipErrorInvalidValue;
+      break;
+    case CF_ZSKIP_UPS: case CF_PAIR_UPS:   // 3x3x3 pad 1 of the nearest-x2 upsampled x, on the low-resolution x
+      if (L.zmode != ZM_UPS || !z2 || up2 || L.res || L.gate) return hipErrorInvalidValue;
+      break;
+    default: return hipErrorInvalidValue;
+  }
   a.Z = L.y.Z;
   if (S != 4 && S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return hipErrorInvalidValue;
-  if (((L.flags & EPI_UP2) || L.zmode == ZM_UPS) ? (L.y.H != 2 * S) : (L.y.H != S)) return hipErrorInvalidValue;
+  if ((up2 || L.zmode == ZM_UPS) ? (L.y.H != 2 * S) : (L.y.H != S)) return hipErrorInvalidValue;
   if (L.res_half) {
     int ls = 0;
     while ((1 << ls) < L.y.H) ++ls;
-    if (!L.res || (1 << ls) != L.y.H || L.y.H != L.y.W || ls < 1 || (L.flags & EPI_UP2)) return hipErrorInvalidValue;
+    if (!L.res || (1 << ls) != L.y.H || L.y.H != L.y.W || ls < 1 || up2) return hipErrorInvalidValue;
     a.res_ls = ls;
   }
-  const long ovox = (long)a.N * a.Z * a.S * a.S;
-  if (L.zmode == ZM_UPS) {
-#define TM_LAUNCHU(WM, TW)                                                                       \
-  do {                                                                                          \
-    using G = C3Geo<2, WM, TW, true>;                                                           \
-    static DevOnce attr_once;                                                                   \
-    if (attr_once.need()) {                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)conv3d_mfma<2, WM, TW, true>,             \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
-      if (e != hipSuccess) return e;                                                            \
-      attr_once.mark();                                                                         \
-    }                                                                                           \
-    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
-    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
-    const long grid = pgs * a.Z * tiles * 4 * a.ntile;                                          \
-    hipLaunchKernelGGL((conv3d_mfma<2, WM, TW, true>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
-  } while (0)
-    const int variant = L.tile_variant ? L.tile_variant : ((ovox / 256) * 4 * a.ntile >= 512 ? 2 : 1);
-    if (L.w.zpair) {                           // packed by conv_pack_zpair_ups_host: the pair form, the tile by the same rule
-#define TM_LAUNCHZU(HALF, TW)                                                                    \
-  do {                                                                                          \
-    using G = ZPGeo<HALF, TW>;                                                                  \
-    constexpr int LDSB = (2 * 12 * 512 + 3 * G::XV * 8) * 4;                                    \
-    static DevOnce attr_once;                                                                   \
-    if (attr_once.need()) {                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)conv3d_zpair_ups<HALF, TW>,               \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);     \
-      if (e != hipSuccess) return e;                                                            \
-      attr_once.mark();                                                                         \
-    }                                                                                           \
-    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
-    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
-    const long grid = pgs * tiles * 4 * a.ntile;                                                \
-    hipLaunchKernelGGL((conv3d_zpair_ups<HALF, TW>), dim3((unsigned)grid), dim3(256), LDSB, s, a); \
-  } while (0)
-      if (S == 4) TM_LAUNCHZU(1, 4);
-      else if (variant == 2) { if (S >= 32) TM_LAUNCHZU(0, 32); else if (S == 16) TM_LAUNCHZU(0, 16); else TM_LAUNCHZU(0, 8); }
-      else { if (S >= 32) TM_LAUNCHZU(1, 32); else if (S == 16) TM_LAUNCHZU(1, 16); else TM_LAUNCHZU(1, 8); }
-#undef TM_LAUNCHZU
-      return hipGetLastError();
-    }
-    if (S < 8) { if (S != 4) return hipErrorInvalidValue; TM_LAUNCHU(1, 4); }
-    else if (variant == 2) { if (S >= 32) TM_LAUNCHU(2, 32); else if (S == 16) TM_LAUNCHU(2, 16); else TM_LAUNCHU(2, 8); }
-    else { if (S >= 32) TM_LAUNCHU(1, 32); else if (S == 16) TM_LAUNCHU(1, 16); else TM_LAUNCHU(1, 8); }
-#undef TM_LAUNCHU
-    return hipGetLastError();
+  // the form is the layer's (fixed at pack time); the tile follows the launch size
+  const bool large = conv_tile(form, (long)a.N * a.Z * a.S * a.S, a.ntile, S, L.tile_variant) == 2;
+  switch (form) {
+    case CF_INPLANE: return launch_c3<1, false>(a, large, s);
+    case CF_PLANES3: return launch_c3<3, false>(a, large, s);
+    case CF_ZSKIP: return launch_c3<2, false>(a, large, s);
+    case CF_ZSKIP_UPS: return launch_c3<2, true>(a, large, s);
+    case CF_PAIR:
+      if (S == 4) return launch_tiled<conv3d_zpair<1, 4, false>, ZPGeo<1, 4>>(a, 1, s);   // 4 patches per workgroup (8 would not
+      return with_tile_width<32>(S, [&](auto tw) {                                        // leave LDS for two workgroups per CU)
+        constexpr int TW = decltype(tw)::value;
+        if (L.fuse_norm) return launch_tiled<conv3d_zpair<0, TW, true>, ZPGeo<0, TW>>(a, 1, s);   // the 128-voxel tile: checked above
+        return large ? launch_tiled<conv3d_zpair<0, TW, false>, ZPGeo<0, TW>>(a, 1, s)
+                     : launch_tiled<conv3d_zpair<1, TW, false>, ZPGeo<1, TW>>(a, 1, s);
+      });
+    case CF_PAIR_UPS:
+      if (S == 4) return launch_tiled<conv3d_zpair_ups<1, 4>, ZPUGeo<1, 4>>(a, 4, s);
+      return with_tile_width<32>(S, [&](auto tw) {
+        constexpr int TW = decltype(tw)::value;
+        return large ? launch_tiled<conv3d_zpair_ups<0, TW>, ZPUGeo<0, TW>>(a, 4, s)
+                     : launch_tiled<conv3d_zpair_ups<1, TW>, ZPUGeo<1, TW>>(a, 4, s);
+      });
+    default:   // CF_XPAIR
+      return with_tile_width<16>(S, [&](auto tw) {
+        constexpr int TW = decltype(tw)::value;
+        return large ? launch_tiled<conv3d_xpair<0, TW>, XPGeo<0, TW>, 64 * XPGeo<0, TW>::NW>(a, 1, s)
+                     : launch_tiled<conv3d_xpair<1, TW>, XPGeo<1, TW>, 64 * XPGeo<1, TW>::NW>(a, 1, s);
+      });
   }
-  if (L.w.xpair) {                             // the form is the layer's (fixed at pack time); the tile follows the launch size
-#define TM_LAUNCHX(HALF, TW)                                                                     \
-  do {                                                                                          \
-    using G = XPGeo<HALF, TW>;                                                                  \
-    static DevOnce attr_once;                                                                   \
-    if (attr_once.need()) {                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)conv3d_xpair<HALF, TW>,                   \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
-      if (e != hipSuccess) return e;                                                            \
-      attr_once.mark();                                                                         \
-    }                                                                                           \
-    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
-    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
-    const long grid = pgs * tiles * a.ntile;                                                    \
-    hipLaunchKernelGGL((conv3d_xpair<HALF, TW>), dim3((unsigned)grid), dim3(64 * G::NW), G::LDS_BYTES, s, a); \
-  } while (0)
-    if (conv_xpair_half(ovox, a.ntile, L.tile_variant)) { if (S >= 16) TM_LAUNCHX(1, 16); else TM_LAUNCHX(1, 8); }
-    else { if (S >= 16) TM_LAUNCHX(0, 16); else TM_LAUNCHX(0, 8); }
-#undef TM_LAUNCHX
-    return hipGetLastError();
-  }
-  int variant = L.tile_variant ? L.tile_variant : ((ovox / 256) * a.ntile >= 512 ? 2 : 1);
-  if (L.fuse_norm && !L.w.zpair) return hipErrorInvalidValue;
-  if (L.w.zpair) {                             // the form is the layer's (fixed at pack time); the tile follows the launch size
-    if (L.zmode != ZM_PAD1 || nzi != 2) return hipErrorInvalidValue;
-#define TM_LAUNCHZ(HALF, TW, FUSE)                                                                \
-  do {                                                                                          \
-    using G = ZPGeo<HALF, TW>;                                                                  \
-    static DevOnce attr_once;                                                                   \
-    if (attr_once.need()) {                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)conv3d_zpair<HALF, TW, FUSE>,             \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
-      if (e != hipSuccess) return e;                                                            \
-      attr_once.mark();                                                                         \
-    }                                                                                           \
-    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
-    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
-    const long grid = pgs * tiles * a.ntile;                                                    \
-    hipLaunchKernelGGL((conv3d_zpair<HALF, TW, FUSE>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
-  } while (0)
-    if (L.fuse_norm) {                         // the 128-voxel tile: checked above (conv_zpair_half)
-      if (S >= 32) TM_LAUNCHZ(0, 32, true); else if (S == 16) TM_LAUNCHZ(0, 16, true); else TM_LAUNCHZ(0, 8, true);
-    } else if (S == 4) TM_LAUNCHZ(1, 4, false);  // 4 patches per workgroup (8 would not leave LDS for two workgroups per CU)
-    else if (variant == 2) { if (S >= 32) TM_LAUNCHZ(0, 32, false); else if (S == 16) TM_LAUNCHZ(0, 16, false); else TM_LAUNCHZ(0, 8, false); }
-    else { if (S >= 32) TM_LAUNCHZ(1, 32, false); else if (S == 16) TM_LAUNCHZ(1, 16, false); else TM_LAUNCHZ(1, 8, false); }
-#undef TM_LAUNCHZ
-    return hipGetLastError();
-  }
-#define TM_LAUNCH3(NZI, WM, TW)                                                                  \
-  do {                                                                                          \
-    using G = C3Geo<NZI, WM, TW>;                                                               \
-    static DevOnce attr_once;                                                                   \
-    if (attr_once.need()) {                                                                     \
-      hipError_t e = hipFuncSetAttribute((const void*)conv3d_mfma<NZI, WM, TW>,                 \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES); \
-      if (e != hipSuccess) return e;                                                            \
-      attr_once.mark();                                                                         \
-    }                                                                                           \
-    const long tiles = (long)(S / TW) * (S / G::TR);                                            \
-    const long pgs = (a.N + G::NPB - 1) / G::NPB;                                               \
-    const long grid = pgs * a.Z * tiles * a.ntile;                                              \
-    hipLaunchKernelGGL((conv3d_mfma<NZI, WM, TW>), dim3((unsigned)grid), dim3(256), G::LDS_BYTES, s, a); \
-  } while (0)
-  if (nzi == 2) {
-    if (S < 8) { if (S != 4) return hipErrorInvalidValue; TM_LAUNCH3(2, 1, 4); }
-    else if (variant == 2) {
-      if (S >= 32) TM_LAUNCH3(2, 2, 32); else if (S == 16) TM_LAUNCH3(2, 2, 16); else TM_LAUNCH3(2, 2, 8);
-    } else {
-      if (S >= 32) TM_LAUNCH3(2, 1, 32); else if (S == 16) TM_LAUNCH3(2, 1, 16); else TM_LAUNCH3(2, 1, 8);
-    }
-  } else if (nzi == 1) {
-    if (S == 4) TM_LAUNCH3(1, 1, 4);
-    else if (variant == 2) {
-      if (S >= 32) TM_LAUNCH3(1, 2, 32); else if (S == 16) TM_LAUNCH3(1, 2, 16); else TM_LAUNCH3(1, 2, 8);
-    } else {                                   // small grids: 128-voxel workgroups fill more CUs
-      if (S >= 32) TM_LAUNCH3(1, 1, 32); else if (S == 16) TM_LAUNCH3(1, 1, 16); else TM_LAUNCH3(1, 1, 8);
-    }
-  } else {
-    if (S == 4) TM_LAUNCH3(3, 1, 4);
-    else if (variant == 2) {
-      if (S >= 32) TM_LAUNCH3(3, 2, 32); else if (S == 16) TM_LAUNCH3(3, 2, 16); else TM_LAUNCH3(3, 2, 8);
-    } else {
-      if (S >= 32) TM_LAUNCH3(3, 1, 32); else if (S == 16) TM_LAUNCH3(3, 1, 16); else TM_LAUNCH3(3, 1, 8);
-    }
-  }
-#undef TM_LAUNCH3
-  return hipGetLastError();
 }
 
 // ==========================================================================================

@@ -52,10 +52,9 @@ struct ResW {
   const uint16_t* skiph = nullptr;
   int emb_off = 0;
   // fp32: out_layers' norm -> modulate -> SiLU runs in c1's epilogue (conv3d_zpair<0, *, true>) wherever the launch takes the
-  // 128-voxel tile.  Decided once, where c1 is packed: pair form, 64 output channels, TM_CONV_FUSE_MID not 0.
+  // 128-voxel tile.  Decided once, where c1 is packed (conv_pick_form)
   bool fuse_mid = false;
-  // a decoder block of the deepest level (its launches are the smallest of the step: the interior patches at patch / 8): its
-  // convs stay on the pair form, whose 64-voxel tile is the faster there (profiles/fp32_xpair.txt).  A role, fixed at pack time.
+  // a decoder block of the deepest level (its launches are the smallest of the step: the interior patches at patch / 8): ROLE_DEEP
   bool dec_deep = false;
 };
 struct AttnW {
@@ -81,10 +80,9 @@ struct DecEntry { int lvl; std::vector<Op> ops; };
 struct tm_model {
   tm_config cfg;
   int z = 0, gn = 0, D = 0, L = 4;
-  bool zpair = false;            // fp32, z == 2: the ResBlock 3x3x3 convs are packed for and run in the pair form (conv3d_zpair)
-  // ... and, of those, the ones tm_model_finalize moves on to the x-pair form (conv3d_xpair): every level's plane is at least
-  // 8 x 8 (patch size 64 or 128; a 4 x 4 plane has no x-pair tile), TM_CONV_XPAIR not 0.  Fixed at pack time, never by N.
-  bool xpair = false;
+  // the form of every fp32 conv is conv_pick_form's, fixed at pack time (tm_model_finalize) and never by N; deep8: every level's
+  // plane is at least 8 x 8 (patch size 64 or 128)
+  bool deep8 = false;
   int rw[4];                          // rna pyramid widths
   std::vector<std::pair<std::string, std::vector<int64_t>>> spec;
   std::map<std::string, HostParam> host;
@@ -115,7 +113,7 @@ struct tm_model {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   size_t prof_used = 0;
   double prof_nominal = 0, prof_bytes = 0;
-  double prof_xpair = 0;              // the part of prof_nominal launched in the x-pair form (18 of the nominal 54 tap-products)
+  double prof_xp_flops = 0;              // the part of prof_nominal launched in the x-pair form (18 of the nominal 54 tap-products)
   struct ProfTag { int cin, cout, S, N; double nominal; };
   std::vector<ProfTag> prof_tag;     // per counted launch (TM_PROF_LAYERS)
 };
@@ -322,8 +320,7 @@ extern "C" int tm_model_create(const tm_config* cfg, tm_model** out) {
   tm_model* m = new tm_model();
   m->cfg = *cfg;
   m->z = (cfg->rna_slc + 1) / 2;
-  m->zpair = m->z == 2 && !is_h16(cfg->dtype) && conv_zpair_enabled();
-  m->xpair = m->zpair && conv_xpair_enabled() && (cfg->patch_size >> 3) >= 8;   // the deepest of the four levels: patch / 8
+  m->deep8 = (cfg->patch_size >> 3) >= 8;                          // the deepest of the four levels: patch / 8
   m->gn = cfg->patch_size / 16;
   m->D = m->gn * m->gn * cfg->rna_slc;
   m->gene_mfma = m->D == 64 && cfg->rna_num <= 232 && cfg->rna_num != 81;
@@ -380,37 +377,32 @@ struct FixH { const uint16_t** slot; size_t off; };   // offsets in floats into 
 
 static const std::vector<float>& P(tm_model* m, const std::string& k) { return m->host[k].data; }
 
+// bias zero padded to the cout tiles
+static void pack_bias(Packer& pk, std::vector<Fix>& fx, ConvW& cw, const std::vector<float>& b) {
+  const size_t boff = pk.reserve((size_t)cw.ntile * 64);
+  for (int i = 0; i < cw.Cout; ++i) pk.buf[boff + i] = b[i];
+  fx.push_back({&cw.bias, boff});
+}
+// fp32 conv weights of `wkey` ([Cout][Cin][27], or [9] / [1] for the 1x3x3 and 1x1x1 convs) in `form`, with the bias
 static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, const std::string& wkey,
-                      const std::string& bkey, int Cout, const std::vector<int>& seg, int taps, bool centre_slice = false,
-                      bool zpair = false, bool xpair = false) {
+                      const std::string& bkey, int Cout, const std::vector<int>& seg, int form) {
   int cbi = 0, cin = 0;
   for (int c : seg) { cbi += (c + 7) / 8; cin += c; }
-  // centre_slice: a 3x3x3 pad-1 conv applied to ONE plane (z_size 1, rna_slc 1) only ever multiplies its kz = 1 slice
+  // CF_INPLANE of a 3x3x3 pad-1 conv: applied to ONE plane (z_size 1, rna_slc 1) it only ever multiplies its kz = 1 slice
   // with data -- pack those 9 taps and run the in-plane kernel
   std::vector<float> centre;
   const float* wsrc = P(m, wkey).data();
-  if (centre_slice) {
+  if (form == CF_INPLANE && P(m, wkey).size() == (size_t)Cout * cin * 27) {
     centre.resize((size_t)Cout * cin * 9);
     for (size_t i = 0; i < (size_t)Cout * cin; ++i)
       for (int t = 0; t < 9; ++t) centre[i * 9 + t] = wsrc[i * 27 + 9 + t];
     wsrc = centre.data();
-    taps = 9;
   }
-  cw.Cout = Cout; cw.Cbi = cbi; cw.taps = taps; cw.ntile = (Cout + 63) / 64;
-  // zpair: a 3x3x3 pad-1 conv over TWO planes (z_size 2) packed for the pair form (three in-plane products per plane pair)
-  // xpair: the same conv packed for the x-pair form instead (36 transformed taps; conv3d_xpair)
-  cw.xpair = (zpair && xpair && taps == 27) ? 1 : 0;
-  cw.zpair = (zpair && taps == 27 && !cw.xpair) ? 1 : 0;
-  if (cw.xpair) cw.taps = taps = 36;
-  size_t off = pk.reserve(conv_pack_floats(Cout, cbi, taps));
-  if (cw.xpair) conv_pack_xpair_host(wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
-  else if (cw.zpair) conv_pack_zpair_host(wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
-  else conv_pack_host(wsrc, Cout, seg.data(), (int)seg.size(), taps, pk.buf.data() + off);
+  cw = conv_w(form, Cout, cbi);
+  size_t off = pk.reserve(conv_pack_floats(form, Cout, cbi));
+  conv_pack_host(form, wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
   fx.push_back({&cw.w, off});
-  size_t boff = pk.reserve((size_t)cw.ntile * 64);
-  const std::vector<float>& b = P(m, bkey);
-  for (int i = 0; i < Cout; ++i) pk.buf[boff + i] = b[i];
-  fx.push_back({&cw.bias, boff});
+  pack_bias(pk, fx, cw, P(m, bkey));
 }
 // 3x3x3 conv for the bf16 path: bf16 packed weights (tm_conv_bf16.hip layout) + the fp32 bias
 static void pack_conv_h(tm_model* m, Packer& pk, std::vector<Fix>& fx, std::vector<FixH>& fxh, ConvW& cw,
@@ -427,16 +419,13 @@ static void pack_conv_h(tm_model* m, Packer& pk, std::vector<Fix>& fx, std::vect
     for (size_t i = 0; i < (size_t)Cout * cin; ++i)
       for (int t = 0; t < 9; ++t) w27[i * 27 + 9 + t] = w9[i * 9 + t];
   }
-  cw.Cout = Cout; cw.Cbi = cbi; cw.taps = 27; cw.ntile = (Cout + 63) / 64; cw.w = nullptr;
+  cw = conv_w(CF_PLANES3, Cout, cbi);                  // geometry and bias only: the 16-bit pack lives in *wslot
   const size_t elems = conv_bf16_pack_elems(Cout, cbi);
   size_t off = pk.reserve((elems + 1) / 2);
   (m->cfg.dtype == TM_DTYPE_F16 ? conv_f16_pack_host : conv_bf16_pack_host)(inplane ? w27.data() : P(m, wkey).data(), Cout, seg.data(),
                                                                             (int)seg.size(), (uint16_t*)(pk.buf.data() + off));
   fxh.push_back({wslot, off});
-  size_t boff = pk.reserve((size_t)cw.ntile * 64);
-  const std::vector<float>& b = P(m, bkey);
-  for (int i = 0; i < Cout; ++i) pk.buf[boff + i] = b[i];
-  fx.push_back({&cw.bias, boff});
+  pack_bias(pk, fx, cw, P(m, bkey));
 }
 // rows of several [rows_i][Cin] matrices stacked into one conv1 weight
 static void pack_linear_stack(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw,
@@ -450,13 +439,11 @@ static void pack_linear_stack(tm_model* m, Packer& pk, std::vector<Fix>& fx, Con
     memcpy(b.data() + i * rows_each, bi.data(), rows_each * sizeof(float));
   }
   int seg = Cin;
-  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.taps = 1; cw.ntile = (Cout + 63) / 64;
-  size_t off = pk.reserve(conv_pack_floats(Cout, cw.Cbi, 1));
-  conv_pack_host(w.data(), Cout, &seg, 1, 1, pk.buf.data() + off);
+  cw = conv_w(CF_1X1, Cout, (Cin + 7) / 8);
+  size_t off = pk.reserve(conv_pack_floats(CF_1X1, Cout, cw.Cbi));
+  conv_pack_host(CF_1X1, w.data(), Cout, &seg, 1, pk.buf.data() + off);
   fx.push_back({&cw.w, off});
-  size_t boff = pk.reserve((size_t)cw.ntile * 64);
-  for (int i = 0; i < Cout; ++i) pk.buf[boff + i] = b[i];
-  fx.push_back({&cw.bias, boff});
+  pack_bias(pk, fx, cw, b);
 }
 static void pack_linear_stack_h(tm_model* m, Packer& pk, std::vector<Fix>& fx, std::vector<FixH>& fxh, ConvW& cw,
                                 const uint16_t** wslot, const std::vector<std::string>& pfx, int rows_each,
@@ -472,15 +459,13 @@ static void pack_linear_stack_h(tm_model* m, Packer& pk, std::vector<Fix>& fx, s
     memcpy(b.data() + i * rows_each, bi.data(), rows_each * sizeof(float));
   }
   (void)is_conv_key;
-  cw.Cout = Cout; cw.Cbi = cbi; cw.taps = 1; cw.ntile = (Cout + 63) / 64; cw.w = nullptr;
+  cw = conv_w(CF_1X1, Cout, cbi);                      // geometry and bias only: the 16-bit pack lives in *wslot
   const size_t elems = conv1_bf16_pack_elems(Cout, cbi);
   size_t off = pk.reserve((elems + 1) / 2);
   (m->cfg.dtype == TM_DTYPE_F16 ? conv1_f16_pack_host : conv1_bf16_pack_host)(w.data(), Cout, seg.data(), (int)seg.size(),
                                                                               (uint16_t*)(pk.buf.data() + off));
   fxh.push_back({wslot, off});
-  size_t boff = pk.reserve((size_t)cw.ntile * 64);
-  for (int i = 0; i < Cout; ++i) pk.buf[boff + i] = b[i];
-  fx.push_back({&cw.bias, boff});
+  pack_bias(pk, fx, cw, b);
 }
 static void pack_vec(Packer& pk, std::vector<Fix>& fx, const float** slot, const std::vector<float>& v,
                      const std::vector<int>& seg) {
@@ -545,7 +530,8 @@ extern "C" int tm_model_finalize(tm_model* m) {
     pack_raw(pk, fx, &m->gene.b1, P(m, g + ".mlp.fc1.bias"));
     pack_transposed(pk, fx, &m->gene.w2_t, P(m, g + ".mlp.fc2.weight"), d, 4 * d);
     pack_raw(pk, fx, &m->gene.b2, P(m, g + ".mlp.fc2.bias"));
-    if (m->downz_mfma) pack_conv(m, pk, fx, m->downz, g + ".down_z.weight", g + ".down_z.bias", c.rna_num, {c.rna_num}, 27);
+    if (m->downz_mfma) pack_conv(m, pk, fx, m->downz, g + ".down_z.weight", g + ".down_z.bias", c.rna_num, {c.rna_num},
+                                 conv_pick_form(3, ZM_VALID, m->z + 2, m->deep8, ROLE_OP));
     else {
       static const int kzt[17] = {0, 1, 0, 0, 3, 0, 0, 0, 5, 0, 0, 0, 0, 0, 0, 0, 9};            // MBAblocks.py:472
       pack_direct(m, pk, fx, m->downz_d, g + ".down_z", c.rna_num, c.rna_num, kzt[c.rna_slc], 3, 3);
@@ -563,7 +549,8 @@ extern "C" int tm_model_finalize(tm_model* m) {
   if (!c.vis_only) {
     for (int rid = 1; rid < 4 && !is_h16(c.dtype); ++rid)
       pack_conv(m, pk, fx, m->pyr[rid - 1], "rna_blocks." + std::to_string(rid) + ".1.weight",
-                "rna_blocks." + std::to_string(rid) + ".1.bias", m->rw[rid], {m->rw[rid - 1]}, 9);
+                "rna_blocks." + std::to_string(rid) + ".1.bias", m->rw[rid], {m->rw[rid - 1]},
+                conv_pick_form(3, ZM_INPLANE, m->z, m->deep8, ROLE_OP));
     if (is_h16(c.dtype))
       for (int rid = 1; rid < 4; ++rid)
         pack_conv_h(m, pk, fx, fxh, m->pyr16[rid - 1], &m->pyrh[rid - 1], "rna_blocks." + std::to_string(rid) + ".1.weight",
@@ -595,34 +582,18 @@ extern "C" int tm_model_finalize(tm_model* m) {
           fxh.push_back({&r.c1uh, off});
         }
       } else {
-        // c1 of a 64-channel block: the pair form fuses the mid norm into its epilogue, an x-pair wave holds 32 of the 64 channels
-        // and leaves the norm to the separate pass.  Measured per step (profiles/fp32_xpair.txt), x-pair + separate pass is the
-        // faster by 0.58 ms over the six launches, so these layers move too; TM_CONV_XPAIR_MID=0 keeps them fused (A/B timing)
-        static const bool xmid = !(getenv("TM_CONV_XPAIR_MID") && atoi(getenv("TM_CONV_XPAIR_MID")) == 0);
-        const bool fuses = m->zpair && r.cout == 64 && conv_fuse_mid_enabled();
-        pack_conv(m, pk, fx, r.c1, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg, 27, m->z == 1,
-                  m->zpair, m->xpair && !r.dec_deep && (!fuses || xmid));
-        r.fuse_mid = r.c1.zpair && r.cout == 64 && conv_fuse_mid_enabled();
-        if (r.up && m->z == 2) {                             // phase weights (conv3d_mfma UPS form) + their own copy of the bias
-          r.c1u = r.c1;
-          r.c1u.taps = 12;
-          r.c1u.xpair = 0;
-          r.c1u.zpair = m->zpair ? 1 : 0;                    // the pair form of the phase weights (conv3d_zpair_ups), under the same switch
-          const size_t off = pk.reserve(conv_pack_ups_floats(r.cout, r.cbi));
-          (m->zpair ? conv_pack_zpair_ups_host : conv_pack_ups_host)(P(m, r.pfx + ".in_layers.2.weight").data(), r.cout, r.seg.data(),
-                                                                    (int)r.seg.size(), pk.buf.data() + off);
-          fx.push_back({&r.c1u.w, off});
-          const size_t boff = pk.reserve((size_t)r.c1u.ntile * 64);
-          const std::vector<float>& b = P(m, r.pfx + ".in_layers.2.bias");
-          for (int i = 0; i < r.cout; ++i) pk.buf[boff + i] = b[i];
-          fx.push_back({&r.c1u.bias, boff});
-        }
-        pack_conv(m, pk, fx, r.c2, r.pfx + ".out_layers.3.weight", r.pfx + ".out_layers.3.bias", r.cout, {r.cout}, 27, m->z == 1,
-                  m->zpair, m->xpair && !r.dec_deep);
+        const int role = ROLE_RES | (r.dec_deep ? ROLE_DEEP : 0);
+        pack_conv(m, pk, fx, r.c1, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg,
+                  conv_pick_form(3, ZM_PAD1, m->z, m->deep8, role | (r.cout == 64 ? ROLE_C1_64 : 0), &r.fuse_mid));
+        if (r.up && m->z == 2)                               // phase weights of the upsampled-input form + their own copy of the bias
+          pack_conv(m, pk, fx, r.c1u, r.pfx + ".in_layers.2.weight", r.pfx + ".in_layers.2.bias", r.cout, r.seg,
+                    conv_pick_form(3, ZM_UPS, m->z, m->deep8, role));
+        pack_conv(m, pk, fx, r.c2, r.pfx + ".out_layers.3.weight", r.pfx + ".out_layers.3.bias", r.cout, {r.cout},
+                  conv_pick_form(3, ZM_PAD1, m->z, m->deep8, role));
       }
       if (r.has_skip) {
         if (bf16) pack_linear_stack_h(m, pk, fx, fxh, r.skip, &r.skiph, {r.pfx + ".skip_connection"}, r.cout, r.seg);
-        else pack_conv(m, pk, fx, r.skip, r.pfx + ".skip_connection.weight", r.pfx + ".skip_connection.bias", r.cout, r.seg, 1);
+        else pack_conv(m, pk, fx, r.skip, r.pfx + ".skip_connection.weight", r.pfx + ".skip_connection.bias", r.cout, r.seg, CF_1X1);
       }
       pack_vec(pk, fx, &r.n1, P(m, r.pfx + ".in_layers.0.weight"), r.seg);
       pack_raw(pk, fx, &r.n2, P(m, r.pfx + ".out_layers.0.weight"));
@@ -695,12 +666,13 @@ extern "C" int tm_profile_collect(tm_model* m, tm_prof_stats* out) {
   // centre slice only (9); Z >= 3: all 27 (zero planes staged)
   // (the 16-bit conv never stages z-padding planes: (3Z - 2) / 3Z of the taps for any Z)
   // per layer: a launch in the x-pair form issues 36 tap-products per FOUR outputs, 18 of the nominal 54
-  out->executed_flops = (m->prof_nominal - m->prof_xpair) *
+  out->executed_flops = (m->prof_nominal - m->prof_xp_flops) *
                             (is_h16(m->cfg.dtype) ? (3.0 * m->z - 2.0) / (3.0 * m->z)
-                                                  : (m->z == 2 ? (m->zpair ? 27.0 / 54.0 : 18.0 / 27.0) : (m->z == 1 ? 9.0 / 27.0 : 1.0))) +
-                        m->prof_xpair * (18.0 / 54.0);
+                                                  : (m->z == 2 ? (conv_pick_form(3, ZM_PAD1, 2, false, ROLE_RES) == CF_PAIR ? 27.0 / 54.0 : 18.0 / 27.0)
+                                                               : (m->z == 1 ? 9.0 / 27.0 : 1.0))) +
+                        m->prof_xp_flops * (18.0 / 54.0);
   out->alg_bytes = m->prof_bytes;
-  m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0; m->prof_xpair = 0;
+  m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0; m->prof_xp_flops = 0;
   return TM_OK;
 }
 
@@ -808,7 +780,7 @@ static void run_conv(Ctx& cx, const TV& x, const ConvW& w, TV y, const TV* res, 
     L.fuse_norm = 1; L.a2 = y; L.norm_w = fuse_rw->n2; L.inv_c = 1.0f / (float)fuse_rw->cout; L.per_image = per_image;
     L.mod_scale = cx.ss + fuse_rw->emb_off; L.mod_shift = cx.ss + fuse_rw->emb_off + fuse_rw->cout; L.mod_stride = m->emb_tot;
   }
-  const bool prof = m->prof_on && (w.taps == 27 || w.xpair || (m->z == 1 && w.taps == 9)) && zmode == ZM_PAD1;
+  const bool prof = m->prof_on && (w.taps == 27 || w.form == CF_XPAIR || (m->z == 1 && w.taps == 9)) && zmode == ZM_PAD1;
   if (prof) {
     if (m->prof_used == m->prof_ev.size()) {
       hipEvent_t a, b;
@@ -823,7 +795,7 @@ static void run_conv(Ctx& cx, const TV& x, const ConvW& w, TV y, const TV* res, 
     m->prof_used++;
     const double vox = (double)x.N * x.Z * x.H * x.W;
     m->prof_nominal += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
-    if (w.xpair) m->prof_xpair += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
+    if (w.form == CF_XPAIR) m->prof_xp_flops += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
     m->prof_tag.push_back({cin_real ? cin_real : x.C, w.Cout, x.H, x.N, 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox});
     m->prof_bytes += 4.0 * (vox * x.Cb * 8 + (double)w.ntile * w.Cbi * w.taps * 512 + vox * y.Cb * 8);
   }
@@ -1061,7 +1033,7 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
   A2 = cx.tensor(N, w.cout, Z, S_out);
   // 64 output channels in the pair form's 128-voxel tile: a wave holds every channel of its voxels, so out_layers' norm ->
   // modulate -> SiLU runs in c1's epilogue and H1 is never written (nor allocated: the dry pass takes the same branch)
-  const bool fuse_mid = w.fuse_mid && Z == 2 && !conv_zpair_half((long)N * Z * S_out * S_out, 1, S_out, 0);
+  const bool fuse_mid = w.fuse_mid && Z == 2 && conv_tile(CF_PAIR, (long)N * Z * S_out * S_out, 1, S_out, 0) == 2;
   if (fuse_mid) {
     run_conv(cx, A, w.c1, A2, nullptr, nullptr, 0, w.cin, ZM_PAD1, false, false, &w, per_image);
   } else {

@@ -100,18 +100,6 @@ static void prep_single_src(PrepLaunch& P, const TV& x) {
   P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
 }
 
-// The weight geometry of the fp32 MFMA conv, and the ONE statement of which convs run in the z-pair form: 3x3x3, pad 1 along z, over
-// two planes (three in-plane products per plane pair, conv3d_zpair).  The host pack (tm_op_conv_mfma_res), the device pack
-// (tm_op_conv_pack_dev) and the launch on a ready pack (conv_packed) all ask here, so a pack and its launch cannot disagree on the
-// layout.  w / bias are left for the caller.
-static ConvW conv_form(int Cin, int Cout, int ksize, int zmode, int Z) {
-  ConvW cw;
-  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.ntile = (Cout + 63) / 64;
-  cw.taps = ksize == 1 ? 1 : (zmode == ZM_INPLANE ? 9 : (zmode == ZM_UPS ? 12 : 27));
-  cw.zpair = (ksize == 3 && zmode == ZM_PAD1 && Z == 2 && conv_zpair_enabled()) ? 1 : 0;
-  return cw;
-}
-
 // fp32 CB8 x -> a 16-bit CB8 copy in `tmp` (prep kernel, no norm / act); `pair`: even block count (zero pad blocks), the
 // operand form of the 16-bit conv kernels.  Launches nothing once `e` holds an error.
 static TVH to_h16(DevTmp& tmp, const TV& x, bool f16, bool pair, hipStream_t st, hipError_t& e) {
@@ -163,6 +151,36 @@ extern "C" int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void
                                int Cout, int Z, int S, int ksize, int zmode, int up2, int tile_variant, void* stream) {
   return tm_op_conv_mfma_res(x_cb8, w_host, bias_host, y_cb8, nullptr, 0, N, Cin, Cout, Z, S, ksize, zmode, up2, tile_variant, stream);
 }
+// One conv of a single-operator hook: the host weights packed for `form` and uploaded with the bias (into `tmp`), and the launch
+// filled in: x [N][Cin][Z][S][S], y [N][Cout][Zout][So][So], the residual (optional) of y's geometry, or with res_half at half its
+// plane size.  The caller adds what is its own and launches L.
+struct ConvOp {
+  DevTmp tmp;
+  ConvLaunch L;
+  TV res;
+};
+static int conv_op(ConvOp& op, int form, const void* w_host, const void* bias_host, const void* x_cb8, void* y_cb8, int N, int Cin,
+                   int Cout, int Z, int S, int Zout, int So, int zmode, int tile_variant, const void* res_cb8 = nullptr,
+                   int res_half = 0) {
+  ConvW cw = conv_w(form, Cout, (Cin + 7) / 8);
+  std::vector<float> pk(conv_pack_floats(form, Cout, cw.Cbi));
+  conv_pack_host(form, (const float*)w_host, Cout, &Cin, 1, pk.data());
+  std::tie(cw.w, cw.bias) = upload_conv(op.tmp, pk, bias_host, Cout);
+  if (op.tmp.err) return op.tmp.report();
+  ConvLaunch& L = op.L;
+  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.w = cw;
+  L.y = view_cb8(y_cb8, N, Cout, Zout, So, So);
+  L.tile_variant = tile_variant;
+  L.zmode = zmode;
+  if (res_cb8) {
+    op.res = view_cb8(const_cast<void*>(res_cb8), N, Cout, Zout, res_half ? So / 2 : So, res_half ? So / 2 : So);
+    L.res = &op.res;
+    L.res_half = res_half ? 1 : 0;
+  }
+  return TM_OK;
+}
+
 extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                                    int res_half, int N, int Cin, int Cout, int Z, int S, int ksize, int zmode, int up2,
                                    int tile_variant, void* stream) {
@@ -173,33 +191,16 @@ extern "C" int tm_op_conv_mfma_res(const void* x_cb8, const void* w_host, const 
   if (res_cb8 && (ksize != 3 || zmode == ZM_UPS)) return fail(TM_ERR_ARG, "residual: k x 3 x 3 forms other than ZM_UPS only");
   if (res_half && (!res_cb8 || up2 || S < 2)) return fail(TM_ERR_ARG, "res_half: needs a residual, S >= 2 and no fused upsample");
   const int Zout = (ksize == 3 && zmode == ZM_VALID) ? Z - 2 : Z;
-  const int So = (up2 || ups) ? 2 * S : S;
-  ConvW cw = conv_form(Cin, Cout, ksize, zmode, Z);                   // the pair form as tm_model_finalize packs c1 / c2
-  std::vector<float> pk(ups ? conv_pack_ups_floats(Cout, cw.Cbi) : conv_pack_floats(Cout, cw.Cbi, cw.taps));
-  if (ups) conv_pack_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  else if (cw.zpair) conv_pack_zpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  else conv_pack_host((const float*)w_host, Cout, &Cin, 1, cw.taps, pk.data());
-  DevTmp tmp;
-  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
-  if (tmp.err) return tmp.report();
-  ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
-  L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Zout, So, So);
-  L.tile_variant = tile_variant;
-  L.zmode = zmode;
-  L.flags = up2 ? EPI_UP2 : 0;
-  TV res;
-  if (res_cb8) {
-    res = view_cb8(const_cast<void*>(res_cb8), N, Cout, Zout, res_half ? So / 2 : So, res_half ? So / 2 : So);
-    L.res = &res;
-    L.res_half = res_half ? 1 : 0;
-  }
-  return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_mfma");
+  ConvOp op;                                            // the pair form at Z == 2, as tm_model_finalize packs c1 / c2 there
+  if (const int rc = conv_op(op, conv_pick_form(ksize, zmode, Z, false, ROLE_OP), w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, Z, S,
+                             Zout, (up2 || ups) ? 2 * S : S, zmode, tile_variant, res_cb8, res_half))
+    return rc;
+  op.L.flags = up2 ? EPI_UP2 : 0;
+  return finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_mfma");
 }
 
 // The fp32 pair-form conv with the ResBlock mid-section in its epilogue (conv3d_zpair<0, *, true>), alone.  The forms the kernel
-// does not take are refused here, before any device call, with the launcher's own rule for the tile (conv_zpair_half).
+// does not take are refused here, before any device call, with the launcher's own rule for the tile (conv_tile).
 extern "C" int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host, const void* bias_host, const void* norm_w_host,
                                           const void* scale_host, const void* shift_host, const void* res_cb8, void* a2_out,
                                           void* h1_out, void* a2_sep_out, int N, int Cin, int Cout, int Z, int S, int per_image,
@@ -211,26 +212,19 @@ extern "C" int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host,
   if (res_cb8) return fail(TM_ERR_ARG, "the fused mid-section takes no residual");
   if (S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return fail(TM_ERR_ARG, "S must be 8, 16, 32, 64 or 128 (got %d)", S);
   if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
-  if (conv_zpair_half((long)N * Z * S * S, 1, S, tile_variant))
+  if (conv_tile(CF_PAIR, (long)N * Z * S * S, 1, S, tile_variant) != 2)
     return fail(TM_ERR_ARG, "the fused mid-section exists in the 128-voxel tile only; this launch takes the 64-voxel one");
   if (a2_sep_out && !h1_out) return fail(TM_ERR_ARG, "a2_sep_out needs h1_out");
-  ConvW cw = conv_form(Cin, Cout, 3, ZM_PAD1, Z);
-  if (!cw.zpair) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
-  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, 27));
-  conv_pack_zpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  DevTmp tmp;
-  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
+  if (conv_pick_form(3, ZM_PAD1, Z, false, ROLE_OP) != CF_PAIR) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
+  ConvOp op;
+  if (const int rc = conv_op(op, CF_PAIR, w_host, bias_host, x_cb8, a2_out, N, Cin, Cout, Z, S, Z, S, ZM_PAD1, tile_variant)) return rc;
   const int nimg = (N + per_image - 1) / per_image;
-  const float* nw = tmp.alloc((size_t)Cout, (const float*)norm_w_host);
-  const float* sc = tmp.alloc((size_t)nimg * Cout, (const float*)scale_host);
-  const float* sh = tmp.alloc((size_t)nimg * Cout, (const float*)shift_host);
-  if (tmp.err) return tmp.report();
+  const float* nw = op.tmp.alloc((size_t)Cout, (const float*)norm_w_host);
+  const float* sc = op.tmp.alloc((size_t)nimg * Cout, (const float*)scale_host);
+  const float* sh = op.tmp.alloc((size_t)nimg * Cout, (const float*)shift_host);
+  if (op.tmp.err) return op.tmp.report();
   hipStream_t st = (hipStream_t)stream;
-  ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
-  L.w = cw;
-  L.tile_variant = tile_variant;
-  L.y = view_cb8(a2_out, N, Cout, Z, S, S);
+  ConvLaunch& L = op.L;
   L.fuse_norm = 1; L.a2 = L.y; L.norm_w = nw; L.mod_scale = sc; L.mod_shift = sh; L.mod_stride = Cout; L.per_image = per_image;
   L.inv_c = 1.0f / (float)Cout;
   hipError_t e = launch_conv_mfma(L, st);
@@ -259,20 +253,11 @@ extern "C" int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, co
   if (Z != 2) return fail(TM_ERR_ARG, "the pair form exists at Z == 2 only (got Z = %d)", Z);
   if (S != 4 && S != 8 && S != 16 && S != 32 && S != 64) return fail(TM_ERR_ARG, "S must be 4, 8, 16, 32 or 64 (got %d)", S);
   if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
-  ConvW cw = conv_form(Cin, Cout, 3, ZM_UPS, Z);
-  cw.zpair = 1;
-  std::vector<float> pk(conv_pack_ups_floats(Cout, cw.Cbi));
-  conv_pack_zpair_ups_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  DevTmp tmp;
-  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
-  if (tmp.err) return tmp.report();
-  ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
-  L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Z, 2 * S, 2 * S);
-  L.tile_variant = tile_variant;
-  L.zmode = ZM_UPS;
-  return finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_ups_pair (fp32)");
+  ConvOp op;
+  if (const int rc = conv_op(op, conv_pick_form(3, ZM_UPS, Z, false, ROLE_OP_PAIR_UPS), w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, Z,
+                             S, Z, 2 * S, ZM_UPS, tile_variant))
+    return rc;
+  return finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_ups_pair (fp32)");
 }
 
 // The x-pair form of the fp32 3x3x3 pad-1 conv at Z == 2 (conv3d_xpair), alone.  Returns the tile it launched (1 = the 64-voxel
@@ -284,37 +269,20 @@ static int xpair_args(const void* x, const void* w, const void* b, const void* y
   if (Z != 2) return fail(TM_ERR_ARG, "the x-pair form exists at Z == 2 only (got Z = %d)", Z);
   if (S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return fail(TM_ERR_ARG, "S must be 8, 16, 32, 64 or 128 (got %d)", S);
   if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
-  if (!conv_xpair_enabled()) return fail(TM_ERR_ARG, "the x-pair form is switched off (TM_CONV_XPAIR=0)");
+  if (conv_pick_form(3, ZM_PAD1, 2, true, ROLE_OP_XPAIR) != CF_XPAIR)
+    return fail(TM_ERR_ARG, "the x-pair form is switched off (TM_CONV_XPAIR=0)");
   return TM_OK;
-}
-static ConvW xpair_form(int Cin, int Cout) {
-  ConvW cw;
-  cw.Cout = Cout; cw.Cbi = (Cin + 7) / 8; cw.ntile = (Cout + 63) / 64; cw.taps = 36; cw.xpair = 1;
-  return cw;
 }
 extern "C" int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                                     int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream) {
   if (const int rc = xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
   if (res_half && !res_cb8) return fail(TM_ERR_ARG, "res_half needs a residual");
-  ConvW cw = xpair_form(Cin, Cout);
-  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, 36));
-  conv_pack_xpair_host((const float*)w_host, Cout, &Cin, 1, pk.data());
-  DevTmp tmp;
-  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
-  if (tmp.err) return tmp.report();
-  ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
-  L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
-  L.tile_variant = tile_variant;
-  TV res;
-  if (res_cb8) {
-    res = view_cb8(const_cast<void*>(res_cb8), N, Cout, Z, res_half ? S / 2 : S, res_half ? S / 2 : S);
-    L.res = &res;
-    L.res_half = res_half ? 1 : 0;
-  }
-  const int rc = finish((hipStream_t)stream, launch_conv_mfma(L, (hipStream_t)stream), "conv_xpair (fp32)");
-  return rc ? rc : (conv_xpair_half((long)N * Z * S * S, cw.ntile, tile_variant) ? 1 : 2);
+  ConvOp op;
+  if (const int rc = conv_op(op, CF_XPAIR, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, Z, S, Z, S, ZM_PAD1, tile_variant, res_cb8,
+                             res_half))
+    return rc;
+  const int rc = finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_xpair (fp32)");
+  return rc ? rc : conv_tile(CF_XPAIR, (long)N * Z * S * S, op.L.w.ntile, S, tile_variant);
 }
 
 // Timing hook (tools/bench_conv_xpair.py): the 3x3x3 pad-1 conv at Z == 2 packed once for `form` (0 = the pair form, 1 = the
@@ -323,23 +291,16 @@ extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, c
                                         int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream) {
   if (const int rc = xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant)) return rc;
   if ((form != 0 && form != 1) || iters < 1 || !ms_out) return fail(TM_ERR_ARG, "form must be 0 or 1, iters >= 1, ms_out non-null");
-  ConvW cw = form ? xpair_form(Cin, Cout) : conv_form(Cin, Cout, 3, ZM_PAD1, 2);
-  if (!form && !cw.zpair) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
-  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, cw.taps));
-  (form ? conv_pack_xpair_host : conv_pack_zpair_host)((const float*)w_host, Cout, &Cin, 1, pk.data());
-  DevTmp tmp;
-  std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
-  hipEvent_t e0 = tmp.event(), e1 = tmp.event();
-  if (tmp.err) return tmp.report();
+  const int cf = conv_pick_form(3, ZM_PAD1, 2, true, form ? ROLE_OP_XPAIR : ROLE_OP);
+  if (!form && cf != CF_PAIR) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
+  ConvOp op;
+  if (const int rc = conv_op(op, cf, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, 2, S, 2, S, ZM_PAD1, tile_variant)) return rc;
+  hipEvent_t e0 = op.tmp.event(), e1 = op.tmp.event();
+  if (op.tmp.err) return op.tmp.report();
   hipStream_t st = (hipStream_t)stream;
-  ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, 2, S, S);
-  L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, 2, S, S);
-  L.tile_variant = tile_variant;
   for (int i = 0; i < iters; ++i) {
     HIP_TRY(hipEventRecord(e0, st));
-    HIP_TRY(launch_conv_mfma(L, st));
+    HIP_TRY(launch_conv_mfma(op.L, st));
     HIP_TRY(hipEventRecord(e1, st));
     HIP_TRY(hipEventSynchronize(e1));
     HIP_TRY(hipEventElapsedTime(ms_out + i, e0, e1));
@@ -365,12 +326,12 @@ extern "C" int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void
   if (gate_cb8 && (gate_cb0 < 0 || gate_cb0 + Cob > gate_cbtot))
     return fail(TM_ERR_ARG, "gate slice: blocks [%d, %d) run past the %d blocks of the tensor", gate_cb0, gate_cb0 + Cob, gate_cbtot);
   if (tile_variant < 0 || tile_variant > 3) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1, 2 or 3 (got %d)", tile_variant);
-  ConvW cw = conv_form(Cin, Cout, 1, ZM_PAD1, Z);
+  ConvW cw = conv_w(CF_1X1, Cout, Cbi);
   const int form = conv1_form((long)N * Z * S * S, cw.ntile, tile_variant);
   if (!form) return fail(TM_ERR_ARG, "tile_variant 3 (128-cout tile) needs an even number of 64-cout tiles (got %d)", cw.ntile);
   if (form_out) *form_out = form;
-  std::vector<float> pk(conv_pack_floats(Cout, cw.Cbi, 1));
-  conv_pack_host((const float*)w_host, Cout, &Cin, 1, 1, pk.data());
+  std::vector<float> pk(conv_pack_floats(CF_1X1, Cout, Cbi));
+  conv_pack_host(CF_1X1, (const float*)w_host, Cout, &Cin, 1, pk.data());
   DevTmp tmp;
   std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
   if (tmp.err) return tmp.report();
@@ -1101,21 +1062,21 @@ static int packed_form(int Cout, int Cin, int ksize, int Z, int role) {
 }
 extern "C" long tm_conv_pack_floats(int Cout, int Cin, int ksize, int Z, int role) {
   if (packed_form(Cout, Cin, ksize, Z, role)) return -1;
-  const int taps = ksize == 1 ? 1 : 27;
-  return (long)(role ? conv_pack_floats(Cin, (Cout + 7) / 8, taps) : conv_pack_floats(Cout, (Cin + 7) / 8, taps));
+  const int form = conv_pick_form(ksize, ZM_PAD1, Z, false, ROLE_OP);
+  return (long)(role ? conv_pack_floats(form, Cin, (Cout + 7) / 8) : conv_pack_floats(form, Cout, (Cin + 7) / 8));
 }
 extern "C" int tm_op_conv_pack_dev(const void* w_dev, void* pack_dev, int Cout, int Cin, int ksize, int Z, int role, void* stream) {
   if (!w_dev || !pack_dev) return fail(TM_ERR_ARG, "null argument");
   if (int rc = packed_form(Cout, Cin, ksize, Z, role)) return rc;
-  const ConvW cw = conv_form(role ? Cout : Cin, role ? Cin : Cout, ksize, ZM_PAD1, Z);   // of the conv that reads the pack
-  HIP_TRY(launch_conv_pack((const float*)w_dev, (float*)pack_dev, Cout, Cin, cw.taps, role, cw.zpair, (hipStream_t)stream));
+  const int form = conv_pick_form(ksize, ZM_PAD1, Z, false, ROLE_OP);                   // of the conv that reads the pack
+  HIP_TRY(launch_conv_pack((const float*)w_dev, (float*)pack_dev, Cout, Cin, form, role, (hipStream_t)stream));
   return TM_OK;
 }
 // y = conv(x) on a ready pack of Cout x Cin; bias_dev [Cout] or null (zero)
 static int conv_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout, int Z, int S,
                        int ksize, hipStream_t st) {
   DevTmp tmp(st);
-  ConvW cw = conv_form(Cin, Cout, ksize, ZM_PAD1, Z);
+  ConvW cw = conv_w(conv_pick_form(ksize, ZM_PAD1, Z, false, ROLE_OP), Cout, (Cin + 7) / 8);
   float* b = tmp.ordered_floats((size_t)cw.ntile * 64, true);       // the epilogues read the bias zero padded to 64 couts
   if (tmp.err) return tmp.report();
   if (bias_dev) HIP_TRY(hipMemcpyAsync(b, bias_dev, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));

@@ -548,12 +548,12 @@ hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin,
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Conv weights packed on the device: w [Cout][Cin][taps] (reference layout) -> the bytes conv_pack_host (pair == 0) or
-// conv_pack_zpair_host (pair == 1: W1, W2 - W1, W0 - W1 per in-plane tap, plain fp32 subtractions) write, pad slots
+// Conv weights packed on the device: w [Cout][Cin][taps] (reference layout) -> the bytes conv_pack_host writes for `form`: the
+// plain tap order, or for CF_PAIR W1, W2 - W1, W0 - W1 per in-plane tap (plain fp32 subtractions); pad slots
 // zero.  role 1 packs the filter of the data gradient: flipped in every axis and cin <-> cout transposed, so the pack
 // has Cin "output" channels over ceil(Cout / 8) "input" blocks.  One thread per packed float.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, float* out, int Cout, int Cin, int taps, int role, int pair,
+__global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, float* out, int Cout, int Cin, int taps, int role, int form,
                                                         long total) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
@@ -568,7 +568,7 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, float* o
     // effective filter e[co][ci][u] = role ? w[ci][co][taps - 1 - u] : w[co][ci][u]
     const float* src = role ? w + ((long)ci * Cin + co) * taps : w + ((long)co * Cin + ci) * taps;
     auto e = [&](int u) { return src[role ? taps - 1 - u : u]; };
-    if (!pair) v = e(t);
+    if (form != CF_PAIR) v = e(t);
     else {
       const int k = t % 9, g = t / 9;
       const float w1 = e(9 + k);
@@ -577,10 +577,11 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, float* o
   }
   out[i] = v;
 }
-hipError_t launch_conv_pack(const float* w, float* out, int Cout, int Cin, int taps, int role, int pair, hipStream_t s) {
-  const int Co = role ? Cin : Cout, Ci = role ? Cout : Cin;
-  const long total = (long)((Co + 63) / 64) * ((Ci + 7) / 8) * taps * 512;
-  hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, out, Cout, Cin, taps, role, pair, total);
+hipError_t launch_conv_pack(const float* w, float* out, int Cout, int Cin, int form, int role, hipStream_t s) {
+  if (form != CF_1X1 && form != CF_PLANES3 && form != CF_ZSKIP && form != CF_PAIR) return hipErrorInvalidValue;
+  const int Co = role ? Cin : Cout, Ci = role ? Cout : Cin, taps = conv_form_taps(form);
+  const long total = (long)conv_pack_floats(form, Co, (Ci + 7) / 8);
+  hipLaunchKernelGGL(conv_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w, out, Cout, Cin, taps, role, form, total);
   return hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 """-m gpu: conv weights packed on the device (tm_op_conv_pack_dev) and the conv ops that run on a ready pack
 (tm_op_conv_mfma_packed, tm_op_conv_dgrad_packed).  The criterion is bit equality with the host-weight entry points
 (tm_op_conv_mfma, tm_op_conv_dgrad) on random normal data: the same kernel reads the pack, so equal output bits for every
-input means the pack bytes are the ones conv_pack_host / conv_pack_zpair_host write."""
+input means the pack bytes are the ones conv_pack_host writes for the plain and the pair form."""
 import pytest
 import torch
 
