@@ -241,6 +241,36 @@ int tm_train_batch_genes(const int32_t* crd, const void* dat, int64_t nnz, const
  * dst == NULL: only *out_bytes (the decoded size) is set.  No GPU involved. */
 int tm_blosc_decompress(const void* src, size_t src_bytes, void* dst, size_t dst_cap, size_t* out_bytes);
 
+/* ---- slice export: the pyramid levels and JPEG tiles of infer_brn.get_ome --------
+ * (infer_brn.py:11-54: `tiffsave(tile=True, compression='jpeg', pyramid=True, bigtiff=True, tile 256 x 256)`), computed
+ * from a resident uint8 plane.  The container is written by teramind_amd.ometiff.
+ *
+ * tm_u8_shrink2: dst [ceil(H / 2)][ceil(W / 2)] uint8 device = (a + b + c + d + 2) >> 2 over the 2 x 2 blocks of
+ *   src [H][W]; an odd last row / column is repeated.  Pitches in bytes, src_pitch >= W, dst_pitch >= ceil(W / 2); bytes of
+ *   dst outside the level are not written.  Asynchronous on `stream`. */
+int tm_u8_shrink2(const void* src, int H, int W, int64_t src_pitch, void* dst, int64_t dst_pitch, void* stream);
+
+/* tm_jpeg_encode_tiles: baseline-JPEG entropy-coded segments (ITU-T T.81; no markers) of tiles [tile0, tile0 + ntiles) of
+ *   the ceil(H / 256) x ceil(W / 256) grid (row-major) of plane [H][W] uint8 device, one 8-bit grey component, one
+ *   256 x 256 tile per scan; pixels beyond the image repeat the last row / column.  Exact integer arithmetic: level shift
+ *   128, the 8 x 8 "islow" integer forward DCT, quantiser (|c| + qv / 2) / qv with qv = q << 3 and q the Annex K.1
+ *   luminance table scaled for `quality` (1 .. 100; s = 5000 / Q below 50, else 200 - 2 Q; q = clamp((base s + 50) / 100,
+ *   1, 255)), zigzag, DC predicted from the previous block of the tile (0 at its start), the typical Huffman tables of
+ *   Annex K.3, byte stuffing, one-bit padding, no restart markers.  The bytes are those libjpeg writes for the tile.
+ *   slots  uint8 [ntiles][slot_bytes] device: slot k belongs to tile tile0 + k
+ *   need   int32 [ntiles] device: always written, the bytes tile tile0 + k takes.  The bytes themselves are written only if
+ *          need[k] <= slot_bytes; a slot that is too small is left untouched (the caller encodes that tile again with a
+ *          slot sized from need: a size query, not a fallback)
+ *   packed / offsets (both or neither): uint8 [ntiles * slot_bytes] and int64 [ntiles + 1] device: the filled slots back
+ *          to back, slot k at offsets[k], offsets[ntiles] = their total (a slot that was too small takes 0 bytes)
+ *   Asynchronous on `stream`; the bit buffers are stream-ordered scratch of the call (at most 512 x 208 KB). */
+int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pitch, int quality, int tile0, int ntiles, void* slots,
+                         int64_t slot_bytes, int32_t* need, void* packed, int64_t* offsets, void* stream);
+
+/* The tables-only datastream SOI DQT DHT(DC) DHT(AC) EOI for `quality`: the TIFF JPEGTables tag of tiles encoded by
+ * tm_jpeg_encode_tiles (which reads the same table statements).  buf == NULL: only *out_bytes is set.  Host only. */
+int tm_jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
+
 /* Measurement hooks (bench.py): while enabled, every launch of the dominant kernel
  * (conv3d_mfma<2,..> in fp32, conv27_bf16 / conv27_f16 in the 16-bit modes: the 3x3x3 implicit-GEMM conv) inside tm_unet_forward is bracketed by two
  * hipEvents recorded on the forward's stream.  tm_profile_collect synchronises on the last

@@ -349,6 +349,18 @@ hipError_t launch_gene_tile_scatter(const int32_t* crd, const float* dat, long n
                                     int gsz, int chan_in, int zpad_ch, float* out, hipStream_t s);
 int blosc_decompress(const void* src, size_t src_bytes, void* dst, size_t dst_cap, size_t* out_bytes);
 
+// ---- slice export (tm_export.hip) -------------------------------------------------------
+// dst [ceil(Hs / 2)][ceil(Ws / 2)] = rounded mean of the 2 x 2 blocks of src, the last row / column repeated at odd sizes
+hipError_t launch_u8_shrink2(const uint8_t* src, int Hs, int Ws, long spitch, uint8_t* dst, long dpitch, hipStream_t s);
+// baseline-JPEG scans of tiles [tile0, tile0 + ntiles) of the plane's 256 x 256 grid: need[k] always, the bytes into slot k if
+// they fit; with `packed` the filled slots back to back at offsets[k] (offsets[ntiles] = their sum).  `scratch`: the
+// workgroups' bit buffers, jpeg_scratch_bytes(ntiles) bytes.
+constexpr int JPEG_MAX_WGS = 512;
+size_t jpeg_scratch_bytes(int ntiles);
+hipError_t launch_jpeg_tiles(const uint8_t* plane, int H, int W, long pitch, int quality, int tile0, int ntiles, uint32_t* scratch,
+                             uint8_t* slots, long slot_bytes, int32_t* need, uint8_t* packed, int64_t* offsets, hipStream_t s);
+int jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
+
 // ---- host helpers of the C-ABI units (tm_model.hip, tm_ops.hip, tm_io.hip) ---------------
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets the tm_last_error() text, returns code
 #define HIP_TRY(expr)                                                                          \

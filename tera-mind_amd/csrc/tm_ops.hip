@@ -1124,6 +1124,28 @@ extern "C" int tm_op_conv_wgrad_dev(const void* x_cb8, const void* dy_cb8, void*
   return TM_OK;
 }
 
+// Baseline-JPEG tile scans of a resident uint8 plane (tm_export.hip); enqueues only, the bit buffers are stream-ordered scratch
+extern "C" int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pitch, int quality, int tile0, int ntiles, void* slots,
+                                    int64_t slot_bytes, int32_t* need, void* packed, int64_t* offsets, void* stream) {
+  const char* fn = "tm_jpeg_encode_tiles";
+  if (!plane || !slots || !need) return fail(TM_ERR_ARG, "%s: null plane / slots / need pointer", fn);
+  if (!packed != !offsets) return fail(TM_ERR_ARG, "%s: packed and offsets go together (both or neither)", fn);
+  if (H < 1 || W < 1) return fail(TM_ERR_ARG, "%s: H and W must be positive, got %d x %d", fn, H, W);
+  if (pitch < W) return fail(TM_ERR_ARG, "%s: pitch %lld below W %d", fn, (long long)pitch, W);
+  if (quality < 1 || quality > 100) return fail(TM_ERR_ARG, "%s: quality %d outside 1 .. 100", fn, quality);
+  const long grid = (long)((H + 255) / 256) * ((W + 255) / 256);
+  if (tile0 < 0 || ntiles < 1 || (long)tile0 + ntiles > grid)
+    return fail(TM_ERR_ARG, "%s: tiles [%d, %d + %d) outside the grid of %ld", fn, tile0, tile0, ntiles, grid);
+  if (slot_bytes < 1) return fail(TM_ERR_ARG, "%s: slot_bytes must be positive", fn);
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp(st);
+  uint32_t* scratch = (uint32_t*)tmp.ordered_floats(jpeg_scratch_bytes(ntiles) / sizeof(float), false);
+  if (tmp.err) return tmp.report();
+  HIP_TRY(launch_jpeg_tiles((const uint8_t*)plane, H, W, (long)pitch, quality, tile0, ntiles, scratch, (uint8_t*)slots, (long)slot_bytes,
+                            need, (uint8_t*)packed, offsets, st));
+  return TM_OK;
+}
+
 // Timing hook of the conv weight gradient on random device data (uniform in [-1, 1)): engine 0 = conv_wgrad_kernel (VALU),
 // 1 = conv_wgrad_mfma_kernel + its chunk reduction.  One warm-up launch, then `reps` measurements of `iters` launches between two
 // events each: ms_per_launch_host[r] = milliseconds per launch of repetition r (their spread is the noise of identical calls).

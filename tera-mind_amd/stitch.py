@@ -3,8 +3,11 @@
 Restates the gather of the reference's infer_brn.py:57-105 (`gen_col`: load every tile of a tile column,
 reorder channels '(c s) h w -> (s c) h w', map [-1, 1] -> uint8 with `((g + 1) * 127.5).astype(uint8)` in
 float16, stack the tiles of the column; `gen_mba`: join the columns) without pyvips: the mosaic is one
-tensor, written with PIL as plain TIFF / JPEG (the reference's tiled pyramidal OME-TIFF needs libvips and is
-out of scope).  Output index `sl = s * n_stain + c` (slice-major, stain-minor), as the reference's
+tensor.  `save_slices` writes it with PIL as plain TIFF / JPEG (small ROIs); `save_slices_pyramid` writes the
+reference's product, one tiled pyramidal OME-TIFF (BigTIFF, 256 x 256 JPEG tiles) per slice, with the level
+reductions and the JPEG tile scans computed on the GPU (ometiff.py).  Pinned there: the JPEG bytes equal
+libjpeg's and Pillow / libtiff reads the container back; not pinned: byte equality with a libvips-written file,
+libvips' level sizes at odd dimensions, QuPath / Bio-Formats (never run).  Output index `sl = s * n_stain + c` (slice-major, stain-minor), as the reference's
 per-slice directories are numbered.
 """
 import os
@@ -13,7 +16,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import formats, tiles
+from . import formats, ometiff, tiles
 
 
 def to_uint8(g: torch.Tensor) -> torch.Tensor:
@@ -61,6 +64,37 @@ def save_slices(mosaic, odir, names: Optional[Sequence[int]] = None, jpeg: bool 
         im.save(os.path.join(str(odir), f"all_{sl}.tif"))
         if jpeg:
             im.save(os.path.join(str(odir), f"all_{sl}.jpg"))
+
+
+def save_slices_pyramid(state, odir, slc: int = 50, slices: Optional[Sequence[int]] = None,
+                        names: Optional[Sequence[int]] = None, quality: int = 75, page: Optional[int] = None,
+                        compression: str = "jpeg", device=None):
+    """'{odir}/all_{sl}.tif' as tiled pyramidal OME-TIFF (infer_brn.py:50-54,100), one plane at a time so that the uint8
+    copy of a whole canvas never exists.  state: the resident float [(c s), H, W] state (plane k of the '(s c)' order is
+    converted with `to_uint8` on its device), or a host / device uint8 mosaic [(s c), H, W] as `stitch_dir` returns
+    (uploaded plane by plane).  slices: indices into the '(s c)' order (default all); names as in `save_slices`.
+    page: also write that pyramid level as 'all_{sl}.jpg', as gen_mba does (infer_brn.py:101-103)."""
+    os.makedirs(str(odir), exist_ok=True)
+    if isinstance(state, np.ndarray):
+        state = torch.from_numpy(state)
+    is_u8 = state.dtype == torch.uint8
+    dev = torch.device(device) if device is not None else (state.device if state.is_cuda else torch.device("cuda"))
+    cs = state.shape[0]
+    if not is_u8 and cs % slc:
+        raise ValueError(f"{cs} state planes are no multiple of slc = {slc}")
+    picks = list(range(cs)) if slices is None else list(slices)
+    bufs = ometiff.JpegBatches(dev, ometiff.BATCH_TILES, ometiff.SLOT_BYTES) if compression == "jpeg" else None
+    for k, idx in enumerate(picks):
+        sl = idx if names is None else names[k]
+        if is_u8:
+            plane = state[idx].to(dev).contiguous()
+        else:
+            s_, c_ = divmod(idx, cs // slc)                        # '(s c)' index -> plane c * slc + s of '(c s)'
+            plane = to_uint8(state[c_ * slc + s_].to(dev)).contiguous()
+        levels = ometiff.write_pyramid(os.path.join(str(odir), f"all_{sl}.tif"), plane, quality, compression, buffers=bufs)
+        if page is not None:
+            from PIL import Image
+            Image.fromarray(levels[page].cpu().numpy(), mode="L").save(os.path.join(str(odir), f"all_{sl}.jpg"))
 
 
 # ---- attention read-out tiles (infer_attn.py:9-39) -----------------------------------------------------------

@@ -100,6 +100,17 @@ def worker(args):
             mosaic = stitch.stitch_state(st, 50, [0, 1, 48, 49]).cpu().numpy()
         stitch.save_slices(mosaic, os.path.join(out_dir, "gen"), names=[0, 1, 48, 49])
         io_s = io_save + time.perf_counter() - t3
+        pyr_s = None
+        if args.pyramid:                        # every plane as tiled pyramidal OME-TIFF (infer_brn.get_ome), encoded on the GPU
+            t4 = time.perf_counter()
+            if world == 1:
+                stitch.save_slices_pyramid(st, os.path.join(out_dir, "gen_pyramid"), 50, quality=args.quality, page=args.page)
+            elif d is not None:                 # several ranks: from the step directory, as the reference's infer_brn does
+                full = stitch.stitch_dir(d, 256, 256, args.hnm, args.wnm, 50)
+                stitch.save_slices_pyramid(full, os.path.join(out_dir, "gen_pyramid"), 50, quality=args.quality, page=args.page)
+            else:
+                raise SystemExit("--pyramid with several ranks needs the tile files (drop --no_tile_files)")
+            pyr_s = round(time.perf_counter() - t4, 2)
         tiles = args.hnm * args.wnm
         T = steps_done
         print(json.dumps({"what": "full ROI sweep, measured", "steps_requested": args.tot_epoch, "steps_measured": steps_done,
@@ -111,7 +122,7 @@ def worker(args):
                           "interior_patch_steps_per_s": round(400 * tiles * T / sweep_s, 1),
                           "first_step_s": round(per_step[0], 2), "last_step_s": round(per_step[-1], 2),
                           "exchange_ms_per_step": round(res["exchange_ms_per_step"], 3),
-                          "save_and_stitch_s": round(io_s, 2), "stitch_from_files_equals_resident": same,
+                          "save_and_stitch_s": round(io_s, 2), "pyramid_export_s": pyr_s, "stitch_from_files_equals_resident": same,
                           "state_finite": bool(torch.isfinite(st.float()).all()), "state_absmax": float(st.float().abs().max()),
                           "state_std": float(st.float().std())}), flush=True)
     if world > 1:
@@ -144,6 +155,10 @@ def main():
     ap.add_argument("--deadline_s", type=float, default=0.0,
                     help="single GPU: do not start a diffusion step that would end later than this many seconds after process start")
     ap.add_argument("--no_tile_files", action="store_true", help="skip save_step / stitch_dir; stitch slice images from the resident canvas")
+    ap.add_argument("--pyramid", action="store_true",
+                    help="also export every plane as '<out_dir>/gen_pyramid/all_{sl}.tif': tiled pyramidal OME-TIFF with JPEG tiles")
+    ap.add_argument("--page", type=int, default=None, help="with --pyramid: also write that pyramid level as all_{sl}.jpg")
+    ap.add_argument("--quality", type=int, default=75, help="with --pyramid: JPEG quality 1 .. 100")
     args = ap.parse_args()
     from teramind_amd import launch
     if args.gene_dir and args.make_genes and not launch.launched_as_rank():
