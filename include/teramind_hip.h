@@ -488,6 +488,30 @@ int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const void* v_cb8, c
 int tm_op_window_attn_kv(const void* q_cb8, const void* kv_cb8, const void* qw_dev, const void* kw_dev, void* out, int N, int C,
                          int Z, int S, int dtype, int kv_half, void* stream);
 
+/* The gene-gene attention block (tm_attn.hip; model/MBAblocks.py:492-501, 551-601 with k = q) in one kernel form per call.
+ *   rna_dense  DEVICE fp32 [B, gn, gn, zs * 500]: token g has D = gn^2 * zs features, feature z * gn^2 + hw read from
+ *              [hw][z * 500 + slot(g)], slot(g) = gidx[g] (gidx HOST int32 [G], each in [0, 500)) or g without a table;
+ *   w_host     twelve HOST fp32 arrays in checkpoint layout ([out][in]), in this order: attn.q.weight [D][D], attn.q.bias,
+ *              attn.v.weight [D][D], attn.v.bias, attn.q_norm.weight, attn.proj.weight [D][D], attn.proj.bias, norm2.weight,
+ *              mlp.fc1.weight [4D][D], mlp.fc1.bias [4D], mlp.fc2.weight [D][4D], mlp.fc2.bias;
+ *   form       0 = the model's rule (the fused kernel iff D == 64, G <= 232 and no table), 1 = the fused D = 64 MFMA kernel,
+ *              2 = the generic kernel (G <= 512, D <= 512; its scratch is allocated inside the call);
+ *   zlo, zhi   slices outside [zlo, zhi) count as zero (the slice-pair maps of tm_gene_attn); 0, zs: none;
+ *   out_tok    DEVICE fp32 CB8 [B][ceil(G/8)][zs][gn][gn][8] or NULL: the block's output; the pad slots g >= G are not written;
+ *   attn_map   DEVICE fp32 [B][G][G] or NULL: the softmax.  At least one of the two outputs.
+ * TM_ERR_ARG with a tm_last_error() text before any device call: a null pointer, B / gn / zs / G < 1, D > 512, G > 512, G > 500
+ * without a table, a table entry outside [0, 500), a mask outside [0, zs]; form 1 with gn^2 * zs != 64, G > 232 or a table. */
+int tm_op_gene_attn(const void* rna_dense_dev, const void* const* w_host, const int* gidx_host, int B, int gn, int zs, int G,
+                    int form, int zlo, int zhi, void* out_tok_cb8, void* attn_map, void* stream);
+/* rna_mid of tm_gene_attn alone: out DEVICE fp32 [B, G, zs - 2, gn, gn]; zs <= 2 writes nothing and succeeds. */
+int tm_op_rna_mid(const void* rna_dense_dev, int B, int gn, int zs, int G, void* out, void* stream);
+/* The pathway read-out of tm_gene_attn_readout (out [B, 4K, 2 gn^2], sub [4, B, K, K] or NULL, glst K HOST indices) in one form:
+ * 0 = the model's rule, 1 = the fused kernel (gn = 4, zs = 4, G <= 232, no table), 2 = the generic map kernel over chunks of 8
+ * patches and the gather kernel.  rna_dense, w_host, gidx_host and the refusals as for tm_op_gene_attn; also zs != 4, K outside
+ * [1, 8] and a glst entry that repeats or lies outside [0, G). */
+int tm_op_gene_readout(const void* rna_dense_dev, const void* const* w_host, const int* gidx_host, int B, int gn, int zs, int G,
+                       const int* glst, int K, int form, void* out, void* sub, void* stream);
+
 /* Generic direct Conv3d (stem / head / RNA path), NCDHW in, NCDHW out. */
 int tm_op_conv_direct(const void* x, const void* w_host, const void* bias_host, void* y, int N,
                       int Cin, int Cout, int Zin, int S, int kz, int ky, int kx, int pz, int py,

@@ -122,7 +122,11 @@ SIGNATURES = {
     "tm_op_window_attn_train": (c_int, [c_void_p] * 12 + [c_int] * 4 + [c_void_p]),
     "tm_op_window_attn": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p]),
     "tm_op_window_attn_kv": (c_int, [c_void_p] * 5 + [c_int] * 6 + [c_void_p]),
-    "tm_op_conv_direct": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 13 + [c_void_p]),
+    "tm_op_gene_attn": (c_int, [c_void_p, C.POINTER(c_void_p), C.POINTER(c_int)] + [c_int] * 7 + [c_void_p] * 3),
+    "tm_op_rna_mid": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p] * 2),
+    "tm_op_gene_readout": (c_int, [c_void_p, C.POINTER(c_void_p), C.POINTER(c_int)] + [c_int] * 4 + [C.POINTER(c_int), c_int, c_int] +
+                           [c_void_p] * 3),
+    "tm_op_conv_direct":(c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 13 + [c_void_p]),
 }
 
 _lib = None

@@ -775,6 +775,32 @@ hipError_t launch_gene_readout_gather(const float* maps, const float* rna, int B
   return hipGetLastError();
 }
 
+// Patches per chunk (GENE_RO_CHUNK) bound the map scratch (4 maps of a chunk) and the generic kernel's slabs independently of B
+size_t gene_readout_ws_floats(int B, int G, int D) {
+  const size_t bc = (size_t)(B < GENE_RO_CHUNK ? B : GENE_RO_CHUNK);
+  return 4 * bc * G * G + bc * gene_generic_split((int)bc) * gene_generic_ws_floats(G, D);
+}
+hipError_t launch_gene_readout_chunks(const float* rna, int B, int gn, int zs, int G, int D, const GeneW& w, const int* gidx,
+                                      const int* glst, int K, float* out, float* sub, float* ws, hipStream_t s) {
+  const int bc = B < GENE_RO_CHUNK ? B : GENE_RO_CHUNK, gg = gn * gn;
+  float* maps = ws;
+  float* gws = maps + (size_t)4 * bc * G * G;
+  for (int n0 = 0; n0 < B; n0 += bc) {
+    const int nb = B - n0 < bc ? B - n0 : bc;
+    const float* rc = rna + (size_t)n0 * gg * zs * 500;
+    // three slice-pair masks then the unmasked map (model/unet_attn.py:162-172)
+    for (int i = 0; i < 4; ++i) {
+      const int lo = (i < 3) ? i : 0, hi = (i < 3) ? i + 2 : zs;
+      hipError_t e = launch_gene_attn_generic(rc, nb, gn, zs, G, D, w, gidx, nullptr, maps + (size_t)i * nb * G * G, lo, hi, gws, s);
+      if (e != hipSuccess) return e;
+    }
+    hipError_t e = launch_gene_readout_gather(maps, rc, nb, gn, zs, G, gidx, glst, K, out + (size_t)n0 * 4 * K * 2 * gg,
+                                              sub ? sub + (size_t)n0 * K * K : nullptr, (long)B * K * K, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 // ==========================================================================================
 // Windowed gene-patch cross attention core (Attention.forward with n_h=2, one head:
 // model/MBAblocks.py:555-595): per (patch, window) RMSNorm(q), RMSNorm(k) over C,

@@ -154,4 +154,9 @@ void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out) {
   }
 }
 
+void transpose_host(const float* w, int rows, int cols, float* out) {
+  for (int r = 0; r < rows; ++r)
+    for (int c = 0; c < cols; ++c) out[(size_t)c * rows + r] = w[(size_t)r * cols + c];
+}
+
 }  // namespace tmk

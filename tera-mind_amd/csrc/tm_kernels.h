@@ -64,6 +64,7 @@ int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse
 // segment i (each padded to x8)
 void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int nseg, float* out);
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out);  // per-cin vector -> virtual order
+void transpose_host(const float* w, int rows, int cols, float* out);         // [rows][cols] -> [cols][rows] (Linear weights of GeneW)
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_UP2 = 2 };
 enum { ZM_PAD1 = 0, ZM_INPLANE = 1, ZM_VALID = 2,    // z structure of a k x 3 x 3 conv (see conv3d_mfma)
@@ -287,6 +288,14 @@ hipError_t launch_gene_readout(const float* rna, int B, int gn, int zs, int G, c
                                float* out, float* sub, hipStream_t s);
 hipError_t launch_gene_readout_gather(const float* maps, const float* rna, int Bc, int gn, int zs, int G, const int* gidx,
                                       const int* glst, int K, float* out, float* sub, long sub_map_stride, hipStream_t s);
+// the model's choice of the fused D = 64 kernels (launch_gene_attn, launch_gene_readout): no gene slot table, G <= 232
+inline bool gene_mfma_rule(int D, int G, bool has_gidx) { return D == 64 && G <= 232 && !has_gidx; }
+// the read-out wherever the fused kernel does not apply: the generic map kernel over chunks of GENE_RO_CHUNK patches (the four maps
+// of a chunk, then the generic kernel's slabs, in `ws` of gene_readout_ws_floats(B, G, D) floats), then gather-and-contract
+constexpr int GENE_RO_CHUNK = 8;
+size_t gene_readout_ws_floats(int B, int G, int D);
+hipError_t launch_gene_readout_chunks(const float* rna, int B, int gn, int zs, int G, int D, const GeneW& w, const int* gidx,
+                                      const int* glst, int K, float* out, float* sub, float* ws, hipStream_t s);
 
 // ---- windowed cross attention core -----------------------------------------------------
 // q, k, v: CB8 token tensors (tokens = voxels (z h w)); n_h x n_h windows over (H, W).
@@ -368,6 +377,8 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3))); 
     hipError_t e_ = (expr);                                                                    \
     if (e_ != hipSuccess) return fail(TM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
+// the read-out's argument rules (tm_gene_attn_readout, tm_op_gene_readout): TM_OK, or TM_ERR_ARG with the text
+int gene_readout_args(int zs, const int* glst, int K, int G);
 inline bool is_h16(int dtype) { return dtype == TM_DTYPE_BF16 || dtype == TM_DTYPE_F16; }   // 16-bit operand modes
 inline TVH as_h(const TV& t) {      // the same geometry and strides over 16-bit storage
   TVH v;

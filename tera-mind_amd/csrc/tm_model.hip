@@ -323,7 +323,7 @@ extern "C" int tm_model_create(const tm_config* cfg, tm_model** out) {
   m->deep8 = (cfg->patch_size >> 3) >= 8;                          // the deepest of the four levels: patch / 8
   m->gn = cfg->patch_size / 16;
   m->D = m->gn * m->gn * cfg->rna_slc;
-  m->gene_mfma = m->D == 64 && cfg->rna_num <= 232 && cfg->rna_num != 81;
+  m->gene_mfma = gene_mfma_rule(m->D, cfg->rna_num, cfg->rna_num == 81);
   m->downz_mfma = cfg->rna_slc == 4 && (m->gn == 4 || m->gn == 8);   // kz == 3 on a grid the MFMA tile forms cover
   m->rw[0] = cfg->rna_num;
   for (int i = 0; i < 3; ++i) m->rw[i + 1] = RNA_TAIL[i];
@@ -483,8 +483,7 @@ static void pack_raw(Packer& pk, std::vector<Fix>& fx, const float** slot, const
 static void pack_transposed(Packer& pk, std::vector<Fix>& fx, const float** slot, const std::vector<float>& w,
                             int rows, int cols) {           // [rows][cols] -> [cols][rows]
   size_t off = pk.reserve((size_t)rows * cols);
-  for (int r = 0; r < rows; ++r)
-    for (int c = 0; c < cols; ++c) pk.buf[off + (size_t)c * rows + r] = w[(size_t)r * cols + c];
+  transpose_host(w.data(), rows, cols, pk.buf.data() + off);
   fx.push_back({slot, off});
 }
 static void pack_direct(tm_model* m, Packer& pk, std::vector<Fix>& fx, DirectW& dw, const std::string& pfx, int Cout,
@@ -1740,22 +1739,12 @@ extern "C" int tm_gene_attn(tm_model* m, const void* rna_dense, int B, void* att
   return TM_OK;
 }
 
-// Patches per chunk of the read-out on the geometries without the fused kernel: bounds the map scratch (4 maps of a chunk) and
-// the generic kernel's slabs independently of B
-static const int RO_CHUNK = 8;
-
 extern "C" size_t tm_gene_attn_readout_workspace_bytes(const tm_model* m, int B, int K) {
   if (!m || B < 1 || m->gene_mfma) return 256;
-  const size_t bc = (size_t)(B < RO_CHUNK ? B : RO_CHUNK), G = (size_t)m->cfg.rna_num;
-  return 256 + (4 * bc * G * G + bc * gene_generic_split((int)bc) * gene_generic_ws_floats(m->cfg.rna_num, m->D)) * sizeof(float);
+  return 256 + gene_readout_ws_floats(B, m->cfg.rna_num, m->D) * sizeof(float);
 }
 
-extern "C" int tm_gene_attn_readout(tm_model* m, const void* rna_dense, int B, const int* glst, int K, void* out, void* sub,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-  if (!m || !rna_dense || !glst || !out || B < 1) return fail(TM_ERR_ARG, "bad argument");
-  if (!m->finalized) return fail(TM_ERR_STATE, "tm_model_finalize has not been called");
-  const tm_config& c = m->cfg;
-  const int G = c.rna_num, zs = c.rna_slc, gg = m->gn * m->gn;
+int tmk::gene_readout_args(int zs, const int* glst, int K, int G) {
   if (zs != 4) return fail(TM_ERR_ARG, "the attention-map read-out is defined for rna_slc = 4 (three slice pairs, model/unet_attn.py:162-172)");
   if (K < 1 || K > 8) return fail(TM_ERR_ARG, "read-out gene list length K = %d outside [1, 8]", K);
   for (int k = 0; k < K; ++k) {
@@ -1763,28 +1752,24 @@ extern "C" int tm_gene_attn_readout(tm_model* m, const void* rna_dense, int B, c
     for (int j = 0; j < k; ++j)
       if (glst[j] == glst[k]) return fail(TM_ERR_ARG, "read-out gene index %d is repeated (glst[%d] and glst[%d])", glst[k], j, k);
   }
+  return TM_OK;
+}
+
+extern "C" int tm_gene_attn_readout(tm_model* m, const void* rna_dense, int B, const int* glst, int K, void* out, void* sub,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+  if (!m || !rna_dense || !glst || !out || B < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (!m->finalized) return fail(TM_ERR_STATE, "tm_model_finalize has not been called");
+  const tm_config& c = m->cfg;
+  const int G = c.rna_num, zs = c.rna_slc;
+  if (int rc = gene_readout_args(zs, glst, K, G)) return rc;
   const size_t need = tm_gene_attn_readout_workspace_bytes(m, B, K);
   if (workspace_bytes < need || (!m->gene_mfma && !workspace)) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
   const float* rna = (const float*)rna_dense;
   hipStream_t s = (hipStream_t)stream;
-  if (m->gene_mfma) {
+  if (m->gene_mfma)
     HIP_TRY(launch_gene_readout(rna, B, m->gn, zs, G, m->gene, glst, K, (float*)out, (float*)sub, s));
-    return TM_OK;
-  }
-  // other geometries: the map kernels over chunks of RO_CHUNK patches into the bounded scratch, then gather-and-contract
-  const int bc = B < RO_CHUNK ? B : RO_CHUNK;
-  float* maps = (float*)workspace;
-  float* gws = maps + (size_t)4 * bc * G * G;
-  for (int n0 = 0; n0 < B; n0 += bc) {
-    const int nb = B - n0 < bc ? B - n0 : bc;
-    const float* rc = rna + (size_t)n0 * gg * zs * 500;
-    for (int i = 0; i < 4; ++i) {
-      const int lo = (i < 3) ? i : 0, hi = (i < 3) ? i + 2 : zs;
-      HIP_TRY(launch_gene_attn_generic(rc, nb, m->gn, zs, G, m->D, m->gene, m->gene_idx, nullptr, maps + (size_t)i * nb * G * G,
-                                       lo, hi, gws, s));
-    }
-    HIP_TRY(launch_gene_readout_gather(maps, rc, nb, m->gn, zs, G, m->gene_idx, glst, K, (float*)out + (size_t)n0 * 4 * K * 2 * gg,
-                                       sub ? (float*)sub + (size_t)n0 * K * K : nullptr, (long)B * K * K, s));
-  }
+  else
+    HIP_TRY(launch_gene_readout_chunks(rna, B, m->gn, zs, G, m->D, m->gene, m->gene_idx, glst, K, (float*)out, (float*)sub,
+                                       (float*)workspace, s));
   return TM_OK;
 }

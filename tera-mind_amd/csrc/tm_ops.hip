@@ -54,6 +54,11 @@ struct DevTmp {
     ptrs.push_back(p);
     return !zero || ok(hipMemsetAsync(p, 0, n * sizeof(float), st), "hipMemsetAsync") ? (float*)p : nullptr;
   }
+  // n floats copied from `host` in `st`'s order; `host` must stay alive until the stream is synchronised (finish)
+  float* ordered_upload(const void* host, size_t n) {
+    float* p = ordered_floats(n, false);
+    return p && ok(hipMemcpyAsync(p, host, n * sizeof(float), hipMemcpyHostToDevice, st), "hipMemcpyAsync") ? p : nullptr;
+  }
   bool ok(hipError_t e, const char* call) {
     if (e != hipSuccess) { err = e; what = call; }
     return e == hipSuccess;
@@ -731,6 +736,97 @@ extern "C" int tm_op_window_attn_kv(const void* q_cb8, const void* kv_cb8, const
   if (e == hipSuccess) e = (f16 ? launch_window_attn_f16 : launch_window_attn_bf16)(hq, hkv.blocks(0, cb), hkv.blocks(cb, cb), qw, kw, o, st);
   return finish(st, e, "window attention");
 }
+// ---- gene-gene attention block (tm_attn.hip), one kernel form per call --------------------------------------------------------
+// The twelve host arrays of the block in checkpoint layout ([out][in]) in the order tm_model_finalize packs them -> GeneW in `tmp`,
+// the Linear weights transposed to [in][out].  `keep` holds the transposed host copies until the hook has synchronised.
+static GeneW upload_gene_w(DevTmp& tmp, const void* const* wh, int D, std::vector<std::vector<float>>& keep) {
+  auto mat = [&](int i, int rows, int cols) {
+    keep.emplace_back((size_t)rows * cols);
+    transpose_host((const float*)wh[i], rows, cols, keep.back().data());
+    return (const float*)tmp.ordered_upload(keep.back().data(), keep.back().size());
+  };
+  auto vec = [&](int i, int n) { return (const float*)tmp.ordered_upload(wh[i], (size_t)n); };
+  GeneW w;
+  w.wq_t = mat(0, D, D); w.bq = vec(1, D);
+  w.wv_t = mat(2, D, D); w.bv = vec(3, D);
+  w.qnorm = vec(4, D);
+  w.wp_t = mat(5, D, D); w.bp = vec(6, D);
+  w.norm2 = vec(7, D);
+  w.w1_t = mat(8, 4 * D, D); w.b1 = vec(9, 4 * D);
+  w.w2_t = mat(10, D, 4 * D); w.b2 = vec(11, D);
+  return w;
+}
+// The geometries launch_gene_attn / launch_gene_attn_generic / launch_gene_readout take, as one readable list: TM_OK and the
+// resolved form in *f (1 = the fused D = 64 kernels, 2 = the generic kernel), or TM_ERR_ARG with the reason (the launchers
+// themselves only answer hipErrorInvalidValue).  Beyond their rules: without a slot table gene g reads slot g of the 500 a slice
+// of the dense tensor has, so G > 500 needs one, and its entries must be slots.
+static int gene_attn_form(const void* rna, const void* const* wh, const int* gidx, int B, int gn, int zs, int G, int form, int* f) {
+  if (!rna || !wh) return fail(TM_ERR_ARG, "null argument");
+  for (int i = 0; i < 12; ++i)
+    if (!wh[i]) return fail(TM_ERR_ARG, "null argument: w_host[%d]", i);
+  if (form < 0 || form > 2) return fail(TM_ERR_ARG, "form = %d: 0 (the model's rule), 1 (fused D = 64 kernel) or 2 (generic kernel)", form);
+  if (B < 1 || gn < 1 || zs < 1 || G < 1) return fail(TM_ERR_ARG, "B = %d, gn = %d, zs = %d, G = %d must all be >= 1", B, gn, zs, G);
+  const long D = (long)gn * gn * zs;
+  if (D > 512) return fail(TM_ERR_ARG, "D = gn^2 * zs = %ld > 512", D);
+  if (G > 512) return fail(TM_ERR_ARG, "G = %d > 512", G);
+  if (!gidx && G > 500) return fail(TM_ERR_ARG, "G = %d > 500 needs a gene slot table (a slice of the dense tensor has 500 slots)", G);
+  for (int g = 0; gidx && g < G; ++g)
+    if (gidx[g] < 0 || gidx[g] >= 500) return fail(TM_ERR_ARG, "gene slot gidx[%d] = %d outside [0, 500)", g, gidx[g]);
+  *f = form ? form : (gene_mfma_rule((int)D, G, gidx != nullptr) ? 1 : 2);
+  if (*f == 1) {
+    if (D != 64) return fail(TM_ERR_ARG, "gn^2 * zs = %ld != D = 64 of the fused kernel", D);
+    if (G > 232) return fail(TM_ERR_ARG, "G = %d > 232 (fused kernel: the tokens of a patch live in LDS)", G);
+    if (gidx) return fail(TM_ERR_ARG, "the fused kernel takes no gene slot table");
+  }
+  return TM_OK;
+}
+
+extern "C" int tm_op_gene_attn(const void* rna_dense_dev, const void* const* w_host, const int* gidx_host, int B, int gn, int zs,
+                               int G, int form, int zlo, int zhi, void* out_tok_cb8, void* attn_map, void* stream) {
+  int f = 0;
+  if (int rc = gene_attn_form(rna_dense_dev, w_host, gidx_host, B, gn, zs, G, form, &f)) return rc;
+  if (!out_tok_cb8 && !attn_map) return fail(TM_ERR_ARG, "null argument: one of out_tok_cb8 and attn_map is required");
+  if (zlo < 0 || zlo > zhi || zhi > zs) return fail(TM_ERR_ARG, "slice mask [%d, %d) outside [0, %d]", zlo, zhi, zs);
+  const int D = gn * gn * zs;
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp(st);
+  std::vector<std::vector<float>> keep;
+  const GeneW w = upload_gene_w(tmp, w_host, D, keep);
+  const int* gidx = gidx_host ? (const int*)tmp.ordered_upload(gidx_host, (size_t)G) : nullptr;
+  float* ws = f == 2 ? tmp.ordered_floats((size_t)B * gene_generic_split(B) * gene_generic_ws_floats(G, D), false) : nullptr;
+  if (tmp.err) return (void)hipStreamSynchronize(st), tmp.report();      // `keep` may still be the source of a queued copy
+  const float* rna = (const float*)rna_dense_dev;
+  const hipError_t e = f == 1 ? launch_gene_attn(rna, B, gn, zs, G, w, (float*)out_tok_cb8, (float*)attn_map, zlo, zhi, st)
+                              : launch_gene_attn_generic(rna, B, gn, zs, G, D, w, gidx, (float*)out_tok_cb8, (float*)attn_map, zlo, zhi, ws, st);
+  return finish(st, e, "gene attention");
+}
+
+extern "C" int tm_op_rna_mid(const void* rna_dense_dev, int B, int gn, int zs, int G, void* out, void* stream) {
+  if (!rna_dense_dev || !out) return fail(TM_ERR_ARG, "null argument");
+  if (B < 1 || gn < 1 || zs < 1 || G < 1 || G > 500) return fail(TM_ERR_ARG, "B = %d, gn = %d, zs = %d >= 1 and 1 <= G = %d <= 500", B, gn, zs, G);
+  return finish((hipStream_t)stream, launch_rna_mid((const float*)rna_dense_dev, B, gn, zs, G, (float*)out, (hipStream_t)stream), "rna_mid");
+}
+
+extern "C" int tm_op_gene_readout(const void* rna_dense_dev, const void* const* w_host, const int* gidx_host, int B, int gn, int zs,
+                                  int G, const int* glst, int K, int form, void* out, void* sub, void* stream) {
+  if (!glst || !out) return fail(TM_ERR_ARG, "null argument");
+  int f = 0;
+  if (int rc = gene_attn_form(rna_dense_dev, w_host, gidx_host, B, gn, zs, G, form, &f)) return rc;
+  if (int rc = gene_readout_args(zs, glst, K, G)) return rc;
+  const int D = gn * gn * zs;
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp(st);
+  std::vector<std::vector<float>> keep;
+  const GeneW w = upload_gene_w(tmp, w_host, D, keep);
+  const int* gidx = gidx_host ? (const int*)tmp.ordered_upload(gidx_host, (size_t)G) : nullptr;
+  float* ws = f == 2 ? tmp.ordered_floats(gene_readout_ws_floats(B, G, D), false) : nullptr;
+  if (tmp.err) return (void)hipStreamSynchronize(st), tmp.report();
+  const float* rna = (const float*)rna_dense_dev;
+  const hipError_t e = f == 1 ? launch_gene_readout(rna, B, gn, zs, G, w, glst, K, (float*)out, (float*)sub, st)
+                              : launch_gene_readout_chunks(rna, B, gn, zs, G, D, w, gidx, glst, K, (float*)out, (float*)sub, ws, st);
+  return finish(st, e, "gene read-out");
+}
+
 extern "C" int tm_op_conv_direct(const void* x, const void* w_host, const void* bias_host, void* y, int N, int Cin,
                                  int Cout, int Zin, int S, int kz, int ky, int kx, int pz, int py, int px, int silu_in,
                                  int up2_out, void* stream) {

@@ -80,6 +80,28 @@ def test_op_argument_checks_without_device():
     # training attention core: Z = 2, S = 6 is a window of 18 tokens
     assert L.tm_op_window_attn_train(p, p, p, p, p, None, p, None, None, None, None, None, 1, 64, 2, 6, None) == -1
     assert b"18 tokens" in L.tm_last_error()
+    # gene-gene attention hooks (args: rna w_host[12] gidx B gn zs G form zlo zhi out_tok attn_map): D = gn^2 zs <= 512, G <= 512,
+    # the fused form is D = 64 with G <= 232; one output is required; the read-out is rna_slc = 4 with 1 <= K <= 8
+    wh = (C.c_void_p * 12)(*[p.value] * 12)
+    gl = (C.c_int * 2)(0, 1)
+    assert L.tm_op_gene_attn(p, wh, None, 1, 8, 16, 229, 0, 0, 16, p, p, None) == -1
+    assert b"D = gn^2 * zs = 1024 > 512" in L.tm_last_error()
+    assert L.tm_op_gene_attn(p, wh, None, 1, 4, 4, 233, 1, 0, 4, p, p, None) == -1
+    assert b"G = 233 > 232" in L.tm_last_error()
+    assert L.tm_op_gene_attn(p, wh, None, 1, 4, 8, 229, 1, 0, 8, p, p, None) == -1
+    assert b"!= D = 64" in L.tm_last_error()
+    assert L.tm_op_gene_attn(p, wh, None, 1, 4, 4, 229, 0, 0, 4, None, None, None) == -1
+    assert b"null" in L.tm_last_error()
+    assert L.tm_op_gene_attn(p, None, None, 1, 4, 4, 229, 0, 0, 4, p, p, None) == -1
+    assert b"null" in L.tm_last_error()
+    assert L.tm_op_rna_mid(p, 1, 4, 4, 229, None, None) == -1
+    assert b"null" in L.tm_last_error()
+    assert L.tm_op_gene_readout(p, wh, None, 1, 4, 4, 229, gl, 9, 0, p, None, None) == -1
+    assert b"outside [1, 8]" in L.tm_last_error()
+    assert L.tm_op_gene_readout(p, wh, None, 1, 4, 8, 229, gl, 2, 0, p, None, None) == -1
+    assert b"rna_slc = 4" in L.tm_last_error()
+    assert L.tm_op_gene_readout(p, wh, None, 1, 4, 4, 229, gl, 2, 0, None, None, None) == -1
+    assert b"null" in L.tm_last_error()
     # prep backward: scale without shift
     assert L.tm_op_prep_bwd(p, p, p, p, None, None, C.c_float(1.0), 1, p, p, p, p, 1, 8, 2, 4, None) == -1
     assert b"scale without shift" in L.tm_last_error()
