@@ -271,6 +271,34 @@ int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pitch, int qua
  * tm_jpeg_encode_tiles (which reads the same table statements).  buf == NULL: only *out_bytes is set.  Host only. */
 int tm_jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
 
+/* ---- ROI evaluation ("evaluation"): the measures of utils/metrics.py:201-541 for a generated / real plane pair ----
+ * Pixels are uint8 or float32, chosen by `dtype`; pitches and plane strides are in bytes.  uint8 pointers need no alignment;
+ * float32 pointers, pitches and strides are multiples of 4. */
+enum { TM_PIX_U8 = 0, TM_PIX_F32 = 1 };
+
+/* tm_ssim_planes: for each of the P plane pairs x[p], y[p] of [H][W] (plane p at x + p * x_plane, row r at + r * x_pitch):
+ *   out[p][0] = sum of ssim_map, out[p][1] = sum of cs_map over the (H - n + 1) x (W - n + 1) valid region of `_ssim`
+ *               (utils/metrics.py:266-305): the separable valid filter of x, y, x^2, y^2, x y with the n taps of win_host
+ *               (float32, host; n odd, 3 .. 33), cs = (2 s12 + C2) / (s1 + s2 + C2),
+ *               ssim = (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1) * cs
+ *   out[p][2] = sum of (x - y)^2 over the whole plane (what PSNR needs); for uint8 the exact integer
+ *   out is double [P][3] on the device.  The filters and maps are fp32, the second moments are formed about one pixel value
+ *   per image and 64 x 32 tile (the variances do not depend on it; no cancellation on near-saturated planes); each lane adds its 8
+ *   outputs in fp32, everything above is fp64 in a fixed tree: no atomics, two calls give the same bits.
+ *   Asynchronous on `stream`; the per-tile partials are stream-ordered scratch of the call.
+ *   TM_ERR_ARG with a text before any device call: a null pointer, an unknown dtype, n even or outside 3 .. 33, H or W below
+ *   n, P outside 1 .. 65535, a pitch below the row, a misaligned float32 operand. */
+int tm_ssim_planes(const void* x, const void* y, int dtype, int P, int H, int W, int64_t x_pitch, int64_t x_plane,
+                   int64_t y_pitch, int64_t y_plane, const float* win_host, int n, float C1, float C2, double* out,
+                   void* stream);
+
+/* tm_avgpool2_pad: one MS-SSIM level (utils/metrics.py:428-430), F.avg_pool2d(kernel 2, stride 2, padding (H % 2, W % 2)):
+ *   dst float32 [P][ceil(H / 2)][ceil(W / 2)], window (i, j) = rows 2 i - H % 2 .., columns 2 j - W % 2 .. of src, a row or
+ *   column -1 being the zero pad; the sum (row-major) times 0.25: the pad is counted.  src uint8 or float32 by `dtype`.
+ *   Asynchronous on `stream`.  TM_ERR_ARG before any device call as for tm_ssim_planes. */
+int tm_avgpool2_pad(const void* src, int dtype, int P, int H, int W, int64_t src_pitch, int64_t src_plane, void* dst,
+                    int64_t dst_pitch, int64_t dst_plane, void* stream);
+
 /* Measurement hooks (bench.py): while enabled, every launch of the dominant kernel
  * (conv3d_mfma<2,..> in fp32, conv27_bf16 / conv27_f16 in the 16-bit modes: the 3x3x3 implicit-GEMM conv) inside tm_unet_forward is bracketed by two
  * hipEvents recorded on the forward's stream.  tm_profile_collect synchronises on the last

@@ -370,6 +370,23 @@ hipError_t launch_jpeg_tiles(const uint8_t* plane, int H, int W, long pitch, int
                              uint8_t* slots, long slot_bytes, int32_t* need, uint8_t* packed, int64_t* offsets, hipStream_t s);
 int jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
 
+// ---- ROI evaluation (tm_metrics.hip) -----------------------------------------------------
+// SSIM statistics of P plane pairs: the valid output is cut into SSIM_TW x SSIM_TH tiles, one workgroup each
+constexpr int SSIM_TW = 64, SSIM_TH = 32, SSIM_MAX_TAPS = 33, SSIM_TAP_PAD = 7;
+struct SsimTaps {                              // by value in the kernel arguments: every tap is a scalar operand
+  float w[SSIM_TAP_PAD + SSIM_MAX_TAPS + SSIM_TAP_PAD];   // tap t at w[SSIM_TAP_PAD + t], zeros around
+  float sum, one_minus_sum;                    // S = (sum of the taps)^2, the weight of the n x n window, and 1 - S: from double, rounded once
+  int n;
+};
+size_t ssim_lds_bytes(int n);
+size_t ssim_partial_doubles(int P, int H, int W, int n);      // per tile and plane: sum ssim, sum cs, sum (x - y)^2
+// out[p][3] = the three sums of plane p in fp64; pitches and plane strides in bytes; partials: ssim_partial_doubles(...) doubles
+hipError_t launch_ssim_planes(const void* x, const void* y, bool is_f32, int P, int H, int W, long xpitch, long xplane, long ypitch,
+                              long yplane, const SsimTaps& taps, float C1, float C2, double* partials, double* out, hipStream_t s);
+// dst fp32 [P][ceil(H / 2)][ceil(W / 2)] = avg_pool2d(kernel 2, stride 2, padding (H % 2, W % 2)) with the pad counted
+hipError_t launch_avgpool2_pad(const void* src, bool is_f32, int P, int H, int W, long spitch, long splane, void* dst, long dpitch,
+                               long dplane, hipStream_t s);
+
 // ---- host helpers of the C-ABI units (tm_model.hip, tm_ops.hip, tm_io.hip) ---------------
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets the tm_last_error() text, returns code
 #define HIP_TRY(expr)                                                                          \

@@ -1242,6 +1242,55 @@ extern "C" int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pit
   return TM_OK;
 }
 
+// SSIM / PSNR sums of plane pairs (tm_metrics.hip); enqueues only, the per-tile partials are stream-ordered scratch
+static int pix_geometry(const char* fn, const char* what, const void* p, int dtype, int W, int64_t pitch, int64_t plane) {
+  const int64_t esz = dtype == TM_PIX_F32 ? 4 : 1;
+  if (pitch < (int64_t)W * esz) return fail(TM_ERR_ARG, "%s: %s pitch %lld below the row of %lld bytes", fn, what, (long long)pitch, (long long)W * esz);
+  if (plane < 0) return fail(TM_ERR_ARG, "%s: negative %s plane stride", fn, what);
+  if (esz == 4 && (((uintptr_t)p | (uintptr_t)pitch | (uintptr_t)plane) & 3))
+    return fail(TM_ERR_ARG, "%s: float32 %s pointer, pitch and plane stride must be multiples of 4 bytes", fn, what);
+  return TM_OK;
+}
+extern "C" int tm_ssim_planes(const void* x, const void* y, int dtype, int P, int H, int W, int64_t x_pitch, int64_t x_plane,
+                              int64_t y_pitch, int64_t y_plane, const float* win_host, int n, float C1, float C2, double* out,
+                              void* stream) {
+  const char* fn = "tm_ssim_planes";
+  if (!x || !y || !win_host || !out) return fail(TM_ERR_ARG, "%s: null x / y / window / out pointer", fn);
+  if (dtype != TM_PIX_U8 && dtype != TM_PIX_F32) return fail(TM_ERR_ARG, "%s: dtype %d is neither TM_PIX_U8 nor TM_PIX_F32", fn, dtype);
+  if (n < 3 || n > SSIM_MAX_TAPS || !(n & 1)) return fail(TM_ERR_ARG, "%s: window of %d taps (odd, 3 .. %d)", fn, n, SSIM_MAX_TAPS);
+  if (P < 1 || P > 65535) return fail(TM_ERR_ARG, "%s: P = %d outside 1 .. 65535", fn, P);
+  if (H < n || W < n) return fail(TM_ERR_ARG, "%s: plane %d x %d below the window of %d taps", fn, H, W, n);
+  if ((H - n) / SSIM_TH >= 65535) return fail(TM_ERR_ARG, "%s: H = %d takes more than 65535 tile rows", fn, H);
+  if (int rc = pix_geometry(fn, "x", x, dtype, W, x_pitch, x_plane)) return rc;
+  if (int rc = pix_geometry(fn, "y", y, dtype, W, y_pitch, y_plane)) return rc;
+  SsimTaps taps = {};
+  double sum = 0.0;
+  for (int t = 0; t < n; ++t) { taps.w[SSIM_TAP_PAD + t] = win_host[t]; sum += (double)win_host[t]; }
+  taps.sum = (float)(sum * sum); taps.one_minus_sum = (float)(1.0 - sum * sum); taps.n = n;   // the n x n window weighs (sum)^2
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp(st);
+  double* partials = (double*)tmp.ordered_floats(2 * ssim_partial_doubles(P, H, W, n), false);
+  if (tmp.err) return tmp.report();
+  HIP_TRY(launch_ssim_planes(x, y, dtype == TM_PIX_F32, P, H, W, (long)x_pitch, (long)x_plane, (long)y_pitch, (long)y_plane, taps, C1, C2,
+                             partials, out, st));
+  return TM_OK;
+}
+
+// One MS-SSIM level (tm_metrics.hip); enqueues only
+extern "C" int tm_avgpool2_pad(const void* src, int dtype, int P, int H, int W, int64_t src_pitch, int64_t src_plane, void* dst,
+                               int64_t dst_pitch, int64_t dst_plane, void* stream) {
+  const char* fn = "tm_avgpool2_pad";
+  if (!src || !dst) return fail(TM_ERR_ARG, "%s: null source / destination", fn);
+  if (dtype != TM_PIX_U8 && dtype != TM_PIX_F32) return fail(TM_ERR_ARG, "%s: dtype %d is neither TM_PIX_U8 nor TM_PIX_F32", fn, dtype);
+  if (P < 1 || P > 65535) return fail(TM_ERR_ARG, "%s: P = %d outside 1 .. 65535", fn, P);
+  if (H < 1 || W < 1) return fail(TM_ERR_ARG, "%s: H and W must be positive, got %d x %d", fn, H, W);
+  if (int rc = pix_geometry(fn, "source", src, dtype, W, src_pitch, src_plane)) return rc;
+  if (int rc = pix_geometry(fn, "destination", dst, TM_PIX_F32, (W + 1) / 2, dst_pitch, dst_plane)) return rc;
+  HIP_TRY(launch_avgpool2_pad(src, dtype == TM_PIX_F32, P, H, W, (long)src_pitch, (long)src_plane, dst, (long)dst_pitch, (long)dst_plane,
+                              (hipStream_t)stream));
+  return TM_OK;
+}
+
 // Timing hook of the conv weight gradient on random device data (uniform in [-1, 1)): engine 0 = conv_wgrad_kernel (VALU),
 // 1 = conv_wgrad_mfma_kernel + its chunk reduction.  One warm-up launch, then `reps` measurements of `iters` launches between two
 // events each: ms_per_launch_host[r] = milliseconds per launch of repetition r (their spread is the noise of identical calls).

@@ -53,6 +53,30 @@ def stitch_dir(step_dir, hst: int, wst: int, hnm: int, wnm: int, slc: int = 50,
     return out
 
 
+def stitch_real_dir(rdir, hst: int, wst: int, hnm: int, wnm: int, slc: int = 50,
+                    slices: Optional[Sequence[int]] = None, size: int = tiles.TILE) -> np.ndarray:
+    """Mosaic of a directory of real tiles (infer_brn.py:67-77 with is_gen=False, test_brn.py:93-99): eight-number names
+    '{r0}_{r1}_{c0}_{c1}_{r0-p}_{r1+p}_{c0-p}_{c1+p}.zip' with the frame p = size // 2, arrays [(c s), size + 2p, size + 2p]
+    in image units.  The centre is cut, '(c s) -> (s c)', `.astype(uint8)` -> uint8 [n_slices, hnm*size, wnm*size]."""
+    out, p = None, size // 2
+    for pw in range(wnm):
+        for ph in range(hnm):
+            r0, c0 = hst + ph * size, wst + pw * size
+            name = f"{r0}_{r0 + size}_{c0}_{c0 + size}_{r0 - p}_{r0 + size + p}_{c0 - p}_{c0 + size + p}.zip"
+            a = formats.read_zarr_zip(os.path.join(str(rdir), name))
+            if a.ndim != 3 or a.shape[1] < size + p or a.shape[2] < size + p:
+                raise ValueError(f"{name}: a real tile is [(c s), {size + 2 * p}, {size + 2 * p}], got {a.shape}")
+            if a.shape[0] % slc:
+                raise ValueError(f"{name}: {a.shape[0]} planes are no multiple of slc = {slc}")
+            t = reorder_slices(torch.from_numpy(np.ascontiguousarray(a[:, p:p + size, p:p + size])), slc).numpy().astype(np.uint8)
+            if slices is not None:
+                t = t[list(slices)]
+            if out is None:
+                out = np.zeros((t.shape[0], hnm * size, wnm * size), dtype=np.uint8)
+            out[:, ph * size:(ph + 1) * size, pw * size:(pw + 1) * size] = t
+    return out
+
+
 def save_slices(mosaic, odir, names: Optional[Sequence[int]] = None, jpeg: bool = True):
     """'{odir}/all_{sl}.tif' (+ '.jpg'), the file names of infer_brn.py:96-101 (flat, non-pyramidal)."""
     from PIL import Image
