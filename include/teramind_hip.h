@@ -497,6 +497,44 @@ int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, const int* coll
                    const void* mod_shift, long mod_stride, int mod_half, int per_image, int act, int variant,
                    void* out_cb8, void* raw_cb8, int iters, float* elapsed_ms, void* stream);
 
+/* One block-input pass in any combination of tensor types the executor launches: tm_op_prep_f32's arguments with
+ *   resample    0 same, 1 nearest x2 (sources at S / 2), 2 the 2 x 2 average (sources at 2 S; norm and SiLU per source voxel,
+ *               then the mean), 3 pick (output (z, y, x) <- source (z, 2 y, 2 x) at 2 S, the collage remap in source coordinates);
+ *   src_dtype, out_dtype, raw_dtype, mod_dtype (per-voxel tensors only): TM_DTYPE_F32 | TM_DTYPE_BF16 | TM_DTYPE_F16 CB8 DEVICE
+ *               tensors; bf16 and f16 may not meet in one call; per-image rows are fp32;
+ *   pad_blocks  all-zero channel blocks behind the last real one of a 16-bit `out` (and of a 16-bit `raw`): those tensors
+ *               hold ceil-8 blocks per source + pad_blocks; an fp32 tensor holds exactly the ceil-8 blocks;
+ *   variant     launch_prep's knob: 0 = the form the model takes, 1 = prep_kernel, 2 | 3 = prep_h16_kernel with one | four waves
+ *               per 64 voxels (all-16-bit calls; 2: at most 32 blocks), 2 on an fp32 call = the wide form.
+ * The call goes through the executor's launcher and nothing else: which kernel runs is part of what a test of it checks.
+ * TM_ERR_ARG with a tm_last_error() text before any device call: the downsample form with a collage, a modulation or more than
+ * one source; up2 with a collage; up2 or pick2 with an odd S; mixed 16-bit types; pad_blocks with an fp32 output; mod_half
+ * without a per-voxel modulation or with an odd S; a variant whose form does not take the call. */
+int tm_op_prep_form(const void* const* src, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
+                    int p1, int p2, int resample, int src_dtype, int out_dtype, const void* norm_w_dev, int c_real,
+                    int mod, int mod_dtype, const void* mod_scale, const void* mod_shift, long mod_stride, int mod_half,
+                    int per_image, int act, int variant, int pad_blocks, void* out, void* raw, int raw_dtype,
+                    int iters, float* elapsed_ms, void* stream);
+
+/* The stem Conv3d(Cin -> Cout, (1, 3, 3), pad (0, 1, 1)) on its own (stem_kernel): x DEVICE fp32 NCHW '(s z) h w'
+ * [N][Cin * Z][S][S]; w [Cout][Cin][1][3][3], bias [Cout] HOST, packed as the model loader packs them; y DEVICE CB8
+ * [N][Cout / 8][Z][S][S][8] of `dtype` (fp32, bf16 or f16).  TM_ERR_ARG before any device call: Cout % 32, another dtype. */
+int tm_op_stem(const void* x, const void* w_host, const void* bias_host, void* y, int N, int Cin, int Cout, int Z, int S,
+               int dtype, void* stream);
+/* The head Conv3d(C -> Cout, (1, 3, 3), pad (0, 1, 1)) on its own (head_kernel<dtype, 4 | 8>): x DEVICE CB8
+ * [N][ceil(C / 8)][Z][S][S][8] of `dtype`, pad channels zero; w [Cout][C][1][3][3], bias [Cout] HOST; y DEVICE fp32 NCHW
+ * [N][Cout * Z][S][S].  TM_ERR_ARG before any device call: Cout > 8, another dtype. */
+int tm_op_head(const void* x_cb8, const void* w_host, const void* bias_host, void* y, int N, int C, int Cout, int Z, int S,
+               int dtype, void* stream);
+/* The timestep embedding on its own (time_embed_kernel): t DEVICE int64 [b]; w1 [E][ch], b1 [E], w2 [E][E], b2 [E] DEVICE fp32;
+ * te = W2 silu(W1 sinusoid(t) + b1) + b2 and te_act = silu(te), DEVICE fp32 [b][E].  TM_ERR_ARG before any device call: odd
+ * ch, more than 64 KB of ch + E floats. */
+int tm_op_time_embed(const void* t_dev, const void* w1, const void* b1, const void* w2, const void* b2, void* te, void* te_act,
+                     int b, int ch, int E, void* stream);
+/* Every emb_layer as one matrix (emb_all_kernel): ss[b][tot] = wall [tot][E] te_act[b][E] + ball [tot], all DEVICE fp32.
+ * TM_ERR_ARG before any device call: E % 64 != 0, E > 1024. */
+int tm_op_emb_all(const void* te_act, const void* wall, const void* ball, void* ss, int b, int E, int tot, void* stream);
+
 /* Windowed gene-patch cross attention core (model/MBAblocks.py:551-601 between the q/k/v Linears and proj):
  * q, k, v fp32 CB8 [N, C, Z, S, S]; qw, kw: device fp32 [C] (q_norm / k_norm weights).
  * dtype TM_DTYPE_F32: fp32 MFMA kernels, out = fp32 CB8.  TM_DTYPE_BF16: inputs are rounded to bf16 first (what the

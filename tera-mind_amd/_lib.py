@@ -98,6 +98,12 @@ SIGNATURES = {
                        [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "tm_op_prep_f32": (c_int, [c_void_p] * 3 + [c_int] * 7 + [c_void_p, c_int, c_int, c_void_p, c_void_p, C.c_long] +
                        [c_int] * 4 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "tm_op_prep_form": (c_int, [c_void_p] * 3 + [c_int] * 9 + [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, C.c_long] +
+                        [c_int] * 5 + [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "tm_op_stem": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "tm_op_head": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
+    "tm_op_time_embed": (c_int, [c_void_p] * 7 + [c_int] * 3 + [c_void_p]),
+    "tm_op_emb_all": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p]),
     "tm_op_prep_train": (c_int, [c_void_p] * 5 + [c_float, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),
     "tm_op_prep_bwd": (c_int, [c_void_p] * 6 + [c_float, c_int] + [c_void_p] * 4 + [c_int] * 4 + [c_void_p]),
     "tm_op_prep_train_rng": (c_int, [c_void_p] * 4 + [C.c_uint64, C.c_uint, c_float, c_int, c_void_p] + [c_int] * 4 + [c_void_p]),

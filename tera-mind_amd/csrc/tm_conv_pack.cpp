@@ -159,4 +159,12 @@ void transpose_host(const float* w, int rows, int cols, float* out) {
     for (int c = 0; c < cols; ++c) out[(size_t)c * rows + r] = w[(size_t)r * cols + c];
 }
 
+void direct_pack_host(const float* w, int Cout, int Cin, int taps, float* out) {
+  const int Cop = (Cout + 7) / 8 * 8;
+  for (size_t i = 0; i < (size_t)taps * Cin * Cop; ++i) out[i] = 0.f;
+  for (int co = 0; co < Cout; ++co)
+    for (int ci = 0; ci < Cin; ++ci)
+      for (int t = 0; t < taps; ++t) out[((size_t)t * Cin + ci) * Cop + co] = w[((size_t)co * Cin + ci) * taps + t];
+}
+
 }  // namespace tmk

@@ -65,6 +65,8 @@ int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse
 void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int nseg, float* out);
 void vec_pack_host(const float* v, const int* seg_c, int nseg, float* out);  // per-cin vector -> virtual order
 void transpose_host(const float* w, int rows, int cols, float* out);         // [rows][cols] -> [cols][rows] (Linear weights of GeneW)
+// the direct kernels' weights (conv_direct, stem, head): w [Cout][Cin][taps] -> out [taps][Cin][ceil(Cout / 8) * 8], pad couts zero
+void direct_pack_host(const float* w, int Cout, int Cin, int taps, float* out);
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_UP2 = 2 };
 enum { ZM_PAD1 = 0, ZM_INPLANE = 1, ZM_VALID = 2,    // z structure of a k x 3 x 3 conv (see conv3d_mfma)

@@ -492,10 +492,7 @@ static void pack_direct(tm_model* m, Packer& pk, std::vector<Fix>& fx, DirectW& 
   const int taps = kz * ky * kx, Cop = (Cout + 7) / 8 * 8;
   const std::vector<float>& w = P(m, pfx + ".weight");
   size_t off = pk.reserve((size_t)taps * Cin * Cop);
-  for (int co = 0; co < Cout; ++co)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int t = 0; t < taps; ++t)
-        pk.buf[off + ((size_t)t * Cin + ci) * Cop + co] = w[((size_t)co * Cin + ci) * taps + t];
+  direct_pack_host(w.data(), Cout, Cin, taps, pk.buf.data() + off);
   fx.push_back({&dw.w, off});
   pack_raw(pk, fx, &dw.bias, P(m, pfx + ".bias"));
 }

@@ -570,6 +570,25 @@ extern "C" int tm_op_conv1_concat(const void* const* x_cb8, const int* cin, cons
   if (e == hipSuccess) e = (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st);
   return finish(st, e, "conv1 concat");
 }
+// the tail of the three prep hooks: `iters` launches of P under launch_prep's variant knob (set and reset around them only);
+// elapsed_ms (host, optional): mean time of launches 2..iters
+static int prep_run(const PrepLaunch& P, int variant, int iters, float* elapsed_ms, hipStream_t st, const char* what) {
+  DevTmp tmp;
+  hipEvent_t e0 = elapsed_ms ? tmp.event() : nullptr, e1 = elapsed_ms ? tmp.event() : nullptr;
+  if (tmp.err) return tmp.report();
+  set_prep_variant(variant);
+  hipError_t e = launch_prep(P, st);                                   // warm-up / the result
+  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e0, st);
+  for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_prep(P, st);
+  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e1, st);
+  set_prep_variant(0);
+  const int rc = finish(st, e, what);
+  if (elapsed_ms) {
+    *elapsed_ms = 0.f;
+    if (rc == TM_OK && iters > 1) { (void)hipEventElapsedTime(elapsed_ms, e0, e1); *elapsed_ms /= (float)(iters - 1); }
+  }
+  return rc;
+}
 extern "C" int tm_op_prep_h16(const void* const* src_h16, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
                               int p1, int p2, int up2, const void* norm_w_dev, int c_real, int mod, const void* mod_scale,
                               const void* mod_shift, long mod_stride, int per_image, int act, int dtype, int variant,
@@ -604,21 +623,7 @@ extern "C" int tm_op_prep_h16(const void* const* src_h16, const int* src_c, cons
   if (mod == MOD_VOXEL) { P.mod_scale_h = (const uint16_t*)mod_scale; P.mod_shift_h = (const uint16_t*)mod_shift; }
   P.out_h = (uint16_t*)out_h16; P.out_h_nstride = (long)cbe * Z * S * S * 8; P.pad_blocks = cbe - cbtot;
   if (raw_h16) { P.raw_h = (uint16_t*)raw_h16; P.raw_h_nstride = P.out_h_nstride; }
-  DevTmp tmp;
-  hipEvent_t e0 = elapsed_ms ? tmp.event() : nullptr, e1 = elapsed_ms ? tmp.event() : nullptr;
-  if (tmp.err) return tmp.report();
-  set_prep_variant(variant);
-  hipError_t e = launch_prep(P, st);                                   // warm-up / the result
-  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e0, st);
-  for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_prep(P, st);
-  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e1, st);
-  set_prep_variant(0);
-  const int rc = finish(st, e, "prep");
-  if (elapsed_ms) {
-    *elapsed_ms = 0.f;
-    if (rc == TM_OK && iters > 1) { (void)hipEventElapsedTime(elapsed_ms, e0, e1); *elapsed_ms /= (float)(iters - 1); }
-  }
-  return rc;
+  return prep_run(P, variant, iters, elapsed_ms, st, "prep");
 }
 extern "C" int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
                               int p1, int p2, int up2, const void* norm_w_dev, int c_real, int mod, const void* mod_scale,
@@ -654,22 +659,128 @@ extern "C" int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, cons
   if (raw_cb8) { P.raw = (float*)raw_cb8; P.raw_nstride = P.out_nstride; }
   if (variant == 2 && !prep_wide_applies(P))
     return fail(TM_ERR_ARG, "the wide form takes 33..%d channel blocks (this call has %d)", PREP_WIDE_MAX_CB, cbtot);
-  DevTmp tmp;
-  hipEvent_t e0 = elapsed_ms ? tmp.event() : nullptr, e1 = elapsed_ms ? tmp.event() : nullptr;
-  if (tmp.err) return tmp.report();
-  set_prep_variant(variant);
-  hipError_t e = launch_prep(P, st);                                   // warm-up / the result
-  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e0, st);
-  for (int i = 1; i < iters && e == hipSuccess; ++i) e = launch_prep(P, st);
-  if (elapsed_ms && e == hipSuccess) e = hipEventRecord(e1, st);
-  set_prep_variant(0);
-  const int rc = finish(st, e, "prep (fp32)");
-  if (elapsed_ms) {
-    *elapsed_ms = 0.f;
-    if (rc == TM_OK && iters > 1) { (void)hipEventElapsedTime(elapsed_ms, e0, e1); *elapsed_ms /= (float)(iters - 1); }
-  }
-  return rc;
+  return prep_run(P, variant, iters, elapsed_ms, st, "prep (fp32)");
 }
+// One PrepLaunch as the executor fills it, in every combination of types launch_prep takes; the form is launch_prep's choice.
+extern "C" int tm_op_prep_form(const void* const* src, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
+                               int p1, int p2, int resample, int src_dtype, int out_dtype, const void* norm_w_dev, int c_real,
+                               int mod, int mod_dtype, const void* mod_scale, const void* mod_shift, long mod_stride, int mod_half,
+                               int per_image, int act, int variant, int pad_blocks, void* out, void* raw, int raw_dtype,
+                               int iters, float* elapsed_ms, void* stream) {
+  if (!src || !src_c || !collage || !out || nsrc < 1 || nsrc > 3 || iters < 1) return fail(TM_ERR_ARG, "bad argument");
+  if (N < 1 || Z < 1 || S < 1 || c_real < 1) return fail(TM_ERR_ARG, "N, Z, S and c_real must be positive");
+  if (variant < 0 || variant > 3) return fail(TM_ERR_ARG, "variant: 0 automatic, 1 generic kernel, 2 | 3 the 16-bit forms (2: the wide fp32 form)");
+  const bool voxel = mod == MOD_VOXEL;
+  const int types[4] = {src_dtype, out_dtype, voxel ? mod_dtype : TM_DTYPE_F32, raw ? raw_dtype : TM_DTYPE_F32};
+  int h = TM_DTYPE_F32;
+  for (int t : types) {
+    if (t != TM_DTYPE_F32 && !is_h16(t)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_F32, TM_DTYPE_BF16 or TM_DTYPE_F16");
+    if (is_h16(t) && h != TM_DTYPE_F32 && t != h) return fail(TM_ERR_ARG, "bf16 and f16 tensors may not be mixed in one call");
+    if (is_h16(t)) h = t;
+  }
+  if (mod < MOD_NONE || mod > MOD_VOXEL) return fail(TM_ERR_ARG, "mod: 0 none, 1 per image, 2 per voxel");
+  if (mod != MOD_NONE && (!mod_scale || !mod_shift)) return fail(TM_ERR_ARG, "modulation tensors missing");
+  if (mod == MOD_IMAGE && mod_dtype != TM_DTYPE_F32) return fail(TM_ERR_ARG, "per-image modulation rows are fp32");
+  if (mod_half && (!voxel || (S & 1))) return fail(TM_ERR_ARG, "mod_half takes a per-voxel modulation and an even S");
+  if (pad_blocks < 0 || (pad_blocks && !is_h16(out_dtype))) return fail(TM_ERR_ARG, "pad_blocks belong to a 16-bit output");
+  bool any_col = false;
+  for (int i = 0; i < nsrc; ++i) any_col = any_col || collage[i];
+  const int q = any_col ? (p1 - 1) * (p2 - 1) : 1;
+  if (any_col && (p1 < 2 || p2 < 2 || N % q)) return fail(TM_ERR_ARG, "collage needs N = b * (p1-1) * (p2-1)");
+  if (resample < RS_SAME || resample > RS_PICK2) return fail(TM_ERR_ARG, "resample: 0 same, 1 up2, 2 down2, 3 pick2");
+  if (resample == RS_UP2 && (any_col || (S & 1))) return fail(TM_ERR_ARG, "up2 takes plain sources and an even S");
+  if (resample == RS_PICK2 && (S & 1)) return fail(TM_ERR_ARG, "pick2 takes an even S");
+  if (resample == RS_DOWN2 && (any_col || nsrc != 1 || mod != MOD_NONE))
+    return fail(TM_ERR_ARG, "the downsample form takes one plain source, no modulation");
+  const int Ss = resample == RS_UP2 ? S / 2 : (resample == RS_SAME ? S : 2 * S);
+  PrepLaunch P;
+  P.nsrc = nsrc;
+  int cbtot = 0;
+  for (int i = 0; i < nsrc; ++i) {
+    const int cb = (src_c[i] + 7) / 8;
+    if (!src[i] || src_c[i] < 1) return fail(TM_ERR_ARG, "bad source %d", i);
+    P.src[i].p = (const float*)src[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
+    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
+    cbtot += cb;
+  }
+  P.src_h = is_h16(src_dtype) ? 1 : 0; P.h_f16 = h == TM_DTYPE_F16;
+  P.resample = resample; P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
+  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act ? 1 : 0; P.per_image = per_image > 0 ? per_image : 1;
+  P.mod = mod; P.mod_stride = mod_stride; P.mod_half = mod_half ? 1 : 0;
+  if (voxel && is_h16(mod_dtype)) { P.mod_scale_h = (const uint16_t*)mod_scale; P.mod_shift_h = (const uint16_t*)mod_shift; }
+  else if (mod != MOD_NONE) { P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift; }
+  const long plane = (long)Z * S * S * 8;
+  if (is_h16(out_dtype)) { P.out_h = (uint16_t*)out; P.out_h_nstride = (cbtot + pad_blocks) * plane; P.pad_blocks = pad_blocks; }
+  else { P.out = (float*)out; P.out_nstride = cbtot * plane; }
+  if (raw && is_h16(raw_dtype)) { P.raw_h = (uint16_t*)raw; P.raw_h_nstride = (cbtot + pad_blocks) * plane; }
+  else if (raw) { P.raw = (float*)raw; P.raw_nstride = cbtot * plane; }
+  // the forms a forced variant names must be the form launch_prep then takes
+  const bool h16_call = P.src_h && P.out_h && !P.raw && resample != RS_DOWN2 && (!voxel || P.mod_scale_h);
+  if (variant == 3 && !(h16_call && cbtot <= 160)) return fail(TM_ERR_ARG, "variant 3 takes an all-16-bit call of at most 160 blocks");
+  if (variant == 2 && !(h16_call && cbtot <= 32) && !prep_wide_applies(P))
+    return fail(TM_ERR_ARG, "variant 2 takes an all-16-bit call of at most 32 blocks, or the wide form's 33..%d fp32 blocks (this call has %d)",
+                PREP_WIDE_MAX_CB, cbtot);
+  hipStream_t st = (hipStream_t)stream;
+  return prep_run(P, variant, iters, elapsed_ms, st, "prep (form)");
+}
+
+// The stem and the head on their own, weights packed as the model loader packs them (direct_pack_host)
+extern "C" int tm_op_stem(const void* x, const void* w_host, const void* bias_host, void* y, int N, int Cin, int Cout, int Z, int S,
+                          int dtype, void* stream) {
+  if (!x || !w_host || !bias_host || !y) return fail(TM_ERR_ARG, "null pointer");
+  if (N < 1 || Cin < 1 || Cout < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "N, Cin, Cout, Z and S must be positive");
+  if (Cout % 32) return fail(TM_ERR_ARG, "the stem computes 32 couts per thread: Cout = %d is no multiple of 32", Cout);
+  if (dtype != TM_DTYPE_F32 && !is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_F32, TM_DTYPE_BF16 or TM_DTYPE_F16");
+  std::vector<float> wt((size_t)9 * Cin * Cout);
+  direct_pack_host((const float*)w_host, Cout, Cin, 9, wt.data());
+  DevTmp tmp;
+  const float* w = tmp.alloc(wt.size(), wt.data());
+  const float* bias = tmp.alloc((size_t)Cout, (const float*)bias_host);
+  if (tmp.err) return tmp.report();
+  const bool h16 = is_h16(dtype);
+  const TV yv = view_cb8(h16 ? nullptr : y, N, Cout, Z, S, S);
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_stem((const float*)x, yv, w, bias, Cin, st, h16 ? (uint16_t*)y : nullptr, yv.nstride, dtype == TM_DTYPE_F16), "stem");
+}
+extern "C" int tm_op_head(const void* x_cb8, const void* w_host, const void* bias_host, void* y, int N, int C, int Cout, int Z, int S,
+                          int dtype, void* stream) {
+  if (!x_cb8 || !w_host || !bias_host || !y) return fail(TM_ERR_ARG, "null pointer");
+  if (N < 1 || C < 1 || Cout < 1 || Z < 1 || S < 1) return fail(TM_ERR_ARG, "N, C, Cout, Z and S must be positive");
+  if (Cout > 8) return fail(TM_ERR_ARG, "the head computes at most 8 couts: Cout = %d", Cout);
+  if (dtype != TM_DTYPE_F32 && !is_h16(dtype)) return fail(TM_ERR_ARG, "dtype must be TM_DTYPE_F32, TM_DTYPE_BF16 or TM_DTYPE_F16");
+  // the kernel walks whole channel blocks: cin zero padded to ceil(C / 8) * 8 before the loader's transpose
+  const int Cp = (C + 7) / 8 * 8;
+  std::vector<float> wp((size_t)Cout * Cp * 9, 0.f), wt((size_t)9 * Cp * 8);
+  for (int co = 0; co < Cout; ++co)
+    memcpy(wp.data() + (size_t)co * Cp * 9, (const float*)w_host + (size_t)co * C * 9, (size_t)C * 9 * sizeof(float));
+  direct_pack_host(wp.data(), Cout, Cp, 9, wt.data());
+  DevTmp tmp;
+  const float* w = tmp.alloc(wt.size(), wt.data());
+  const float* bias = tmp.alloc((size_t)Cout, (const float*)bias_host);
+  if (tmp.err) return tmp.report();
+  hipStream_t st = (hipStream_t)stream;
+  const TV xv = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
+  return finish(st, launch_head(xv, (float*)y, w, bias, Cout, st, dtype == TM_DTYPE_F32 ? 0 : (dtype == TM_DTYPE_F16 ? 2 : 1)), "head");
+}
+
+// The timestep embedding and the emb_layers matrix on their own; every pointer is a device pointer
+extern "C" int tm_op_time_embed(const void* t_dev, const void* w1, const void* b1, const void* w2, const void* b2, void* te,
+                                void* te_act, int b, int ch, int E, void* stream) {
+  if (!t_dev || !w1 || !b1 || !w2 || !b2 || !te || !te_act) return fail(TM_ERR_ARG, "null pointer");
+  if (b < 1 || ch < 2 || (ch & 1) || E < 1) return fail(TM_ERR_ARG, "b and E must be positive, ch even and at least 2");
+  if ((long)(ch + E) * 4 > 65536) return fail(TM_ERR_ARG, "ch + E = %d floats do not fit 64 KB of LDS", ch + E);
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_time_embed((const int64_t*)t_dev, b, ch, E, (const float*)w1, (const float*)b1, (const float*)w2,
+                                      (const float*)b2, (float*)te, (float*)te_act, st), "time_embed");
+}
+extern "C" int tm_op_emb_all(const void* te_act, const void* wall, const void* ball, void* ss, int b, int E, int tot, void* stream) {
+  if (!te_act || !wall || !ball || !ss) return fail(TM_ERR_ARG, "null pointer");
+  if (b < 1 || tot < 1 || E < 64) return fail(TM_ERR_ARG, "b and tot must be positive, E at least 64");
+  if (E % 64 || E > 1024) return fail(TM_ERR_ARG, "a wave splits a row over 64 lanes, 16 floats each: E = %d must be a multiple of 64, at most 1024", E);
+  hipStream_t st = (hipStream_t)stream;
+  return finish(st, launch_emb_all((const float*)te_act, b, E, (const float*)wall, (const float*)ball, tot, (float*)ss, st), "emb_all");
+}
+
 extern "C" int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const void* v_cb8, const void* qw_dev,
                                  const void* kw_dev, void* out, int N, int C, int Z, int S, int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
@@ -833,11 +944,8 @@ extern "C" int tm_op_conv_direct(const void* x, const void* w_host, const void* 
   const int taps = kz * ky * kx, Cop = (Cout + 7) / 8 * 8;
   const int Zout = Zin + 2 * pz - kz + 1;
   if (Zout < 1 || py != ky / 2 || px != kx / 2) return fail(TM_ERR_ARG, "unsupported geometry");
-  std::vector<float> wt((size_t)taps * Cin * Cop, 0.f);
-  const float* w = (const float*)w_host;
-  for (int co = 0; co < Cout; ++co)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int t = 0; t < taps; ++t) wt[((size_t)t * Cin + ci) * Cop + co] = w[((size_t)co * Cin + ci) * taps + t];
+  std::vector<float> wt((size_t)taps * Cin * Cop);
+  direct_pack_host((const float*)w_host, Cout, Cin, taps, wt.data());
   DevTmp tmp;
   DirectLaunch L;
   std::tie(L.w, L.bias) = upload_conv(tmp, wt, bias_host, Cout);
