@@ -241,6 +241,45 @@ int tm_train_batch_genes(const int32_t* crd, const void* dat, int64_t nnz, const
  * dst == NULL: only *out_bytes (the decoded size) is set.  No GPU involved. */
 int tm_blosc_decompress(const void* src, size_t src_bytes, void* dst, size_t dst_cap, size_t* out_bytes);
 
+/* ---- Blosc-lz4 encoder: the frames tm_blosc_decompress reads, written on the GPU ----------------------------------
+ * What zarr.save_array (test_brn.py:225) gives a state tile by default: Blosc-1, lz4 codec, byte shuffle.
+ *   header   [2][1][flags][typesize][nbytes LE32][blocksize LE32][cbytes LE32]; flags = 0x20 (lz4) | 0x01 (byte shuffle,
+ *            typesize > 1) | 0x10 (blocks not split); never 0x02 (memcpyed) or 0x04 (bit shuffle)
+ *   blocks   of min(blocksize, nbytes) bytes (rounded down to whole elements above one element); bstarts int32 [nblocks]
+ *            after the header; a block of >= 128 elements is split into `typesize` streams, a shorter one and the short last
+ *            block are one stream (whole elements shuffled, the odd bytes after them); a stream is an LE32 length and its bytes
+ *   streams  strict LZ4 blocks (what LZ4_decompress_safe accepts: minimum match 4, the last 5 bytes literals, the last match
+ *            starts >= 12 bytes before the end), always SHORTER than the plain stream: one that would not be is stored, and
+ *            length == plain size is how a decoder tells.  Offsets are <= 65535 because a stream is <= 65536 bytes.
+ * Two calls on the same input give the same bytes: nothing depends on the CU count or on the order waves run in.  Pinned:
+ * the frames decode (tm_blosc_decompress, and a strict decoder in the tests), the header fields equal c-blosc's for the same
+ * arguments, and frames are within 15 % of c-blosc 1.21 (clevel 5) on recorded buffers.  Not pinned: byte equality with c-blosc.
+ * Accepted: nbytes >= 1 (and a bound below 2^31), typesize 1, 2 or 4, blocksize a multiple of 4 in [256, 65536]; anything else
+ * is TM_ERR_ARG with a text, before any device call.
+ *
+ * tm_blosc_bound: the largest frame the arguments can give, 16 + 4 nblocks + 4 (number of streams) + nbytes (every stream
+ *   stored).  0 for arguments that are not accepted (text in tm_last_error()).  Host only. */
+size_t tm_blosc_bound(size_t nbytes, int typesize, int blocksize);
+
+/* tm_blosc_compress: one frame of the `nbytes` contiguous bytes at src (device, no alignment needed) into frame (device,
+ *   frame_cap >= tm_blosc_bound(...) bytes); *out_bytes (int64, device) = the frame's length.  Bytes of `frame` past that
+ *   length are not written.  Asynchronous on `stream`; the stream slots are stream-ordered scratch (nbytes + tables). */
+int tm_blosc_compress(const void* src, size_t nbytes, int typesize, int blocksize, void* frame, size_t frame_cap,
+                      int64_t* out_bytes, void* stream);
+
+/* tm_blosc_compress_tiles: one frame per state tile [C][TH][TW], cut in place out of a resident canvas and written as
+ *   float16 (typesize 2, blocksize 65536: the reference's tile [100][256][256] is 200 whole blocks).
+ *   canvas       device, TM_DTYPE_F16 or TM_DTYPE_F32, `canvas_elems` elements; element (c, y, x) of tile k sits at
+ *                origins[k] + c * chan_stride + y * pitch + x.  float32 is rounded as Tensor.half() rounds: to nearest even,
+ *                overflow to +-inf, subnormals and -0.0 kept, NaN as the hardware conversion gives it
+ *   origins      int64 [ntiles] device, origins_host its host mirror (checked against canvas_elems before any device call)
+ *   packed       uint8 [packed_cap] device, packed_cap >= ntiles * tm_blosc_bound(2 C TH TW, 2, 65536): the frames back to back
+ *   offsets      int64 [ntiles + 1] device: frame k at packed + offsets[k], offsets[ntiles] = their total
+ *   Asynchronous on `stream`; stream-ordered scratch of ntiles x (tile bytes + tables). */
+int tm_blosc_compress_tiles(const void* canvas, int dtype, int64_t canvas_elems, int C, int TH, int TW, int64_t chan_stride,
+                            int64_t pitch, const int64_t* origins, const int64_t* origins_host, int ntiles, void* packed,
+                            int64_t packed_cap, int64_t* offsets, void* stream);
+
 /* ---- slice export: the pyramid levels and JPEG tiles of infer_brn.get_ome --------
  * (infer_brn.py:11-54: `tiffsave(tile=True, compression='jpeg', pyramid=True, bigtiff=True, tile 256 x 256)`), computed
  * from a resident uint8 plane.  The container is written by teramind_amd.ometiff.

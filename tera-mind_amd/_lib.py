@@ -69,6 +69,10 @@ SIGNATURES = {
     "tm_train_batch_genes": (c_int, [c_void_p, c_void_p, C.c_int64, c_void_p, c_void_p] + [c_int] * 4 + [c_void_p, c_void_p] +
                              [c_int] * 5 + [c_void_p, c_void_p]),
     "tm_blosc_decompress": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, C.POINTER(c_size_t)]),
+    "tm_blosc_bound": (c_size_t, [c_size_t, c_int, c_int]),
+    "tm_blosc_compress": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "tm_blosc_compress_tiles": (c_int, [c_void_p, c_int, C.c_int64] + [c_int] * 3 + [C.c_int64] * 2 + [c_void_p, c_void_p, c_int, c_void_p,
+                                        C.c_int64, c_void_p, c_void_p]),
     "tm_u8_shrink2": (c_int, [c_void_p, c_int, c_int, C.c_int64, c_void_p, C.c_int64, c_void_p]),
     "tm_jpeg_encode_tiles": (c_int, [c_void_p, c_int, c_int, C.c_int64] + [c_int] * 3 + [c_void_p, C.c_int64] + [c_void_p] * 4),
     "tm_jpeg_tables": (c_int, [c_int, c_void_p, c_size_t, C.POINTER(c_size_t)]),

@@ -100,6 +100,7 @@ class TileSweep:
         W = wnm * tiles.TILE + 2 * PAD
         self.epoch = 0
         self._pending, self._noise_tiles, self._noise_cap = {}, {}, 18
+        self.snapshot_tiles = 64                         # save_step(compressor="blosc"): tiles per encoder call
         # halo-exchange accounting (bench.py --sweep): seconds (device-synchronised when time_exchange is set), bytes
         # sent + received by this rank, number of exchanges
         self.time_exchange, self.exchange_s, self.exchange_bytes, self.exchanges = False, 0.0, 0, 0
@@ -409,13 +410,21 @@ class TileSweep:
 
     def save_step(self, out_dir, compressor: Optional[str] = None) -> str:
         """Write this rank's tiles as the reference would have after `self.epoch` steps: one zarr-v2 .zip per
-        tile, float16 [(stain z), 256, 256], named '{r0}_{r1}_{c0}_{c1}.zip' (test_brn.py:222-226)."""
+        tile, float16 [(stain z), 256, 256], named '{r0}_{r1}_{c0}_{c1}.zip' (test_brn.py:222-226).
+        compressor: None (raw chunk) or "zlib": the band goes to the host as float16 and is encoded there; "blosc": the chunk
+        encoding zarr.save_array writes by default (Blosc-1, lz4, byte shuffle), the frames of a tile row encoded on the GPU
+        straight from the canvas (tm_blosc_compress_tiles) -- the host copies the packed frames and writes the containers."""
         import os
         from . import formats
+        if compressor not in (None, "zlib", "blosc"):
+            raise ValueError(f"compressor must be None, 'zlib' or 'blosc', got {compressor!r}")
         if self.epoch == 0:
             raise ValueError("step 0 is noise regenerated from the tile seeds; the reference stores no '_0' directory")
         d = self.step_dir(out_dir)
         os.makedirs(d, exist_ok=True)
+        if compressor == "blosc":
+            self._save_step_blosc(d)
+            return d
         for lr in range(self.nrows):
             band = self.cur[:, PAD + lr * tiles.TILE:PAD + (lr + 1) * tiles.TILE, PAD:-PAD].half().cpu().numpy()
             for c in range(self.wnm):
@@ -423,6 +432,41 @@ class TileSweep:
                 formats.write_state_tile(os.path.join(d, name + ".zip"), band[:, :, c * tiles.TILE:(c + 1) * tiles.TILE],
                                          compressor)
         return d
+
+    def _save_step_blosc(self, d):
+        """save_step(compressor="blosc"): per tile row one encoder call over the row's tiles in the canvas (either layout: the
+        float32 canvas is rounded to float16 as `.half()` does), one copy of the frames to the host, one container per tile.
+        A row wider than `snapshot_tiles` takes several calls, so that a whole-brain row (414 tiles) needs 1.7 GB beside the
+        canvas instead of 11."""
+        import os
+        from . import _lib, formats
+        if not self.cur.is_cuda:
+            raise RuntimeError("save_step(compressor='blosc') encodes on the GPU: the sweep's canvas is not on one")
+        L = _lib.lib()
+        cur, T_ = self.cur, tiles.TILE
+        assert cur.is_contiguous()
+        dtype = {torch.float32: 0, torch.float16: 2}[cur.dtype]                       # TM_DTYPE_F32 / TM_DTYPE_F16
+        bound = L.tm_blosc_bound(self.chn * T_ * T_ * 2, 2, 65536)
+        if not bound:
+            _lib.check(-1, "tm_blosc_bound")
+        per = min(self.wnm, self.snapshot_tiles)                     # tiles per call: scratch + frames are 2 x 13.1 MB a tile
+        with torch.cuda.device(self.dev):
+            packed = torch.empty(per * bound, dtype=torch.uint8, device=self.dev)
+            offsets = torch.empty(per + 1, dtype=torch.int64, device=self.dev)
+            for lr in range(self.nrows):
+                for c0 in range(0, self.wnm, per):
+                    n = min(per, self.wnm - c0)
+                    orig = torch.tensor([(PAD + lr * T_) * cur.stride(1) + PAD + (c0 + k) * T_ for k in range(n)], dtype=torch.int64)
+                    orig_dev = orig.to(self.dev)
+                    _lib.check(L.tm_blosc_compress_tiles(_lib.ptr(cur), dtype, cur.numel(), self.chn, T_, T_, cur.stride(0),
+                                                         cur.stride(1), _lib.ptr(orig_dev), _lib.ptr(orig), n, _lib.ptr(packed),
+                                                         packed.numel(), _lib.ptr(offsets), _lib.current_stream_ptr()),
+                               "tm_blosc_compress_tiles")
+                    off = offsets[:n + 1].cpu().tolist()
+                    frames = packed[:off[-1]].cpu().numpy()
+                    for k in range(n):
+                        name = tiles.state_tile_name(self.row0 + self.r0 + lr, self.col0 + c0 + k)
+                        formats.write_zarr_zip_blosc(os.path.join(d, name + ".zip"), (self.chn, T_, T_), "<f2", frames[off[k]:off[k + 1]])
 
     def load_step(self, out_dir, epoch: int):
         """Resume from a reference-format step directory (`--cur_epoch`, test_brn.py:290-292): read this rank's

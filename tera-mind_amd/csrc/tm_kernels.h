@@ -372,6 +372,29 @@ hipError_t launch_jpeg_tiles(const uint8_t* plane, int H, int W, long pitch, int
                              uint8_t* slots, long slot_bytes, int32_t* need, uint8_t* packed, int64_t* offsets, hipStream_t s);
 int jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
 
+// ---- Blosc-lz4 frames (tm_blosc.hip) --------------------------------------------------------
+constexpr int BLOSC_ENC_MIN_BLOCK = 256, BLOSC_ENC_MAX_BLOCK = 65536;
+struct BloscGeo {                              // the layout of one frame; every frame of a call has the same
+  int nbytes, typesize, bs;                    // bs: effective block size = min(blocksize, nbytes), a multiple of the typesize above it
+  int nblocks, nfull, leftover;                // nfull blocks of bs bytes, then one of `leftover` bytes if that is not 0
+  int split, nsplits, nstreams;                // bs / typesize >= 128: full blocks are split, into nsplits = typesize streams (else 1); streams per frame
+  size_t bound;                                // 16 + 4 nblocks + 4 nstreams + nbytes: every stream stored
+};
+enum { BLOSC_SRC_BYTES = 0, BLOSC_SRC_F16 = 1, BLOSC_SRC_F32 = 2 };
+struct BloscSrc {                              // where the frames' bytes come from
+  const uint8_t* base;                         // BYTES: the buffer of the one frame; F16 / F32: the canvas the tiles are cut from
+  int mode, TH, TW;                            // tiles [C][TH][TW], written as IEEE half (F32: rounded to nearest even)
+  long cstride, pitch;                         // channel stride and row pitch of the canvas in elements
+  const int64_t* origins;                      // device, per frame: element offset of the tile's first element
+};
+// false: nbytes < 1, typesize not 1 / 2 / 4, blocksize no multiple of 4 in [256, 65536], or a frame that could pass 2^31 - 1 bytes
+bool blosc_geometry(size_t nbytes, int typesize, int blocksize, BloscGeo* g);
+size_t blosc_scratch_bytes(const BloscGeo& g, int nframes);
+// nframes <= 65535 frames back to back into `packed` (nframes * g.bound bytes always suffice); offsets [nframes + 1] and
+// *total (device) are optional; scratch: blosc_scratch_bytes(g, nframes) bytes, 4-byte aligned
+hipError_t launch_blosc_frames(const BloscSrc& src, const BloscGeo& g, int nframes, void* scratch, uint8_t* packed, int64_t* offsets,
+                               int64_t* total, hipStream_t s);
+
 // ---- ROI evaluation (tm_metrics.hip) -----------------------------------------------------
 // SSIM statistics of P plane pairs: the valid output is cut into SSIM_TW x SSIM_TH tiles, one workgroup each
 constexpr int SSIM_TW = 64, SSIM_TH = 32, SSIM_MAX_TAPS = 33, SSIM_TAP_PAD = 7;

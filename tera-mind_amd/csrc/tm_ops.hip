@@ -1350,6 +1350,68 @@ extern "C" int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pit
   return TM_OK;
 }
 
+// Blosc-lz4 frames (tm_blosc.hip); enqueue only, the stream slots and length tables are stream-ordered scratch
+static int blosc_args(const char* fn, size_t nbytes, int typesize, int blocksize, BloscGeo* g) {
+  if (nbytes < 1) return fail(TM_ERR_ARG, "%s: nothing to compress (nbytes = 0)", fn);
+  if (typesize != 1 && typesize != 2 && typesize != 4) return fail(TM_ERR_ARG, "%s: typesize %d is not 1, 2 or 4", fn, typesize);
+  if (blocksize < BLOSC_ENC_MIN_BLOCK || blocksize > BLOSC_ENC_MAX_BLOCK || (blocksize & 3))
+    return fail(TM_ERR_ARG, "%s: blocksize %d is not a multiple of 4 in [%d, %d]", fn, blocksize, BLOSC_ENC_MIN_BLOCK, BLOSC_ENC_MAX_BLOCK);
+  if (!blosc_geometry(nbytes, typesize, blocksize, g))
+    return fail(TM_ERR_ARG, "%s: %zu bytes do not fit a Blosc-1 frame (2^31 - 1 bytes with its tables)", fn, nbytes);
+  return TM_OK;
+}
+extern "C" size_t tm_blosc_bound(size_t nbytes, int typesize, int blocksize) {
+  BloscGeo g;
+  return blosc_args("tm_blosc_bound", nbytes, typesize, blocksize, &g) ? 0 : g.bound;
+}
+static int blosc_run(const BloscSrc& src, const BloscGeo& g, int nframes, void* packed, int64_t* offsets, int64_t* total, hipStream_t st) {
+  DevTmp tmp(st);
+  void* scratch = tmp.ordered_floats((blosc_scratch_bytes(g, nframes) + 3) / 4, false);
+  if (tmp.err) return tmp.report();
+  HIP_TRY(launch_blosc_frames(src, g, nframes, scratch, (uint8_t*)packed, offsets, total, st));
+  return TM_OK;
+}
+extern "C" int tm_blosc_compress(const void* src, size_t nbytes, int typesize, int blocksize, void* frame, size_t frame_cap,
+                                 int64_t* out_bytes, void* stream) {
+  const char* fn = "tm_blosc_compress";
+  if (!src || !frame || !out_bytes) return fail(TM_ERR_ARG, "%s: null source / frame / out_bytes pointer", fn);
+  BloscGeo g;
+  if (int rc = blosc_args(fn, nbytes, typesize, blocksize, &g)) return rc;
+  if (frame_cap < g.bound) return fail(TM_ERR_ARG, "%s: frame buffer of %zu bytes below the bound %zu (tm_blosc_bound)", fn, frame_cap, g.bound);
+  BloscSrc s = {};
+  s.base = (const uint8_t*)src; s.mode = BLOSC_SRC_BYTES;
+  return blosc_run(s, g, 1, frame, nullptr, out_bytes, (hipStream_t)stream);
+}
+extern "C" int tm_blosc_compress_tiles(const void* canvas, int dtype, int64_t canvas_elems, int C, int TH, int TW, int64_t chan_stride,
+                                       int64_t pitch, const int64_t* origins, const int64_t* origins_host, int ntiles, void* packed,
+                                       int64_t packed_cap, int64_t* offsets, void* stream) {
+  const char* fn = "tm_blosc_compress_tiles";
+  if (!canvas || !origins || !origins_host || !packed || !offsets)
+    return fail(TM_ERR_ARG, "%s: null canvas / origins (device array and its host mirror) / packed / offsets pointer", fn);
+  if (dtype != TM_DTYPE_F32 && dtype != TM_DTYPE_F16) return fail(TM_ERR_ARG, "%s: dtype %d is neither TM_DTYPE_F32 nor TM_DTYPE_F16", fn, dtype);
+  if ((uintptr_t)canvas & (dtype == TM_DTYPE_F32 ? 3 : 1)) return fail(TM_ERR_ARG, "%s: canvas pointer is not aligned to its element", fn);
+  if (C < 1 || TH < 1 || TW < 1) return fail(TM_ERR_ARG, "%s: C, TH and TW must be positive, got %d x %d x %d", fn, C, TH, TW);
+  if (ntiles < 1 || ntiles > 65535) return fail(TM_ERR_ARG, "%s: ntiles = %d outside 1 .. 65535", fn, ntiles);
+  const int64_t elems = (int64_t)C * TH * TW;
+  if (elems > (int64_t)1 << 29) return fail(TM_ERR_ARG, "%s: a tile of %lld elements is larger than 2^29", fn, (long long)elems);
+  if (pitch < TW) return fail(TM_ERR_ARG, "%s: row pitch %lld below TW %d", fn, (long long)pitch, TW);
+  const int64_t plane = (int64_t)(TH - 1) * pitch + TW;                 // elements from a channel's first to past its last
+  if (chan_stride < plane) return fail(TM_ERR_ARG, "%s: channel stride %lld below the %lld elements a channel spans", fn, (long long)chan_stride, (long long)plane);
+  const int64_t span = (int64_t)(C - 1) * chan_stride + plane;
+  for (int k = 0; k < ntiles; ++k)
+    if (origins_host[k] < 0 || origins_host[k] > canvas_elems - span)
+      return fail(TM_ERR_ARG, "%s: tile %d at element %lld (+ %lld) leaves the canvas of %lld elements", fn, k, (long long)origins_host[k],
+                  (long long)span, (long long)canvas_elems);
+  BloscGeo g;
+  if (int rc = blosc_args(fn, (size_t)elems * 2, 2, BLOSC_ENC_MAX_BLOCK, &g)) return rc;
+  if (packed_cap < 0 || (size_t)packed_cap < (size_t)ntiles * g.bound)
+    return fail(TM_ERR_ARG, "%s: packed buffer of %lld bytes below ntiles x bound = %d x %zu", fn, (long long)packed_cap, ntiles, g.bound);
+  BloscSrc s = {};
+  s.base = (const uint8_t*)canvas; s.mode = dtype == TM_DTYPE_F32 ? BLOSC_SRC_F32 : BLOSC_SRC_F16;
+  s.TH = TH; s.TW = TW; s.cstride = (long)chan_stride; s.pitch = (long)pitch; s.origins = origins;
+  return blosc_run(s, g, ntiles, packed, offsets, nullptr, (hipStream_t)stream);
+}
+
 // SSIM / PSNR sums of plane pairs (tm_metrics.hip); enqueues only, the per-tile partials are stream-ordered scratch
 static int pix_geometry(const char* fn, const char* what, const void* p, int dtype, int W, int64_t pitch, int64_t plane) {
   const int64_t esz = dtype == TM_PIX_F32 ? 4 : 1;

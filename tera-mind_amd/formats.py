@@ -15,7 +15,8 @@ their published layouts (zarr storage spec v2; pydata/sparse 0.15.5 `save_npz`; 
   * readers accept what zarr 2.14.1 writes by default (Blosc lz4 + byte shuffle, decoded by
     `tm_blosc_decompress` in the C-ABI library), zlib, or no compressor;
   * writers emit spec-conformant archives that `zarr.load` / `sparse.load_npz` open
-    (state tiles: one uncompressed or zlib chunk).
+    (state tiles: one chunk, uncompressed or zlib from the host, or a Blosc lz4 frame encoded on the GPU by
+    `tm_blosc_compress_tiles` and wrapped by `write_zarr_zip_blosc`: the encoding zarr itself writes).
 Only safe loaders are used (`numpy.load(allow_pickle=False)`, `zipfile`, `json`).
 """
 import ctypes as C
@@ -131,7 +132,8 @@ def read_zarr_zip(path) -> np.ndarray:
 
 def write_zarr_zip(path, arr: np.ndarray, compressor: Optional[str] = None, level: int = 1, date_time=None):
     """A single-chunk zarr-v2 array in a ZIP_STORED ZipStore (the layout zarr.save_array produces, with the
-    chunk either raw or zlib-compressed so that no Blosc encoder is needed).  date_time: a fixed
+    chunk either raw or zlib-compressed: this writer runs on the host alone; frames of the GPU Blosc encoder go through
+    write_zarr_zip_blosc).  date_time: a fixed
     (y, m, d, H, M, S) for the members instead of the clock, for files that must be reproducible byte for byte."""
     arr = np.ascontiguousarray(arr)
     if compressor not in (None, "zlib"):
@@ -153,6 +155,34 @@ def write_zarr_zip(path, arr: np.ndarray, compressor: Optional[str] = None, leve
     with zipfile.ZipFile(tmp, "w", compression=zipfile.ZIP_STORED, allowZip64=True) as z:
         z.writestr(member(".zarray"), json.dumps(meta, indent=4, sort_keys=True))
         z.writestr(member(".".join("0" for _ in arr.shape) if arr.ndim else "0"), payload)
+    os.replace(tmp, path)                                  # a reader never sees a half-written tile
+
+
+BLOSC_COMPRESSOR = {"blocksize": 0, "clevel": 5, "cname": "lz4", "id": "blosc", "shuffle": 1}     # numcodecs.Blosc(): zarr's default
+
+
+def write_zarr_zip_blosc(path, shape: Sequence[int], dtype: str, frame, date_time=None):
+    """A single-chunk zarr-v2 array in a ZIP_STORED ZipStore whose chunk is `frame`: one Blosc-1 lz4 frame of the array's
+    C-order bytes, already encoded (tm_blosc_compress / tm_blosc_compress_tiles).  The metadata is what zarr.save_array
+    writes; members and date_time as in write_zarr_zip."""
+    shape, dt = [int(s) for s in shape], np.dtype(dtype)
+    frame = bytes(frame)
+    nbytes = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+    if len(frame) < 16 or int.from_bytes(frame[4:8], "little") != nbytes or int.from_bytes(frame[12:16], "little") != len(frame):
+        raise ValueError(f"{path}: not a Blosc frame of the {nbytes} bytes of a {dt.str} array of shape {tuple(shape)}")
+    meta = {"chunks": shape, "compressor": dict(BLOSC_COMPRESSOR), "dtype": dt.str, "fill_value": 0.0 if dt.kind == "f" else 0,
+            "filters": None, "order": "C", "shape": shape, "zarr_format": 2}
+    tmp = str(path) + ".tmp"
+    def member(name):
+        if date_time is None:
+            return name
+        zi = zipfile.ZipInfo(name, date_time=tuple(date_time))
+        zi.compress_type, zi.external_attr = zipfile.ZIP_STORED, 0o600 << 16
+        return zi
+
+    with zipfile.ZipFile(tmp, "w", compression=zipfile.ZIP_STORED, allowZip64=True) as z:
+        z.writestr(member(".zarray"), json.dumps(meta, indent=4, sort_keys=True))
+        z.writestr(member(".".join("0" for _ in shape) if shape else "0"), frame)
     os.replace(tmp, path)                                  # a reader never sees a half-written tile
 
 

@@ -23,7 +23,7 @@ FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-ffp-contract=fast", "--
 def main():
     show_all = "--all" in sys.argv
     srcs = [("tm_kernels.hip", []), ("tm_conv_bf16.hip", []), ("tm_conv_bf16.hip", ["-DTM_H16_F16"]), ("tm_attn.hip", []),
-            ("tm_sampler.hip", ["-ffp-contract=off"]), ("tm_io.hip", []), ("tm_train.hip", [])]
+            ("tm_sampler.hip", ["-ffp-contract=off"]), ("tm_io.hip", []), ("tm_blosc.hip", []), ("tm_train.hip", [])]
     print(f"{'source':22s} {'kernel':84s} {'instr':>6s} {'VGPR':>5s} {'div':>4s} {'lane':>5s} {'scr':>4s} {'v_mov':>6s}")
     with tempfile.TemporaryDirectory() as tmp:
         for src, extra in srcs:

@@ -84,7 +84,7 @@ def worker(args):
     t2 = time.perf_counter()
     io_save, d = 0.0, None
     if not args.no_tile_files:
-        d = sw.save_step(os.path.join(out_dir, "timestep"))
+        d = sw.save_step(os.path.join(out_dir, "timestep"), compressor=None if args.tile_compressor == "none" else args.tile_compressor)
         if world > 1:
             import torch.distributed as dist
             dist.barrier()
@@ -115,7 +115,7 @@ def worker(args):
         T = steps_done
         print(json.dumps({"what": "full ROI sweep, measured", "steps_requested": args.tot_epoch, "steps_measured": steps_done,
                           "step_s": [round(v, 2) for v in per_step], "process_age_s": round(time.monotonic() - _T_START, 1),
-                          "tile_files_written": d is not None, "dtype": args.dtype, "state": args.state, "tiles": tiles, "T": T,
+                          "tile_files_written": d is not None, "tile_compressor": args.tile_compressor, "dtype": args.dtype, "state": args.state, "tiles": tiles, "T": T,
                           "n_gpus": world, "genes": "on-disk COO .npz via GeneTileDir + tm_gene_tile_dense" if args.gene_dir else "synthetic, device resident",
                           "init": args.init, "batch_tiles": args.batch_tiles, "share_halo": bool(args.share_halo), "batch_rows": args.batch_rows, "cache_level0": bool(args.cache_level0), "overlap_streams": args.overlap_streams,
                           "sweep_s": round(sweep_s, 2), "sweep_min": round(sweep_s / 60, 2), "s_per_tile_step": round(sweep_s * world / (tiles * T), 4),
@@ -155,6 +155,9 @@ def main():
     ap.add_argument("--deadline_s", type=float, default=0.0,
                     help="single GPU: do not start a diffusion step that would end later than this many seconds after process start")
     ap.add_argument("--no_tile_files", action="store_true", help="skip save_step / stitch_dir; stitch slice images from the resident canvas")
+    ap.add_argument("--tile_compressor", choices=["none", "zlib", "blosc"], default="none",
+                    help="chunk encoding of the state tile files: raw, zlib on the host, or Blosc-lz4 frames encoded on the GPU "
+                         "(what zarr.save_array writes by default)")
     ap.add_argument("--pyramid", action="store_true",
                     help="also export every plane as '<out_dir>/gen_pyramid/all_{sl}.tif': tiled pyramidal OME-TIFF with JPEG tiles")
     ap.add_argument("--page", type=int, default=None, help="with --pyramid: also write that pyramid level as all_{sl}.jpg")
