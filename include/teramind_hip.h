@@ -444,6 +444,15 @@ int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void* bias_host
  * x 64 couts per workgroup, 2 = 256 x 64, 3 = 256 x 128; 0 = refused (tile_variant 3 with an odd ntile).  Host only. */
 int tm_conv1_form(long vox, int ntile, int tile_variant);
 
+/* Where the lanes of the fp32 LDS-DMA conv kernels address LDS (no device call; for bank-conflict models of the operand images).
+ * kernel 0 = conv3d_zpair, 1 = conv3d_zpair_ups, 2 = conv3d_xpair; half 0 | 1 = the large | small tile; tw = tile width (4 | 8 |
+ * 16 | 32; x-pair 8 | 16); wave 0..3.  what 0: the weight fragment (ds_read_b128) of product p (0..2), window row ky, column kx
+ * (x-pair: the wave's q-th transform position) and 32-cout sub-tile sub; what 1: the activation fragment of (p, ky, kx), sub =
+ * the output phase 2 py + px of kernel 1 (else 0); what 2: the staging store (ds_write_b128) into plane p of the thread's ky-th
+ * item (x-pair: ky 0, kx = the q-plane).  out64[lane] = byte address in the workgroup's dynamic LDS, -1 for a lane that stores
+ * nothing.  Returns 0, or -1 if there is no such instantiation, fragment or item. */
+int tm_conv_frag_addrs(int kernel, int half, int tw, int what, int wave, int p, int ky, int kx, int sub, int* out64);
+
 /* 16-bit variant of the 3x3x3 pad-1 conv (Z == 2): x fp32 CB8 is rounded to `dtype` (TM_DTYPE_BF16 | TM_DTYPE_F16, RNE) on
  * the device, w rounded on the host; fp32 accumulate, fp32 CB8 output.  waves: 0 = the launcher's choice, 4 | 8 = force
  * the 4-wave (128 x 256 / 64 x 512 tile) or 8-wave (128 x 512 / 64 x 1024) workgroup form.

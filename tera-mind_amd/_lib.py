@@ -86,6 +86,7 @@ SIGNATURES = {
     "tm_op_conv_mfma_res": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 10 + [c_void_p]),
     "tm_op_conv1_f32": (c_int, [c_void_p] * 6 + [c_int] * 12 + [C.POINTER(c_int), c_void_p]),
     "tm_conv1_form": (c_int, [C.c_long, c_int, c_int]),
+    "tm_conv_frag_addrs": (c_int, [c_int] * 9 + [c_void_p]),
     "tm_op_conv27_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 2 + [c_int] * 2 + [c_void_p]),
     "tm_op_conv27_fused": (c_int, [c_void_p] * 7 + [c_int] * 7 + [c_void_p]),
     "tm_op_conv27_h16_z": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 6 + [c_void_p] * 2 + [c_int] * 3 + [c_void_p]),

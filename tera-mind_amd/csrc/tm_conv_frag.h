@@ -1,0 +1,55 @@
+// The LDS operand images of the fp32 LDS-DMA conv kernels (conv3d_zpair, conv3d_zpair_ups, conv3d_xpair) as plain functions:
+// where a lane reads its MFMA fragments and where a staging thread stores.  Shared by the kernels, the weight packers (the
+// pack IS the LDS image: LDS-DMA copies it linearly) and the host entry point tm_conv_frag_addrs, which hands the addresses
+// to the bank model of tests/test_conv_frag_banks.py.  No device builtins in here.
+//
+// An operand fragment is the 16 bytes (4 of the 8 channels of a block: k-half h = lane >> 5) of one row (a cout, a voxel or an
+// x-pair position).  `ds_read_b128` is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
+// same of lanes 32-63 -- and a group takes one LDS cycle only if its sixteen 16-byte slots differ mod 16 (256 bytes = all 64
+// banks).  All lanes of a group share h.  An image of [row][8 floats] puts row r, half h at slot 2 r + h: a group lands on eight
+// slots, each of them twice.  The images below keep the two k-halves as two arrays of 16-byte slots, [2 halves][rows][4 floats]:
+// a group whose rows differ mod 16 is conflict-free, whatever the constant (tap, plane, window) offset.
+//   weights  the 64 couts of a tap: a group's lanes are rows i32 (mod 32) themselves, {0-3, 12-15, 20-27} = all residues.
+//   x-pair   the q-planes have no x halo: a wave's 32 pair positions are consecutive rows.
+//   z-pair   rows are halo positions (tile row * pitch + column), so the rows of a group depend on the tile width:
+//            TW = 32  a wave is one tile row: consecutive.
+//            TW = 16  two rows of 16 at pitch 18: a row is conflict-free in itself, so lanes are mapped group -> row.
+//            TW = 8   four rows of 8; at pitch 10 residue 0 occurs three times among the 32 rows (no map can help), at pitch
+//                     12 rows {0, 2} and {1, 3} each cover every residue once: lanes are mapped group -> row pair.
+//            TW = 4   (4 x 4 planes) two patches of four rows of 4 at pitch 6; with the patches 40 rows apart (36 + 4 unused)
+//                     the rows {0, 2} of both patches cover every residue once, and so do the rows {1, 3}.
+// Staging stores (`ds_write_b128`, eight groups of 8 consecutive lanes, 32 banks): item i of a plane is (half (i >> 3) & 1,
+// row 8 (i >> 4) + (i & 7)), so that a group writes eight consecutive slots of ONE half (conflict-free as the interleaved
+// [row][8] image was), while 16 consecutive lanes still load the same 256 contiguous bytes of eight voxels from global memory.
+#pragma once
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define TM_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define TM_HD inline
+#endif
+
+namespace tmk {
+
+// float offset of (row, k-half h) in an image of `rows` rows per half
+TM_HD constexpr int conv_frag_off(int row, int h, int rows) { return (h * rows + row) * 4; }
+// weights: float offset inside a tap's 512 floats of cin c8 (0..7) of cout col (0..63); the lane's fragment is c8 = 4 h
+TM_HD constexpr int conv_w_off(int col, int c8) { return conv_frag_off(col, c8 >> 2, 64) + (c8 & 3); }
+
+// staging item i of a plane -> k-half and row (see above); rows past the image (a partial last group of eight) store nothing
+TM_HD constexpr int conv_stage_half(int i) { return (i >> 3) & 1; }
+TM_HD constexpr int conv_stage_row(int i) { return (i >> 4) * 8 + (i & 7); }
+TM_HD constexpr int conv_stage_items(int rows) { return (rows + 7) / 8 * 16; }
+
+// z-pair kernels: the row pitch of the halo image, the rows from one patch of hr halo rows to the next, and voxel (0..31,
+// row-major in the wave's part of the tile) of lane i32.  The 4-lane blocks b = i32 >> 2 of the first read group are {0, 3, 5, 6};
+// they take voxel blocks 0..3 (TW 16: tile row 0), 0, 1, 4, 5 (TW 8: tile rows 0 and 2) or 0, 2, 4, 6 (TW 4: rows 0 and 2 of
+// both patches), the second group's the rest.  A table of eight nibbles.
+TM_HD constexpr int conv_halo_pitch(int tw) { return tw == 8 ? 12 : tw + 2; }
+TM_HD constexpr int conv_halo_patch(int tw, int hr) { return tw == 4 ? 40 : hr * conv_halo_pitch(tw); }
+TM_HD constexpr int conv_lane_voxel(int tw, int i32) {
+  const unsigned tbl = tw == 16 ? 0x73261540u : tw == 8 ? 0x75461320u : tw == 4 ? 0x76452310u : 0x76543210u;
+  return (int)((tbl >> (4 * (i32 >> 2))) & 7u) * 4 + (i32 & 3);
+}
+
+}  // namespace tmk

@@ -1,4 +1,5 @@
 // The forms of the fp32 MFMA conv (ConvForm, tm_kernels.h): which form a layer runs in, and the host packers of each.  Host only.
+#include "tm_conv_frag.h"
 #include "tm_kernels.h"
 
 #include <stdlib.h>
@@ -57,8 +58,9 @@ static void seg_counts(const int* seg_c, int nseg, int& Cin, int& Cbi) {
   Cin = Cbi = 0;
   for (int s = 0; s < nseg; ++s) { Cin += seg_c[s]; Cbi += (seg_c[s] + 7) / 8; }
 }
-// w [Cout][Cin][taps] -> [n_tile][cblk][tap][64 cout][8 cin], pad slots zero
-static void pack_taps(const float* w, int Cout, const int* seg_c, int nseg, int taps, float* out) {
+// w [Cout][Cin][taps] -> [n_tile][cblk][tap][64 cout][8 cin], pad slots zero.  HALVES (the forms that reach LDS by LDS-DMA: the
+// pack is the LDS image): a tap is [2 k-halves][64 cout][4 cin] instead (conv_w_off, tm_conv_frag.h): the same floats permuted
+static void pack_taps(const float* w, int Cout, const int* seg_c, int nseg, int taps, float* out, bool halves = false) {
   int Cin, Cbi;
   seg_counts(seg_c, nseg, Cin, Cbi);
   memset(out, 0, (size_t)((Cout + 63) / 64) * Cbi * taps * 512 * sizeof(float));
@@ -70,7 +72,7 @@ static void pack_taps(const float* w, int Cout, const int* seg_c, int nseg, int 
       for (int co = 0; co < Cout; ++co) {
         const int nt = co / 64, col = co % 64;
         const float* src = w + ((size_t)co * Cin + ci) * taps;
-        float* dst = out + (((size_t)nt * Cbi + cb) * taps) * 512 + (size_t)col * 8 + c8;
+        float* dst = out + (((size_t)nt * Cbi + cb) * taps) * 512 + (halves ? conv_w_off(col, c8) : col * 8 + c8);
         for (int t = 0; t < taps; ++t) dst[(size_t)t * 512] = src[t];
       }
     }
@@ -129,15 +131,15 @@ void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int ns
   seg_counts(seg_c, nseg, Cin, Cbi);
   const size_t n = (size_t)Cout * Cin;
   if (form == CF_PAIR) {
-    pack_taps(z_diff(w, n, 9).data(), Cout, seg_c, nseg, 27, out);
+    pack_taps(z_diff(w, n, 9).data(), Cout, seg_c, nseg, 27, out, true);
   } else if (form == CF_XPAIR) {
-    pack_taps(f23_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, 36, out);
+    pack_taps(f23_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, 36, out, true);
   } else if (form_ups(form)) {               // [phase = 2 py + px][the 12-tap pack of that phase's weights]
     const size_t per = conv_pack_floats(form, Cout, Cbi) / 4;
     for (int ph = 0; ph < 4; ++ph) {
       std::vector<float> v = phase_sums(w, n, ph >> 1, ph & 1);
       if (form == CF_PAIR_UPS) v = z_diff(v.data(), n, 4);
-      pack_taps(v.data(), Cout, seg_c, nseg, 12, out + ph * per);
+      pack_taps(v.data(), Cout, seg_c, nseg, 12, out + ph * per, form == CF_PAIR_UPS);
     }
   } else {
     pack_taps(w, Cout, seg_c, nseg, conv_form_taps(form), out);

@@ -4,6 +4,7 @@
 // kernels: moved into functions here they changed the compiler's wait counts and the instruction order of the K loop
 // (profiles/conv_family_refactor.txt).
 #pragma once
+#include "tm_conv_frag.h"
 #include "tm_device.h"
 
 namespace tmk {
@@ -38,17 +39,18 @@ __device__ __forceinline__ ConvTile conv_tile_of(const ConvArgs& a) {
   return t;
 }
 
-// The lane's fragment: voxel v of the workgroup's tile (rows of TWV voxels; LDS rows of ROWW voxels, HR per patch) -> patch ps of
-// the workgroup, tile row r and column c, and the LDS float offset xb of its window (starting (dy, dx) further)
+// The lane's fragment: voxel v of the workgroup's tile (rows of TWV voxels; LDS rows of ROWW positions, PS positions per patch, ROWS
+// in the image) -> patch ps of the workgroup, tile row r and column c, and the LDS float offset xb of its window (starting (dy, dx)
+// further) in an image of two k-half arrays (tm_conv_frag.h)
 struct ConvLane { int xb, ps, r, c; };
-template <int TR, int TWV, int HR, int ROWW>
-__device__ __forceinline__ ConvLane conv_lane_of(int v, int h, int dy, int dx) {
+template <int TR, int TWV, int PS, int ROWW, int ROWS>
+__host__ __device__ __forceinline__ ConvLane conv_lane_of(int v, int h, int dy, int dx) {
   ConvLane l;
   l.ps = v / (TR * TWV);
   const int rem = v - l.ps * (TR * TWV);
   l.r = rem / TWV;
   l.c = rem - l.r * TWV;
-  l.xb = ((l.ps * HR + l.r + dy) * ROWW + l.c + dx) * 8 + 4 * h;
+  l.xb = conv_frag_off(l.ps * PS + (l.r + dy) * ROWW + l.c + dx, h, ROWS);
   return l;
 }
 

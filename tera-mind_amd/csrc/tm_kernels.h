@@ -98,6 +98,9 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
 // plane has the small tile only.  The one statement of the rule, for the launcher and for whoever must know the tile beforehand
 // (the fused mid-section exists in the large tile only).  No device call.
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant);
+// byte addresses in LDS of the 64 lanes of wave wv for one fragment read or staging store of conv3d_zpair (kernel 0),
+// conv3d_zpair_ups (1), conv3d_xpair (2), instantiation <half, tw> (tm_kernels.hip); -1: no such thing; no device call
+int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out);
 // which conv1_mfma instantiation a CF_1X1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
 int conv1_form(long vox, int ntile, int tile_variant);
 

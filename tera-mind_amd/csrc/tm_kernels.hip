@@ -198,6 +198,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_mfma(ConvArgs a) {
 // One workgroup owns an in-plane tile of MV voxels, BOTH output planes and 64 couts.  HALF = 0: 128 voxels, wave = 32 voxels x
 // 64 couts (3 x 2 accumulators); HALF = 1: 64 voxels, wave = 32 voxels x 32 couts (small launches).  Every output element
 // sees the same order in both -- cin block outer, then product, tap, k -- so the two tiles give identical bits.
+// LDS images (tm_conv_frag.h): the weights of a tap and every staged X plane are two k-half arrays of 16-byte slots,
+// [2][64 couts][4] and [2][XV halo positions][4], and the lane -> voxel map follows the tile width (conv_lane_voxel), so that
+// each 16-lane group of a ds_read_b128 fragment read meets sixteen different slots: 4 LDS cycles per read, not 8.
 // FUSE (HALF = 0, 64 couts, one cout tile): the wave holds every channel of its 32 voxels, so the ResBlock mid-section (RMSNorm
 // over channels -> modulate -> SiLU, zpair_norm_epilogue) runs on each output plane in place of the plain epilogue and the
 // second conv's input is written instead of the conv output.  The K loop is the same code; layers that do not fuse run <.., false>.
@@ -207,13 +210,20 @@ struct ZPGeo {
   static constexpr int MV = HALF ? 64 : 128;                     // in-plane voxels per workgroup (2 MV outputs)
   static constexpr int TR = (MV / TW < TW) ? (MV / TW) : TW;     // tile rows
   static constexpr int NPB = MV / (TR * TW);                     // patches per workgroup
-  static constexpr int HR = TR + 2, HC = TW + 2;
-  static constexpr int XV = NPB * HR * HC;                       // halo voxels of ONE staged plane
-  static constexpr int XPIECES = XV * 2;                         // 16-byte pieces per plane
+  static constexpr int HR = TR + 2, HW = TW + 2;                 // halo rows and columns
+  static constexpr int HC = conv_halo_pitch(TW);                 // row pitch of the LDS image (tm_conv_frag.h: HW, at TW = 8 12)
+  static constexpr int PS = conv_halo_patch(TW, HR);             // rows of a patch (HR * HC, at TW = 4 four more)
+  static constexpr int XV = NPB * PS;                            // rows (halo positions) of ONE staged plane, [2 k-halves][XV][4]
+  static constexpr int XPIECES = conv_stage_items(XV);           // staging items (16-byte pieces) per plane
   static constexpr int PX = (XPIECES + 255) / 256;
   static constexpr int WFLOATS = 27 * 512;                       // three 9-tap slots of the LDS-DMA weight ring
   static constexpr int LDS_BYTES = (WFLOATS + 3 * XV * 8) * 4;  // weights + the planes X0 + X1, X1, X0
 };
+// The constant part of a fragment address of the two z-pair kernels (floats; the lane's part is wb / xb below): tap `tap` of the
+// weight area, 32-cout sub-tile ct; window position (ky, kx) of staged plane p.  Shared with tm_conv_frag_addrs.
+TM_HD constexpr int zp_wtap(int tap, int ct) { return tap * 512 + conv_w_off(ct * 32, 0); }
+template <class G>
+TM_HD constexpr int zp_xtap(int p, int ky, int kx) { return p * G::XV * 8 + conv_frag_off(ky * G::HC + kx, 0, G::XV); }
 
 template <int HALF, int TW, bool FUSE = false>
 __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
@@ -221,8 +231,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   using G = ZPGeo<HALF, TW>;
   constexpr int NC = HALF ? 1 : 2;                               // 32-cout sub-tiles per wave
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* lw = lds;                                               // [27][512]
-  float* lx = lds + G::WFLOATS;                                  // [3][XV][8]
+  float* lw = lds;                                               // [27][2 k-halves][64][4]
+  float* lx = lds + G::WFLOATS;                                  // [3][2 k-halves][XV][4]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
@@ -239,14 +249,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
     const int i = tid + k * 256;
     long off = -1;
     if (i < G::XPIECES) {
-      const int half = i & 1;
-      int v = i >> 1;
-      const int hc = v % G::HC; v /= G::HC;
-      const int hr = v % G::HR;
-      const int ps = v / G::HR;
+      const int half = conv_stage_half(i);
+      int v = conv_stage_row(i);
+      const int ps = v / G::PS; v -= ps * G::PS;                 // ps == NPB: past the image, nothing is stored
+      const int hr = v / G::HC, hc = v % G::HC;                  // (rows from HR and columns from HW of the pitches are never read)
       const int n = pg * G::NPB + ps;
       const int y = tr * G::TR + hr - 1, x = tc * TW + hc - 1;
-      if (n < a.N && y >= 0 && y < S && x >= 0 && x < S) off = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
+      if (ps < G::NPB && hr < G::HR && hc < G::HW && n < a.N && y >= 0 && y < S && x >= 0 && x < S)
+        off = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
     }
     xoff[k] = off;
   }
@@ -257,7 +267,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
   const int ct0 = HALF ? (wv >> 1) : 0;                          // its first 32-cout sub-tile
   int xb, on[1], ooff0[1], ooff1[1];
   {
-    const ConvLane l = conv_lane_of<G::TR, TW, G::HR, G::HC>(vt * 32 + i32, h, 0, 0);
+    const ConvLane l = conv_lane_of<G::TR, TW, G::PS, G::HC, G::XV>(vt * 32 + conv_lane_voxel(TW, i32), h, 0, 0);
     xb = l.xb;
     const int n = pg * G::NPB + l.ps;
     on[0] = n;
@@ -267,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
       else { ooff0[0] = (y * S + x) * 8; ooff1[0] = ooff0[0] + S * S * 8; }
     } else { ooff0[0] = -1; ooff1[0] = -1; }
   }
-  const int wb = ct0 * 256 + i32 * 8 + 4 * h;
+  const int wb = conv_w_off(ct0 * 32 + i32, 4 * h);
 
   f32x16 acc[3][NC];
   clear_acc(acc);
@@ -313,8 +323,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int k = 0; k < G::PX; ++k)
-      if (tid + k * 256 < G::XPIECES) {
-        float* d = lx + (tid + k * 256) * 4;
+      if (conv_stage_row(tid + k * 256) < G::XV) {
+        float* d = lx + conv_frag_off(conv_stage_row(tid + k * 256), conv_stage_half(tid + k * 256), G::XV);
         *(f32x4*)(d) = xr[0][k] + xr[1][k];
         *(f32x4*)(d + G::XV * 8) = xr[1][k];
         *(f32x4*)(d + 2 * G::XV * 8) = xr[0][k];
@@ -345,8 +355,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
           const int tap = p * 9 + ky * 3 + kx;
           f32x4 wf[NC];
 #pragma unroll
-          for (int ct = 0; ct < NC; ++ct) wf[ct] = *(const f32x4*)(lw + tap * 512 + ct * 256 + wb);
-          const f32x4 xf = *(const f32x4*)(lx + p * G::XV * 8 + (ky * G::HC + kx) * 8 + xb);
+          for (int ct = 0; ct < NC; ++ct) wf[ct] = *(const f32x4*)(lw + zp_wtap(tap, ct) + wb);
+          const f32x4 xf = *(const f32x4*)(lx + zp_xtap<G>(p, ky, kx) + xb);
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -390,8 +400,9 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair(ConvArgs a) {
 //   vmcnt(0) | B0 | X(cb) -> LDS | B1 | 12 taps from slot cb & 1, with X(cb + 1) -> registers and the six pieces each wave owns of
 //   W(cb + 1) -> slot (cb + 1) & 1 behind the first six taps
 // Slot (cb + 1) & 1 was last read in block cb - 1, which every wave left before B0; a wave's own pieces of W(cb) are retired by
-// its vmcnt(0) in front of B0 and everybody's are visible behind it.  LDS: 2 x 24 576 B of weights + 3 X planes (at most 19 584 B)
-// = 68 736 B at most: two workgroups per CU.  Tiles, wave layout and accumulation order per output element (cin block, product,
+// its vmcnt(0) in front of B0 and everybody's are visible behind it.  LDS: 2 x 24 576 B of weights + 3 X planes (at most 23 040 B,
+// the 8-wide tile at pitch 12) = 72 192 B at most: two workgroups per CU.
+// Tiles, wave layout and accumulation order per output element (cin block, product,
 // tap, k) are conv3d_zpair's, so HALF = 0 and 1 give identical bits.
 template <int HALF, int TW>
 struct ZPUGeo : ZPGeo<HALF, TW> {
@@ -405,8 +416,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
   constexpr int NC = HALF ? 1 : 2;
   constexpr int WSLOT = G::WSLOT;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* lw = lds;                                               // [2][12][512]
-  float* lx = lds + 2 * WSLOT;                                   // [3][XV][8]
+  float* lw = lds;                                               // [2][12][2 k-halves][64][4]
+  float* lx = lds + 2 * WSLOT;                                   // [3][2 k-halves][XV][4]
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
@@ -422,14 +433,14 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
     const int i = tid + k * 256;
     long off = -1;
     if (i < G::XPIECES) {
-      const int half = i & 1;
-      int v = i >> 1;
-      const int hc = v % G::HC; v /= G::HC;
-      const int hr = v % G::HR;
-      const int ps = v / G::HR;
+      const int half = conv_stage_half(i);
+      int v = conv_stage_row(i);
+      const int ps = v / G::PS; v -= ps * G::PS;                 // ps == NPB: past the image, nothing is stored
+      const int hr = v / G::HC, hc = v % G::HC;                  // (rows from HR and columns from HW of the pitches are never read)
       const int n = pg * G::NPB + ps;
       const int y = tr * G::TR + hr - 1, x = tc * TW + hc - 1;
-      if (n < a.N && y >= 0 && y < S && x >= 0 && x < S) off = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
+      if (ps < G::NPB && hr < G::HR && hc < G::HW && n < a.N && y >= 0 && y < S && x >= 0 && x < S)
+        off = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
     }
     xoff[k] = off;
   }
@@ -439,15 +450,15 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
   const int ct0 = HALF ? (wv >> 1) : 0;
   int xb, on[1], ooff0[1], ooff1[1];
   {
-    const ConvLane l = conv_lane_of<G::TR, TW, G::HR, G::HC>(vt * 32 + i32, h, py, px);   // the phase's window starts at
-    xb = l.xb;                                                                            // (y + py - 1, x + px - 1)
+    const ConvLane l = conv_lane_of<G::TR, TW, G::PS, G::HC, G::XV>(vt * 32 + conv_lane_voxel(TW, i32), h, py, px);
+    xb = l.xb;                                                   // the phase's window starts at (y + py - 1, x + px - 1)
     const int n = pg * G::NPB + l.ps;
     on[0] = n;
     const int y = tr * G::TR + l.r, x = tc * TW + l.c;
     if (n < a.N) { ooff0[0] = ((2 * y + py) * 2 * S + 2 * x + px) * 8; ooff1[0] = ooff0[0] + 4 * S * S * 8; }
     else { ooff0[0] = -1; ooff1[0] = -1; }
   }
-  const int wb = ct0 * 256 + i32 * 8 + 4 * h;
+  const int wb = conv_w_off(ct0 * 32 + i32, 4 * h);
 
   f32x16 acc[3][NC];
   clear_acc(acc);
@@ -482,8 +493,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
     asm volatile("" ::: "memory");
 #pragma unroll
     for (int k = 0; k < G::PX; ++k)
-      if (tid + k * 256 < G::XPIECES) {
-        float* d = lx + (tid + k * 256) * 4;
+      if (conv_stage_row(tid + k * 256) < G::XV) {
+        float* d = lx + conv_frag_off(conv_stage_row(tid + k * 256), conv_stage_half(tid + k * 256), G::XV);
         *(f32x4*)(d) = xr[0][k] + xr[1][k];
         *(f32x4*)(d + G::XV * 8) = xr[1][k];
         *(f32x4*)(d + 2 * G::XV * 8) = xr[0][k];
@@ -506,8 +517,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
           const int tap = p * 4 + ky * 2 + kx;
           f32x4 wf[NC];
 #pragma unroll
-          for (int ct = 0; ct < NC; ++ct) wf[ct] = *(const f32x4*)(lwc + tap * 512 + ct * 256 + wb);
-          const f32x4 xf = *(const f32x4*)(lx + p * G::XV * 8 + (ky * G::HC + kx) * 8 + xb);
+          for (int ct = 0; ct < NC; ++ct) wf[ct] = *(const f32x4*)(lwc + zp_wtap(tap, ct) + wb);
+          const f32x4 xf = *(const f32x4*)(lx + zp_xtap<G>(p, ky, kx) + xb);
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
@@ -549,8 +560,10 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
 // wave); after the K loop the q halves swap the one tile per product the other needs through LDS (A1 one way, A2 the other),
 // then waves 0/1 finish the even columns and waves 2/3 the odd ones.  Every output sees one order of sums in both -- cin
 // block, product, ky, k inside an accumulator, then the fixed output transform -- so the two tiles give identical bits.
-// LDS: per product four q-planes of XP = NPB x HR x TW/2 pair positions (no x halo: the transform consumed it), fragment
-// addresses contiguous in the pair index; weights are a ring of two PRODUCT slots (12 taps x 512 floats, the (ky, q) of one
+// LDS: per product four q-planes of XP = NPB x HR x TW/2 pair positions (no x halo: the transform consumed it), each two k-half
+// arrays [2][XP][4] (tm_conv_frag.h; the weights of a tap likewise [2][64 couts][4]), fragment addresses contiguous in the pair
+// index: a wave's 32 positions are consecutive rows, so every 16-lane group of a fragment read meets sixteen different slots;
+// weights are a ring of two PRODUCT slots (12 taps x 512 floats, the (ky, q) of one
 // product) filled by LDS-DMA as in conv3d_zpair_ups: product n = 3 cb + p reads slot n & 1, the pieces of product n + 1 go out
 // behind its first taps into the slot every wave left at the barrier in front of product n, and a wave retires its own with the
 // vmcnt(0) in front of the next product's barrier.  A cin block costs four barriers:
@@ -568,18 +581,22 @@ struct XPGeo {
   static constexpr int HR = TR + 2;
   static constexpr int XP = NPB * HR * PWD;                      // pair positions of one q-plane (y halo only)
   static constexpr int XITEMS = XP * 2;                          // staging items: (position, half block), one per thread
+  static_assert(XP % 8 == 0, "whole groups of eight staging items (tm_conv_frag.h)");
   static constexpr int WSLOT = 12 * 512;                         // floats of one product of a (cout tile, cin block)
   static constexpr int KP = 24 / NW;                             // LDS-DMA pieces (256 floats) of a slot per wave
   static constexpr int LDS_BYTES = (2 * WSLOT + 12 * XP * 8) * 4;
 };
+// The constant part of conv3d_xpair's X fragment address (floats): row ky of q-plane (p, q).  Shared with tm_conv_frag_addrs.
+template <class G>
+TM_HD constexpr int xp_xtap(int p, int q, int ky) { return (p * 4 + q) * G::XP * 8 + conv_frag_off(ky * G::PWD, 0, G::XP); }
 
 template <int HALF, int TW>
 __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
   using G = XPGeo<HALF, TW>;
   static_assert(G::XITEMS <= 64 * G::NW, "one staging item per thread");
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* lw = lds;                                               // [2][12][512]: the LDS-DMA destinations stay below 64 KiB
-  // the X planes [3 products][4 q][XP][8] follow at float 2 * WSLOT, up to byte 79 872 (addressed through xw / xb below)
+  float* lw = lds;                                               // [2][12][2 k-halves][64][4]: the LDS-DMA destinations stay below 64 KiB
+  // the X planes [3 products][4 q][2 k-halves][XP][4] follow at float 2 * WSLOT, up to byte 79 872 (addressed through xw / xb below)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wv = tid >> 6;
@@ -593,8 +610,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
   long xoff = -1;
   bool okl = false, okr = false;                                 // columns 2j - 1 and 2j + 2 lie inside the plane
   if (tid < G::XITEMS) {
-    const int half = tid & 1;
-    int v = tid >> 1;
+    const int half = conv_stage_half(tid);
+    int v = conv_stage_row(tid);
     const int j = v % G::PWD; v /= G::PWD;
     const int hr = v % G::HR;
     const int ps = v / G::HR;
@@ -607,7 +624,8 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
     }
   }
   const long zplane = (long)S * S * 8;
-  int xw = 2 * G::WSLOT + tid * 4;                               // this item's slot of a q-plane (base hidden as xb's below)
+  // this item's slot of a q-plane (base hidden as xb's below)
+  int xw = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP);
   asm volatile("" : "+v"(xw));
 
   // ---- per-lane fragment addresses ----
@@ -616,17 +634,19 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
   const int q0 = HALF ? (wv >> 1) * 2 : 0;                       // its first q
   int xb, on[1], ooff0;                                          // ooff0: the even column of plane 0 (or -1)
   {
-    const ConvLane l = conv_lane_of<G::TR, G::PWD, G::HR, G::PWD>(pt * 32 + i32, h, 0, 0);
+    const ConvLane l = conv_lane_of<G::TR, G::PWD, G::HR * G::PWD, G::PWD, G::XP>(pt * 32 + i32, h, 0, 0);
     // lx's offset is part of the lane's base and hidden from the compiler, so that the (product, q, ky) of a fragment is a
     // 16-bit ds_read offset of ONE register (folded into the constant it would pass 64 KiB and take a register per plane)
-    xb = 2 * G::WSLOT + q0 * G::XP * 8 + l.xb;
+    // xb counts 16-byte slots: as a float index the hidden base hid the alignment as well, and the compiler split every X
+    // fragment read into two ds_read2_b32 (dword banking: 4-way conflicts on the k-half image, 8-way on [row][8])
+    xb = (2 * G::WSLOT + q0 * G::XP * 8 + l.xb) / 4;
     asm volatile("" : "+v"(xb));
     const int n = pg * G::NPB + l.ps;
     on[0] = n;
     const int y = tr * G::TR + l.r, x = tc * TW + 2 * l.c;
     ooff0 = n < a.N ? (y * S + x) * 8 : -1;
   }
-  const int wb = q0 * 512 + ch * 256 + i32 * 8 + 4 * h;
+  const int wb = q0 * 512 + conv_w_off(ch * 32 + i32, 4 * h);
 
   f32x16 acc[3][G::NQ];
   clear_acc(acc);
@@ -704,7 +724,7 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
         for (int q = 0; q < G::NQ; ++q) {                        // (q counts from the wave's q0: in both bases)
           const int tap = ky * 4 + q;
           const f32x4 wf = *(const f32x4*)(lwc + tap * 512);
-          const f32x4 xf = *(const f32x4*)(lds + xb + ((p * 4 + q) * G::XP + ky * G::PWD) * 8);
+          const f32x4 xf = ((const f32x4*)lds)[xb + xp_xtap<G>(p, q, ky) / 4];
 #pragma unroll
           for (int kk = 0; kk < 4; ++kk) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[kk], xf[kk], acc[p][q], 0, 0, 0);
           if (ky * G::NQ + q < G::KP && (p < 2 || more)) issue_piece(n + 1, ky * G::NQ + q);   // a piece of product n + 1 behind each of the first six taps
@@ -1062,6 +1082,65 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
                      : launch_tiled<conv3d_xpair<1, TW>, XPGeo<1, TW>, 64 * XPGeo<1, TW>::NW>(a, 1, s);
       });
   }
+}
+
+// ---- the lane -> LDS address maps of the three LDS-DMA conv kernels, evaluated on the host (no device call) ----
+// The same functions the kernels address with (tm_conv_frag.h, conv_lane_of, zp_wtap / zp_xtap / xp_xtap), composed as the
+// kernels compose them: out[lane] = byte address inside the workgroup's dynamic LDS of what lane `lane` of wave wv reads or
+// stores, -1 for a lane that stores nothing.  what 0: the weight fragment of tap (p, ky, kx) and 32-cout sub-tile `sub` (slot 0
+// of a ring); 1: the X fragment of (p, ky, kx), `sub` = the output phase 2 py + px of the upsampled form; 2: the staging store
+// into plane p of the thread's item ky (its k-th of PX).  conv3d_xpair: kx is the wave's q (0 .. NQ - 1), in what 2 the q-plane.
+template <class G, int HALF, int TW, bool UPS>
+static int zpair_frag_addrs(int what, int wv, int p, int ky, int kx, int sub, int* out) {
+  constexpr int NC = HALF ? 1 : 2, KW = UPS ? 2 : 3;
+  constexpr int lx = G::LDS_BYTES / 4 - 3 * G::XV * 8;           // the X planes close the allocation
+  if (p < 0 || p > 2) return -1;
+  if (what == 2 ? (ky < 0 || ky >= G::PX) : (ky < 0 || ky >= KW || kx < 0 || kx >= KW)) return -1;
+  if (what == 0 ? (sub < 0 || sub >= NC) : what == 1 ? (sub < 0 || sub > (UPS ? 3 : 0)) : false) return -1;
+  const int vt = HALF ? (wv & 1) : wv, ct0 = HALF ? (wv >> 1) : 0;
+  for (int lane = 0; lane < 64; ++lane) {
+    const int i32 = lane & 31, h = lane >> 5;
+    int a = -1;
+    if (what == 0) a = zp_wtap(UPS ? p * 4 + ky * 2 + kx : p * 9 + ky * 3 + kx, sub) + conv_w_off(ct0 * 32 + i32, 4 * h);
+    else if (what == 1)
+      a = lx + zp_xtap<G>(p, ky, kx) + conv_lane_of<G::TR, TW, G::PS, G::HC, G::XV>(vt * 32 + conv_lane_voxel(TW, i32), h, sub >> 1, sub & 1).xb;
+    else {
+      const int i = wv * 64 + lane + ky * 256;
+      if (conv_stage_row(i) < G::XV) a = lx + p * G::XV * 8 + conv_frag_off(conv_stage_row(i), conv_stage_half(i), G::XV);
+    }
+    out[lane] = a < 0 ? -1 : a * 4;
+  }
+  return 0;
+}
+template <int HALF, int TW>
+static int xpair_frag_addrs(int what, int wv, int p, int ky, int q, int* out) {
+  using G = XPGeo<HALF, TW>;
+  if (p < 0 || p > 2 || q < 0 || q >= (what == 2 ? 4 : G::NQ) || ky < 0 || ky > (what == 2 ? 0 : 2)) return -1;
+  const int pt = HALF ? 0 : (wv >> 1), ch = wv & 1, q0 = HALF ? (wv >> 1) * 2 : 0;
+  for (int lane = 0; lane < 64; ++lane) {
+    const int i32 = lane & 31, h = lane >> 5, tid = wv * 64 + lane;
+    int a = -1;
+    if (what == 0) a = q0 * 512 + conv_w_off(ch * 32 + i32, 4 * h) + (ky * 4 + q) * 512;
+    else if (what == 1)
+      a = 2 * G::WSLOT + q0 * G::XP * 8 + conv_lane_of<G::TR, G::PWD, G::HR * G::PWD, G::PWD, G::XP>(pt * 32 + i32, h, 0, 0).xb + xp_xtap<G>(p, q, ky);
+    else if (tid < G::XITEMS)
+      a = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP) + (p * 4 + q) * G::XP * 8;
+    out[lane] = a < 0 ? -1 : a * 4;
+  }
+  return 0;
+}
+int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out) {
+  if (!out || kernel < 0 || kernel > 2 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > 3) return -1;
+#define TM_FRAG(H, T)                                                                                              \
+  if (half == H && tw == T) {                                                                                      \
+    if (kernel == 0) return zpair_frag_addrs<ZPGeo<H, T>, H, T, false>(what, wv, p, ky, kx, sub, out);              \
+    if (kernel == 1) return zpair_frag_addrs<ZPUGeo<H, T>, H, T, true>(what, wv, p, ky, kx, sub, out);              \
+  }
+  TM_FRAG(1, 4) TM_FRAG(0, 8) TM_FRAG(1, 8) TM_FRAG(0, 16) TM_FRAG(1, 16) TM_FRAG(0, 32) TM_FRAG(1, 32)
+#undef TM_FRAG
+  if (kernel == 2 && tw == 8) return half ? xpair_frag_addrs<1, 8>(what, wv, p, ky, kx, out) : xpair_frag_addrs<0, 8>(what, wv, p, ky, kx, out);
+  if (kernel == 2 && tw == 16) return half ? xpair_frag_addrs<1, 16>(what, wv, p, ky, kx, out) : xpair_frag_addrs<0, 16>(what, wv, p, ky, kx, out);
+  return -1;                                                     // no such instantiation
 }
 
 // ==========================================================================================

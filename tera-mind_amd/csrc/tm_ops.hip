@@ -317,6 +317,9 @@ extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, c
 static bool half_gate_ok(int S) { return S >= 2 && (S & (S - 1)) == 0; }
 
 extern "C" int tm_conv1_form(long vox, int ntile, int tile_variant) { return conv1_form(vox, ntile, tile_variant); }
+extern "C" int tm_conv_frag_addrs(int kernel, int half, int tw, int what, int wave, int p, int ky, int kx, int sub, int* out64) {
+  return conv_frag_addrs(kernel, half, tw, what, wave, p, ky, kx, sub, out64);
+}
 
 extern "C" int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                                const void* gate_cb8, int x_cbtot, int x_cb0, int gate_cbtot, int gate_cb0, int gate_half, int gelu,

@@ -7,6 +7,7 @@
 // re-packed by the host (tm_op_conv_dgrad in tm_ops.hip).
 // fp32 throughout (training in the reference is fp16-mixed on top of fp32 master weights; the slice checks gradients
 // against torch.autograd of the fp32 oracle).  Layout: CB8 fp32 [N][Cb][Z][H][W][8] as everywhere.
+#include "tm_conv_frag.h"
 #include "tm_device.h"
 
 #include <algorithm>
@@ -549,7 +550,7 @@ hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin,
 
 // ------------------------------------------------------------------------------------------------------------------
 // Conv weights packed on the device: w [Cout][Cin][taps] (reference layout) -> the bytes conv_pack_host writes for `form`: the
-// plain tap order, or for CF_PAIR W1, W2 - W1, W0 - W1 per in-plane tap (plain fp32 subtractions); pad slots
+// plain tap order, or for CF_PAIR W1, W2 - W1, W0 - W1 per in-plane tap (plain fp32 subtractions) in the k-half image; pad slots
 // zero.  role 1 packs the filter of the data gradient: flipped in every axis and cin <-> cout transposed, so the pack
 // has Cin "output" channels over ceil(Cout / 8) "input" blocks.  One thread per packed float.
 // ------------------------------------------------------------------------------------------------------------------
@@ -558,7 +559,10 @@ __global__ __launch_bounds__(256) void conv_pack_kernel(const float* w, float* o
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
   const int Co = role ? Cin : Cout, Ci = role ? Cout : Cin, Cbi = (Ci + 7) / 8;
-  const int c8 = (int)(i & 7), col = (int)((i >> 3) & 63);
+  // CF_PAIR: a tap is [2 k-halves][64 cout][4 cin] (conv_w_off, tm_conv_frag.h), every other form [64 cout][8 cin]
+  const int c8 = form == CF_PAIR ? (int)(((i >> 8) & 1) * 4 + (i & 3)) : (int)(i & 7);
+  const int col = form == CF_PAIR ? (int)((i >> 2) & 63) : (int)((i >> 3) & 63);
+  static_assert(conv_w_off(63, 7) == 511 && conv_w_off(5, 6) == 256 + 5 * 4 + 2, "the decode above inverts conv_w_off");
   long r = i >> 9;
   const int t = (int)(r % taps); r /= taps;
   const int cb = (int)(r % Cbi), nt = (int)(r / Cbi);
