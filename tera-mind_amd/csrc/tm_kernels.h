@@ -24,6 +24,14 @@ struct TV {
     return v;
   }
 };
+// a dense CB8 tensor at p: the one place that computes Cb and nstride (p == nullptr: a geometry-only descriptor)
+inline TV cb8_view(void* p, int N, int C, int Z, int H, int W) {
+  TV t;
+  t.p = (float*)p; t.N = N; t.C = C; t.Cb = (C + 7) / 8; t.Z = Z; t.H = H; t.W = W;
+  t.nstride = (long)t.Cb * t.plane();
+  return t;
+}
+inline int pair_cb(int cb) { return (cb + 1) / 2 * 2; }   // the even block count of a 16-bit conv operand (zero pad block)
 
 // ---- packed conv weights for the MFMA implicit-GEMM kernels ----------------------------
 // layout: [n_tile][cblk][tap][64 cout][8 cin] fp32, cout padded to a multiple of 64,
@@ -216,6 +224,37 @@ struct PrepLaunch {
   float drop_scale = 1.f;
 };
 hipError_t launch_prep(const PrepLaunch& L, hipStream_t s);
+// The builder: a launch starts with its output geometry and no source, and each helper states one thing.  Sources are added in
+// concat order; all sources of a launch have one element type (a TVH source makes them 16-bit: src_h).
+inline PrepLaunch prep_start(int N, int Z, int S) {
+  PrepLaunch P;
+  P.nsrc = 0; P.N = N; P.Z = Z; P.S = S;
+  return P;
+}
+inline void prep_add_src(PrepLaunch& P, const void* p, long nstride, int Cb, bool collage, bool h16) {
+  const int i = P.nsrc++;
+  P.src[i].p = (const float*)p; P.src[i].nstride = nstride; P.src[i].Cb = Cb; P.src[i].collage = collage ? 1 : 0;
+  P.src_h = h16 ? 1 : 0;
+}
+inline void prep_src(PrepLaunch& P, const TV& t, bool collage = false) { prep_add_src(P, t.p, t.nstride, t.Cb, collage, false); }
+inline void prep_src(PrepLaunch& P, const TVH& t, bool collage = false) { prep_add_src(P, t.p, t.nstride, t.Cb, collage, true); }
+inline void prep_out(PrepLaunch& P, const TV& y) { P.out = y.p; P.out_nstride = y.nstride; }
+// 16-bit output; real_cb: the channel blocks the sources fill, the rest of y's are the zero pad blocks
+inline void prep_out_h(PrepLaunch& P, const TVH& y, int real_cb) { P.out_h = y.p; P.out_h_nstride = y.nstride; P.pad_blocks = y.Cb - real_cb; }
+inline void prep_raw(PrepLaunch& P, const TV& r) { P.raw = r.p; P.raw_nstride = r.nstride; }
+inline void prep_raw_h(PrepLaunch& P, const TVH& r) { P.raw_h = r.p; P.raw_h_nstride = r.nstride; }
+inline void prep_norm(PrepLaunch& P, const float* norm_w, int c_real) { P.norm_w = norm_w; P.inv_c = 1.0f / (float)c_real; }
+// per-image rows [b][emb_tot] of all emb_layers: scale at emb_off, shift at emb_off + cout
+inline void prep_mod_image(PrepLaunch& P, const float* ss, int emb_off, int cout, int emb_tot) {
+  P.mod = MOD_IMAGE; P.mod_scale = ss + emb_off; P.mod_shift = ss + emb_off + cout; P.mod_stride = emb_tot;
+}
+// per-voxel: two channel-block slices of one modulation tensor (they share its nstride)
+inline void prep_mod_voxel(PrepLaunch& P, const TV& scale, const TV& shift, bool half) {
+  P.mod = MOD_VOXEL; P.mod_scale = scale.p; P.mod_shift = shift.p; P.mod_stride = scale.nstride; P.mod_half = half ? 1 : 0;
+}
+inline void prep_mod_voxel(PrepLaunch& P, const TVH& scale, const TVH& shift, bool half) {
+  P.mod = MOD_VOXEL; P.mod_scale_h = scale.p; P.mod_shift_h = shift.p; P.mod_stride = scale.nstride; P.mod_half = half ? 1 : 0;
+}
 // training forward with the keep mask DRAWN in the kernel instead of supplied (drop_keep8: Philox4x32-10; drop_mask
 // null): out = act(...) * keep * L.drop_scale.  One fp32 source, fp32 out, RS_SAME, no collage (prep_kernel<1, *, true>).  The draw
 // parameters travel beside PrepLaunch (PrepDropArgs), so that the inference instantiations keep their arguments and code.

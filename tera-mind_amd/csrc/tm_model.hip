@@ -11,6 +11,7 @@
 #include <cmath>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include <stdarg.h>
 #include <stdio.h>
@@ -383,23 +384,29 @@ static void pack_bias(Packer& pk, std::vector<Fix>& fx, ConvW& cw, const std::ve
   for (int i = 0; i < cw.Cout; ++i) pk.buf[boff + i] = b[i];
   fx.push_back({&cw.bias, boff});
 }
+// real channels and padded channel blocks of a concat: every segment is padded to a multiple of 8 ("virtual" cin order)
+struct SegSum { int cin = 0, cbi = 0; };
+static SegSum seg_sum(const std::vector<int>& seg) {
+  SegSum t;
+  for (int c : seg) { t.cin += c; t.cbi += (c + 7) / 8; }
+  return t;
+}
 // fp32 conv weights of `wkey` ([Cout][Cin][27], or [9] / [1] for the 1x3x3 and 1x1x1 convs) in `form`, with the bias
 static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, const std::string& wkey,
                       const std::string& bkey, int Cout, const std::vector<int>& seg, int form) {
-  int cbi = 0, cin = 0;
-  for (int c : seg) { cbi += (c + 7) / 8; cin += c; }
+  const SegSum t = seg_sum(seg);
   // CF_INPLANE of a 3x3x3 pad-1 conv: applied to ONE plane (z_size 1, rna_slc 1) it only ever multiplies its kz = 1 slice
   // with data -- pack those 9 taps and run the in-plane kernel
   std::vector<float> centre;
   const float* wsrc = P(m, wkey).data();
-  if (form == CF_INPLANE && P(m, wkey).size() == (size_t)Cout * cin * 27) {
-    centre.resize((size_t)Cout * cin * 9);
-    for (size_t i = 0; i < (size_t)Cout * cin; ++i)
-      for (int t = 0; t < 9; ++t) centre[i * 9 + t] = wsrc[i * 27 + 9 + t];
+  if (form == CF_INPLANE && P(m, wkey).size() == (size_t)Cout * t.cin * 27) {
+    centre.resize((size_t)Cout * t.cin * 9);
+    for (size_t i = 0; i < (size_t)Cout * t.cin; ++i)
+      for (int k = 0; k < 9; ++k) centre[i * 9 + k] = wsrc[i * 27 + 9 + k];
     wsrc = centre.data();
   }
-  cw = conv_w(form, Cout, cbi);
-  size_t off = pk.reserve(conv_pack_floats(form, Cout, cbi));
+  cw = conv_w(form, Cout, t.cbi);
+  size_t off = pk.reserve(conv_pack_floats(form, Cout, t.cbi));
   conv_pack_host(form, wsrc, Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
   fx.push_back({&cw.w, off});
   pack_bias(pk, fx, cw, P(m, bkey));
@@ -408,70 +415,55 @@ static void pack_conv(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw, 
 static void pack_conv_h(tm_model* m, Packer& pk, std::vector<Fix>& fx, std::vector<FixH>& fxh, ConvW& cw,
                         const uint16_t** wslot, const std::string& wkey, const std::string& bkey, int Cout,
                         const std::vector<int>& seg, bool inplane = false) {
-  int cbi = 0, cin = 0;
-  for (int c : seg) { cbi += (c + 7) / 8; cin += c; }
+  const SegSum t = seg_sum(seg);
   // inplane: a Conv3d(k = (1,3,3), pad (0,1,1)) run by the 3x3x3 kernel -- its 9 taps sit in the centre z slice, the z - 1
   // and z + 1 slices are zero
   std::vector<float> w27;
   if (inplane) {
     const std::vector<float>& w9 = P(m, wkey);
-    w27.assign((size_t)Cout * cin * 27, 0.f);
-    for (size_t i = 0; i < (size_t)Cout * cin; ++i)
-      for (int t = 0; t < 9; ++t) w27[i * 27 + 9 + t] = w9[i * 9 + t];
+    w27.assign((size_t)Cout * t.cin * 27, 0.f);
+    for (size_t i = 0; i < (size_t)Cout * t.cin; ++i)
+      for (int k = 0; k < 9; ++k) w27[i * 27 + 9 + k] = w9[i * 9 + k];
   }
-  cw = conv_w(CF_PLANES3, Cout, cbi);                  // geometry and bias only: the 16-bit pack lives in *wslot
-  const size_t elems = conv_bf16_pack_elems(Cout, cbi);
+  cw = conv_w(CF_PLANES3, Cout, t.cbi);                // geometry and bias only: the 16-bit pack lives in *wslot
+  const size_t elems = conv_bf16_pack_elems(Cout, t.cbi);
   size_t off = pk.reserve((elems + 1) / 2);
   (m->cfg.dtype == TM_DTYPE_F16 ? conv_f16_pack_host : conv_bf16_pack_host)(inplane ? w27.data() : P(m, wkey).data(), Cout, seg.data(),
                                                                             (int)seg.size(), (uint16_t*)(pk.buf.data() + off));
   fxh.push_back({wslot, off});
   pack_bias(pk, fx, cw, P(m, bkey));
 }
-// rows of several [rows_i][Cin] matrices stacked into one conv1 weight
-static void pack_linear_stack(tm_model* m, Packer& pk, std::vector<Fix>& fx, ConvW& cw,
-                              const std::vector<std::string>& pfx, int rows_each, int Cin) {
+// rows of several [rows_i][Cin] matrices (Linears, or a 1x1x1 conv over the concat `seg`) stacked into one conv1 weight, with the
+// stacked bias.  wslot == nullptr: the fp32 pack behind cw.w; otherwise the 16-bit pack behind *wslot, cw carrying the geometry
+// and the bias only.
+static void pack_linear_stack(tm_model* m, Packer& pk, std::vector<Fix>& fx, std::vector<FixH>& fxh, ConvW& cw,
+                              const uint16_t** wslot, const std::vector<std::string>& pfx, int rows_each,
+                              const std::vector<int>& seg) {
+  const SegSum t = seg_sum(seg);
   const int Cout = rows_each * (int)pfx.size();
-  std::vector<float> w((size_t)Cout * Cin), b(Cout);
+  std::vector<float> w((size_t)Cout * t.cin), b(Cout);
   for (size_t i = 0; i < pfx.size(); ++i) {
     const std::vector<float>& wi = P(m, pfx[i] + ".weight");
     const std::vector<float>& bi = P(m, pfx[i] + ".bias");
-    memcpy(w.data() + i * (size_t)rows_each * Cin, wi.data(), (size_t)rows_each * Cin * sizeof(float));
+    memcpy(w.data() + i * (size_t)rows_each * t.cin, wi.data(), (size_t)rows_each * t.cin * sizeof(float));
     memcpy(b.data() + i * rows_each, bi.data(), rows_each * sizeof(float));
   }
-  int seg = Cin;
-  cw = conv_w(CF_1X1, Cout, (Cin + 7) / 8);
-  size_t off = pk.reserve(conv_pack_floats(CF_1X1, Cout, cw.Cbi));
-  conv_pack_host(CF_1X1, w.data(), Cout, &seg, 1, pk.buf.data() + off);
-  fx.push_back({&cw.w, off});
-  pack_bias(pk, fx, cw, b);
-}
-static void pack_linear_stack_h(tm_model* m, Packer& pk, std::vector<Fix>& fx, std::vector<FixH>& fxh, ConvW& cw,
-                                const uint16_t** wslot, const std::vector<std::string>& pfx, int rows_each,
-                                const std::vector<int>& seg, bool is_conv_key = false) {
-  int Cin = 0, cbi = 0;
-  for (int c : seg) { Cin += c; cbi += (c + 7) / 8; }
-  const int Cout = rows_each * (int)pfx.size();
-  std::vector<float> w((size_t)Cout * Cin), b(Cout);
-  for (size_t i = 0; i < pfx.size(); ++i) {
-    const std::vector<float>& wi = P(m, pfx[i] + ".weight");
-    const std::vector<float>& bi = P(m, pfx[i] + ".bias");
-    memcpy(w.data() + i * (size_t)rows_each * Cin, wi.data(), (size_t)rows_each * Cin * sizeof(float));
-    memcpy(b.data() + i * rows_each, bi.data(), rows_each * sizeof(float));
+  cw = conv_w(CF_1X1, Cout, t.cbi);
+  if (wslot) {
+    const size_t off = pk.reserve((conv1_bf16_pack_elems(Cout, t.cbi) + 1) / 2);
+    (m->cfg.dtype == TM_DTYPE_F16 ? conv1_f16_pack_host : conv1_bf16_pack_host)(w.data(), Cout, seg.data(), (int)seg.size(),
+                                                                                (uint16_t*)(pk.buf.data() + off));
+    fxh.push_back({wslot, off});
+  } else {
+    const size_t off = pk.reserve(conv_pack_floats(CF_1X1, Cout, t.cbi));
+    conv_pack_host(CF_1X1, w.data(), Cout, seg.data(), (int)seg.size(), pk.buf.data() + off);
+    fx.push_back({&cw.w, off});
   }
-  (void)is_conv_key;
-  cw = conv_w(CF_1X1, Cout, cbi);                      // geometry and bias only: the 16-bit pack lives in *wslot
-  const size_t elems = conv1_bf16_pack_elems(Cout, cbi);
-  size_t off = pk.reserve((elems + 1) / 2);
-  (m->cfg.dtype == TM_DTYPE_F16 ? conv1_f16_pack_host : conv1_bf16_pack_host)(w.data(), Cout, seg.data(), (int)seg.size(),
-                                                                              (uint16_t*)(pk.buf.data() + off));
-  fxh.push_back({wslot, off});
   pack_bias(pk, fx, cw, b);
 }
 static void pack_vec(Packer& pk, std::vector<Fix>& fx, const float** slot, const std::vector<float>& v,
                      const std::vector<int>& seg) {
-  int cbi = 0;
-  for (int c : seg) cbi += (c + 7) / 8;
-  size_t off = pk.reserve((size_t)cbi * 8);
+  size_t off = pk.reserve((size_t)seg_sum(seg).cbi * 8);
   vec_pack_host(v.data(), seg.data(), (int)seg.size(), pk.buf.data() + off);
   fx.push_back({slot, off});
 }
@@ -587,33 +579,19 @@ extern "C" int tm_model_finalize(tm_model* m) {
         pack_conv(m, pk, fx, r.c2, r.pfx + ".out_layers.3.weight", r.pfx + ".out_layers.3.bias", r.cout, {r.cout},
                   conv_pick_form(3, ZM_PAD1, m->z, m->deep8, role));
       }
-      if (r.has_skip) {
-        if (bf16) pack_linear_stack_h(m, pk, fx, fxh, r.skip, &r.skiph, {r.pfx + ".skip_connection"}, r.cout, r.seg);
-        else pack_conv(m, pk, fx, r.skip, r.pfx + ".skip_connection.weight", r.pfx + ".skip_connection.bias", r.cout, r.seg, CF_1X1);
-      }
+      if (r.has_skip)
+        pack_linear_stack(m, pk, fx, fxh, r.skip, bf16 ? &r.skiph : nullptr, {r.pfx + ".skip_connection"}, r.cout, r.seg);
       pack_vec(pk, fx, &r.n1, P(m, r.pfx + ".in_layers.0.weight"), r.seg);
       pack_raw(pk, fx, &r.n2, P(m, r.pfx + ".out_layers.0.weight"));
     }
     for (AttnW& a : m->attn) {
-      if (bf16) {
-        pack_linear_stack_h(m, pk, fx, fxh, a.ada, &a.adah, {a.pfx + ".adaLN_modulation.1"}, 7 * a.C, {a.G});
-        pack_linear_stack_h(m, pk, fx, fxh, a.q, &a.qh, {a.pfx + ".attn.q"}, a.C, {a.C});
-        pack_linear_stack_h(m, pk, fx, fxh, a.kv, &a.kvh, {a.pfx + ".attn.k", a.pfx + ".attn.v"}, a.C, {a.C});
-        pack_linear_stack_h(m, pk, fx, fxh, a.proj, &a.projh, {a.pfx + ".attn.proj"}, a.C, {a.C});
-        pack_linear_stack_h(m, pk, fx, fxh, a.fc1, &a.fc1h, {a.pfx + ".mlp.fc1"}, 4 * a.C, {a.C});
-        pack_linear_stack_h(m, pk, fx, fxh, a.fc2, &a.fc2h, {a.pfx + ".mlp.fc2"}, a.C, {4 * a.C});
-        pack_raw(pk, fx, &a.n1, P(m, a.pfx + ".norm1.weight"));
-        pack_raw(pk, fx, &a.n2, P(m, a.pfx + ".norm2.weight"));
-        pack_raw(pk, fx, &a.qn, P(m, a.pfx + ".attn.q_norm.weight"));
-        pack_raw(pk, fx, &a.kn, P(m, a.pfx + ".attn.k_norm.weight"));
-        continue;
-      }
-      pack_linear_stack(m, pk, fx, a.ada, {a.pfx + ".adaLN_modulation.1"}, 7 * a.C, a.G);
-      pack_linear_stack(m, pk, fx, a.q, {a.pfx + ".attn.q"}, a.C, a.C);
-      pack_linear_stack(m, pk, fx, a.kv, {a.pfx + ".attn.k", a.pfx + ".attn.v"}, a.C, a.C);
-      pack_linear_stack(m, pk, fx, a.proj, {a.pfx + ".attn.proj"}, a.C, a.C);
-      pack_linear_stack(m, pk, fx, a.fc1, {a.pfx + ".mlp.fc1"}, 4 * a.C, a.C);
-      pack_linear_stack(m, pk, fx, a.fc2, {a.pfx + ".mlp.fc2"}, a.C, 4 * a.C);
+      auto slot = [&](const uint16_t** h) { return bf16 ? h : nullptr; };
+      pack_linear_stack(m, pk, fx, fxh, a.ada, slot(&a.adah), {a.pfx + ".adaLN_modulation.1"}, 7 * a.C, {a.G});
+      pack_linear_stack(m, pk, fx, fxh, a.q, slot(&a.qh), {a.pfx + ".attn.q"}, a.C, {a.C});
+      pack_linear_stack(m, pk, fx, fxh, a.kv, slot(&a.kvh), {a.pfx + ".attn.k", a.pfx + ".attn.v"}, a.C, {a.C});
+      pack_linear_stack(m, pk, fx, fxh, a.proj, slot(&a.projh), {a.pfx + ".attn.proj"}, a.C, {a.C});
+      pack_linear_stack(m, pk, fx, fxh, a.fc1, slot(&a.fc1h), {a.pfx + ".mlp.fc1"}, 4 * a.C, {a.C});
+      pack_linear_stack(m, pk, fx, fxh, a.fc2, slot(&a.fc2h), {a.pfx + ".mlp.fc2"}, a.C, {4 * a.C});
       pack_raw(pk, fx, &a.n1, P(m, a.pfx + ".norm1.weight"));
       pack_raw(pk, fx, &a.n2, P(m, a.pfx + ".norm2.weight"));
       pack_raw(pk, fx, &a.qn, P(m, a.pfx + ".attn.q_norm.weight"));
@@ -684,7 +662,7 @@ extern "C" int tm_model_destroy(tm_model* m) {
 // executor
 // ------------------------------------------------------------------------------------------
 struct Ctx {
-  tm_model* m;
+  tm_model* m = nullptr;
   char* base = nullptr;
   size_t cap = 0, top = 0, peak = 0;
   bool dry = false;
@@ -693,6 +671,16 @@ struct Ctx {
   hipError_t err = hipSuccess;
   const float* ss = nullptr;      // [b][emb_tot]
 
+  // buf: the workspace or pyramid buffer the tensors are carved from; nullptr: a dry run (sizes and layout only)
+  void init(tm_model* m_, int b_, int p1_, int p2_, void* buf, size_t bytes, hipStream_t s_) {
+    m = m_; s = s_;
+    b = b_; p1 = p1_; p2 = p2_; Ne = b * p1 * p2; Nd = b * (p1 - 1) * (p2 - 1);
+    if (buf) {
+      base = (char*)(((uintptr_t)buf + 255) / 256 * 256);
+      cap = bytes - (size_t)(base - (char*)buf);
+    } else dry = true;
+  }
+  bool h16() const { return is_h16(m->cfg.dtype); }
   float* alloc_f(size_t nfloats) {
     size_t off = (top + 255) / 256 * 256;
     top = off + nfloats * sizeof(float);
@@ -702,30 +690,36 @@ struct Ctx {
     return (float*)(base + off);
   }
   TV tensor(int N, int C, int Z, int S) {
-    TV t;
-    t.N = N; t.C = C; t.Cb = (C + 7) / 8; t.Z = Z; t.H = S; t.W = S;
-    t.nstride = (long)t.Cb * t.plane();
+    TV t = cb8_view(nullptr, N, C, Z, S, S);
     t.p = alloc_f((size_t)N * t.nstride);
     return t;
   }
   TVH tensor_h(int N, int Cb_even, int Z, int S) {           // bf16 CB8 (conv27_bf16 input)
-    TVH t;
-    t.N = N; t.Cb = Cb_even; t.C = Cb_even * 8; t.Z = Z; t.H = S; t.W = S;
-    t.nstride = (long)Cb_even * Z * S * S * 8;
+    TVH t = as_h(cb8_view(nullptr, N, Cb_even * 8, Z, S, S));
     t.p = (uint16_t*)alloc_f(((size_t)N * t.nstride + 1) / 2);
     return t;
   }
   // Activation-stream tensor (block outputs, skips, RNA pyramid levels): fp32 CB8 in TM_DTYPE_F32; in the 16-bit modes
   // the SAME geometry with 16-bit elements (the TV's `p` then points at uint16_t data and `nstride` counts elements).
   TV tensor_s(int N, int C, int Z, int S) {
-    if (!is_h16(m->cfg.dtype)) return tensor(N, C, Z, S);
-    TV t;
-    t.N = N; t.C = C; t.Cb = (C + 7) / 8; t.Z = Z; t.H = S; t.W = S;
-    t.nstride = (long)t.Cb * t.plane();
-    t.p = alloc_f(((size_t)N * t.nstride + 1) / 2);
+    TV t = cb8_view(nullptr, N, C, Z, S, S);
+    t.p = alloc_f(h16() ? ((size_t)N * t.nstride + 1) / 2 : (size_t)N * t.nstride);
     return t;
   }
   void check(hipError_t e) { if (e != hipSuccess && err == hipSuccess) err = e; }
+  // A block-input / glue pass (launch_prep) of N output patches of Z x S x S, with what the context knows; per_image: output
+  // patches per image (the row of a per-image modulation)
+  PrepLaunch prep(int N, int Z, int S, int per_image = 1) const {
+    PrepLaunch P = prep_start(N, Z, S);
+    P.p1 = p1; P.p2 = p2; P.per_image = per_image; P.h_f16 = m->cfg.dtype == TM_DTYPE_F16;
+    return P;
+  }
+  // a stream tensor (tensor_s) as a source of P: fp32, or 16-bit in the 16-bit modes
+  void stream_src(PrepLaunch& P, const TV& t, bool collage = false) const {
+    if (h16()) prep_src(P, as_h(t), collage);
+    else prep_src(P, t, collage);
+  }
+  void run(const PrepLaunch& P) { if (!dry) check(launch_prep(P, s)); }
 };
 struct Src { TV t; bool collage; };
 
@@ -745,13 +739,11 @@ static void dump_tv(Ctx& cx, const std::string& name, const TV& t_in) {
   if (hipMalloc((void**)&dev, n * sizeof(float)) != hipSuccess) return;
   if (is_h16(cx.m->cfg.dtype)) {              // 16-bit stream tensor -> fp32 CB8 copy (prep kernel, no norm / act)
     if (hipMalloc((void**)&f32copy, (size_t)t.N * t.nstride * sizeof(float)) != hipSuccess) { (void)hipFree(dev); return; }
-    PrepLaunch P;
-    P.nsrc = 1;
-    P.src[0].p = t.p; P.src[0].nstride = t.nstride; P.src[0].Cb = t.Cb;
-    P.N = t.N; P.Z = t.Z; P.S = t.H; P.src_h = 1; P.h_f16 = cx.m->cfg.dtype == TM_DTYPE_F16;
-    P.out = f32copy; P.out_nstride = t.nstride;
-    if (launch_prep(P, cx.s) != hipSuccess) { (void)hipFree(dev); (void)hipFree(f32copy); return; }
+    PrepLaunch P = cx.prep(t.N, t.Z, t.H);
+    prep_src(P, as_h(t));
     t.p = f32copy;
+    prep_out(P, t);
+    if (launch_prep(P, cx.s) != hipSuccess) { (void)hipFree(dev); (void)hipFree(f32copy); return; }
   }
   std::vector<float> host(n);
   if (launch_from_cb8(t, dev, cx.s) == hipSuccess && hipStreamSynchronize(cx.s) == hipSuccess &&
@@ -763,90 +755,108 @@ static void dump_tv(Ctx& cx, const std::string& name, const TV& t_in) {
   if (f32copy) (void)hipFree(f32copy);
 }
 
-// fuse_rw (with y = the second conv's input A2): the fused mid-section of ResBlock *fuse_rw in this conv's epilogue
-static void run_conv(Ctx& cx, const TV& x, const ConvW& w, TV y, const TV* res, const TV* gate, int flags,
-                     int cin_real = 0, int zmode = ZM_PAD1, bool gate_half = false, bool res_half = false,
-                     const ResW* fuse_rw = nullptr, int per_image = 1) {
-  if (cx.dry) return;
+// ---- conv launches: the caller fills the launch struct by name, the runners add the dry-run rule, the error latch and the books ----
+static ConvLaunch conv(const TV& x, const ConvW& w, const TV& y) {
   ConvLaunch L;
-  L.x = x; L.w = w; L.y = y; L.res = res; L.gate = gate; L.flags = flags; L.zmode = zmode; L.gate_half = gate_half ? 1 : 0;
-  L.res_half = res_half ? 1 : 0;
-  tm_model* m = cx.m;
-  if (fuse_rw) {
-    L.fuse_norm = 1; L.a2 = y; L.norm_w = fuse_rw->n2; L.inv_c = 1.0f / (float)fuse_rw->cout; L.per_image = per_image;
-    L.mod_scale = cx.ss + fuse_rw->emb_off; L.mod_shift = cx.ss + fuse_rw->emb_off + fuse_rw->cout; L.mod_stride = m->emb_tot;
-  }
-  const bool prof = m->prof_on && (w.taps == 27 || w.form == CF_XPAIR || (m->z == 1 && w.taps == 9)) && zmode == ZM_PAD1;
-  if (prof) {
-    if (m->prof_used == m->prof_ev.size()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { cx.check(hipErrorOutOfMemory); return; }
-      m->prof_ev.emplace_back(a, b);
-    }
-    cx.check(hipEventRecord(m->prof_ev[m->prof_used].first, cx.s));
-  }
-  cx.check(launch_conv_mfma(L, cx.s));
-  if (prof) {
-    cx.check(hipEventRecord(m->prof_ev[m->prof_used].second, cx.s));
-    m->prof_used++;
-    const double vox = (double)x.N * x.Z * x.H * x.W;
-    m->prof_nominal += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
-    if (w.form == CF_XPAIR) m->prof_xp_flops += 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox;
-    m->prof_tag.push_back({cin_real ? cin_real : x.C, w.Cout, x.H, x.N, 2.0 * (cin_real ? cin_real : x.C) * w.Cout * 27.0 * vox});
-    m->prof_bytes += 4.0 * (vox * x.Cb * 8 + (double)w.ntile * w.Cbi * w.taps * 512 + vox * y.Cb * 8);
-  }
+  L.x = x; L.w = w; L.y = y;
+  return L;
+}
+// cw: the geometry and the bias of the 16-bit pack `w`.  y: fp32 output, or with out_h the geometry of the 16-bit one
+static ConvLaunchH conv_h(const TVH& x, const uint16_t* w, const ConvW& cw, const TV& y) {
+  ConvLaunchH L;
+  L.x = x; L.w = w; L.bias = cw.bias; L.Cout = cw.Cout; L.y = y;
+  return L;
+}
+static void out_h(ConvLaunchH& L, const TVH& o) { L.y_h = o.p; L.yh_nstride = o.nstride; }   // write 16-bit o instead of L.y
+// The fused mid-section of ResBlock w (out_layers' norm -> modulate -> SiLU) in the epilogue of its first conv, which then writes
+// a2, the second conv's input, instead of L.y
+template <class Launch, class A2>
+static void fuse_mid_section(Launch& L, const Ctx& cx, const ResW& w, int per_image, const A2& a2) {
+  L.fuse_norm = 1; L.a2 = a2; L.norm_w = w.n2; L.per_image = per_image;
+  L.mod_scale = cx.ss + w.emb_off; L.mod_shift = cx.ss + w.emb_off + w.cout; L.mod_stride = cx.m->emb_tot;
+  if constexpr (std::is_same<Launch, ConvLaunch>::value) L.inv_c = 1.0f / (float)w.cout;   // the 16-bit kernel knows its Cout
 }
 
-// y: geometry of the output; y16: `y.p` is a 16-bit stream tensor (written as such); res16: 16-bit stream residual
-static void run_conv_h(Ctx& cx, const TVH& x, const uint16_t* w, const ConvW& cw, TV y, const TV* res16, int cin_real,
-                       const TVH* fuse_a2 = nullptr, const ResW* rw = nullptr, int per_image = 1, bool y16 = false,
-                       bool count = true, bool ups = false, bool res_half = false) {
-  if (cx.dry) return;
-  ConvLaunchH L;
-  L.x = x; L.w = w; L.bias = cw.bias; L.Cout = cw.Cout; L.y = y; L.ups = ups ? 1 : 0; L.res_half = res_half ? 1 : 0;
-  TVH resh;
-  if (res16) { resh = as_h(*res16); L.res_h = &resh; }
-  if (y16) { L.y_h = (uint16_t*)y.p; L.yh_nstride = y.nstride; }
+// What one counted 3x3x3 launch adds to the books of tm_profile_collect
+struct ConvBook { int cin, cout, S, N; double vox, bytes; bool xpair; };
+// The profiling bracket of the 3x3x3 launchers: ensure an event pair, record, launch, record, book.  book == nullptr or
+// profiling off: the launch alone.
+template <class LaunchFn>
+static void launch_booked(Ctx& cx, const ConvBook* book, LaunchFn launch) {
   tm_model* m = cx.m;
-  if (fuse_a2) {
-    L.fuse_norm = 1; L.a2 = *fuse_a2; L.norm_w = rw->n2; L.per_image = per_image;
-    L.mod_scale = cx.ss + rw->emb_off; L.mod_shift = cx.ss + rw->emb_off + rw->cout; L.mod_stride = m->emb_tot;
+  if (!book || !m->prof_on) { cx.check(launch()); return; }
+  if (m->prof_used == m->prof_ev.size()) {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    for (int i = 0; i < 2; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) {
+        if (i) (void)hipEventDestroy(ev[0]);
+        cx.check(hipErrorOutOfMemory);
+        return;
+      }
+    m->prof_ev.emplace_back(ev[0], ev[1]);
   }
-  const bool prof = m->prof_on && count;    // count = false: not a ResBlock 3x3x3 conv (the in-plane pyramid convs: 9 real taps)
-  if (prof) {
-    if (m->prof_used == m->prof_ev.size()) {
-      hipEvent_t a, b;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { cx.check(hipErrorOutOfMemory); return; }
-      m->prof_ev.emplace_back(a, b);
-    }
-    cx.check(hipEventRecord(m->prof_ev[m->prof_used].first, cx.s));
-  }
-  cx.check(m->cfg.dtype == TM_DTYPE_F16 ? launch_conv27_f16(L, cx.s) : launch_conv27_bf16(L, cx.s));
-  if (prof) {
-    cx.check(hipEventRecord(m->prof_ev[m->prof_used].second, cx.s));
-    m->prof_used++;
-    const double vox = (double)x.N * x.Z * x.H * x.W;
-    m->prof_nominal += 2.0 * cin_real * cw.Cout * 27.0 * vox;
-    m->prof_tag.push_back({cin_real, cw.Cout, x.H, x.N, 2.0 * cin_real * cw.Cout * 27.0 * vox});
-    m->prof_bytes += 2.0 * vox * x.Cb * 8 + 2.0 * (double)conv_bf16_pack_elems(cw.Cout, cw.Cbi) +
-                     ((y16 || fuse_a2) ? 2.0 : 4.0) * vox * y.Cb * 8 + (res16 ? 2.0 * vox * y.Cb * 8 : 0.0);
-  }
+  cx.check(hipEventRecord(m->prof_ev[m->prof_used].first, cx.s));
+  cx.check(launch());
+  cx.check(hipEventRecord(m->prof_ev[m->prof_used].second, cx.s));
+  m->prof_used++;
+  const double nominal = 2.0 * book->cin * book->cout * 27.0 * book->vox;
+  m->prof_nominal += nominal;
+  if (book->xpair) m->prof_xp_flops += nominal;
+  m->prof_tag.push_back({book->cin, book->cout, book->S, book->N, nominal});
+  m->prof_bytes += book->bytes;
 }
 
-static void run_conv1_h(Ctx& cx, const TVH& x, const uint16_t* w, const ConvW& cw, TV y, const TV* res, const TV* gate,
-                        int flags, TVH* y_h = nullptr, const TVH* gate_h = nullptr, const TVH* res_h = nullptr,
-                        const std::vector<Src>* concat = nullptr, bool gate_half = false) {
+// fp32 conv (launch_conv_mfma: every form).  count_cin: the real input channels of a ResBlock 3x3x3 conv, which is counted; 0:
+// not counted (1x1 convs and Linears, the pyramid convs, down_z, the upsampled-input form)
+static void run_conv(Ctx& cx, const ConvLaunch& L, int count_cin = 0) {
   if (cx.dry) return;
-  ConvLaunchH L;
-  L.x = x; L.w = w; L.bias = cw.bias; L.Cout = cw.Cout; L.y = y; L.res = res; L.gate = gate; L.flags = flags;
-  L.gate_h = gate_h; L.res_h = res_h; L.gate_half = gate_half ? 1 : 0;
-  if (concat) {                       // x = th.cat(sources, 1) (+ to_collage) read in place; `x` carries the geometry only
-    L.nsrc = (int)concat->size();
-    for (int i = 0; i < L.nsrc; ++i) { L.xs[i] = as_h((*concat)[i].t); L.xs_collage[i] = (*concat)[i].collage ? 1 : 0; }
-    L.p1 = cx.p1; L.p2 = cx.p2;
-  }
-  if (y_h) { L.y_h = y_h->p; L.yh_nstride = y_h->nstride; }
+  const double vox = (double)L.x.N * L.x.Z * L.x.H * L.x.W;
+  const ConvBook book = {count_cin, L.w.Cout, L.x.H, L.x.N, vox,
+                         4.0 * (vox * L.x.Cb * 8 + (double)L.w.ntile * L.w.Cbi * L.w.taps * 512 + vox * L.y.Cb * 8), L.w.form == CF_XPAIR};
+  launch_booked(cx, count_cin ? &book : nullptr, [&] { return launch_conv_mfma(L, cx.s); });
+}
+// 16-bit 3x3x3 conv; cw: the ConvW behind L.w (pack size).  count_cin as above (0: the in-plane pyramid convs, 9 real taps, and
+// the upsampled-input form)
+static void run_conv27_h(Ctx& cx, const ConvLaunchH& L, const ConvW& cw, int count_cin) {
+  if (cx.dry) return;
+  const double vox = (double)L.x.N * L.x.Z * L.x.H * L.x.W;
+  const ConvBook book = {count_cin, cw.Cout, L.x.H, L.x.N, vox,
+                         2.0 * vox * L.x.Cb * 8 + 2.0 * (double)conv_bf16_pack_elems(cw.Cout, cw.Cbi) +
+                             ((L.y_h || L.fuse_norm) ? 2.0 : 4.0) * vox * L.y.Cb * 8 + (L.res_h ? 2.0 * vox * L.y.Cb * 8 : 0.0),
+                         false};
+  launch_booked(cx, count_cin ? &book : nullptr,
+                [&] { return cx.m->cfg.dtype == TM_DTYPE_F16 ? launch_conv27_f16(L, cx.s) : launch_conv27_bf16(L, cx.s); });
+}
+// 16-bit 1x1 conv / Linear
+static void run_conv1_h(Ctx& cx, const ConvLaunchH& L) {
+  if (cx.dry) return;
   cx.check(cx.m->cfg.dtype == TM_DTYPE_F16 ? launch_conv1_f16(L, cx.s) : launch_conv1_bf16(L, cx.s));
+}
+// x = th.cat(sources, 1) (+ to_collage) read in place by the 16-bit 1x1 conv; L.x then carries the geometry only
+static void concat_sources(ConvLaunchH& L, const Ctx& cx, const std::vector<Src>& src) {
+  L.nsrc = (int)src.size();
+  for (int i = 0; i < L.nsrc; ++i) { L.xs[i] = as_h(src[i].t); L.xs_collage[i] = src[i].collage ? 1 : 0; }
+  L.p1 = cx.p1; L.p2 = cx.p2;
+}
+
+// The block-input pass of ResBlock w: th.cat of the sources (+ to_collage), resampled by `mode`, in_layers' norm and SiLU; the
+// caller adds the outputs
+static PrepLaunch block_input(const Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, int Z, int S, int per_image, int mode) {
+  PrepLaunch P = cx.prep(N, Z, S, per_image);
+  for (const Src& sv : src) cx.stream_src(P, sv.t, sv.collage);
+  P.resample = mode; P.act = 1;
+  prep_norm(P, w.n1, w.cin);
+  return P;
+}
+// The mid-section pass of ResBlock w where it is not fused into the first conv: out_layers' norm, the per-image modulation and
+// SiLU from H1; the caller adds the output (the second conv's operand)
+static PrepLaunch mid_section(const Ctx& cx, const ResW& w, const TV& H1, int per_image) {
+  PrepLaunch P = cx.prep(H1.N, H1.Z, H1.H, per_image);
+  cx.stream_src(P, H1);
+  P.act = 1;
+  prep_norm(P, w.n2, w.cout);
+  prep_mod_image(P, cx.ss, w.emb_off, w.cout, cx.m->emb_tot);
+  return P;
 }
 
 // ResBlock._forward (model/MBAblocks.py:237-299) in the 16-bit modes: every tensor that crosses a block boundary (sources,
@@ -856,111 +866,88 @@ static void run_conv1_h(Ctx& cx, const TVH& x, const uint16_t* w, const ConvW& c
 static TV res_block_h16(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, int per_image, int S_out, int mode) {
   tm_model* m = cx.m;
   const int Z = m->z;
-  const int h_f16 = m->cfg.dtype == TM_DTYPE_F16;
   TV out = cx.tensor_s(N, w.cout, Z, S_out);
   const size_t mark = cx.top;
-  const int cbe = (w.cbi + 1) / 2 * 2;
-  static const bool no_ups = getenv("TM_CONV_UPS") && atoi(getenv("TM_CONV_UPS")) == 0;           // A/B timing only
-  if (mode == RS_UP2 && w.c1uh && !no_ups && src.size() == 1 && !src[0].collage && !w.has_skip && !(S_out & (S_out - 1)) &&
-      S_out >= 16) {
+  const int cbe = pair_cb(w.cbi);
+  const TV geom = cb8_view(nullptr, N, w.cout, Z, S_out, S_out);      // of the first conv's output where it goes to A2 directly
+  const TVH outh = as_h(out);
+  if (mode == RS_UP2 && w.c1uh && src.size() == 1 && !src[0].collage && !w.has_skip && !(S_out & (S_out - 1)) && S_out >= 16) {
     // ResBlock(up=True) (MBAblocks.py:254-261,297) without upsampling anything: norm + SiLU on the low-resolution x, the first
     // conv in its upsampled-input form (per-phase 2 x 2 in-plane weights: 8 instead of 18 taps), the second conv's epilogue
     // reads the residual Upsample(x) at (z, y >> 1, x >> 1) of x itself (see the fp32 twin in res_block)
     const int S_in = S_out / 2;
     TVH Al = cx.tensor_h(N, cbe, Z, S_in);
-    if (!cx.dry) {
-      PrepLaunch P;
-      P.nsrc = 1; P.src_h = 1; P.h_f16 = h_f16;
-      P.src[0].p = src[0].t.p; P.src[0].nstride = src[0].t.nstride; P.src[0].Cb = src[0].t.Cb;
-      P.N = N; P.Z = Z; P.S = S_in; P.norm_w = w.n1; P.inv_c = 1.0f / (float)w.cin; P.act = 1; P.per_image = per_image;
-      P.out_h = Al.p; P.out_h_nstride = Al.nstride; P.pad_blocks = Al.Cb - w.cbi;
-      cx.check(launch_prep(P, cx.s));
-    }
-    const bool fuse_up = w.cout == 128;
-    TVH A2u = cx.tensor_h(N, (w.cout / 8 + 1) / 2 * 2, Z, S_out);
-    TV geom_u; geom_u.N = N; geom_u.C = w.cout; geom_u.Cb = w.cout / 8; geom_u.Z = Z; geom_u.H = S_out; geom_u.W = S_out;
-    geom_u.nstride = (long)geom_u.Cb * geom_u.plane();
-    if (fuse_up) {
-      run_conv_h(cx, Al, w.c1uh, w.c1, geom_u, nullptr, w.cin, &A2u, &w, per_image, false, false, true);
+    PrepLaunch P = block_input(cx, w, src, N, Z, S_in, per_image, RS_SAME);
+    prep_out_h(P, Al, w.cbi);
+    cx.run(P);
+    TVH A2u = cx.tensor_h(N, pair_cb(w.cout / 8), Z, S_out);
+    ConvLaunchH L1 = conv_h(Al, w.c1uh, w.c1, geom);
+    L1.ups = 1;
+    if (w.cout == 128) {
+      fuse_mid_section(L1, cx, w, per_image, A2u);
+      run_conv27_h(cx, L1, w.c1, 0);
     } else {
       TV H1 = cx.tensor_s(N, w.cout, Z, S_out);
-      run_conv_h(cx, Al, w.c1uh, w.c1, H1, nullptr, w.cin, nullptr, nullptr, 1, true, false, true);
-      if (!cx.dry) {
-        PrepLaunch P;
-        P.nsrc = 1;
-        P.src[0].p = H1.p; P.src[0].nstride = H1.nstride; P.src[0].Cb = H1.Cb;
-        P.src_h = 1;
-        P.N = N; P.Z = Z; P.S = S_out;
-        P.norm_w = w.n2; P.inv_c = 1.0f / (float)w.cout; P.act = 1; P.per_image = per_image;
-        P.mod = MOD_IMAGE; P.mod_scale = cx.ss + w.emb_off; P.mod_shift = cx.ss + w.emb_off + w.cout;
-        P.mod_stride = m->emb_tot;
-        P.out_h = A2u.p; P.out_h_nstride = A2u.nstride; P.pad_blocks = A2u.Cb - w.cout / 8; P.h_f16 = h_f16;
-        cx.check(launch_prep(P, cx.s));
-      }
+      L1.y = H1;
+      out_h(L1, as_h(H1));
+      run_conv27_h(cx, L1, w.c1, 0);
+      PrepLaunch Q = mid_section(cx, w, H1, per_image);
+      prep_out_h(Q, A2u, w.cout / 8);
+      cx.run(Q);
     }
-    run_conv_h(cx, A2u, w.c2h, w.c2, out, &src[0].t, w.cout, nullptr, nullptr, 1, true, true, false, true);
+    const TVH xh = as_h(src[0].t);
+    ConvLaunchH L2 = conv_h(A2u, w.c2h, w.c2, out);
+    out_h(L2, outh);
+    L2.res_h = &xh; L2.res_half = 1;
+    run_conv27_h(cx, L2, w.c2, w.cout);
     cx.top = mark;
     return out;
   }
   TVH Ah = cx.tensor_h(N, cbe, Z, S_out), rawh;
   // The concatenated / re-tiled x (MBAblocks.py:252-258,297) is only materialised where it is the RESIDUAL of a block
   // without skip conv (the up / down blocks: resampled x); the skip conv reads the sources in place (conv1's concat input)
-  static const bool ab_raw = getenv("TM_AB_RAW") != nullptr;       // A/B switch: materialise the concat for the skip conv too
-  const bool need_raw = (ab_raw || !w.has_skip) && (w.has_skip || mode != RS_SAME || src.size() > 1 || src[0].collage);
+  const bool need_raw = !w.has_skip && (mode != RS_SAME || src.size() > 1 || src[0].collage);
   if (w.has_skip && mode != RS_SAME) { cx.check(hipErrorInvalidValue); return out; }    // never in this model family
   if (need_raw) rawh = cx.tensor_h(N, cbe, Z, S_out);
-  if (!cx.dry) {
-    PrepLaunch P;
-    P.nsrc = (int)src.size();
-    for (size_t i = 0; i < src.size(); ++i) {
-      P.src[i].p = src[i].t.p; P.src[i].nstride = src[i].t.nstride; P.src[i].Cb = src[i].t.Cb;
-      P.src[i].collage = src[i].collage ? 1 : 0;
-    }
-    P.src_h = 1; P.h_f16 = h_f16;
-    P.resample = mode; P.N = N; P.Z = Z; P.S = S_out; P.p1 = cx.p1; P.p2 = cx.p2;
-    P.norm_w = w.n1; P.inv_c = 1.0f / (float)w.cin; P.act = 1; P.per_image = per_image;
-    P.out_h = Ah.p; P.out_h_nstride = Ah.nstride; P.pad_blocks = Ah.Cb - w.cbi;
-    if (need_raw) { P.raw_h = rawh.p; P.raw_h_nstride = rawh.nstride; }
-    cx.check(launch_prep(P, cx.s));
-  }
-  // Cout in {64, 128}: one workgroup holds every cout of its voxels, so out_layers' norm -> modulate -> SiLU runs in the
-  // first conv's epilogue and writes the second conv's 16-bit input directly
-  const bool fuse_mid = w.cout == 64 || w.cout == 128;
-  TVH A2h = cx.tensor_h(N, (w.cout / 8 + 1) / 2 * 2, Z, S_out);
-  TV geom; geom.N = N; geom.C = w.cout; geom.Cb = w.cout / 8; geom.Z = Z; geom.H = S_out; geom.W = S_out;
-  geom.nstride = (long)geom.Cb * geom.plane();
-  if (fuse_mid) {
-    run_conv_h(cx, Ah, w.c1h, w.c1, geom, nullptr, w.cin, &A2h, &w, per_image);
+  PrepLaunch P = block_input(cx, w, src, N, Z, S_out, per_image, mode);
+  prep_out_h(P, Ah, w.cbi);
+  if (need_raw) prep_raw_h(P, rawh);
+  cx.run(P);
+  TVH A2h = cx.tensor_h(N, pair_cb(w.cout / 8), Z, S_out);
+  ConvLaunchH L1 = conv_h(Ah, w.c1h, w.c1, geom);
+  if (w.cout == 64 || w.cout == 128) {
+    // Cout in {64, 128}: one workgroup holds every cout of its voxels, so out_layers' norm -> modulate -> SiLU runs in the
+    // first conv's epilogue and writes the second conv's 16-bit input directly
+    fuse_mid_section(L1, cx, w, per_image, A2h);
+    run_conv27_h(cx, L1, w.c1, w.cin);
   } else {
     // Cout > 128 (several cout tiles per voxel): the conv output goes through a 16-bit tensor like every other conv
     // output of the 16-bit modes -- under the reference's autocast in_layers' Conv3d returns fp16 and out_layers'
     // LlamaRMSNorm takes its statistics from those half values (MBAblocks.py:21-43 casts the half input up)
     TV H1 = cx.tensor_s(N, w.cout, Z, S_out);
-    run_conv_h(cx, Ah, w.c1h, w.c1, H1, nullptr, w.cin, nullptr, nullptr, 1, true);
-    if (!cx.dry) {
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src[0].p = H1.p; P.src[0].nstride = H1.nstride; P.src[0].Cb = H1.Cb;
-      P.src_h = 1;
-      P.N = N; P.Z = Z; P.S = S_out;
-      P.norm_w = w.n2; P.inv_c = 1.0f / (float)w.cout; P.act = 1; P.per_image = per_image;
-      P.mod = MOD_IMAGE; P.mod_scale = cx.ss + w.emb_off; P.mod_shift = cx.ss + w.emb_off + w.cout;
-      P.mod_stride = m->emb_tot;
-      P.out_h = A2h.p; P.out_h_nstride = A2h.nstride; P.pad_blocks = A2h.Cb - w.cout / 8; P.h_f16 = h_f16;
-      cx.check(launch_prep(P, cx.s));
-    }
+    L1.y = H1;
+    out_h(L1, as_h(H1));
+    run_conv27_h(cx, L1, w.c1, w.cin);
+    PrepLaunch Q = mid_section(cx, w, H1, per_image);
+    prep_out_h(Q, A2h, w.cout / 8);
+    cx.run(Q);
   }
-  TV rawv = geom; rawv.p = (float*)rawh.p; rawv.nstride = rawh.nstride;   // the residual view of rawh (channels < cout only)
-  const TV* r = nullptr;
+  TVH resh = as_h(src[0].t);                           // the residual: a single plain source as it stands,
   if (w.has_skip) {
-    TVH outh = as_h(out), xg = Ah;                       // geometry + padded block count of the virtual concat
-    xg.p = nullptr;
-    if (ab_raw) run_conv1_h(cx, rawh, w.skiph, w.skip, out, nullptr, nullptr, 0, &outh);
-    else run_conv1_h(cx, xg, w.skiph, w.skip, out, nullptr, nullptr, 0, &outh, nullptr, nullptr, &src);
-    r = &out;
-  } else if (need_raw) r = &rawv;
-  else r = &src[0].t;
-  run_conv_h(cx, A2h, w.c2h, w.c2, out, r, w.cout, nullptr, nullptr, 1, true);
+    ConvLaunchH Ls = conv_h(Ah, w.skiph, w.skip, out); // (geometry + padded block count of the virtual concat)
+    Ls.x.p = nullptr;
+    concat_sources(Ls, cx, src);
+    out_h(Ls, outh);
+    run_conv1_h(cx, Ls);
+    resh = outh;                                       // the skip conv's output, in place,
+  } else if (need_raw) {
+    resh = as_h(geom);                                 // or rawh (channels < cout only)
+    resh.p = rawh.p; resh.nstride = rawh.nstride;
+  }
+  ConvLaunchH L2 = conv_h(A2h, w.c2h, w.c2, out);
+  out_h(L2, outh);
+  L2.res_h = &resh;
+  run_conv27_h(cx, L2, w.c2, w.cout);
   cx.top = mark;
   return out;
 }
@@ -969,12 +956,11 @@ static TV res_block_h16(Ctx& cx, const ResW& w, const std::vector<Src>& src, int
 static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, int per_image, int S_out, int mode,
                     TV* out_opt) {
   tm_model* m = cx.m;
-  if (is_h16(m->cfg.dtype)) return res_block_h16(cx, w, src, N, per_image, S_out, mode);
+  if (cx.h16()) return res_block_h16(cx, w, src, N, per_image, S_out, mode);
   const int Z = m->z;
   TV out = out_opt ? *out_opt : cx.tensor(N, w.cout, Z, S_out);
   const size_t mark = cx.top;
-  static const bool no_ups = getenv("TM_CONV_UPS") && atoi(getenv("TM_CONV_UPS")) == 0;           // A/B timing only
-  if (mode == RS_UP2 && w.c1u.w && !no_ups && src.size() == 1 && !src[0].collage && !w.has_skip && !(S_out & (S_out - 1))) {
+  if (mode == RS_UP2 && w.c1u.w && src.size() == 1 && !src[0].collage && !w.has_skip && !(S_out & (S_out - 1))) {
     // ResBlock(up=True) (MBAblocks.py:254-261,297): h = Upsample(x) feeds in_layers, x = Upsample(x) is the residual.  Nothing
     // is upsampled here: norm and SiLU act per voxel, so they run on the low-resolution x (a quarter of the bytes); the first
     // conv is the upsampled-input form (per-phase 2 x 2 in-plane weights: conv3d_zpair_ups, 12 tap-products per plane pair, or
@@ -982,79 +968,51 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
     // conv's epilogue reads the residual at (z, y >> 1, x >> 1) of x itself.
     const int S_in = S_out / 2;
     TV A = cx.tensor(N, w.cbi * 8, Z, S_in);
-    if (!cx.dry) {
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src[0].p = src[0].t.p; P.src[0].nstride = src[0].t.nstride; P.src[0].Cb = src[0].t.Cb;
-      P.N = N; P.Z = Z; P.S = S_in; P.norm_w = w.n1; P.inv_c = 1.0f / (float)w.cin; P.act = 1; P.per_image = per_image;
-      P.out = A.p; P.out_nstride = A.nstride;
-      cx.check(launch_prep(P, cx.s));
-    }
+    PrepLaunch P = block_input(cx, w, src, N, Z, S_in, per_image, RS_SAME);
+    prep_out(P, A);
+    cx.run(P);
     TV A2 = cx.tensor(N, w.cout, Z, S_out), H1 = cx.tensor(N, w.cout, Z, S_out);
-    run_conv(cx, A, w.c1u, H1, nullptr, nullptr, 0, w.cin, ZM_UPS);
-    if (!cx.dry) {
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src[0].p = H1.p; P.src[0].nstride = H1.nstride; P.src[0].Cb = H1.Cb;
-      P.N = N; P.Z = Z; P.S = S_out;
-      P.norm_w = w.n2; P.inv_c = 1.0f / (float)w.cout; P.act = 1; P.per_image = per_image;
-      P.mod = MOD_IMAGE; P.mod_scale = cx.ss + w.emb_off; P.mod_shift = cx.ss + w.emb_off + w.cout;
-      P.mod_stride = m->emb_tot;
-      P.out = A2.p; P.out_nstride = A2.nstride;
-      cx.check(launch_prep(P, cx.s));
-    }
-    run_conv(cx, A2, w.c2, out, &src[0].t, nullptr, 0, 0, ZM_PAD1, false, true);
+    ConvLaunch L1 = conv(A, w.c1u, H1);
+    L1.zmode = ZM_UPS;
+    run_conv(cx, L1);
+    PrepLaunch Q = mid_section(cx, w, H1, per_image);
+    prep_out(Q, A2);
+    cx.run(Q);
+    ConvLaunch L2 = conv(A2, w.c2, out);
+    L2.res = &src[0].t; L2.res_half = 1;
+    run_conv(cx, L2, w.cout);
     cx.top = mark;
     return out;
   }
   int cin_pad = w.cbi * 8;
-  TV A = cx.tensor(N, cin_pad, Z, S_out), raw, H1, A2;
+  TV A = cx.tensor(N, cin_pad, Z, S_out), raw;
   // the residual / skip-conv input is the CONCATENATED (and resampled) x, MBAblocks.py:252-258,297:
   // it equals a stored tensor only for a single plain source
   const bool need_raw = w.has_skip || mode != RS_SAME || src.size() > 1 || src[0].collage;
   if (need_raw) raw = cx.tensor(N, cin_pad, Z, S_out);
-  if (!cx.dry) {
-    PrepLaunch P;
-    P.nsrc = (int)src.size();
-    for (size_t i = 0; i < src.size(); ++i) {
-      P.src[i].p = src[i].t.p; P.src[i].nstride = src[i].t.nstride; P.src[i].Cb = src[i].t.Cb;
-      P.src[i].collage = src[i].collage ? 1 : 0;
-    }
-    P.resample = mode; P.N = N; P.Z = Z; P.S = S_out; P.p1 = cx.p1; P.p2 = cx.p2;
-    P.norm_w = w.n1; P.inv_c = 1.0f / (float)w.cin; P.act = 1; P.per_image = per_image;
-    P.out = A.p; P.out_nstride = A.nstride;
-    if (need_raw) { P.raw = raw.p; P.raw_nstride = raw.nstride; }
-    cx.check(launch_prep(P, cx.s));
-  }
-  A2 = cx.tensor(N, w.cout, Z, S_out);
+  PrepLaunch P = block_input(cx, w, src, N, Z, S_out, per_image, mode);
+  prep_out(P, A);
+  if (need_raw) prep_raw(P, raw);
+  cx.run(P);
+  TV A2 = cx.tensor(N, w.cout, Z, S_out);
+  ConvLaunch L1 = conv(A, w.c1, A2);
   // 64 output channels in the pair form's 128-voxel tile: a wave holds every channel of its voxels, so out_layers' norm ->
   // modulate -> SiLU runs in c1's epilogue and H1 is never written (nor allocated: the dry pass takes the same branch)
-  const bool fuse_mid = w.fuse_mid && Z == 2 && conv_tile(CF_PAIR, (long)N * Z * S_out * S_out, 1, S_out, 0) == 2;
-  if (fuse_mid) {
-    run_conv(cx, A, w.c1, A2, nullptr, nullptr, 0, w.cin, ZM_PAD1, false, false, &w, per_image);
+  if (w.fuse_mid && Z == 2 && conv_tile(CF_PAIR, (long)N * Z * S_out * S_out, 1, S_out, 0) == 2) {
+    fuse_mid_section(L1, cx, w, per_image, A2);
+    run_conv(cx, L1, w.cin);
   } else {
-    H1 = cx.tensor(N, w.cout, Z, S_out);
-    run_conv(cx, A, w.c1, H1, nullptr, nullptr, 0, w.cin);
+    TV H1 = cx.tensor(N, w.cout, Z, S_out);
+    L1.y = H1;
+    run_conv(cx, L1, w.cin);
+    PrepLaunch Q = mid_section(cx, w, H1, per_image);
+    prep_out(Q, A2);
+    cx.run(Q);
   }
-  if (!cx.dry && !fuse_mid) {
-    PrepLaunch P;
-    P.nsrc = 1;
-    P.src[0].p = H1.p; P.src[0].nstride = H1.nstride; P.src[0].Cb = H1.Cb;
-    P.N = N; P.Z = Z; P.S = S_out;
-    P.norm_w = w.n2; P.inv_c = 1.0f / (float)w.cout; P.act = 1; P.per_image = per_image;
-    P.mod = MOD_IMAGE; P.mod_scale = cx.ss + w.emb_off; P.mod_shift = cx.ss + w.emb_off + w.cout;
-    P.mod_stride = m->emb_tot;
-    P.out = A2.p; P.out_nstride = A2.nstride;
-    cx.check(launch_prep(P, cx.s));
-  }
-  if (w.has_skip) {
-    run_conv(cx, raw, w.skip, out, nullptr, nullptr, 0);
-    run_conv(cx, A2, w.c2, out, &out, nullptr, 0);
-  } else if (need_raw) {
-    run_conv(cx, A2, w.c2, out, &raw, nullptr, 0);
-  } else {
-    run_conv(cx, A2, w.c2, out, &src[0].t, nullptr, 0);
-  }
+  if (w.has_skip) run_conv(cx, conv(raw, w.skip, out));
+  ConvLaunch L2 = conv(A2, w.c2, out);
+  L2.res = w.has_skip ? &out : (need_raw ? &raw : &src[0].t);
+  run_conv(cx, L2, w.cout);
   cx.top = mark;
   return out;
 }
@@ -1111,57 +1069,37 @@ static void attn_cond_run(Ctx& cx, const AttnW& w, const AttnCond& A, int N, int
                           const TV* cond_act) {
   const size_t mark = cx.top;
   const AttnGeom g = attn_geom(cx.m, w, Z, S);
-  const bool half = g.half;
   const int C = w.C, cb = C / 8, Sc = g.Sc;
-  if (is_h16(cx.m->cfg.dtype)) {
+  // SiLU(cond), through the collage remap and at half resolution where the geometry says so
+  PrepLaunch P = cx.prep(N, Z, Sc, per_image);
+  cx.stream_src(P, cond.t, cond.collage);
+  P.resample = g.half ? RS_PICK2 : RS_SAME; P.act = 1;
+  if (cx.h16()) {
     // bf16 operands for every Linear (fp32 accumulate).  Activations that only feed a Linear, and the 7C modulation tensor
     // (shift/scale/gate/cross-cond chunks), are produced directly in bf16: the cross-cond chunk is the kv Linear's input as
     // it stands.
-    const int h_f16 = cx.m->cfg.dtype == TM_DTYPE_F16;
-    const int gbe = ((w.G + 7) / 8 + 1) / 2 * 2;
-    const long cplane = (long)Z * Sc * Sc * 8;                     // elements per channel block on the conditioning side
-    TVH cact = cx.tensor_h(N, gbe, Z, Sc);
-    if (!cx.dry) {
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src_h = 1;
-      P.src[0].p = cond.t.p; P.src[0].nstride = cond.t.nstride; P.src[0].Cb = cond.t.Cb; P.src[0].collage = cond.collage ? 1 : 0;
-      P.N = N; P.Z = Z; P.S = Sc; P.p1 = cx.p1; P.p2 = cx.p2; P.act = 1; P.per_image = per_image;
-      P.resample = half ? RS_PICK2 : RS_SAME;
-      P.inv_c = 1.0f / (float)w.G;
-      P.out_h = cact.p; P.out_h_nstride = cact.nstride; P.pad_blocks = cact.Cb - cond.t.Cb; P.h_f16 = h_f16;
-      cx.check(launch_prep(P, cx.s));
+    TVH cact = cx.tensor_h(N, pair_cb((w.G + 7) / 8), Z, Sc);
+    prep_out_h(P, cact, cond.t.Cb);
+    cx.run(P);
+    ConvLaunchH La = conv_h(cact, w.adah, w.ada, cb8_view(nullptr, N, 7 * C, Z, Sc, Sc));
+    out_h(La, A.mod_h);
+    run_conv1_h(cx, La);
+    ConvLaunchH Lk = conv_h(A.mod_h.blocks(3 * cb, cb), w.kvh, w.kv, A.kv);
+    if (g.mfma_core) {                                   // k, v leave their Linear as 16-bit (the attention core's MFMA operands)
+      Lk.y = cb8_view(nullptr, N, 2 * C, Z, Sc, Sc);
+      out_h(Lk, A.kv_h);
     }
-    TV geom;
-    geom.N = N; geom.Z = Z; geom.H = Sc; geom.W = Sc;
-    TV mod_geom = geom; mod_geom.Cb = 7 * cb; mod_geom.C = 7 * C; mod_geom.nstride = (long)7 * cb * cplane;
-    TVH mod = A.mod_h;
-    run_conv1_h(cx, cact, w.adah, w.ada, mod_geom, nullptr, nullptr, 0, &mod);
-    const TVH crs = A.mod_h.blocks(3 * cb, cb);
-    if (g.mfma_core) {
-      // k, v leave their Linear as 16-bit (the attention core's MFMA operands)
-      TV kv_geom = geom; kv_geom.Cb = 2 * cb; kv_geom.C = 2 * C; kv_geom.nstride = (long)2 * cb * cplane;
-      TVH kv = A.kv_h;
-      run_conv1_h(cx, crs, w.kvh, w.kv, kv_geom, nullptr, nullptr, 0, &kv);
-    } else {
-      run_conv1_h(cx, crs, w.kvh, w.kv, A.kv, nullptr, nullptr, 0);
-    }
+    run_conv1_h(cx, Lk);
     cx.top = mark;
     return;
   }
-  TV cact = (cond_act && !half) ? *cond_act : cx.tensor(N, (w.G + 7) / 8 * 8, Z, Sc);
-  if (!cx.dry && (half || !cond_act)) {
-    PrepLaunch P;
-    P.nsrc = 1;
-    P.src[0].p = cond.t.p; P.src[0].nstride = cond.t.nstride; P.src[0].Cb = cond.t.Cb;
-    P.src[0].collage = cond.collage ? 1 : 0;
-    P.resample = half ? RS_PICK2 : RS_SAME;
-    P.N = N; P.Z = Z; P.S = Sc; P.p1 = cx.p1; P.p2 = cx.p2; P.act = 1; P.per_image = per_image;
-    P.out = cact.p; P.out_nstride = cact.nstride;
-    cx.check(launch_prep(P, cx.s));
+  TV cact = (cond_act && !g.half) ? *cond_act : cx.tensor(N, (w.G + 7) / 8 * 8, Z, Sc);
+  if (g.half || !cond_act) {
+    prep_out(P, cact);
+    cx.run(P);
   }
-  run_conv(cx, cact, w.ada, A.mod, nullptr, nullptr, 0);
-  run_conv(cx, A.mod.blocks(3 * cb, cb), w.kv, A.kv, nullptr, nullptr, 0);
+  run_conv(cx, conv(cact, w.ada, A.mod));
+  run_conv(cx, conv(A.mod.blocks(3 * cb, cb), w.kv, A.kv));
   cx.top = mark;
 }
 
@@ -1179,54 +1117,59 @@ static void attn_block(Ctx& cx, const AttnW& w, TV x, const Src& cond, int per_i
     attn_cond_run(cx, w, loc, N, Z, S, cond, per_image, cond_act);
     pre = &loc;
   }
-  if (is_h16(cx.m->cfg.dtype)) {
-    const int h_f16 = cx.m->cfg.dtype == TM_DTYPE_F16;
+  if (cx.h16()) {
+    const bool f16 = cx.m->cfg.dtype == TM_DTYPE_F16;
     // The residual stream x, q/k/v and the softmax stay fp32; the Linears take 16-bit operands (see attn_cond_run).
-    // src16: the source is a 16-bit stream tensor (x); otherwise an fp32 scratch tensor
-    auto prep_h = [&](const float* p, long ns, int Cbs, const float* nw, const TVH* sc, const TVH* sh, TVH dst, int Creal,
-                      bool src16 = true) {
-      if (cx.dry) return;
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src_h = src16 ? 1 : 0;
-      P.src[0].p = p; P.src[0].nstride = ns; P.src[0].Cb = Cbs;
-      P.N = N; P.Z = Z; P.S = S; P.p1 = cx.p1; P.p2 = cx.p2; P.per_image = per_image;
-      P.norm_w = nw; P.inv_c = 1.0f / (float)Creal;
-      if (sc) { P.mod = MOD_VOXEL; P.mod_scale_h = sc->p; P.mod_shift_h = sh->p; P.mod_stride = sc->nstride; P.mod_half = half ? 1 : 0; }
-      P.out_h = dst.p; P.out_h_nstride = dst.nstride; P.pad_blocks = dst.Cb - Cbs; P.h_f16 = h_f16;
-      cx.check(launch_prep(P, cx.s));
-    };
     const TVH mod = pre->mod_h;
     // chunk order (MBAblocks.py:487): shift_msa, scale_msa, gate_msa, crss_cnd, shift_mlp, scale_mlp, gate_mlp
     TVH sh_a = mod.blocks(0 * cb, cb), sc_a = mod.blocks(1 * cb, cb), g_a = mod.blocks(2 * cb, cb);
     TVH sh_m = mod.blocks(4 * cb, cb), sc_m = mod.blocks(5 * cb, cb), g_m = mod.blocks(6 * cb, cb);
     TVH xa = cx.tensor_h(N, cb, Z, S), oh = cx.tensor_h(N, cb, Z, S);
-    prep_h(x.p, x.nstride, x.Cb, w.n1, &sc_a, &sh_a, xa, C);
+    auto modulate = [&](const float* nw, const TVH& sc, const TVH& sh) {      // xa <- norm(x) (1 + scale) + shift
+      PrepLaunch P = cx.prep(N, Z, S, per_image);
+      prep_src(P, as_h(x));
+      prep_norm(P, nw, C);
+      prep_mod_voxel(P, sc, sh, half);
+      prep_out_h(P, xa, x.Cb);
+      cx.run(P);
+    };
+    modulate(w.n1, sc_a, sh_a);
     if (g.mfma_core) {
       // q leaves its Linear as 16-bit like k, v (the attention core's MFMA operands); softmax and accumulation are fp32
       TVH q = cx.tensor_h(N, cb, Z, S);
       const TVH kv = pre->kv_h;
-      TV q_geom = x; q_geom.p = nullptr;
-      q_geom.nstride = (long)cb * x.plane();
-      run_conv1_h(cx, xa, w.qh, w.q, q_geom, nullptr, nullptr, 0, &q);
-      if (!cx.dry) cx.check((h_f16 ? launch_window_attn_f16 : launch_window_attn_bf16)(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, oh, cx.s));
+      ConvLaunchH Lq = conv_h(xa, w.qh, w.q, cb8_view(nullptr, N, C, Z, S, S));
+      out_h(Lq, q);
+      run_conv1_h(cx, Lq);
+      if (!cx.dry) cx.check((f16 ? launch_window_attn_f16 : launch_window_attn_bf16)(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, oh, cx.s));
     } else {
       // other window sizes (z_size 1 / 4 / 8, patch_size 128): fp32 q / k / v into the generic fp32 attention core, its
       // output rounded to the 16-bit type for proj
       TV q = cx.tensor(N, C, Z, S), o = cx.tensor(N, C, Z, S);
       const TV kv = pre->kv;
-      run_conv1_h(cx, xa, w.qh, w.q, q, nullptr, nullptr, 0);
+      run_conv1_h(cx, conv_h(xa, w.qh, w.q, q));
       if (!cx.dry) cx.check(launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, o, cx.s));
-      prep_h(o.p, o.nstride, o.Cb, nullptr, nullptr, nullptr, oh, C, false);
+      PrepLaunch P = cx.prep(N, Z, S, per_image);
+      prep_src(P, o);
+      prep_out_h(P, oh, o.Cb);
+      cx.run(P);
     }
     // x <- x + gate * Linear(.): the 16-bit stream tensor is updated in place (each element is read and written by one lane)
-    TVH xh = as_h(x);
-    run_conv1_h(cx, oh, w.projh, w.proj, x, nullptr, nullptr, 0, &xh, &g_a, &xh, nullptr, half);
-    prep_h(x.p, x.nstride, x.Cb, w.n2, &sc_m, &sh_m, xa, C);
+    const TVH xh = as_h(x);
+    auto gated = [&](const TVH& in, const uint16_t* wh, const ConvW& cw, const TVH& gate) {
+      ConvLaunchH L = conv_h(in, wh, cw, x);
+      out_h(L, xh);
+      L.res_h = &xh; L.gate_h = &gate; L.gate_half = half ? 1 : 0;
+      run_conv1_h(cx, L);
+    };
+    gated(oh, w.projh, w.proj, g_a);
+    modulate(w.n2, sc_m, sh_m);
     TVH h1 = cx.tensor_h(N, 4 * cb, Z, S);
-    TV h1_geom = x; h1_geom.Cb = 4 * cb; h1_geom.C = 4 * C; h1_geom.p = nullptr; h1_geom.nstride = (long)4 * cb * x.plane();
-    run_conv1_h(cx, xa, w.fc1h, w.fc1, h1_geom, nullptr, nullptr, EPI_GELU, &h1);
-    run_conv1_h(cx, h1, w.fc2h, w.fc2, x, nullptr, nullptr, 0, &xh, &g_m, &xh, nullptr, half);
+    ConvLaunchH L1 = conv_h(xa, w.fc1h, w.fc1, cb8_view(nullptr, N, 4 * C, Z, S, S));
+    L1.flags = EPI_GELU;
+    out_h(L1, h1);
+    run_conv1_h(cx, L1);
+    gated(h1, w.fc2h, w.fc2, g_m);
     cx.top = mark;
     return;
   }
@@ -1236,25 +1179,30 @@ static void attn_block(Ctx& cx, const AttnW& w, TV x, const Src& cond, int per_i
   TV sh_a = mod.blocks(0 * cb, cb), sc_a = mod.blocks(1 * cb, cb), g_a = mod.blocks(2 * cb, cb);
   TV sh_m = mod.blocks(4 * cb, cb), sc_m = mod.blocks(5 * cb, cb), g_m = mod.blocks(6 * cb, cb);
   TV xa = cx.tensor(N, C, Z, S);
-  auto modulate = [&](const float* nw, const TV& sc, const TV& sh, TV dst) {
-    if (cx.dry) return;
-    PrepLaunch P;
-    P.nsrc = 1;
-    P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
-    P.N = N; P.Z = Z; P.S = S; P.norm_w = nw; P.inv_c = 1.0f / (float)C; P.per_image = per_image;
-    P.mod = MOD_VOXEL; P.mod_scale = sc.p; P.mod_shift = sh.p; P.mod_stride = mod.nstride; P.mod_half = half ? 1 : 0;
-    P.out = dst.p; P.out_nstride = dst.nstride;
-    cx.check(launch_prep(P, cx.s));
+  auto modulate = [&](const float* nw, const TV& sc, const TV& sh) {          // xa <- norm(x) (1 + scale) + shift
+    PrepLaunch P = cx.prep(N, Z, S, per_image);
+    prep_src(P, x);
+    prep_norm(P, nw, C);
+    prep_mod_voxel(P, sc, sh, half);
+    prep_out(P, xa);
+    cx.run(P);
   };
-  modulate(w.n1, sc_a, sh_a, xa);
+  auto gated = [&](const TV& in, const ConvW& cw, const TV& gate) {          // x <- x + gate * Linear(in)
+    ConvLaunch L = conv(in, cw, x);
+    L.res = &x; L.gate = &gate; L.gate_half = half ? 1 : 0;
+    run_conv(cx, L);
+  };
+  modulate(w.n1, sc_a, sh_a);
   TV q = cx.tensor(N, C, Z, S), o = cx.tensor(N, C, Z, S);
-  run_conv(cx, xa, w.q, q, nullptr, nullptr, 0);
+  run_conv(cx, conv(xa, w.q, q));
   if (!cx.dry) cx.check(launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), w.qn, w.kn, o, cx.s));
-  run_conv(cx, o, w.proj, x, &x, &g_a, 0, 0, ZM_PAD1, half);
-  modulate(w.n2, sc_m, sh_m, xa);
+  gated(o, w.proj, g_a);
+  modulate(w.n2, sc_m, sh_m);
   TV h1 = cx.tensor(N, 4 * C, Z, S);
-  run_conv(cx, xa, w.fc1, h1, nullptr, nullptr, EPI_GELU);
-  run_conv(cx, h1, w.fc2, x, &x, &g_m, 0, 0, ZM_PAD1, half);
+  ConvLaunch L1 = conv(xa, w.fc1, h1);
+  L1.flags = EPI_GELU;
+  run_conv(cx, L1);
+  gated(h1, w.fc2, g_m);
   cx.top = mark;
 }
 
@@ -1287,7 +1235,7 @@ static void rna_stage(Ctx& cx, const float* rna, RnaOut& R, const void* l0_in = 
   tm_model* m = cx.m;
   const tm_config& c = m->cfg;
   const int Z = m->z, Ne = cx.Ne;
-  const bool h16 = is_h16(c.dtype), run = !cx.dry && (rna != nullptr || l0_in != nullptr);
+  const bool h16 = cx.h16(), run = !cx.dry && (rna != nullptr || l0_in != nullptr);
   const bool head = l0_in == nullptr;                            // gene attention + down_z run in this call
   int S = m->gn * 2;
   for (int i = 0; i < 4; ++i) { R.rl[i] = cx.tensor_s(Ne, m->rw[i], Z, S); S *= 2; }
@@ -1312,70 +1260,64 @@ static void rna_stage(Ctx& cx, const float* rna, RnaOut& R, const void* l0_in = 
   }
   const bool was_dry = cx.dry;
   cx.dry = !run;
+  auto down_z = [&](const TV& y) {                               // down_z + Upsample into fp32 y
+    if (m->downz_mfma) {
+      ConvLaunch L = conv(tok, m->downz, y);
+      L.flags = EPI_UP2; L.zmode = ZM_VALID;
+      run_conv(cx, L);
+    } else {
+      // generic (kz, gn): direct conv straight from / to the CB8 tensors, nearest x2 fused into the store
+      const Acc5 ax = acc_cb8(tok), ay = acc_cb8(y);
+      if (run) cx.check(hipMemsetAsync(y.p, 0, (size_t)Ne * y.nstride * sizeof(float), cx.s));           // pad channels
+      run_direct(cx, m->downz_d, tok.p, ax, y.p, ay, Ne, c.rna_slc, Z, m->gn, 0, 0, 1);
+    }
+  };
   if (h16) {
     // 16-bit modes: gene attention and down_z stay fp32 (they read the fp32 gene counts; < 0.3 % of the FLOPs), level 0
     // enters the 16-bit stream behind down_z, and the three SiLU -> Conv3d(1,3,3) -> Upsample stages
     // (model/unet_ours.py:290-295) run as 16-bit convs like every other conv under the reference's autocast: the in-plane
     // conv is the 3x3x3 kernel on weights whose z - 1 / z + 1 slices are zero, its output leaves at the conv's resolution
     // and ONE pass of the block-input kernel writes both the x2 level (raw copy) and SiLU of it (the next conv's input).
-    const int h_f16 = c.dtype == TM_DTYPE_F16;
     int S0 = m->gn * 2;
     TV rl0 = cx.tensor(Ne, m->rw[0], Z, S0);
     if (head) {
-      if (m->downz_mfma) run_conv(cx, tok, m->downz, rl0, nullptr, nullptr, EPI_UP2, 0, ZM_VALID);      // down_z + Upsample
-      else {
-        const Acc5 ax = acc_cb8(tok), ay = acc_cb8(rl0);
-        if (run) cx.check(hipMemsetAsync(rl0.p, 0, (size_t)Ne * rl0.nstride * sizeof(float), cx.s));     // pad channels
-        run_direct(cx, m->downz_d, tok.p, ax, rl0.p, ay, Ne, c.rna_slc, Z, m->gn, 0, 0, 1);
-      }
-      if (run) {
-        PrepLaunch P;                                              // fp32 level 0 -> the 16-bit stream tensor
-        P.nsrc = 1;
-        P.src[0].p = rl0.p; P.src[0].nstride = rl0.nstride; P.src[0].Cb = rl0.Cb;
-        P.N = Ne; P.Z = Z; P.S = S0; P.h_f16 = h_f16;
-        P.out_h = (uint16_t*)R.rl[0].p; P.out_h_nstride = R.rl[0].nstride;
-        cx.check(launch_prep(P, cx.s));
-      }
+      down_z(rl0);
+      PrepLaunch P = cx.prep(Ne, Z, S0);                           // fp32 level 0 -> the 16-bit stream tensor
+      prep_src(P, rl0);
+      prep_out_h(P, as_h(R.rl[0]), rl0.Cb);
+      cx.run(P);
     }
     if (l0_out) { cx.dry = was_dry; cx.top = rna_mark; return; }
-    const int cbe0 = (rl0.Cb + 1) / 2 * 2;
-    TVH act = cx.tensor_h(Ne, cbe0, Z, S0);                        // SiLU(level) = the conv input (even block count)
-    if (run) {
-      PrepLaunch Q;                                                // SiLU of it, pair-padded
-      Q.nsrc = 1; Q.src_h = 1; Q.h_f16 = h_f16;
-      Q.src[0].p = R.rl[0].p; Q.src[0].nstride = R.rl[0].nstride; Q.src[0].Cb = R.rl[0].Cb;
-      Q.N = Ne; Q.Z = Z; Q.S = S0; Q.act = 1;
-      Q.out_h = act.p; Q.out_h_nstride = act.nstride; Q.pad_blocks = act.Cb - R.rl[0].Cb;
-      cx.check(launch_prep(Q, cx.s));
-    }
+    auto silu_pair = [&](const TV& lvl, int Sl, const TVH& dst) {  // SiLU(level), pair-padded: the next conv's input
+      PrepLaunch Q = cx.prep(Ne, Z, Sl);
+      prep_src(Q, as_h(lvl));
+      Q.act = 1;
+      prep_out_h(Q, dst, lvl.Cb);
+      cx.run(Q);
+    };
+    TVH act = cx.tensor_h(Ne, pair_cb(rl0.Cb), Z, S0);
+    silu_pair(R.rl[0], S0, act);
     int S = S0;
     for (int i = 1; i < 4; ++i) {
       TV y = cx.tensor_s(Ne, m->rw[i], Z, S);                      // conv output at the conv's resolution (16-bit)
-      run_conv_h(cx, act, m->pyrh[i - 1], m->pyr16[i - 1], y, nullptr, m->rw[i - 1], nullptr, nullptr, 1, true, false);
+      ConvLaunchH L = conv_h(act, m->pyrh[i - 1], m->pyr16[i - 1], y);
+      out_h(L, as_h(y));
+      run_conv27_h(cx, L, m->pyr16[i - 1], 0);
       S *= 2;
       TVH nxt;
-      if (i < 3) nxt = cx.tensor_h(Ne, (R.rl[i].Cb + 1) / 2 * 2, Z, S);
-      if (run) {
-        PrepLaunch U;                                              // Upsample: level i (raw) and SiLU(level i)
-        U.nsrc = 1; U.src_h = 1; U.h_f16 = h_f16; U.resample = RS_UP2;
-        U.src[0].p = y.p; U.src[0].nstride = y.nstride; U.src[0].Cb = y.Cb;
-        U.N = Ne; U.Z = Z; U.S = S;
-        if (i < 3 && nxt.Cb == R.rl[i].Cb) {
-          U.act = 1; U.out_h = nxt.p; U.out_h_nstride = nxt.nstride;
-          U.raw_h = (uint16_t*)R.rl[i].p; U.raw_h_nstride = R.rl[i].nstride;
-          cx.check(launch_prep(U, cx.s));
-        } else {
-          U.out_h = (uint16_t*)R.rl[i].p; U.out_h_nstride = R.rl[i].nstride;
-          cx.check(launch_prep(U, cx.s));
-          if (i < 3) {                                             // odd block count: the pair-padded SiLU copy on its own
-            PrepLaunch Q;
-            Q.nsrc = 1; Q.src_h = 1; Q.h_f16 = h_f16;
-            Q.src[0].p = R.rl[i].p; Q.src[0].nstride = R.rl[i].nstride; Q.src[0].Cb = R.rl[i].Cb;
-            Q.N = Ne; Q.Z = Z; Q.S = S; Q.act = 1;
-            Q.out_h = nxt.p; Q.out_h_nstride = nxt.nstride; Q.pad_blocks = nxt.Cb - R.rl[i].Cb;
-            cx.check(launch_prep(Q, cx.s));
-          }
-        }
+      if (i < 3) nxt = cx.tensor_h(Ne, pair_cb(R.rl[i].Cb), Z, S);
+      PrepLaunch U = cx.prep(Ne, Z, S);                            // Upsample: level i (raw) and SiLU(level i)
+      prep_src(U, as_h(y));
+      U.resample = RS_UP2;
+      if (i < 3 && nxt.Cb == R.rl[i].Cb) {
+        U.act = 1;
+        prep_out_h(U, nxt, y.Cb);
+        prep_raw_h(U, as_h(R.rl[i]));
+        cx.run(U);
+      } else {
+        prep_out_h(U, as_h(R.rl[i]), y.Cb);
+        cx.run(U);
+        if (i < 3) silu_pair(R.rl[i], S, nxt);                     // odd block count: the pair-padded SiLU copy on its own
       }
       act = nxt;
     }
@@ -1385,26 +1327,17 @@ static void rna_stage(Ctx& cx, const float* rna, RnaOut& R, const void* l0_in = 
   }
   TV* rl = R.rl;
   TV* rs = R.rs;
-  if (head) {
-    if (m->downz_mfma) run_conv(cx, tok, m->downz, rl[0], nullptr, nullptr, EPI_UP2, 0, ZM_VALID);      // down_z + Upsample
-    else {
-      // generic (kz, gn): direct conv straight from / to the CB8 tensors, nearest x2 fused into the store
-      const Acc5 ax = acc_cb8(tok), ay = acc_cb8(rl[0]);
-      if (run) cx.check(hipMemsetAsync(rl[0].p, 0, (size_t)Ne * rl[0].nstride * sizeof(float), cx.s));   // pad channels
-      run_direct(cx, m->downz_d, tok.p, ax, rl[0].p, ay, Ne, c.rna_slc, Z, m->gn, 0, 0, 1);
-    }
-  }
+  if (head) down_z(rl[0]);
   if (l0_out) { cx.dry = was_dry; cx.top = rna_mark; return; }
   for (int i = 1; i < 4; ++i) {
-    if (run) {
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src[0].p = rl[i - 1].p; P.src[0].nstride = rl[i - 1].nstride; P.src[0].Cb = rl[i - 1].Cb;
-      P.N = Ne; P.Z = Z; P.S = rl[i - 1].H; P.act = 1;
-      P.out = rs[i - 1].p; P.out_nstride = rs[i - 1].nstride;
-      cx.check(launch_prep(P, cx.s));
-    }
-    run_conv(cx, rs[i - 1], m->pyr[i - 1], rl[i], nullptr, nullptr, EPI_UP2, 0, ZM_INPLANE);   // SiLU -> conv -> Upsample
+    PrepLaunch P = cx.prep(Ne, Z, rl[i - 1].H);
+    prep_src(P, rl[i - 1]);
+    P.act = 1;
+    prep_out(P, rs[i - 1]);
+    cx.run(P);
+    ConvLaunch L = conv(rs[i - 1], m->pyr[i - 1], rl[i]);          // SiLU -> conv -> Upsample
+    L.flags = EPI_UP2; L.zmode = ZM_INPLANE;
+    run_conv(cx, L);
   }
   cx.dry = was_dry;
   cx.top = rna_mark;                                              // tok / fp32 scratch are dead (the stream orders reuse)
@@ -1523,16 +1456,13 @@ static int forward_impl(Ctx& cx, const float* x, const int64_t* t, const float* 
     // head: RMSNorm -> SiLU -> Conv3d(1,3,3) -> 'b s z h w -> b (s z) h w'  (unet_ours.py:271-275,423-424)
     // (16-bit modes: the normalised, activated tensor is a 16-bit tensor like every other conv input)
     TV A = cx.tensor_s(N, c.net_ch, Z, ps);
-    if (!cx.dry) {
-      PrepLaunch P;
-      P.nsrc = 1;
-      P.src[0].p = hd.p; P.src[0].nstride = hd.nstride; P.src[0].Cb = hd.Cb;
-      P.src_h = h16 ? 1 : 0; P.h_f16 = c.dtype == TM_DTYPE_F16;
-      P.N = N; P.Z = Z; P.S = ps; P.norm_w = m->out_norm; P.inv_c = 1.0f / (float)c.net_ch; P.act = 1; P.per_image = per;
-      if (h16) { P.out_h = (uint16_t*)A.p; P.out_h_nstride = A.nstride; }
-      else { P.out = A.p; P.out_nstride = A.nstride; }
-      cx.check(launch_prep(P, cx.s));
-    }
+    PrepLaunch P = cx.prep(N, Z, ps, per);
+    cx.stream_src(P, hd);
+    prep_norm(P, m->out_norm, c.net_ch);
+    P.act = 1;
+    if (h16) prep_out_h(P, as_h(A), A.Cb);
+    else prep_out(P, A);
+    cx.run(P);
     if (!cx.dry) cx.check(launch_head(A, outp, m->head.w, m->head.bias, c.n_stain, cx.s, h16 ? (c.dtype == TM_DTYPE_F16 ? 2 : 1) : 0));
     cx.top = mark;
   };
@@ -1552,10 +1482,20 @@ static int check_fwd_args(const tm_model* m, int b, int p1, int p2) {
 extern "C" size_t tm_workspace_bytes(const tm_model* m, int b, int p1, int p2, int want_pred2) {
   if (check_fwd_args(m, b, p1, p2) != TM_OK) return 0;
   Ctx cx;
-  cx.m = const_cast<tm_model*>(m); cx.dry = true;
-  cx.b = b; cx.p1 = p1; cx.p2 = p2; cx.Ne = b * p1 * p2; cx.Nd = b * (p1 - 1) * (p2 - 1);
+  cx.init(const_cast<tm_model*>(m), b, p1, p2, nullptr, 0, nullptr);
   forward_impl(cx, nullptr, nullptr, nullptr, nullptr, (float*)256, want_pred2 ? (float*)256 : nullptr);
   return cx.peak + 256;
+}
+// tm_workspace_bytes is an upper bound for every forward entry point (it includes the RNA scratch)
+static int check_workspace(const tm_model* m, int b, int p1, int p2, bool want_pred2, size_t workspace_bytes) {
+  const size_t need = tm_workspace_bytes(m, b, p1, p2, want_pred2);
+  if (workspace_bytes < need) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  return TM_OK;
+}
+// the shared tail of the entry points: the first launch error of the call, if any
+static int fwd_status(const Ctx& cx) {
+  if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
+  return TM_OK;
 }
 
 extern "C" int tm_unet_forward(tm_model* m, const void* x, const int64_t* t, const void* rna_dense, int b, int p1,
@@ -1564,31 +1504,18 @@ extern "C" int tm_unet_forward(tm_model* m, const void* x, const int64_t* t, con
   int rc = check_fwd_args(m, b, p1, p2);
   if (rc != TM_OK) return rc;
   if (!x || !t || !rna_dense || !pred || !workspace) return fail(TM_ERR_ARG, "null tensor argument");
+  if ((rc = check_workspace(m, b, p1, p2, pred2_or_null != nullptr, workspace_bytes)) != TM_OK) return rc;
   Ctx cx;
-  cx.m = m; cx.s = (hipStream_t)stream;
-  cx.base = (char*)(((uintptr_t)workspace + 255) / 256 * 256);
-  cx.cap = workspace_bytes - (size_t)(cx.base - (char*)workspace);
-  cx.b = b; cx.p1 = p1; cx.p2 = p2; cx.Ne = b * p1 * p2; cx.Nd = b * (p1 - 1) * (p2 - 1);
-  const size_t need = tm_workspace_bytes(m, b, p1, p2, pred2_or_null != nullptr);
-  if (workspace_bytes < need) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  cx.init(m, b, p1, p2, workspace, workspace_bytes, (hipStream_t)stream);
   forward_impl(cx, (const float*)x, t, (const float*)rna_dense, nullptr, (float*)pred, (float*)pred2_or_null);
-  if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
-  return TM_OK;
+  return fwd_status(cx);
 }
 
 // ---- RNA conditioning computed once for many steps (mode A: the genes do not change over the reverse loop) ----
-static void pyramid_ctx(Ctx& cx, tm_model* m, int b, int p1, int p2, void* buf, size_t bytes, hipStream_t s) {
-  cx.m = m; cx.s = s;
-  cx.b = b; cx.p1 = p1; cx.p2 = p2; cx.Ne = b * p1 * p2; cx.Nd = b * (p1 - 1) * (p2 - 1);
-  if (buf) {
-    cx.base = (char*)(((uintptr_t)buf + 255) / 256 * 256);
-    cx.cap = bytes - (size_t)(cx.base - (char*)buf);
-  } else cx.dry = true;
-}
 extern "C" size_t tm_rna_pyramid_bytes(const tm_model* m, int b, int p1, int p2) {
   if (check_fwd_args(m, b, p1, p2) != TM_OK) return 0;
   Ctx cx;
-  pyramid_ctx(cx, const_cast<tm_model*>(m), b, p1, p2, nullptr, 0, nullptr);
+  cx.init(const_cast<tm_model*>(m), b, p1, p2, nullptr, 0, nullptr);
   RnaOut R;
   rna_stage(cx, nullptr, R);
   attn_cond_stage(cx, R, false);
@@ -1602,46 +1529,36 @@ extern "C" int tm_rna_pyramid(tm_model* m, const void* rna_dense, int b, int p1,
   const size_t need = tm_rna_pyramid_bytes(m, b, p1, p2);
   if (pyramid_bytes < need) return fail(TM_ERR_WORKSPACE, "pyramid buffer %zu B < required %zu B", pyramid_bytes, need);
   Ctx cx;
-  pyramid_ctx(cx, m, b, p1, p2, pyramid, pyramid_bytes, (hipStream_t)stream);
+  cx.init(m, b, p1, p2, pyramid, pyramid_bytes, (hipStream_t)stream);
   RnaOut R;
   rna_stage(cx, (const float*)rna_dense, R);
   attn_cond_stage(cx, R, true);
-  if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
-  return TM_OK;
+  return fwd_status(cx);
 }
 // ---- level 0 of the RNA conditioning on its own (the sweep's per-window cache) ----
-static TV level0_geom(const tm_model* m, int Ne) {
-  TV t;
-  t.N = Ne; t.C = m->rw[0]; t.Cb = (m->rw[0] + 7) / 8; t.Z = m->z; t.H = m->gn * 2; t.W = m->gn * 2;
-  t.nstride = (long)t.Cb * t.plane();
-  return t;
-}
 extern "C" size_t tm_rna_level0_bytes(const tm_model* m, int b, int p1, int p2) {
   if (check_fwd_args(m, b, p1, p2) != TM_OK) return 0;
-  const TV t = level0_geom(m, b * p1 * p2);
+  const TV t = cb8_view(nullptr, b * p1 * p2, m->rw[0], m->z, m->gn * 2, m->gn * 2);
   return (size_t)t.N * t.nstride * (is_h16(m->cfg.dtype) ? 2 : 4);
 }
-static void plain_ctx(Ctx& cx, tm_model* m, int b, int p1, int p2, void* workspace, size_t workspace_bytes, hipStream_t s) {
-  cx.m = m; cx.s = s;
-  cx.base = (char*)(((uintptr_t)workspace + 255) / 256 * 256);
-  cx.cap = workspace_bytes - (size_t)(cx.base - (char*)workspace);
-  cx.b = b; cx.p1 = p1; cx.p2 = p2; cx.Ne = b * p1 * p2; cx.Nd = b * (p1 - 1) * (p2 - 1);
+// the level-0 buffer of a call: aligned for the kernels' 16-byte accesses and large enough for (b, p1, p2)
+static int check_level0(const tm_model* m, int b, int p1, int p2, const void* level0, size_t level0_bytes) {
+  if (((uintptr_t)level0 & 15) != 0) return fail(TM_ERR_ARG, "level0 buffer must be 16-byte aligned");
+  if (level0_bytes < tm_rna_level0_bytes(m, b, p1, p2)) return fail(TM_ERR_WORKSPACE, "level-0 buffer too small for (b, p1, p2)");
+  return TM_OK;
 }
 extern "C" int tm_rna_level0(tm_model* m, const void* rna_dense, int b, int p1, int p2, void* level0, size_t level0_bytes,
                              void* workspace, size_t workspace_bytes, void* stream) {
   int rc = check_fwd_args(m, b, p1, p2);
   if (rc != TM_OK) return rc;
   if (!rna_dense || !level0 || !workspace) return fail(TM_ERR_ARG, "null tensor argument");
-  if (((uintptr_t)level0 & 15) != 0) return fail(TM_ERR_ARG, "level0 buffer must be 16-byte aligned");
-  if (level0_bytes < tm_rna_level0_bytes(m, b, p1, p2)) return fail(TM_ERR_WORKSPACE, "level-0 buffer too small for (b, p1, p2)");
-  const size_t need = tm_workspace_bytes(m, b, p1, p2, 0);
-  if (workspace_bytes < need) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  if ((rc = check_level0(m, b, p1, p2, level0, level0_bytes)) != TM_OK) return rc;
+  if ((rc = check_workspace(m, b, p1, p2, false, workspace_bytes)) != TM_OK) return rc;
   Ctx cx;
-  plain_ctx(cx, m, b, p1, p2, workspace, workspace_bytes, (hipStream_t)stream);
+  cx.init(m, b, p1, p2, workspace, workspace_bytes, (hipStream_t)stream);
   RnaOut R;
   rna_stage(cx, (const float*)rna_dense, R, nullptr, level0);
-  if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
-  return TM_OK;
+  return fwd_status(cx);
 }
 extern "C" int tm_unet_forward_level0(tm_model* m, const void* x, const int64_t* t, const void* level0, size_t level0_bytes,
                                       int b, int p1, int p2, void* pred, void* pred2_or_null, void* workspace,
@@ -1649,15 +1566,12 @@ extern "C" int tm_unet_forward_level0(tm_model* m, const void* x, const int64_t*
   int rc = check_fwd_args(m, b, p1, p2);
   if (rc != TM_OK) return rc;
   if (!x || !t || !level0 || !pred || !workspace) return fail(TM_ERR_ARG, "null tensor argument");
-  if (((uintptr_t)level0 & 15) != 0) return fail(TM_ERR_ARG, "level0 buffer must be 16-byte aligned");
-  if (level0_bytes < tm_rna_level0_bytes(m, b, p1, p2)) return fail(TM_ERR_WORKSPACE, "level-0 buffer too small for (b, p1, p2)");
-  const size_t need = tm_workspace_bytes(m, b, p1, p2, pred2_or_null != nullptr);
-  if (workspace_bytes < need) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  if ((rc = check_level0(m, b, p1, p2, level0, level0_bytes)) != TM_OK) return rc;
+  if ((rc = check_workspace(m, b, p1, p2, pred2_or_null != nullptr, workspace_bytes)) != TM_OK) return rc;
   Ctx cx;
-  plain_ctx(cx, m, b, p1, p2, workspace, workspace_bytes, (hipStream_t)stream);
+  cx.init(m, b, p1, p2, workspace, workspace_bytes, (hipStream_t)stream);
   forward_impl(cx, (const float*)x, t, nullptr, nullptr, (float*)pred, (float*)pred2_or_null, level0);
-  if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
-  return TM_OK;
+  return fwd_status(cx);
 }
 extern "C" int tm_unet_forward_rna(tm_model* m, const void* x, const int64_t* t, const void* pyramid, size_t pyramid_bytes,
                                    int b, int p1, int p2, void* pred, void* pred2_or_null, void* workspace,
@@ -1666,25 +1580,17 @@ extern "C" int tm_unet_forward_rna(tm_model* m, const void* x, const int64_t* t,
   if (rc != TM_OK) return rc;
   if (!x || !t || !pyramid || !pred || !workspace) return fail(TM_ERR_ARG, "null tensor argument");
   if (pyramid_bytes < tm_rna_pyramid_bytes(m, b, p1, p2)) return fail(TM_ERR_WORKSPACE, "pyramid buffer too small for (b, p1, p2)");
+  if ((rc = check_workspace(m, b, p1, p2, pred2_or_null != nullptr, workspace_bytes)) != TM_OK) return rc;
   // the layout of the persistent tensors inside the pyramid buffer is a pure function of (b, p1, p2): replay it
   Ctx px;
-  pyramid_ctx(px, m, b, p1, p2, const_cast<void*>(pyramid), pyramid_bytes, (hipStream_t)stream);
+  px.init(m, b, p1, p2, const_cast<void*>(pyramid), pyramid_bytes, (hipStream_t)stream);
   RnaOut R;
   rna_stage(px, nullptr, R);
   attn_cond_stage(px, R, false);
-  // TM_ATTN_HOIST=0: every AttnBlock computes its conditioning side in-step, as tm_unet_forward does (A/B timing)
-  static const bool no_hoist = getenv("TM_ATTN_HOIST") && atoi(getenv("TM_ATTN_HOIST")) == 0;
-  if (no_hoist) R.ac.clear();
   Ctx cx;
-  cx.m = m; cx.s = (hipStream_t)stream;
-  cx.base = (char*)(((uintptr_t)workspace + 255) / 256 * 256);
-  cx.cap = workspace_bytes - (size_t)(cx.base - (char*)workspace);
-  cx.b = b; cx.p1 = p1; cx.p2 = p2; cx.Ne = b * p1 * p2; cx.Nd = b * (p1 - 1) * (p2 - 1);
-  const size_t need = tm_workspace_bytes(m, b, p1, p2, pred2_or_null != nullptr);      // upper bound (it includes the RNA scratch)
-  if (workspace_bytes < need) return fail(TM_ERR_WORKSPACE, "workspace %zu B < required %zu B", workspace_bytes, need);
+  cx.init(m, b, p1, p2, workspace, workspace_bytes, (hipStream_t)stream);
   forward_impl(cx, (const float*)x, t, nullptr, &R, (float*)pred, (float*)pred2_or_null);
-  if (cx.err != hipSuccess) return fail(TM_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(cx.err));
-  return TM_OK;
+  return fwd_status(cx);
 }
 
 // ------------------------------------------------------------------------------------------

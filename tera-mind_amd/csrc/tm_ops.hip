@@ -91,31 +91,33 @@ static int finish(hipStream_t st, hipError_t e, const char* what) {
   return e == hipSuccess ? TM_OK : fail(TM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 
-static TV view_cb8(void* p, int N, int C, int Z, int H, int W) {
-  TV t;
-  t.p = (float*)p; t.N = N; t.C = C; t.Cb = (C + 7) / 8; t.Z = Z; t.H = H; t.W = W;
-  t.nstride = (long)t.Cb * t.plane();
-  return t;
-}
-static TVH view_h16(void* p, int N, int C, int Z, int H, int W) { return as_h(view_cb8(p, N, C, Z, H, W)); }
+static TVH view_h16(void* p, int N, int C, int Z, int H, int W) { return as_h(cb8_view(p, N, C, Z, H, W)); }
 
-// the prep kernel's one plain fp32 CB8 source
-static void prep_single_src(PrepLaunch& P, const TV& x) {
-  P.nsrc = 1;
-  P.src[0].p = x.p; P.src[0].nstride = x.nstride; P.src[0].Cb = x.Cb;
+// the sources of the prep hooks: nsrc dense CB8 tensors of src_c[i] channels on Ss x Ss planes (the patch count of a source plays
+// no part in its view); returns their channel blocks
+static int prep_op_sources(PrepLaunch& P, const void* const* src, const int* src_c, const int* collage, int nsrc, int Z, int Ss,
+                           bool h16) {
+  int cbtot = 0;
+  for (int i = 0; i < nsrc; ++i) {
+    const TV t = cb8_view(const_cast<void*>(src[i]), 0, src_c[i], Z, Ss, Ss);
+    if (h16) prep_src(P, as_h(t), collage[i] != 0);
+    else prep_src(P, t, collage[i] != 0);
+    cbtot += t.Cb;
+  }
+  return cbtot;
 }
 
 // fp32 CB8 x -> a 16-bit CB8 copy in `tmp` (prep kernel, no norm / act); `pair`: even block count (zero pad blocks), the
 // operand form of the 16-bit conv kernels.  Launches nothing once `e` holds an error.
 static TVH to_h16(DevTmp& tmp, const TV& x, bool f16, bool pair, hipStream_t st, hipError_t& e) {
   if (e != hipSuccess) return TVH();
-  const int Cb = pair ? (x.Cb + 1) / 2 * 2 : x.Cb;
+  const int Cb = pair ? pair_cb(x.Cb) : x.Cb;
   const TVH h = view_h16(tmp.alloc<uint16_t>((size_t)x.N * Cb * x.plane()), x.N, Cb * 8, x.Z, x.H, x.W);
   if (tmp.err) { e = tmp.err; return h; }
-  PrepLaunch P;
-  prep_single_src(P, x);
-  P.N = x.N; P.Z = x.Z; P.S = x.H; P.h_f16 = f16 ? 1 : 0;
-  P.out_h = h.p; P.out_h_nstride = h.nstride; P.pad_blocks = Cb - x.Cb;
+  PrepLaunch P = prep_start(x.N, x.Z, x.H);
+  prep_src(P, x);
+  P.h_f16 = f16 ? 1 : 0;
+  prep_out_h(P, h, x.Cb);
   e = launch_prep(P, st);
   return h;
 }
@@ -145,11 +147,11 @@ static hipError_t download_rows(void* host, const float* dev, int rows, int C, i
 // single-operator entry points (tests)
 // ------------------------------------------------------------------------------------------
 extern "C" int tm_op_to_cb8(const void* x, void* y, int N, int C, int Z, int H, int W, void* stream) {
-  HIP_TRY(launch_to_cb8((const float*)x, view_cb8(y, N, C, Z, H, W), (hipStream_t)stream));
+  HIP_TRY(launch_to_cb8((const float*)x, cb8_view(y, N, C, Z, H, W), (hipStream_t)stream));
   return TM_OK;
 }
 extern "C" int tm_op_from_cb8(const void* x, void* y, int N, int C, int Z, int H, int W, void* stream) {
-  HIP_TRY(launch_from_cb8(view_cb8(const_cast<void*>(x), N, C, Z, H, W), (float*)y, (hipStream_t)stream));
+  HIP_TRY(launch_from_cb8(cb8_view(const_cast<void*>(x), N, C, Z, H, W), (float*)y, (hipStream_t)stream));
   return TM_OK;
 }
 extern "C" int tm_op_conv_mfma(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
@@ -173,13 +175,13 @@ static int conv_op(ConvOp& op, int form, const void* w_host, const void* bias_ho
   std::tie(cw.w, cw.bias) = upload_conv(op.tmp, pk, bias_host, Cout);
   if (op.tmp.err) return op.tmp.report();
   ConvLaunch& L = op.L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.x = cb8_view(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
   L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Zout, So, So);
+  L.y = cb8_view(y_cb8, N, Cout, Zout, So, So);
   L.tile_variant = tile_variant;
   L.zmode = zmode;
   if (res_cb8) {
-    op.res = view_cb8(const_cast<void*>(res_cb8), N, Cout, Zout, res_half ? So / 2 : So, res_half ? So / 2 : So);
+    op.res = cb8_view(const_cast<void*>(res_cb8), N, Cout, Zout, res_half ? So / 2 : So, res_half ? So / 2 : So);
     L.res = &op.res;
     L.res_half = res_half ? 1 : 0;
   }
@@ -235,14 +237,15 @@ extern "C" int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host,
   hipError_t e = launch_conv_mfma(L, st);
   if (e == hipSuccess && h1_out) {                      // the same conv, plain epilogue, then (a2_sep_out) the separate pass on it
     ConvLaunch U = L;
-    U.fuse_norm = 0; U.y = view_cb8(h1_out, N, Cout, Z, S, S);
+    U.fuse_norm = 0; U.y = cb8_view(h1_out, N, Cout, Z, S, S);
     e = launch_conv_mfma(U, st);
     if (e == hipSuccess && a2_sep_out) {
-      PrepLaunch P;
-      prep_single_src(P, U.y);
-      P.N = N; P.Z = Z; P.S = S; P.norm_w = nw; P.inv_c = L.inv_c; P.act = 1; P.per_image = per_image;
-      P.mod = MOD_IMAGE; P.mod_scale = sc; P.mod_shift = sh; P.mod_stride = Cout;
-      P.out = (float*)a2_sep_out; P.out_nstride = U.y.nstride;
+      PrepLaunch P = prep_start(N, Z, S);
+      prep_src(P, U.y);
+      prep_norm(P, nw, Cout);
+      P.mod = MOD_IMAGE; P.mod_scale = sc; P.mod_shift = sh; P.mod_stride = Cout;   // rows of their own, not slices of one matrix
+      P.act = 1; P.per_image = per_image;
+      prep_out(P, cb8_view(a2_sep_out, N, Cout, Z, S, S));
       e = launch_prep(P, st);
     }
   }
@@ -344,16 +347,16 @@ extern "C" int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void
   std::tie(cw.w, cw.bias) = upload_conv(tmp, pk, bias_host, Cout);
   if (tmp.err) return tmp.report();
   ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, x_cbtot * 8, Z, S, S).blocks(x_cb0, Cbi);
+  L.x = cb8_view(const_cast<void*>(x_cb8), N, x_cbtot * 8, Z, S, S).blocks(x_cb0, Cbi);
   L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.y = cb8_view(y_cb8, N, Cout, Z, S, S);
   L.tile_variant = tile_variant;
   L.flags = gelu ? EPI_GELU : 0;
   TV res = L.y, gate;
   if (res_cb8) { res.p = (float*)const_cast<void*>(res_cb8); L.res = &res; }      // res_cb8 == y_cb8: x <- x + gate * Linear(.)
   if (gate_cb8) {
     const int Sg = gate_half ? S / 2 : S;
-    gate = view_cb8(const_cast<void*>(gate_cb8), N, gate_cbtot * 8, Z, Sg, Sg).blocks(gate_cb0, Cob);
+    gate = cb8_view(const_cast<void*>(gate_cb8), N, gate_cbtot * 8, Z, Sg, Sg).blocks(gate_cb0, Cob);
     L.gate = &gate;
     L.gate_half = gate_half ? 1 : 0;
   }
@@ -374,7 +377,7 @@ static int conv27_launch(ConvLaunchH& L, int N, int Cin, int Cout, int Z, int S,
   const int So = ups ? 2 * S : S;
   L.x = view_h16(nullptr, N, ((Cin + 7) / 8 + 1) / 2 * 16, Z, S, S);
   L.Cout = Cout; L.force_waves = waves; L.ups = ups;
-  L.y = view_cb8(nullptr, N, Cout, Z, So, So);
+  L.y = cb8_view(nullptr, N, Cout, Z, So, So);
   if (fused) { L.fuse_norm = 1; L.a2 = view_h16(nullptr, N, Cout, Z, So, So); }
   return TM_OK;
 }
@@ -404,7 +407,7 @@ static int op_conv27_h16(const void* x_cb8, const void* w_host, const void* bias
   }
   if (tmp.err) return tmp.report();
   hipError_t e = hipSuccess;
-  L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
+  L.x = to_h16(tmp, cb8_view(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
   L.y.p = (float*)y_cb8;
   L.res_half = res_half;
   TVH resh = as_h(L.y);
@@ -525,9 +528,9 @@ extern "C" int tm_op_conv1_h16_gate(const void* x_cb8, const void* w_host, const
   std::tie(L.w, L.bias) = upload_conv(tmp, pk, bias_host, Cout);
   if (tmp.err) return tmp.report();
   hipError_t e = hipSuccess;
-  L.x = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
+  L.x = to_h16(tmp, cb8_view(const_cast<void*>(x_cb8), N, Cin, Z, S, S), f16, true, st, e);
   L.Cout = Cout; L.flags = gelu ? EPI_GELU : 0; L.force_waves = waves;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.y = cb8_view(y_cb8, N, Cout, Z, S, S);
   TVH resh = as_h(L.y), gateh;
   if (res_h16) { resh.p = (uint16_t*)const_cast<void*>(res_h16); L.res_h = &resh; }
   if (gate_h16) {                                         // [N][gate_cbtot][Z][Sg][Sg][8], blocks from gate_cb0
@@ -562,14 +565,14 @@ extern "C" int tm_op_conv1_concat(const void* const* x_cb8, const int* cin, cons
   if (tmp.err) return tmp.report();
   hipError_t e = hipSuccess;
   for (int i = 0; i < nsrc; ++i) {
-    L.xs[i] = to_h16(tmp, view_cb8(const_cast<void*>(x_cb8[i]), collage[i] ? Nsrc_col : N, cin[i], Z, S, S), f16, false, st, e);
+    L.xs[i] = to_h16(tmp, cb8_view(const_cast<void*>(x_cb8[i]), collage[i] ? Nsrc_col : N, cin[i], Z, S, S), f16, false, st, e);
     L.xs_collage[i] = collage[i] ? 1 : 0;
   }
   L.nsrc = nsrc; L.p1 = p1; L.p2 = p2;
   L.x = view_h16(nullptr, N, (Cbi + 1) / 2 * 16, Z, S, S);
   L.x.nstride = 0;
   L.Cout = Cout; L.force_waves = waves;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.y = cb8_view(y_cb8, N, Cout, Z, S, S);
   if (e == hipSuccess) e = (f16 ? launch_conv1_f16 : launch_conv1_bf16)(L, st);
   return finish(st, e, "conv1 concat");
 }
@@ -608,24 +611,18 @@ extern "C" int tm_op_prep_h16(const void* const* src_h16, const int* src_c, cons
   if (up2 == 1 && (any_col || (S & 1))) return fail(TM_ERR_ARG, "up2 takes plain sources and an even S");
   if (up2 == 2 && (any_col || nsrc != 1 || mod != MOD_NONE)) return fail(TM_ERR_ARG, "the downsample form takes one plain source, no modulation");
   const int Ss = up2 == 1 ? S / 2 : (up2 == 2 ? 2 * S : S);
-  PrepLaunch P;
-  P.nsrc = nsrc;
-  int cbtot = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    const int cb = (src_c[i] + 7) / 8;
-    P.src[i].p = (const float*)src_h16[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
-    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
-    cbtot += cb;
-  }
-  const int cbe = (cbtot + 1) / 2 * 2;
-  P.src_h = 1; P.h_f16 = dtype == TM_DTYPE_F16;
-  P.resample = up2 == 1 ? RS_UP2 : (up2 == 2 ? RS_DOWN2 : RS_SAME); P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
-  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act; P.per_image = per_image > 0 ? per_image : 1;
+  PrepLaunch P = prep_start(N, Z, S);
+  const int cbtot = prep_op_sources(P, src_h16, src_c, collage, nsrc, Z, Ss, true);
+  const int cbe = pair_cb(cbtot);
+  P.h_f16 = dtype == TM_DTYPE_F16;
+  P.resample = up2 == 1 ? RS_UP2 : (up2 == 2 ? RS_DOWN2 : RS_SAME); P.p1 = p1; P.p2 = p2;
+  prep_norm(P, (const float*)norm_w_dev, c_real);
+  P.act = act; P.per_image = per_image > 0 ? per_image : 1;
   P.mod = mod; P.mod_stride = mod_stride;
   if (mod == MOD_IMAGE) { P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift; }
   if (mod == MOD_VOXEL) { P.mod_scale_h = (const uint16_t*)mod_scale; P.mod_shift_h = (const uint16_t*)mod_shift; }
-  P.out_h = (uint16_t*)out_h16; P.out_h_nstride = (long)cbe * Z * S * S * 8; P.pad_blocks = cbe - cbtot;
-  if (raw_h16) { P.raw_h = (uint16_t*)raw_h16; P.raw_h_nstride = P.out_h_nstride; }
+  prep_out_h(P, view_h16(out_h16, N, cbe * 8, Z, S, S), cbtot);
+  if (raw_h16) prep_raw_h(P, view_h16(raw_h16, N, cbe * 8, Z, S, S));
   return prep_run(P, variant, iters, elapsed_ms, st, "prep");
 }
 extern "C" int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, const int* collage, int nsrc, int N, int Z, int S,
@@ -645,21 +642,15 @@ extern "C" int tm_op_prep_f32(const void* const* src_cb8, const int* src_c, cons
   if (up2 < 0 || up2 > 1) return fail(TM_ERR_ARG, "up2: 0 same, 1 nearest x2");
   if (up2 == 1 && (any_col || (S & 1))) return fail(TM_ERR_ARG, "up2 takes plain sources and an even S");
   const int Ss = up2 == 1 ? S / 2 : S;
-  PrepLaunch P;
-  P.nsrc = nsrc;
-  int cbtot = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    const int cb = (src_c[i] + 7) / 8;
-    P.src[i].p = (const float*)src_cb8[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
-    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
-    cbtot += cb;
-  }
-  P.resample = up2 == 1 ? RS_UP2 : RS_SAME; P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
-  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act; P.per_image = per_image > 0 ? per_image : 1;
+  PrepLaunch P = prep_start(N, Z, S);
+  const int cbtot = prep_op_sources(P, src_cb8, src_c, collage, nsrc, Z, Ss, false);
+  P.resample = up2 == 1 ? RS_UP2 : RS_SAME; P.p1 = p1; P.p2 = p2;
+  prep_norm(P, (const float*)norm_w_dev, c_real);
+  P.act = act; P.per_image = per_image > 0 ? per_image : 1;
   P.mod = mod; P.mod_stride = mod_stride; P.mod_half = mod_half ? 1 : 0;
   P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift;
-  P.out = (float*)out_cb8; P.out_nstride = (long)cbtot * Z * S * S * 8;
-  if (raw_cb8) { P.raw = (float*)raw_cb8; P.raw_nstride = P.out_nstride; }
+  prep_out(P, cb8_view(out_cb8, N, cbtot * 8, Z, S, S));
+  if (raw_cb8) prep_raw(P, cb8_view(raw_cb8, N, cbtot * 8, Z, S, S));
   if (variant == 2 && !prep_wide_applies(P))
     return fail(TM_ERR_ARG, "the wide form takes 33..%d channel blocks (this call has %d)", PREP_WIDE_MAX_CB, cbtot);
   return prep_run(P, variant, iters, elapsed_ms, st, "prep (fp32)");
@@ -696,27 +687,22 @@ extern "C" int tm_op_prep_form(const void* const* src, const int* src_c, const i
   if (resample == RS_DOWN2 && (any_col || nsrc != 1 || mod != MOD_NONE))
     return fail(TM_ERR_ARG, "the downsample form takes one plain source, no modulation");
   const int Ss = resample == RS_UP2 ? S / 2 : (resample == RS_SAME ? S : 2 * S);
-  PrepLaunch P;
-  P.nsrc = nsrc;
-  int cbtot = 0;
-  for (int i = 0; i < nsrc; ++i) {
-    const int cb = (src_c[i] + 7) / 8;
+  for (int i = 0; i < nsrc; ++i)
     if (!src[i] || src_c[i] < 1) return fail(TM_ERR_ARG, "bad source %d", i);
-    P.src[i].p = (const float*)src[i]; P.src[i].Cb = cb; P.src[i].collage = collage[i] ? 1 : 0;
-    P.src[i].nstride = (long)cb * Z * Ss * Ss * 8;
-    cbtot += cb;
-  }
-  P.src_h = is_h16(src_dtype) ? 1 : 0; P.h_f16 = h == TM_DTYPE_F16;
-  P.resample = resample; P.N = N; P.Z = Z; P.S = S; P.p1 = p1; P.p2 = p2;
-  P.norm_w = (const float*)norm_w_dev; P.inv_c = 1.0f / (float)c_real; P.act = act ? 1 : 0; P.per_image = per_image > 0 ? per_image : 1;
+  PrepLaunch P = prep_start(N, Z, S);
+  const int cbtot = prep_op_sources(P, src, src_c, collage, nsrc, Z, Ss, is_h16(src_dtype));
+  P.h_f16 = h == TM_DTYPE_F16;
+  P.resample = resample; P.p1 = p1; P.p2 = p2;
+  prep_norm(P, (const float*)norm_w_dev, c_real);
+  P.act = act ? 1 : 0; P.per_image = per_image > 0 ? per_image : 1;
   P.mod = mod; P.mod_stride = mod_stride; P.mod_half = mod_half ? 1 : 0;
   if (voxel && is_h16(mod_dtype)) { P.mod_scale_h = (const uint16_t*)mod_scale; P.mod_shift_h = (const uint16_t*)mod_shift; }
   else if (mod != MOD_NONE) { P.mod_scale = (const float*)mod_scale; P.mod_shift = (const float*)mod_shift; }
-  const long plane = (long)Z * S * S * 8;
-  if (is_h16(out_dtype)) { P.out_h = (uint16_t*)out; P.out_h_nstride = (cbtot + pad_blocks) * plane; P.pad_blocks = pad_blocks; }
-  else { P.out = (float*)out; P.out_nstride = cbtot * plane; }
-  if (raw && is_h16(raw_dtype)) { P.raw_h = (uint16_t*)raw; P.raw_h_nstride = (cbtot + pad_blocks) * plane; }
-  else if (raw) { P.raw = (float*)raw; P.raw_nstride = cbtot * plane; }
+  const int cb_h = cbtot + pad_blocks;                 // blocks of a 16-bit output / raw copy: the pad blocks behind the real ones
+  if (is_h16(out_dtype)) prep_out_h(P, view_h16(out, N, cb_h * 8, Z, S, S), cbtot);
+  else prep_out(P, cb8_view(out, N, cbtot * 8, Z, S, S));
+  if (raw && is_h16(raw_dtype)) prep_raw_h(P, view_h16(raw, N, cb_h * 8, Z, S, S));
+  else if (raw) prep_raw(P, cb8_view(raw, N, cbtot * 8, Z, S, S));
   // the forms a forced variant names must be the form launch_prep then takes
   const bool h16_call = P.src_h && P.out_h && !P.raw && resample != RS_DOWN2 && (!voxel || P.mod_scale_h);
   if (variant == 3 && !(h16_call && cbtot <= 160)) return fail(TM_ERR_ARG, "variant 3 takes an all-16-bit call of at most 160 blocks");
@@ -741,7 +727,7 @@ extern "C" int tm_op_stem(const void* x, const void* w_host, const void* bias_ho
   const float* bias = tmp.alloc((size_t)Cout, (const float*)bias_host);
   if (tmp.err) return tmp.report();
   const bool h16 = is_h16(dtype);
-  const TV yv = view_cb8(h16 ? nullptr : y, N, Cout, Z, S, S);
+  const TV yv = cb8_view(h16 ? nullptr : y, N, Cout, Z, S, S);
   hipStream_t st = (hipStream_t)stream;
   return finish(st, launch_stem((const float*)x, yv, w, bias, Cin, st, h16 ? (uint16_t*)y : nullptr, yv.nstride, dtype == TM_DTYPE_F16), "stem");
 }
@@ -762,7 +748,7 @@ extern "C" int tm_op_head(const void* x_cb8, const void* w_host, const void* bia
   const float* bias = tmp.alloc((size_t)Cout, (const float*)bias_host);
   if (tmp.err) return tmp.report();
   hipStream_t st = (hipStream_t)stream;
-  const TV xv = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
+  const TV xv = cb8_view(const_cast<void*>(x_cb8), N, C, Z, S, S);
   return finish(st, launch_head(xv, (float*)y, w, bias, Cout, st, dtype == TM_DTYPE_F32 ? 0 : (dtype == TM_DTYPE_F16 ? 2 : 1)), "head");
 }
 
@@ -788,10 +774,10 @@ extern "C" int tm_op_window_attn(const void* q_cb8, const void* k_cb8, const voi
                                  const void* kw_dev, void* out, int N, int C, int Z, int S, int dtype, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (C % 64) return fail(TM_ERR_ARG, "C must be a multiple of 64");
-  const TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S);
-  const TV v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
+  const TV q = cb8_view(const_cast<void*>(q_cb8), N, C, Z, S, S), k = cb8_view(const_cast<void*>(k_cb8), N, C, Z, S, S);
+  const TV v = cb8_view(const_cast<void*>(v_cb8), N, C, Z, S, S);
   const float *qw = (const float*)qw_dev, *kw = (const float*)kw_dev;
-  if (dtype == TM_DTYPE_F32) return finish(st, launch_window_attn(q, k, v, qw, kw, view_cb8(out, N, C, Z, S, S), st), "window attention");
+  if (dtype == TM_DTYPE_F32) return finish(st, launch_window_attn(q, k, v, qw, kw, cb8_view(out, N, C, Z, S, S), st), "window attention");
   DevTmp tmp;
   hipError_t e = hipSuccess;
   const TVH hq = to_h16(tmp, q, false, false, st, e), hk = to_h16(tmp, k, false, false, st, e), hv = to_h16(tmp, v, false, false, st, e);
@@ -836,11 +822,11 @@ extern "C" int tm_op_window_attn_kv(const void* q_cb8, const void* kv_cb8, const
   if (int rc = window_attn_form(N, C, Z, S, dtype, kv_half)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int cb = C / 8, Sc = kv_half ? S / 2 : S;
-  const TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), kv = view_cb8(const_cast<void*>(kv_cb8), N, 2 * C, Z, Sc, Sc);
+  const TV q = cb8_view(const_cast<void*>(q_cb8), N, C, Z, S, S), kv = cb8_view(const_cast<void*>(kv_cb8), N, 2 * C, Z, Sc, Sc);
   const float *qw = (const float*)qw_dev, *kw = (const float*)kw_dev;
   // k and v are the two channel-block halves of kv, as attn_block (tm_model.hip) hands them over: their n stride is kv's
   if (dtype == TM_DTYPE_F32)
-    return finish(st, launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), qw, kw, view_cb8(out, N, C, Z, S, S), st), "window attention");
+    return finish(st, launch_window_attn(q, kv.blocks(0, cb), kv.blocks(cb, cb), qw, kw, cb8_view(out, N, C, Z, S, S), st), "window attention");
   const bool f16 = dtype == TM_DTYPE_F16;
   DevTmp tmp;
   hipError_t e = hipSuccess;
@@ -983,14 +969,15 @@ static int prep_train_impl(const void* x_cb8, const void* norm_w_host, const voi
   const float *dsc = nullptr, *dsh = nullptr;
   if (scale_host) { dsc = upload_rows(tmp, scale_host, nimg, C, Cp); dsh = upload_rows(tmp, shift_host, nimg, C, Cp); }
   if (tmp.err) return tmp.report();
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
-  PrepLaunch P;
-  prep_single_src(P, x);
-  P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 1; P.per_image = per_image;
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, C, Z, S, S), y = cb8_view(y_cb8, N, C, Z, S, S);
+  PrepLaunch P = prep_start(N, Z, S);
+  prep_src(P, x);
+  prep_norm(P, dw, C);
+  P.act = 1; P.per_image = per_image;
   if (dsc) { P.mod = MOD_IMAGE; P.mod_scale = dsc; P.mod_shift = dsh; P.mod_stride = Cp; }
   if (mask_cb8) { P.drop_mask = (const float*)mask_cb8; P.drop_ns = x.nstride; P.drop_scale = drop_scale; }
   if (rng) P.drop_scale = drop_scale;
-  P.out = y.p; P.out_nstride = y.nstride;
+  prep_out(P, y);
   hipStream_t st = (hipStream_t)stream;
   return finish(st, rng ? launch_prep_drop(P, *rng, st) : launch_prep(P, st), "prep (training forward)");
 }
@@ -1028,7 +1015,7 @@ static int prep_bwd_impl(const void* x_cb8, const void* g_cb8, const void* norm_
   }
   float* scratch = tmp.zeros(prep_bwd_scratch_floats(N, Cb, Z, S, scale_host != nullptr));
   if (tmp.err) return tmp.report();
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, C, Z, S, S);
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = launch_prep_bwd(x.p, x.nstride, (const float*)g_cb8, x.nstride, (const float*)mask_cb8, x.nstride, drop_scale, dwt,
                                  dsc, dsh, Cp, per_image, (float*)dx_cb8, x.nstride, ddw, ddsc, ddsh, N, Cb, C, Z, S, scratch, st, rng);
@@ -1085,12 +1072,12 @@ extern "C" int tm_op_modnorm(const void* x_cb8, const void* norm_w_host, const v
   DevTmp tmp;
   const float* dw = upload_rows(tmp, norm_w_host, 1, C, Cp);
   if (tmp.err) return tmp.report();
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S), y = view_cb8(y_cb8, N, C, Z, S, S);
-  PrepLaunch P;
-  prep_single_src(P, x);
-  P.N = N; P.Z = Z; P.S = S; P.norm_w = dw; P.inv_c = 1.0f / (float)C; P.act = 0;
-  P.mod = MOD_VOXEL; P.mod_scale = (const float*)scale_cb8; P.mod_shift = (const float*)shift_cb8; P.mod_stride = x.nstride;
-  P.out = y.p; P.out_nstride = y.nstride;
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, C, Z, S, S), y = cb8_view(y_cb8, N, C, Z, S, S);
+  PrepLaunch P = prep_start(N, Z, S);
+  prep_src(P, x);
+  prep_norm(P, dw, C);
+  prep_mod_voxel(P, cb8_view(const_cast<void*>(scale_cb8), N, C, Z, S, S), cb8_view(const_cast<void*>(shift_cb8), N, C, Z, S, S), false);
+  prep_out(P, y);
   return finish((hipStream_t)stream, launch_prep(P, (hipStream_t)stream), "modulate(norm)");
 }
 
@@ -1105,7 +1092,7 @@ extern "C" int tm_op_modnorm_bwd(const void* x_cb8, const void* g_cb8, const voi
   const long vox = (long)N * Z * S * S;
   float* scratch = tmp.zeros((size_t)((vox + 63) / 64) * Cp);
   if (tmp.err) return tmp.report();
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S, S);
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, C, Z, S, S);
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = launch_modnorm_bwd(x, (const float*)g_cb8, dwt, (const float*)scale_cb8, (float*)dx_cb8, (float*)dscale_cb8,
                                     (float*)dshift_cb8, ddw, C, scratch, st);
@@ -1134,8 +1121,8 @@ extern "C" int tm_op_window_attn_train(const void* q_cb8, const void* k_cb8, con
   float *gq = bwd ? tmp.zeros(Cp) : nullptr, *gk = bwd ? tmp.zeros(Cp) : nullptr;
   float* scratch = lng ? tmp.alloc<float>(attn_train_long_scratch_floats(N, Cb, Z, S, bwd)) : bwd ? tmp.zeros((size_t)2 * N * 4 * Cp) : nullptr;
   if (tmp.err) return tmp.report();
-  TV q = view_cb8(const_cast<void*>(q_cb8), N, C, Z, S, S), k = view_cb8(const_cast<void*>(k_cb8), N, C, Z, S, S),
-     v = view_cb8(const_cast<void*>(v_cb8), N, C, Z, S, S);
+  TV q = cb8_view(const_cast<void*>(q_cb8), N, C, Z, S, S), k = cb8_view(const_cast<void*>(k_cb8), N, C, Z, S, S),
+     v = cb8_view(const_cast<void*>(v_cb8), N, C, Z, S, S);
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = (lng ? launch_attn_train_long : shrt ? launch_attn_train_short : launch_attn_train)(q, k, v, dqw_in, dkw_in, (const float*)dout_cb8, (float*)o_cb8,
                                                                     (float*)dq_cb8, (float*)dk_cb8, (float*)dv_cb8, gq, gk, scratch, bwd, st);
@@ -1173,12 +1160,11 @@ extern "C" int tm_op_rows(int op, const void* x_dev, const void* w_dev, const vo
 extern "C" int tm_op_resample(const void* x_cb8, void* y_cb8, int N, int C, int Z, int S_out, int mode, void* stream) {
   if (!x_cb8 || !y_cb8 || (mode != 1 && mode != 2) || (mode == 1 && (S_out & 1))) return fail(TM_ERR_ARG, "bad argument");
   const int S_in = mode == 1 ? S_out / 2 : S_out * 2;
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, C, Z, S_in, S_in), y = view_cb8(y_cb8, N, C, Z, S_out, S_out);
-  PrepLaunch P;
-  prep_single_src(P, x);
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, C, Z, S_in, S_in), y = cb8_view(y_cb8, N, C, Z, S_out, S_out);
+  PrepLaunch P = prep_start(N, Z, S_out);
+  prep_src(P, x);
   P.resample = mode == 1 ? RS_UP2 : RS_DOWN2;
-  P.N = N; P.Z = Z; P.S = S_out; P.inv_c = 1.0f / (float)C;
-  P.out = y.p; P.out_nstride = y.nstride;
+  prep_out(P, y);
   return finish((hipStream_t)stream, launch_prep(P, (hipStream_t)stream), "resample");
 }
 
@@ -1243,7 +1229,7 @@ extern "C" int tm_op_conv_wgrad(const void* x_cb8, const void* dy_cb8, void* dw_
   if (Z < 1 || Z > 4) return fail(TM_ERR_ARG, "weight gradient: Z must be 1 .. 4 (the kernel stages up to four z planes)");
   const int taps = ksize == 1 ? 1 : 27;
   hipStream_t st = (hipStream_t)stream;
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = view_cb8(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = cb8_view(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
   DevTmp tmp;
   const size_t nw = (size_t)Cout * Cin * taps;
   float* ddw = tmp.zeros(nw);
@@ -1289,9 +1275,9 @@ static int conv_packed(const void* x_cb8, const void* pack_dev, const void* bias
   if (bias_dev) HIP_TRY(hipMemcpyAsync(b, bias_dev, (size_t)Cout * sizeof(float), hipMemcpyDeviceToDevice, st));
   cw.w = (const float*)pack_dev; cw.bias = b;
   ConvLaunch L;
-  L.x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
+  L.x = cb8_view(const_cast<void*>(x_cb8), N, Cin, Z, S, S);
   L.w = cw;
-  L.y = view_cb8(y_cb8, N, Cout, Z, S, S);
+  L.y = cb8_view(y_cb8, N, Cout, Z, S, S);
   L.zmode = ZM_PAD1;
   HIP_TRY(launch_conv_mfma(L, st));
   return TM_OK;
@@ -1321,7 +1307,7 @@ extern "C" int tm_op_conv_wgrad_dev(const void* x_cb8, const void* dy_cb8, void*
   if (accumulate != 0 && accumulate != 1) return fail(TM_ERR_ARG, "accumulate must be 0 or 1");
   const int taps = ksize == 1 ? 1 : 27;
   hipStream_t st = (hipStream_t)stream;
-  TV x = view_cb8(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = view_cb8(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
+  TV x = cb8_view(const_cast<void*>(x_cb8), N, Cin, Z, S, S), dy = cb8_view(const_cast<void*>(dy_cb8), N, Cout, Z, S, S);
   DevTmp tmp(st);
   const size_t ns = conv_wgrad_scratch_floats(N, Z, S, Cin, Cout, taps);
   float* scratch = ns ? tmp.ordered_floats(ns, false) : nullptr;
@@ -1480,7 +1466,7 @@ extern "C" int tm_op_conv_wgrad_time(int N, int Cin, int Cout, int Z, int S, int
   if (int rc = resident_geo(N, Cin, Cout, Z, S, ksize)) return rc;
   const int taps = ksize == 1 ? 1 : 27;
   hipStream_t st = (hipStream_t)stream;
-  TV x = view_cb8(nullptr, N, Cin, Z, S, S), dy = view_cb8(nullptr, N, Cout, Z, S, S);
+  TV x = cb8_view(nullptr, N, Cin, Z, S, S), dy = cb8_view(nullptr, N, Cout, Z, S, S);
   const size_t nx = (size_t)N * x.nstride, ny = (size_t)N * dy.nstride, ns = conv_wgrad_scratch_floats(N, Z, S, Cin, Cout, taps);
   DevTmp tmp;
   x.p = tmp.alloc<float>(nx); dy.p = tmp.alloc<float>(ny);
