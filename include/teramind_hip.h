@@ -280,6 +280,49 @@ int tm_blosc_compress_tiles(const void* canvas, int dtype, int64_t canvas_elems,
                             int64_t pitch, const int64_t* origins, const int64_t* origins_host, int ntiles, void* packed,
                             int64_t packed_cap, int64_t* offsets, void* stream);
 
+/* ---- Blosc-lz4 decoder on the GPU: the way back from a step directory into a resident canvas ----------------------
+ * Reads what tm_blosc_decompress reads -- the frames of tm_blosc_compress_tiles and those c-blosc writes for zarr (any block
+ * size, so streams of any length; blocks split or not; byte shuffle or none; memcpyed frames as a plain copy; typesize 1, 2
+ * or 4) -- with the same leniency: the LZ4 end-of-block rules are not enforced, a file the host route reads reads the same
+ * here.  The host walks header, bstarts and stream lengths of every frame (its host mirror) before any device call; the
+ * kernels decode one stream per wave with the decoded history in LDS and never read back global memory they wrote.
+ *
+ * tm_blosc_frame_info: one frame (host memory, no device call).  TM_OK and *out filled: gpu = 1, the GPU decoder takes the
+ *   frame (nstreams and the longest stream's plain size set); gpu = 0, "host only": bit shuffle, a codec other than lz4, a
+ *   typesize other than 1 / 2 / 4 or more than 2^30 plain bytes (nstreams = longest = 0).  TM_ERR_ARG with a text: a frame
+ *   shorter than its header, cbytes beyond the buffer, a block table, bstarts entry or stream length outside the frame. */
+typedef struct tm_blosc_frame {
+  int64_t nbytes;        /* plain bytes */
+  int32_t typesize, blocksize, nstreams, longest, flags, gpu;
+} tm_blosc_frame;
+int tm_blosc_frame_info(const void* frame, size_t frame_bytes, tm_blosc_frame* out);
+
+/* tm_blosc_decompress_dev: nframes (1 .. 65535) frames; frame k is the bytes [frame_offsets[k], frame_offsets[k + 1]) of
+ *   `frames` (device, no alignment needed) and of `frames_host`, its host mirror (what the zip reader holds); frame_offsets
+ *   int64 [nframes + 1] host, non-decreasing from >= 0.  The plain bytes of frame k go to dst + dst_offsets[k] (device;
+ *   dst_offsets int64 [nframes] host, every range inside dst_cap; bytes outside the ranges are not written).
+ *   status int32 [nframes] device: 0, or which rule a stream of the frame broke (1 ends short of its plain size, 2 length
+ *   extension off the end, 3 literals past the stream, 4 literals past the plain size, 5 offset cut, 6 offset 0, 7 offset
+ *   beyond the bytes produced, 8 match past the plain size; the largest of the frame's streams).  A frame with a non-zero
+ *   status has no bytes delivered; the other frames of the call are unaffected.
+ *   TM_ERR_ARG with a text and nothing launched: anything tm_blosc_frame_info refuses or answers "host only", a null
+ *   pointer, a range outside dst_cap.  Asynchronous on `stream`; stream-ordered scratch of the plain size plus tables. */
+int tm_blosc_decompress_dev(const void* frames, const void* frames_host, const int64_t* frame_offsets, int nframes, void* dst,
+                            int64_t dst_cap, const int64_t* dst_offsets, int32_t* status, void* stream);
+
+/* tm_blosc_decompress_tiles: the same into a canvas (the mirror of tm_blosc_compress_tiles).  Frame k is a float16 chunk
+ *   [chunk[0]][chunk[1]][chunk[2]] (typesize 2, nbytes = 2 x its elements: zarr stores edge chunks full size); its element
+ *   (c, y, x) with c < clip[0], y < clip[1], x < clip[2] lands at origin + c * chan_stride + y * pitch + x of the canvas
+ *   (TM_DTYPE_F16: copied; TM_DTYPE_F32: widened, as .float() does); 1 <= clip[i] <= chunk[i].  boxes [nframes] host; every
+ *   box is checked against canvas_elems before any device call.  Elements outside the boxes are not written. */
+typedef struct tm_blosc_box {
+  int64_t origin;
+  int32_t chunk[3], clip[3];
+} tm_blosc_box;
+int tm_blosc_decompress_tiles(const void* frames, const void* frames_host, const int64_t* frame_offsets, int nframes, void* canvas,
+                              int dtype, int64_t canvas_elems, int64_t chan_stride, int64_t pitch, const tm_blosc_box* boxes,
+                              int32_t* status, void* stream);
+
 /* ---- slice export: the pyramid levels and JPEG tiles of infer_brn.get_ome --------
  * (infer_brn.py:11-54: `tiffsave(tile=True, compression='jpeg', pyramid=True, bigtiff=True, tile 256 x 256)`), computed
  * from a resident uint8 plane.  The container is written by teramind_amd.ometiff.

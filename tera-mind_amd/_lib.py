@@ -34,6 +34,15 @@ class TmProfStats(C.Structure):
                 ("executed_flops", C.c_double), ("alg_bytes", C.c_double)]
 
 
+class TmBloscFrame(C.Structure):
+    _fields_ = [("nbytes", C.c_int64), ("typesize", C.c_int32), ("blocksize", C.c_int32), ("nstreams", C.c_int32),
+                ("longest", C.c_int32), ("flags", C.c_int32), ("gpu", C.c_int32)]
+
+
+class TmBloscBox(C.Structure):
+    _fields_ = [("origin", C.c_int64), ("chunk", C.c_int32 * 3), ("clip", C.c_int32 * 3)]
+
+
 # name -> (restype, argtypes); mirrors include/teramind_hip.h one to one
 SIGNATURES = {
     "tm_version": (c_int, []),
@@ -73,6 +82,9 @@ SIGNATURES = {
     "tm_blosc_compress": (c_int, [c_void_p, c_size_t, c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "tm_blosc_compress_tiles": (c_int, [c_void_p, c_int, C.c_int64] + [c_int] * 3 + [C.c_int64] * 2 + [c_void_p, c_void_p, c_int, c_void_p,
                                         C.c_int64, c_void_p, c_void_p]),
+    "tm_blosc_frame_info": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "tm_blosc_decompress_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, C.c_int64, c_void_p, c_void_p, c_void_p]),
+    "tm_blosc_decompress_tiles": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int] + [C.c_int64] * 3 + [c_void_p] * 3),
     "tm_u8_shrink2": (c_int, [c_void_p, c_int, c_int, C.c_int64, c_void_p, C.c_int64, c_void_p]),
     "tm_jpeg_encode_tiles": (c_int, [c_void_p, c_int, c_int, C.c_int64] + [c_int] * 3 + [c_void_p, C.c_int64] + [c_void_p] * 4),
     "tm_jpeg_tables": (c_int, [c_int, c_void_p, c_size_t, C.POINTER(c_size_t)]),

@@ -100,7 +100,8 @@ class TileSweep:
         W = wnm * tiles.TILE + 2 * PAD
         self.epoch = 0
         self._pending, self._noise_tiles, self._noise_cap = {}, {}, 18
-        self.snapshot_tiles = 64                         # save_step(compressor="blosc"): tiles per encoder call
+        self.snapshot_tiles = 64                         # save_step(compressor="blosc") / load_step(decoder="gpu"): tiles per call
+        self.decode_fallbacks = 0                        # load_step(decoder="gpu"): tiles of the last call that took the host route
         # halo-exchange accounting (bench.py --sweep): seconds (device-synchronised when time_exchange is set), bytes
         # sent + received by this rank, number of exchanges
         self.time_exchange, self.exchange_s, self.exchange_bytes, self.exchanges = False, 0.0, 0, 0
@@ -468,18 +469,29 @@ class TileSweep:
                         name = tiles.state_tile_name(self.row0 + self.r0 + lr, self.col0 + c0 + k)
                         formats.write_zarr_zip_blosc(os.path.join(d, name + ".zip"), (self.chn, T_, T_), "<f2", frames[off[k]:off[k + 1]])
 
-    def load_step(self, out_dir, epoch: int):
+    def load_step(self, out_dir, epoch: int, decoder: str = "host"):
         """Resume from a reference-format step directory (`--cur_epoch`, test_brn.py:290-292): read this rank's
         tiles of '{out_dir}_{epoch}', then exchange halos.  Works on directories written by the reference
-        (Blosc-lz4 chunks) and by save_step."""
+        (Blosc-lz4 chunks) and by save_step.
+        decoder: "host" decodes tile by tile on the host and copies the plain tiles; "gpu" copies the chunk members of up to
+        `snapshot_tiles` tiles as they are and decodes them on the GPU straight into the canvas (tm_blosc_decompress_tiles;
+        either canvas layout, the same bits as "host").  A tile the GPU decoder does not take (zlib or raw chunks, a "host
+        only" frame) goes through the host route and is counted in `self.decode_fallbacks`."""
         import os
         import numpy as np
         from . import formats
+        if decoder not in ("host", "gpu"):
+            raise ValueError(f"decoder must be 'host' or 'gpu', got {decoder!r}")
         if not 0 < epoch <= self.T:
             raise ValueError(f"epoch {epoch} outside 1..{self.T}")
         d = self.step_dir(out_dir, epoch)
         self.cur.fill_(-1.0)
         self._pending, self._noise_tiles = {}, {}
+        if decoder == "gpu":
+            self._load_step_gpu(d)
+            self.epoch = epoch
+            self._exchange(self.cur)
+            return
         for lr in range(self.nrows):
             for c in range(self.wnm):
                 name = tiles.state_tile_name(self.row0 + self.r0 + lr, self.col0 + c)
@@ -489,6 +501,42 @@ class TileSweep:
                 self._centre(self.cur, lr, c).copy_(torch.from_numpy(a.astype(np.float32)))
         self.epoch = epoch
         self._exchange(self.cur)
+
+    def _load_step_gpu(self, d):
+        """load_step(decoder="gpu"): per `snapshot_tiles` tiles one host buffer of their chunk members, one copy to the device
+        and one decoder call into the canvas; then the status of every frame is checked."""
+        import os
+        import numpy as np
+        from . import formats
+        if not self.cur.is_cuda:
+            raise RuntimeError("load_step(decoder='gpu') decodes on the GPU: the sweep's canvas is not on one")
+        cur, T_ = self.cur, tiles.TILE
+        assert cur.is_contiguous()
+        self.decode_fallbacks = 0
+        todo = [(lr, c) for lr in range(self.nrows) for c in range(self.wnm)]
+        per = max(1, int(self.snapshot_tiles))
+        for g0 in range(0, len(todo), per):
+            jobs, owner = [], []
+            for lr, c in todo[g0:g0 + per]:
+                name = tiles.state_tile_name(self.row0 + self.r0 + lr, self.col0 + c)
+                path = os.path.join(d, name + ".zip")
+                meta, members = formats.read_zarr_zip_frames(path)
+                if tuple(meta["shape"]) != (self.chn, T_, T_):
+                    raise ValueError(f"{name}.zip: shape {tuple(meta['shape'])}, expected {(self.chn, T_, T_)}")
+                origin = (PAD + lr * T_) * cur.stride(1) + PAD + c * T_
+                tile_jobs = formats.gpu_chunk_jobs(path, meta, members, origin, cur.stride(0), cur.stride(1))
+                if tile_jobs is None:                               # the host route, for this tile
+                    self.decode_fallbacks += 1
+                    a = formats.read_state_tile(path)
+                    self._centre(cur, lr, c).copy_(torch.from_numpy(a.astype(np.float32)))
+                    continue
+                jobs += tile_jobs
+                owner += [path] * len(tile_jobs)
+            if jobs:
+                status = formats.decode_chunks_dev(cur, jobs)
+                for path, st in zip(owner, status):
+                    if st:
+                        raise ValueError(f"{path}: corrupt Blosc-lz4 stream (decoder status {st})")
 
 
 def synthetic_gene_provider(conf: PathConfig, total_slc: int = 50, density: float = 0.02, device="cpu"):

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/teramind_hip.h"
 
 namespace tmk {
@@ -436,6 +438,34 @@ size_t blosc_scratch_bytes(const BloscGeo& g, int nframes);
 // *total (device) are optional; scratch: blosc_scratch_bytes(g, nframes) bytes, 4-byte aligned
 hipError_t launch_blosc_frames(const BloscSrc& src, const BloscGeo& g, int nframes, void* scratch, uint8_t* packed, int64_t* offsets,
                                int64_t* total, hipStream_t s);
+
+// Blosc-lz4 decoder (tm_blosc.hip).  The host walks the frames' headers, bstarts and stream lengths (blosc_dec_walk: every
+// range checked against the frame) into a stream table; the device never parses a frame.
+struct BloscStream {                           // one LZ4 (or stored: clen == plen) stream
+  long long src, dst;                          // byte offsets: in the device copy of the frames, in the scratch
+  int clen, plen, frame, pad;
+};
+struct BloscDecFrame {                         // one frame for blosc_unshuffle_kernel
+  long long scratch, dst;                      // bytes in the scratch (16-byte aligned); plain sink: byte offset, canvas sink: element origin
+  int nbytes, typesize, blocksize, shuffled;
+  int chunk[3], clip[3];                       // canvas sink: the chunk [C][H][W] and the part of it inside the array
+};
+struct BloscDecInfo { long long nbytes; int typesize, blocksize, nstreams, longest, flags, gpu; };
+enum { BLOSC_SINK_BYTES = 0, BLOSC_SINK_F16 = 1, BLOSC_SINK_F32 = 2 };
+struct BloscSink {
+  void* base;                                  // BYTES: dst; F16 / F32: the canvas
+  int mode;
+  long cstride, pitch;                         // canvas: channel stride and row pitch in elements
+};
+// One frame of `len` bytes at f (host).  TM_OK with info->gpu = 0: a frame the host decoder may read and the GPU decoder does
+// not take (nothing appended); TM_ERR_ARG with a text: a range outside the frame.  Otherwise the frame's streams are appended
+// to *tab (if given) with src relative to src_base and dst to dst_base, and *longest_lz4 (if given) is raised to the longest
+// plain size of a stream that is not stored.
+int blosc_dec_walk(const char* fn, int k, const uint8_t* f, size_t len, BloscDecInfo* info, std::vector<BloscStream>* tab, long long src_base,
+                   long long dst_base, int* longest_lz4);
+// decode `nstreams` streams into the scratch, then unshuffle `nframes` frames into the sink; status [nframes] is zeroed first
+hipError_t launch_blosc_decode(const uint8_t* frames, const BloscStream* tab, int nstreams, int longest_lz4, const BloscDecFrame* fr,
+                               int nframes, int max_nbytes, uint8_t* scratch, const BloscSink& sink, int32_t* status, hipStream_t s);
 
 // ---- ROI evaluation (tm_metrics.hip) -----------------------------------------------------
 // SSIM statistics of P plane pairs: the valid output is cut into SSIM_TW x SSIM_TH tiles, one workgroup each

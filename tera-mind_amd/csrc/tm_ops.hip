@@ -1401,6 +1401,126 @@ extern "C" int tm_blosc_compress_tiles(const void* canvas, int dtype, int64_t ca
   return blosc_run(s, g, ntiles, packed, offsets, nullptr, (hipStream_t)stream);
 }
 
+// Blosc-lz4 decoder (tm_blosc.hip): the host walks the frames into a stream table (every range checked), then enqueues
+extern "C" int tm_blosc_frame_info(const void* frame, size_t frame_bytes, tm_blosc_frame* out) {
+  const char* fn = "tm_blosc_frame_info";
+  if (!frame || !out) return fail(TM_ERR_ARG, "%s: null frame / out pointer", fn);
+  BloscDecInfo in = {};
+  const int rc = blosc_dec_walk(fn, 0, (const uint8_t*)frame, frame_bytes, &in, nullptr, 0, 0, nullptr);
+  out->nbytes = in.nbytes; out->typesize = in.typesize; out->blocksize = in.blocksize; out->flags = in.flags;
+  out->nstreams = rc == TM_OK && in.gpu ? in.nstreams : 0;
+  out->longest = rc == TM_OK && in.gpu ? in.longest : 0;
+  out->gpu = rc == TM_OK ? in.gpu : 0;
+  return rc;
+}
+namespace {
+struct BloscDecPlan {
+  std::vector<BloscStream> tab;
+  std::vector<BloscDecFrame> fr;
+  size_t scratch = 0;
+  int longest_lz4 = 0, max_nbytes = 0;
+};
+}  // namespace
+// walks every frame of the host mirror; fr[k].dst and the canvas fields are left to the caller
+static int blosc_dec_plan(const char* fn, const void* frames_host, const int64_t* frame_offsets, int nframes, BloscDecPlan* P) {
+  if (!frames_host || !frame_offsets) return fail(TM_ERR_ARG, "%s: null host mirror of the frames / frame_offsets pointer", fn);
+  if (nframes < 1 || nframes > 65535) return fail(TM_ERR_ARG, "%s: nframes = %d outside 1 .. 65535", fn, nframes);
+  if (frame_offsets[0] < 0) return fail(TM_ERR_ARG, "%s: frame_offsets[0] is negative", fn);
+  for (int k = 0; k < nframes; ++k)
+    if (frame_offsets[k + 1] < frame_offsets[k]) return fail(TM_ERR_ARG, "%s: frame_offsets decrease at frame %d", fn, k);
+  P->tab.clear(); P->fr.assign((size_t)nframes, BloscDecFrame{});
+  for (int k = 0; k < nframes; ++k) {
+    BloscDecInfo in = {};
+    const uint8_t* f = (const uint8_t*)frames_host + frame_offsets[k];
+    if (int rc = blosc_dec_walk(fn, k, f, (size_t)(frame_offsets[k + 1] - frame_offsets[k]), &in, &P->tab, frame_offsets[k], (long long)P->scratch,
+                                &P->longest_lz4))
+      return rc;
+    if (!in.gpu)
+      return fail(TM_ERR_ARG, "%s: frame %d is host only (flags 0x%02x, typesize %d, %lld bytes): bit shuffle, a codec other than lz4, a typesize "
+                  "other than 1 / 2 / 4 or more than 2^30 bytes go through tm_blosc_decompress", fn, k, in.flags, in.typesize, in.nbytes);
+    BloscDecFrame& d = P->fr[(size_t)k];
+    const bool memcpyed = in.flags & 2;
+    d.scratch = (long long)P->scratch; d.nbytes = (int)in.nbytes; d.typesize = in.typesize;
+    d.blocksize = memcpyed || in.blocksize < 1 ? (in.nbytes > 0 ? (int)in.nbytes : 1) : in.blocksize;
+    d.shuffled = !memcpyed && (in.flags & 1) && in.typesize > 1;
+    if (d.nbytes > P->max_nbytes) P->max_nbytes = d.nbytes;
+    P->scratch += ((size_t)in.nbytes + 15) & ~(size_t)15;
+  }
+  if (P->tab.size() > (size_t)INT32_MAX) return fail(TM_ERR_ARG, "%s: %zu streams in one call", fn, P->tab.size());
+  return TM_OK;
+}
+static int blosc_dec_run(const char* fn, const void* frames, BloscDecPlan& P, const BloscSink& sink, int32_t* status, hipStream_t st) {
+  DevTmp tmp(st);
+  const size_t tab_b = (P.tab.size() * sizeof(BloscStream) + 15) & ~(size_t)15, fr_b = (P.fr.size() * sizeof(BloscDecFrame) + 15) & ~(size_t)15;
+  uint8_t* dev = (uint8_t*)tmp.ordered_floats((P.scratch + tab_b + fr_b) / 4, false);   // the frames' images (16-byte multiples), the tables
+  if (tmp.err) return tmp.report();
+  uint8_t* tab_d = dev + P.scratch;
+  uint8_t* fr_d = tab_d + tab_b;
+  // pageable host memory: the runtime has taken the bytes when the call returns
+  if (!P.tab.empty()) HIP_TRY(hipMemcpyAsync(tab_d, P.tab.data(), P.tab.size() * sizeof(BloscStream), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(fr_d, P.fr.data(), P.fr.size() * sizeof(BloscDecFrame), hipMemcpyHostToDevice, st));
+  HIP_TRY(launch_blosc_decode((const uint8_t*)frames, (const BloscStream*)tab_d, (int)P.tab.size(), P.longest_lz4, (const BloscDecFrame*)fr_d,
+                              (int)P.fr.size(), P.max_nbytes, dev, sink, status, st));
+  (void)fn;
+  return TM_OK;
+}
+extern "C" int tm_blosc_decompress_dev(const void* frames, const void* frames_host, const int64_t* frame_offsets, int nframes, void* dst,
+                                       int64_t dst_cap, const int64_t* dst_offsets, int32_t* status, void* stream) {
+  const char* fn = "tm_blosc_decompress_dev";
+  static thread_local BloscDecPlan P;
+  P = BloscDecPlan();
+  if (int rc = blosc_dec_plan(fn, frames_host, frame_offsets, nframes, &P)) return rc;
+  if (!frames || !dst || !dst_offsets || !status) return fail(TM_ERR_ARG, "%s: null frames / dst / dst_offsets / status pointer", fn);
+  for (int k = 0; k < nframes; ++k) {
+    if (dst_offsets[k] < 0 || dst_offsets[k] > dst_cap - P.fr[(size_t)k].nbytes)
+      return fail(TM_ERR_ARG, "%s: frame %d: %d bytes at offset %lld leave the destination of %lld bytes", fn, k, P.fr[(size_t)k].nbytes,
+                  (long long)dst_offsets[k], (long long)dst_cap);
+    P.fr[(size_t)k].dst = dst_offsets[k];
+  }
+  BloscSink sink = {};
+  sink.base = dst; sink.mode = BLOSC_SINK_BYTES;
+  return blosc_dec_run(fn, frames, P, sink, status, (hipStream_t)stream);
+}
+extern "C" int tm_blosc_decompress_tiles(const void* frames, const void* frames_host, const int64_t* frame_offsets, int nframes, void* canvas,
+                                         int dtype, int64_t canvas_elems, int64_t chan_stride, int64_t pitch, const tm_blosc_box* boxes,
+                                         int32_t* status, void* stream) {
+  const char* fn = "tm_blosc_decompress_tiles";
+  static thread_local BloscDecPlan P;
+  P = BloscDecPlan();
+  if (int rc = blosc_dec_plan(fn, frames_host, frame_offsets, nframes, &P)) return rc;
+  if (!frames || !canvas || !boxes || !status) return fail(TM_ERR_ARG, "%s: null frames / canvas / boxes / status pointer", fn);
+  if (dtype != TM_DTYPE_F32 && dtype != TM_DTYPE_F16) return fail(TM_ERR_ARG, "%s: dtype %d is neither TM_DTYPE_F32 nor TM_DTYPE_F16", fn, dtype);
+  if ((uintptr_t)canvas & (dtype == TM_DTYPE_F32 ? 3 : 1)) return fail(TM_ERR_ARG, "%s: canvas pointer is not aligned to its element", fn);
+  if (pitch < 1 || chan_stride < 1) return fail(TM_ERR_ARG, "%s: pitch and chan_stride must be positive", fn);
+  for (int k = 0; k < nframes; ++k) {
+    const tm_blosc_box& b = boxes[k];
+    BloscDecFrame& d = P.fr[(size_t)k];
+    int64_t elems = 1;
+    for (int i = 0; i < 3; ++i) {
+      if (b.chunk[i] < 1 || b.clip[i] < 1 || b.clip[i] > b.chunk[i])
+        return fail(TM_ERR_ARG, "%s: frame %d: chunk %d x %d x %d, clip %d x %d x %d (1 <= clip <= chunk)", fn, k, b.chunk[0], b.chunk[1], b.chunk[2],
+                    b.clip[0], b.clip[1], b.clip[2]);
+      elems *= b.chunk[i];
+      if (elems > (int64_t)1 << 29) return fail(TM_ERR_ARG, "%s: frame %d: a chunk of more than 2^29 elements", fn, k);
+    }
+    if (d.typesize != 2 || (int64_t)d.nbytes != 2 * elems)
+      return fail(TM_ERR_ARG, "%s: frame %d holds %d bytes at typesize %d, not the %lld float16 of its chunk", fn, k, d.nbytes, d.typesize, (long long)elems);
+    if (pitch < b.clip[2]) return fail(TM_ERR_ARG, "%s: frame %d: row pitch %lld below the %d columns kept", fn, k, (long long)pitch, b.clip[2]);
+    const int64_t plane = (int64_t)(b.clip[1] - 1) * pitch + b.clip[2];
+    if (chan_stride < plane) return fail(TM_ERR_ARG, "%s: frame %d: channel stride %lld below the %lld elements a channel spans", fn, k, (long long)chan_stride, (long long)plane);
+    const int64_t span = (int64_t)(b.clip[0] - 1) * chan_stride + plane;
+    if (b.origin < 0 || b.origin > canvas_elems - span)
+      return fail(TM_ERR_ARG, "%s: frame %d at element %lld (+ %lld) leaves the canvas of %lld elements", fn, k, (long long)b.origin, (long long)span,
+                  (long long)canvas_elems);
+    d.dst = b.origin;
+    for (int i = 0; i < 3; ++i) { d.chunk[i] = b.chunk[i]; d.clip[i] = b.clip[i]; }
+  }
+  BloscSink sink = {};
+  sink.base = canvas; sink.mode = dtype == TM_DTYPE_F32 ? BLOSC_SINK_F32 : BLOSC_SINK_F16;
+  sink.cstride = (long)chan_stride; sink.pitch = (long)pitch;
+  return blosc_dec_run(fn, frames, P, sink, status, (hipStream_t)stream);
+}
+
 // SSIM / PSNR sums of plane pairs (tm_metrics.hip); enqueues only, the per-tile partials are stream-ordered scratch
 static int pix_geometry(const char* fn, const char* what, const void* p, int dtype, int W, int64_t pitch, int64_t plane) {
   const int64_t esz = dtype == TM_PIX_F32 ? 4 : 1;

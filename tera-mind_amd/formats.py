@@ -194,5 +194,126 @@ def read_state_tile(path) -> np.ndarray:
     return a
 
 
+# ---- state tiles decoded on the GPU (tm_blosc_decompress_tiles) ------------------------------------------------------
+def read_zarr_zip_frames(path):
+    """-> (the .zarray metadata, {chunk key: the member's raw bytes}): the container opened as read_zarr_zip opens it, nothing
+    decoded.  Chunks that are absent from the archive (fill value) are absent from the dict."""
+    with zipfile.ZipFile(path) as z:
+        names = set(z.namelist())
+        if ".zarray" not in names:
+            raise ValueError(f"{path}: no .zarray at the archive root (not a zarr-v2 array store)")
+        meta = json.loads(z.read(".zarray"))
+        if meta.get("zarr_format") != 2:
+            raise ValueError(f"{path}: zarr_format {meta.get('zarr_format')!r}, expected 2")
+        if meta.get("filters"):
+            raise NotImplementedError("zarr filters")
+        shape, chunks = tuple(meta["shape"]), tuple(meta["chunks"])
+        sep = meta.get("dimension_separator", ".")
+        members = {}
+        for idx in product(*[range((s + c - 1) // c) for s, c in zip(shape, chunks)]):
+            key = sep.join(str(i) for i in idx) if idx else "0"
+            if key in names:
+                members[key] = z.read(key)
+    return meta, members
+
+
+def blosc_frame_info(buf: bytes, what="frame"):
+    """tm_blosc_frame_info of one frame -> _lib.TmBloscFrame (.gpu: the GPU decoder takes it); ValueError for a frame whose
+    ranges leave it."""
+    from . import _lib
+    L = _lib.lib()
+    info = _lib.TmBloscFrame()
+    if L.tm_blosc_frame_info(buf, len(buf), C.byref(info)) != 0:
+        raise ValueError(f"{what}: {L.tm_last_error().decode(errors='replace')}")
+    return info
+
+
+def gpu_chunk_jobs(path, meta, members, origin: int, chan_stride: int, pitch: int):
+    """The chunks of one float16 [C, H, W] array as jobs of decode_chunks_dev: [(frame, origin element, chunk shape, clipped
+    shape)] with element (c, y, x) of the array at origin + c * chan_stride + y * pitch + x -- or None where the GPU decoder
+    does not take the array (not Blosc, not float16 in C order, a chunk absent, a "host only" frame): the host route's."""
+    comp = meta.get("compressor")
+    shape, chunks = tuple(meta["shape"]), tuple(meta["chunks"])
+    if not comp or comp.get("id") != "blosc" or np.dtype(meta["dtype"]) != np.dtype("<f2") or meta.get("order", "C") != "C" or len(shape) != 3:
+        return None
+    sep = meta.get("dimension_separator", ".")
+    jobs = []
+    for idx in product(*[range((s + c - 1) // c) for s, c in zip(shape, chunks)]):
+        frame = members.get(sep.join(str(i) for i in idx))
+        if frame is None:
+            return None
+        info = blosc_frame_info(frame, f"{path}, chunk {idx}")
+        if not info.gpu:
+            return None
+        if info.typesize != 2 or info.nbytes != 2 * int(np.prod(chunks)):
+            raise ValueError(f"{path}, chunk {idx}: a frame of {info.nbytes} bytes at typesize {info.typesize}, not a float16 chunk {chunks}")
+        clip = tuple(min(c, s - i * c) for i, c, s in zip(idx, chunks, shape))
+        at = origin + idx[0] * chunks[0] * chan_stride + idx[1] * chunks[1] * pitch + idx[2] * chunks[2]
+        jobs.append((frame, at, chunks, clip))
+    return jobs
+
+
+decode_timings = None            # a list: decode_chunks_dev appends (ms of the decoder call by hipEvents, frames, frame bytes); tools/bench_load_step.py
+
+
+def decode_chunks_dev(canvas, jobs):
+    """One host buffer of the jobs' frames, one copy to canvas.device, one tm_blosc_decompress_tiles into `canvas` (a contiguous
+    float16 / float32 [C, H, W] device tensor) -> the per-frame status as a list (0: decoded; see teramind_hip.h)."""
+    import torch
+    from . import _lib
+    L = _lib.lib()
+    assert canvas.is_cuda and canvas.is_contiguous() and canvas.dim() == 3
+    n = len(jobs)
+    offs = np.zeros(n + 1, np.int64)
+    for k, job in enumerate(jobs):
+        offs[k + 1] = offs[k] + ((len(job[0]) + 15) & ~15)              # frames start at multiples of 16
+    host = np.zeros(int(offs[n]), np.uint8)
+    boxes = (_lib.TmBloscBox * n)()
+    for k, (frame, at, chunks, clip) in enumerate(jobs):
+        host[offs[k]:offs[k] + len(frame)] = np.frombuffer(frame, np.uint8)
+        boxes[k].origin = at
+        boxes[k].chunk[:], boxes[k].clip[:] = chunks, clip
+    with torch.cuda.device(canvas.device):
+        dev = torch.from_numpy(host).to(canvas.device)
+        status = torch.empty(n, dtype=torch.int32, device=canvas.device)
+        dtype = {torch.float32: 0, torch.float16: 2}[canvas.dtype]                       # TM_DTYPE_F32 / TM_DTYPE_F16
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if decode_timings is not None else None
+        if ev:
+            ev[0].record()
+        _lib.check(L.tm_blosc_decompress_tiles(_lib.ptr(dev), host.ctypes.data, offs.ctypes.data, n, _lib.ptr(canvas), dtype, canvas.numel(),
+                                               canvas.stride(0), canvas.stride(1), C.cast(boxes, C.c_void_p), _lib.ptr(status),
+                                               _lib.current_stream_ptr()), "tm_blosc_decompress_tiles")
+        if ev:
+            ev[1].record()
+        out = status.cpu().tolist()                                     # waits for the stream: `dev` and `host` may go
+        if ev:
+            decode_timings.append((ev[0].elapsed_time(ev[1]), n, int(offs[n])))
+        return out
+
+
+def read_zarr_zip_dev(path, device):
+    """read_zarr_zip as a tensor on `device`: a float16 [C, H, W] array of Blosc-lz4 chunks is decoded there (-> (tensor, True)),
+    anything else is read on the host and copied (-> (tensor, False))."""
+    import torch
+    meta, members = read_zarr_zip_frames(path)
+    shape = tuple(meta["shape"])
+    jobs = gpu_chunk_jobs(path, meta, members, 0, shape[1] * shape[2], shape[2]) if len(shape) == 3 else None
+    if jobs is None:
+        return torch.from_numpy(read_zarr_zip(path)).to(device), False
+    out = torch.empty(shape, dtype=torch.float16, device=device)
+    status = decode_chunks_dev(out, jobs)
+    if any(status):
+        raise ValueError(f"{path}: corrupt Blosc-lz4 stream (decoder status {max(status)})")
+    return out, True
+
+
+def read_state_tile_dev(path, device):
+    """read_state_tile as a float16 tensor on `device`, decoded there where the file holds Blosc-lz4 chunks."""
+    a = read_zarr_zip_dev(path, device)[0]
+    if a.dim() != 3:
+        raise ValueError(f"{path}: state tile must be 3-D, got {tuple(a.shape)}")
+    return a
+
+
 def write_state_tile(path, tile, compressor: Optional[str] = None):
     write_zarr_zip(path, np.asarray(tile, dtype=np.float16), compressor)

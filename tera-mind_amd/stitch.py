@@ -37,15 +37,31 @@ def stitch_state(state: torch.Tensor, slc: int = 50, slices: Optional[Sequence[i
     return out if slices is None else out[list(slices)]
 
 
+def _decoder_device(decoder: str, device):
+    if decoder not in ("host", "gpu"):
+        raise ValueError(f"decoder must be 'host' or 'gpu', got {decoder!r}")
+    return None if decoder == "host" else torch.device("cuda" if device is None else device)
+
+
 def stitch_dir(step_dir, hst: int, wst: int, hnm: int, wnm: int, slc: int = 50,
-               slices: Optional[Sequence[int]] = None, size: int = tiles.TILE) -> np.ndarray:
+               slices: Optional[Sequence[int]] = None, size: int = tiles.TILE, decoder: str = "host", device=None):
     """Mosaic of a reference-format step directory ('{r0}_{r1}_{c0}_{c1}.zip' tiles; infer_brn.py:70-76 with
-    is_gen=True) -> uint8 [n_slices, hnm*size, wnm*size]."""
+    is_gen=True) -> uint8 [n_slices, hnm*size, wnm*size].  decoder="gpu": the tiles are decoded on `device`
+    (formats.read_state_tile_dev), `to_uint8` / `reorder_slices` run there and the mosaic is a uint8 tensor on it, equal to
+    the host route's array."""
+    dev = _decoder_device(decoder, device)
     out = None
     for pw in range(wnm):
         for ph in range(hnm):
             r0, c0 = hst + ph * size, wst + pw * size
-            a = formats.read_state_tile(os.path.join(str(step_dir), f"{r0}_{r0 + size}_{c0}_{c0 + size}.zip"))
+            path = os.path.join(str(step_dir), f"{r0}_{r0 + size}_{c0}_{c0 + size}.zip")
+            if dev is not None:
+                t = stitch_state(formats.read_state_tile_dev(path, dev), slc, slices)
+                if out is None:
+                    out = torch.zeros((t.shape[0], hnm * size, wnm * size), dtype=torch.uint8, device=dev)
+                out[:, ph * size:(ph + 1) * size, pw * size:(pw + 1) * size] = t
+                continue
+            a = formats.read_state_tile(path)
             t = stitch_state(torch.from_numpy(a), slc, slices).numpy()
             if out is None:
                 out = np.zeros((t.shape[0], hnm * size, wnm * size), dtype=np.uint8)
@@ -54,15 +70,30 @@ def stitch_dir(step_dir, hst: int, wst: int, hnm: int, wnm: int, slc: int = 50,
 
 
 def stitch_real_dir(rdir, hst: int, wst: int, hnm: int, wnm: int, slc: int = 50,
-                    slices: Optional[Sequence[int]] = None, size: int = tiles.TILE) -> np.ndarray:
+                    slices: Optional[Sequence[int]] = None, size: int = tiles.TILE, decoder: str = "host", device=None):
     """Mosaic of a directory of real tiles (infer_brn.py:67-77 with is_gen=False, test_brn.py:93-99): eight-number names
     '{r0}_{r1}_{c0}_{c1}_{r0-p}_{r1+p}_{c0-p}_{c1+p}.zip' with the frame p = size // 2, arrays [(c s), size + 2p, size + 2p]
-    in image units.  The centre is cut, '(c s) -> (s c)', `.astype(uint8)` -> uint8 [n_slices, hnm*size, wnm*size]."""
+    in image units.  The centre is cut, '(c s) -> (s c)', `.astype(uint8)` -> uint8 [n_slices, hnm*size, wnm*size].
+    decoder="gpu": as in stitch_dir (float16 Blosc-lz4 tiles are decoded on `device`, others read on the host and copied)."""
+    dev = _decoder_device(decoder, device)
     out, p = None, size // 2
     for pw in range(wnm):
         for ph in range(hnm):
             r0, c0 = hst + ph * size, wst + pw * size
             name = f"{r0}_{r0 + size}_{c0}_{c0 + size}_{r0 - p}_{r0 + size + p}_{c0 - p}_{c0 + size + p}.zip"
+            if dev is not None:
+                a = formats.read_zarr_zip_dev(os.path.join(str(rdir), name), dev)[0]
+                if a.dim() != 3 or a.shape[1] < size + p or a.shape[2] < size + p:
+                    raise ValueError(f"{name}: a real tile is [(c s), {size + 2 * p}, {size + 2 * p}], got {tuple(a.shape)}")
+                if a.shape[0] % slc:
+                    raise ValueError(f"{name}: {a.shape[0]} planes are no multiple of slc = {slc}")
+                t = reorder_slices(a[:, p:p + size, p:p + size], slc).to(torch.uint8)
+                if slices is not None:
+                    t = t[list(slices)]
+                if out is None:
+                    out = torch.zeros((t.shape[0], hnm * size, wnm * size), dtype=torch.uint8, device=dev)
+                out[:, ph * size:(ph + 1) * size, pw * size:(pw + 1) * size] = t
+                continue
             a = formats.read_zarr_zip(os.path.join(str(rdir), name))
             if a.ndim != 3 or a.shape[1] < size + p or a.shape[2] < size + p:
                 raise ValueError(f"{name}: a real tile is [(c s), {size + 2 * p}, {size + 2 * p}], got {a.shape}")

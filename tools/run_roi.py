@@ -61,15 +61,22 @@ def worker(args):
     def on_step(sw, s):
         if rank == 0:
             print(f"[run_roi] step {sw.epoch}/{T}: {s:.2f} s  (process age {time.monotonic() - _T_START:.0f} s)", file=sys.stderr, flush=True)
+        if args.save_steps and sw.epoch < T:    # every step's directory, as the reference leaves them (test_brn.py:241-249)
+            sw.save_step(os.path.join(args.out_dir, "timestep"), compressor=None if args.tile_compressor == "none" else args.tile_compressor)
         # the GPU runner ends a command at a fixed wall-clock limit: never start a step that cannot finish inside it
         if args.deadline_s and sw.epoch < T and time.monotonic() - _T_START + 1.03 * s > args.deadline_s:
             raise Deadline()
 
     steps_done = T
+    first = args.cur_epoch or 0                 # --cur_epoch N: the state after N steps comes from '{out_dir}/timestep_N' (test_brn.py:290-292)
+    resume = None
+    if first:
+        def resume():
+            holder["sweep"].load_step(os.path.join(args.out_dir, "timestep"), first, decoder=args.tile_decoder)
     try:
         res = launch.run_sweep(cfg, SpacedDiffusionBeatGans(T, "ddim"), model, genes, hnm=args.hnm, wnm=args.wnm, total_epochs=T,
-                               steps=T, warmup=0, device=dev, batch_tiles=args.batch_tiles, init=args.init, state=args.state,
-                               on_step=on_step, holder=holder, share_halo=bool(args.share_halo),
+                               steps=T - first, warmup=0, device=dev, batch_tiles=args.batch_tiles, init=args.init, state=args.state,
+                               on_step=on_step, after_warmup=resume, holder=holder, share_halo=bool(args.share_halo),
                                batch_rows=args.batch_rows, prefetch_genes=not args.share_halo,
                                cache_level0=bool(args.cache_level0))
     except Deadline:
@@ -112,10 +119,12 @@ def worker(args):
                 raise SystemExit("--pyramid with several ranks needs the tile files (drop --no_tile_files)")
             pyr_s = round(time.perf_counter() - t4, 2)
         tiles = args.hnm * args.wnm
-        T = steps_done
+        T = max(1, steps_done - first)          # steps run by this process
+        per_step = per_step or [0.0]
+        sweep_s = sweep_s or 1e-9
         print(json.dumps({"what": "full ROI sweep, measured", "steps_requested": args.tot_epoch, "steps_measured": steps_done,
                           "step_s": [round(v, 2) for v in per_step], "process_age_s": round(time.monotonic() - _T_START, 1),
-                          "tile_files_written": d is not None, "tile_compressor": args.tile_compressor, "dtype": args.dtype, "state": args.state, "tiles": tiles, "T": T,
+                          "resumed_from_step": first or None, "tile_decoder": args.tile_decoder, "tile_files_written": d is not None, "tile_compressor": args.tile_compressor, "dtype": args.dtype, "state": args.state, "tiles": tiles, "T": T,
                           "n_gpus": world, "genes": "on-disk COO .npz via GeneTileDir + tm_gene_tile_dense" if args.gene_dir else "synthetic, device resident",
                           "init": args.init, "batch_tiles": args.batch_tiles, "share_halo": bool(args.share_halo), "batch_rows": args.batch_rows, "cache_level0": bool(args.cache_level0), "overlap_streams": args.overlap_streams,
                           "sweep_s": round(sweep_s, 2), "sweep_min": round(sweep_s / 60, 2), "s_per_tile_step": round(sweep_s * world / (tiles * T), 4),
@@ -158,11 +167,27 @@ def main():
     ap.add_argument("--tile_compressor", choices=["none", "zlib", "blosc"], default="none",
                     help="chunk encoding of the state tile files: raw, zlib on the host, or Blosc-lz4 frames encoded on the GPU "
                          "(what zarr.save_array writes by default)")
+    ap.add_argument("--cur_epoch", type=int, default=None, metavar="N",
+                    help="resume: read the state after N steps from '<out_dir>/timestep_N' (written by an earlier run with --save_steps, or "
+                         "by the reference) and run steps N + 1 .. tot_epoch (test_brn.py:290-292)")
+    ap.add_argument("--tile_decoder", choices=["host", "gpu"], default="host",
+                    help="with --cur_epoch: decode the tile files on the host, or their Blosc-lz4 chunks on the GPU straight into the canvas")
+    ap.add_argument("--save_steps", action="store_true", help="write '<out_dir>/timestep_<k>' after every step, not only after the last")
     ap.add_argument("--pyramid", action="store_true",
                     help="also export every plane as '<out_dir>/gen_pyramid/all_{sl}.tif': tiled pyramidal OME-TIFF with JPEG tiles")
     ap.add_argument("--page", type=int, default=None, help="with --pyramid: also write that pyramid level as all_{sl}.jpg")
     ap.add_argument("--quality", type=int, default=75, help="with --pyramid: JPEG quality 1 .. 100")
     args = ap.parse_args()
+    if args.save_steps and not args.out_dir:
+        ap.error("--save_steps needs --out_dir")
+    if args.cur_epoch is not None:              # refused here, before a model is built or a rank is started
+        if not 1 <= args.cur_epoch <= args.tot_epoch:
+            ap.error(f"--cur_epoch {args.cur_epoch} is outside 1 .. tot_epoch = {args.tot_epoch}")
+        if not args.out_dir:
+            ap.error("--cur_epoch needs --out_dir: the state is read from '<out_dir>/timestep_<N>'")
+        step_dir = os.path.join(args.out_dir, "timestep") + f"_{args.cur_epoch}"
+        if not os.path.isdir(step_dir):
+            ap.error(f"--cur_epoch {args.cur_epoch}: there is no step directory {step_dir}")
     from teramind_amd import launch
     if args.gene_dir and args.make_genes and not launch.launched_as_rank():
         t0 = time.perf_counter()
