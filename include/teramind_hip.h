@@ -466,8 +466,14 @@ int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, const void* b
  * the pair form of the same conv. */
 int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                          int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream);
-/* Timing hook (tools/bench_conv_xpair.py): that conv packed once for `form` (0 = the pair form, 1 = the x-pair form), then
- * `iters` launches, each between two events of its own: ms_out[i] (HOST) = the time of launch i. */
+/* The same conv in its x-quad form (conv3d_xquad: the pair form in z composed with Winograd F(4,3) along x, 54 tap-products per
+ * eight outputs), arguments as tm_op_conv_xpair_f32.  tile_variant 1 | 2 = 64 | 128 four-column groups per workgroup.  Returns the
+ * tile launched (1 | 2).  TM_ERR_ARG before any device call: Z != 2, S outside {8, .., 128} (so S = 4 and every S that is no
+ * multiple of 4), the form switched off (TM_CONV_XQUAD=0). */
+int tm_op_conv_xquad_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                         int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream);
+/* Timing hook (tools/bench_conv_xpair.py): that conv packed once for `form` (0 = the pair form, 1 = the x-pair form, 2 = the
+ * x-quad form), then `iters` launches, each between two events of its own: ms_out[i] (HOST) = the time of launch i. */
 int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                              int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream);
 
@@ -493,7 +499,8 @@ int tm_conv1_form(long vox, int ntile, int tile_variant);
  * (x-pair: the wave's q-th transform position) and 32-cout sub-tile sub; what 1: the activation fragment of (p, ky, kx), sub =
  * the output phase 2 py + px of kernel 1 (else 0); what 2: the staging store (ds_write_b128) into plane p of the thread's ky-th
  * item (x-pair: ky 0, kx = the q-plane).  out64[lane] = byte address in the workgroup's dynamic LDS, -1 for a lane that stores
- * nothing.  Returns 0, or -1 if there is no such instantiation, fragment or item. */
+ * nothing.  kernel 4 = conv3d_xquad (3 is no kernel and stays refused): tw 8 | 16, wave 0..7 (0..3 in the small tile), kx = the wave's q-th transform position
+ * (0..2), in what 2 the q-plane (0..5).  Returns 0, or -1 if there is no such instantiation, fragment or item. */
 int tm_conv_frag_addrs(int kernel, int half, int tw, int what, int wave, int p, int ky, int kx, int sub, int* out64);
 
 /* 16-bit variant of the 3x3x3 pad-1 conv (Z == 2): x fp32 CB8 is rounded to `dtype` (TM_DTYPE_BF16 | TM_DTYPE_F16, RNE) on

@@ -15,6 +15,7 @@ int conv_form_taps(int form) {
     case CF_INPLANE: return 9;
     case CF_ZSKIP_UPS: case CF_PAIR_UPS: return 12;
     case CF_XPAIR: return 36;
+    case CF_XQUAD: return 54;
     default: return 27;
   }
 }
@@ -34,7 +35,8 @@ static bool switch_on(const char* name) {        // an A/B switch: on unless the
 }
 int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse_mid) {
   static const bool zpair_on = switch_on("TM_CONV_ZPAIR"), xpair_on = switch_on("TM_CONV_XPAIR"),
-                    xmid_on = switch_on("TM_CONV_XPAIR_MID"), fuse_on = switch_on("TM_CONV_FUSE_MID");
+                    xmid_on = switch_on("TM_CONV_XPAIR_MID"), fuse_on = switch_on("TM_CONV_FUSE_MID"),
+                    xquad_on = switch_on("TM_CONV_XQUAD");
   if (fuse_mid) *fuse_mid = false;
   if (ksize == 1) return CF_1X1;
   if (zmode == ZM_INPLANE) return CF_INPLANE;
@@ -43,6 +45,7 @@ int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse
   if (zmode == ZM_UPS) return ((role & ROLE_OP_PAIR_UPS) || ((role & ROLE_RES) && pair)) ? CF_PAIR_UPS : CF_ZSKIP_UPS;
   if (Z != 2) return (Z == 1 && (role & ROLE_RES)) ? CF_INPLANE : CF_PLANES3;
   if ((role & ROLE_OP_XPAIR) && xpair_on) return CF_XPAIR;
+  if ((role & ROLE_OP_XQUAD) && xquad_on) return CF_XQUAD;
   if (!pair) return CF_ZSKIP;
   // c1 of a 64-channel block: the pair form fuses the mid norm into its epilogue, an x-pair wave holds 32 of the 64 channels and
   // leaves the norm to the separate pass.  Measured per step (profiles/fp32_xpair.txt), x-pair + separate pass is the faster by
@@ -50,6 +53,8 @@ int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse
   const bool fuses = (role & ROLE_C1_64) && fuse_on;
   const bool xp = (role & ROLE_RES) && !(role & ROLE_DEEP) && xpair_on && deep8 && (!fuses || xmid_on);
   if (fuse_mid) *fuse_mid = fuses && !xp;
+  // the x-pair layers move on to the x-quad form (F(4,3) along x, 0.75 of the x-pair's MFMAs); TM_CONV_XQUAD=0 keeps them
+  if (xp && xquad_on) return CF_XQUAD;
   return xp ? CF_XPAIR : CF_PAIR;
 }
 
@@ -126,11 +131,51 @@ static std::vector<float> f23_rows(const float* w, size_t n) {
   return o;
 }
 
+// F(4,3) filter transform of the three kx taps of every (product, ky) row: U0 = g0 / 4, U1 = -((g0 + g1) + g2) / 6,
+// U2 = -((g0 - g1) + g2) / 6, U3 = (g0 / 24 + g1 / 12) + g2 / 6, U4 = (g0 / 24 - g1 / 12) + g2 / 6, U5 = g2.  Divisions, not
+// rounded reciprocals: weights that are multiples of 24 transform exactly.  [n][9 rows][3] -> [n][9 rows][6]
+static std::vector<float> f43_rows(const float* w, size_t n) {
+  std::vector<float> o(n * 54);
+  for (size_t r = 0; r < n * 9; ++r) {
+    const float* g = w + r * 3;
+    float* u = o.data() + r * 6;
+    u[0] = g[0] / 4.f;
+    u[1] = -((g[0] + g[1]) + g[2]) / 6.f;
+    u[2] = -((g[0] - g[1]) + g[2]) / 6.f;
+    u[3] = (g[0] / 24.f + g[1] / 12.f) + g[2] / 6.f;
+    u[4] = (g[0] / 24.f - g[1] / 12.f) + g[2] / 6.f;
+    u[5] = g[2];
+  }
+  return o;
+}
+// The x-quad pack: a workgroup of conv3d_xquad owns 32 couts, so the tiles are of 32 couts and a tap is [2 k-halves][32 cout][4 cin],
+// one contiguous 1 KiB LDS-DMA piece: w [Cout][Cin][54] -> [ceil(Cout / 64) * 2 tiles][cblk][54 taps][256], pad slots zero
+static void pack_taps32(const float* w, int Cout, const int* seg_c, int nseg, float* out) {
+  int Cin, Cbi;
+  seg_counts(seg_c, nseg, Cin, Cbi);
+  memset(out, 0, conv_pack_floats(CF_XQUAD, Cout, Cbi) * sizeof(float));
+  int ci0 = 0, cb0 = 0;
+  for (int s = 0; s < nseg; ++s) {
+    for (int c = 0; c < seg_c[s]; ++c) {
+      const int ci = ci0 + c, cb = cb0 + c / 8, c8 = c % 8;
+      for (int co = 0; co < Cout; ++co) {
+        const float* src = w + ((size_t)co * Cin + ci) * 54;
+        float* dst = out + (((size_t)(co / 32) * Cbi + cb) * 54) * 256 + conv_frag_off(co % 32, c8 >> 2, 32) + (c8 & 3);
+        for (int t = 0; t < 54; ++t) dst[(size_t)t * 256] = src[t];
+      }
+    }
+    ci0 += seg_c[s];
+    cb0 += (seg_c[s] + 7) / 8;
+  }
+}
+
 void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int nseg, float* out) {
   int Cin, Cbi;
   seg_counts(seg_c, nseg, Cin, Cbi);
   const size_t n = (size_t)Cout * Cin;
-  if (form == CF_PAIR) {
+  if (form == CF_XQUAD) {
+    pack_taps32(f43_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, out);
+  } else if (form == CF_PAIR) {
     pack_taps(z_diff(w, n, 9).data(), Cout, seg_c, nseg, 27, out, true);
   } else if (form == CF_XPAIR) {
     pack_taps(f23_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, 36, out, true);

@@ -80,10 +80,10 @@ __device__ __forceinline__ rsrc_words weight_rsrc(const float* base, int bytes) 
 // statement that uses it.  NOP: wait states between the SALU writes and the load (4 where the source offset may come straight from the SALU: five
 // wait states ahead of a VMEM read of it).  hipcc does not count these loads: it neither drains them at a barrier nor waits for
 // them in front of the fragment reads -- the kernels retire them with their own vmcnt waits.
-template <int NOP, int NPIECES>
+template <int NOP, int NPIECES, int NWV = 4>                   // NWV: the waves that share the slot's pieces (piece j = NWV k + wvu)
 __device__ __forceinline__ void lds_dma_piece(unsigned lw_lds, int slot, int src, int k, int wvu, int wvo, const rsrc_words& rs) {
-  const int j = k * 4 + wvu;
-  if ((k + 1) * 4 <= NPIECES || j < NPIECES) {
+  const int j = k * NWV + wvu;
+  if ((k + 1) * NWV <= NPIECES || j < NPIECES) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop %5\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)

@@ -804,6 +804,264 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
   }
 }
 
+// ---- x-quad form of the 3x3x3 pad-1 conv at Z == 2 (fp32): the pair form in z composed with Winograd F(4,3) along x ----
+// F(4,3) gives four neighbouring outputs of a 3-tap filter g with six products instead of twelve: with d0..d5 the inputs at
+// columns 4j - 1 .. 4j + 4 (zero outside the plane),
+//   T0 = (4 d0 - 5 d2) + d4           U0 = g0 / 4                               (T: while staging; U: at pack time,
+//   T1 = (d3 + d4) - 4 (d1 + d2)      U1 = -((g0 + g1) + g2) / 6                 conv_pack_host, CF_XQUAD)
+//   T2 = 4 (d1 - d2) - (d3 - d4)      U2 = -((g0 - g1) + g2) / 6
+//   T3 = 2 (d3 - d1) + (d4 - d2)      U3 = (g0 / 24 + g1 / 12) + g2 / 6
+//   T4 = 2 (d1 - d3) + (d4 - d2)      U4 = (g0 / 24 - g1 / 12) + g2 / 6
+//   T5 = (4 d1 - 5 d3) + d5           U5 = g2
+//   A_q = sum over cin, ky of U_q[ky] T_q[y + ky - 1][j];  s = A1 + A2, d = A1 - A2, s' = A3 + A4, d' = A3 - A4
+//   out[4j] = (A0 + s) + s'   out[4j + 1] = d + 2 d'   out[4j + 2] = s + 4 s'   out[4j + 3] = (d + 8 d') + A5.
+// As in conv3d_xpair it applies to each of the three z products (V = W1, W2 - W1, W0 - W1 on X0 + X1, X1, X0): 54 tap-products
+// per eight outputs, 6.75 per output against the x-pair's 9.  ORDER OF SUMS of every output, in both tiles: cin block, product,
+// ky, k inside an accumulator A_q(p); then the output transform exactly as written above; then Y(z0) = P(1) + P(2), Y(z1) =
+// P(1) + P(3); then the common epilogue.  So HALF = 0 and 1 give identical bits.
+// A workgroup owns MG four-column groups, both output planes and 32 couts (a 64-cout ring of two product slots would pass the
+// 64 KiB an LDS-DMA destination must stay below).  A wave owns 32 groups x 32 couts and three of the six q (3 products x 3 q = 9
+// accumulators); wave & 1 is the q half, wave >> 1 the group tile.  HALF = 0: 8 waves, 128 groups (1024 output voxels), one
+// workgroup per CU; HALF = 1 (launches that do not fill the chip): 4 waves, 64 groups.  After the K loop the q halves exchange one
+// tile per product through LDS (d one way, s' the other); half 0 finishes columns 0 and 2, half 1 columns 1 and 3.
+// LDS: the weight ring [2 product slots][18 taps (ky, q)][2 k-halves][32 couts][4] = 36 864 B first (LDS-DMA destinations below
+// 64 KiB), then per product six q-planes [2 k-halves][XP][4] of XP = NPB x HR x TW/4 group positions (no x halo).  The planes end
+// past 64 KiB, so a lane keeps one hidden base per product (16-byte slots: every fragment read is one ds_read_b128 with a
+// 16-bit offset).  At TW = 8 a wave's 32 groups span two patches 20 rows apart: the lanes of the first ds_read_b128 group take
+// the first patch, the others the second (conv_lane_voxel's TW = 16 table), so each group reads sixteen consecutive rows.
+// Ring schedule and barriers are conv3d_xpair's: product n = 3 cb + p reads slot n & 1, the pieces of product n + 1 go out behind
+// its first taps, a wave retires its own with the vmcnt(0) in front of the next product's barrier.
+template <int HALF, int TW>
+struct XQGeo {
+  static constexpr int TW_ = TW;
+  static constexpr int NW = HALF ? 4 : 8;                        // waves per workgroup
+  static constexpr int MG = 16 * NW;                             // four-column groups per workgroup
+  static constexpr int GW = TW / 4;                              // groups per tile row
+  static constexpr int TR = (MG / GW < TW) ? (MG / GW) : TW;     // tile rows
+  static constexpr int NPB = MG / (TR * GW);                     // patches per workgroup
+  static constexpr int HR = TR + 2;
+  static constexpr int XP = NPB * HR * GW;                       // group positions of one q-plane (y halo only)
+  static constexpr int XITEMS = XP * 2;                          // staging items: (position, half block), one per thread
+  static_assert(XP % 8 == 0, "whole groups of eight staging items (tm_conv_frag.h)");
+  static constexpr int WTAP = 256;                               // floats of one tap of 32 couts
+  static constexpr int WSLOT = 18 * WTAP;                        // floats of one product of a (cout tile, cin block)
+  static constexpr int KP = (18 + NW - 1) / NW;                  // LDS-DMA pieces (one tap each) of a slot per wave, at most
+  static constexpr int LDS_BYTES = (2 * WSLOT + 18 * XP * 8) * 4;
+  static_assert(2 * WSLOT * 4 <= 65536 && LDS_BYTES <= 160 * 1024, "LDS-DMA destinations below 64 KiB, the CU's LDS");
+};
+// the lane's group (0 .. 31 of the wave's tile) and the float offset of tap (ky, q) in a product slot
+TM_HD constexpr int xq_lane_group(int tw, int i32) { return tw == 8 ? conv_lane_voxel(16, i32) : i32; }
+// The constant part of conv3d_xquad's X fragment address (floats) inside a product's six planes: row ky of q-plane q.
+template <class G>
+TM_HD constexpr int xq_xtap(int q, int ky) { return q * G::XP * 8 + conv_frag_off(ky * G::GW, 0, G::XP); }
+
+template <int HALF, int TW>
+__global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) {
+  using G = XQGeo<HALF, TW>;
+  static_assert(G::XITEMS <= 64 * G::NW, "one staging item per thread");
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  float* lw = lds;                                               // the weight ring; the X planes follow at float 2 * WSLOT
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wv = tid >> 6;
+  const int i32 = lane & 31, h = lane >> 5;
+
+  const int S = a.S;
+  const ConvTile t = conv_tile_of<TW, G::TR, false, false>(a);   // a.ntile counts 32-cout tiles here
+  const int nt = t.nt, pg = t.pg, tr = t.tr, tc = t.tc;
+
+  // ---- staging descriptor: this thread's (row, group, half block); xoff addresses column 4j of plane 0 ----
+  long xoff = -1;
+  bool okl = false, okr = false;                                 // columns 4j - 1 and 4j + 4 lie inside the plane
+  if (tid < G::XITEMS) {
+    const int half = conv_stage_half(tid);
+    int v = conv_stage_row(tid);
+    const int j = v % G::GW; v /= G::GW;
+    const int hr = v % G::HR;
+    const int ps = v / G::HR;
+    const int n = pg * G::NPB + ps;
+    const int y = tr * G::TR + hr - 1, x = tc * TW + 4 * j;
+    if (n < a.N && y >= 0 && y < S) {
+      xoff = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
+      okl = x > 0;
+      okr = x + 4 < S;
+    }
+  }
+  const long zplane = (long)S * S * 8;
+  int xw = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP);
+  asm volatile("" : "+v"(xw));
+
+  // ---- per-lane fragment addresses ----
+  const int gt = wv >> 1;                                        // 32-group tile of this wave
+  const int qh = wv & 1;                                         // its q half: q = 3 qh .. 3 qh + 2
+  int xb[3], on[1], ooff0;                                       // ooff0: column 4j of plane 0 (or -1)
+  {
+    const ConvLane l = conv_lane_of<G::TR, G::GW, G::HR * G::GW, G::GW, G::XP>(gt * 32 + xq_lane_group(TW, i32), h, 0, 0);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {                                // one hidden base per product, in 16-byte slots
+      xb[p] = (2 * G::WSLOT + (p * 6 + 3 * qh) * G::XP * 8 + l.xb) / 4;
+      asm volatile("" : "+v"(xb[p]));
+    }
+    const int n = pg * G::NPB + l.ps;
+    on[0] = n;
+    const int y = tr * G::TR + l.r, x = tc * TW + 4 * l.c;
+    ooff0 = n < a.N ? (y * S + x) * 8 : -1;
+  }
+  const int wb = 3 * qh * G::WTAP + conv_frag_off(i32, h, 32);
+
+  f32x16 acc[3][3];
+  clear_acc(acc);
+
+  const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
+  const rsrc_words wrs = weight_rsrc<true>(a.w + (long)nt * a.Cbi * 3 * G::WSLOT, a.Cbi * 3 * G::WSLOT * 4);
+  const int wvo = lane * 16;
+  const int wvu = __builtin_amdgcn_readfirstlane(wv);
+  // piece k of this wave of product n: tap j = NW k + wave of the product's 18
+  auto issue_piece = [&](int n, int k) __attribute__((always_inline)) {
+    lds_dma_piece<4, 18, G::NW>(lw_lds, (n & 1) * G::WSLOT, n * G::WSLOT, k, wvu, wvo, wrs);
+  };
+
+  f32x4 xr[2][6];                                                // [plane][column 4j - 1 .. 4j + 4]
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  auto load_x = [&](int cb) {
+    const float* xp = a.x + (long)cb * a.x_plane;
+#pragma unroll
+    for (int z = 0; z < 2; ++z) {
+      const float* b = xp + xoff + z * zplane;
+      xr[z][0] = okl ? *(const f32x4*)(b - 8) : zero4;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xr[z][1 + c] = xoff >= 0 ? *(const f32x4*)(b + 8 * c) : zero4;
+      xr[z][5] = okr ? *(const f32x4*)(b + 32) : zero4;
+    }
+  };
+  // the six transform planes of one product from its six columns
+  auto put_t = [&](int p, const f32x4 (&d)[6]) __attribute__((always_inline)) {
+    float* o = lds + xw + p * 6 * G::XP * 8;
+    const f32x4 e42 = d[4] - d[2];
+    *(f32x4*)(o) = (4.f * d[0] - 5.f * d[2]) + d[4];
+    *(f32x4*)(o + G::XP * 8) = (d[3] + d[4]) - 4.f * (d[1] + d[2]);
+    *(f32x4*)(o + 2 * G::XP * 8) = 4.f * (d[1] - d[2]) - (d[3] - d[4]);
+    *(f32x4*)(o + 3 * G::XP * 8) = 2.f * (d[3] - d[1]) + e42;
+    *(f32x4*)(o + 4 * G::XP * 8) = 2.f * (d[1] - d[3]) + e42;
+    *(f32x4*)(o + 5 * G::XP * 8) = (4.f * d[1] - 5.f * d[3]) + d[5];
+  };
+
+  load_x(0);
+#pragma unroll
+  for (int k = 0; k < G::KP; ++k) issue_piece(0, k);
+  // one cin block; MORE = another block follows (the last block is its own instantiation: no branch around a piece)
+  auto stage = [&](int cb, auto more_c) __attribute__((always_inline)) {
+    constexpr bool more = decltype(more_c)::value;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // X(cb) in registers; this wave's pieces of product 3 cb landed
+    __builtin_amdgcn_s_barrier();                                // B0: every wave is through block cb - 1: the planes and the other slot are free
+    asm volatile("" ::: "memory");
+    if (tid < G::XITEMS) {
+      put_t(2, xr[0]);                                           // X0 first: its registers then take X0 + X1 (no temporaries)
+#pragma unroll
+      for (int c = 0; c < 6; ++c) xr[0][c] = xr[0][c] + xr[1][c];
+      put_t(0, xr[0]);
+      put_t(1, xr[1]);
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0) only
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_barrier();                                // B1
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+    if (more) load_x(cb + 1);
+
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+      const int n = cb * 3 + p;
+      if (p > 0) {                                               // B2, B3: this wave's pieces of product n landed, everybody's are visible
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // behind the barrier, and the slot of product n - 1 is free
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      const float* lwc = lw + (n & 1) * G::WSLOT + wb;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {                            // (q counts from the wave's 3 qh: in both bases)
+          const f32x4 wf = *(const f32x4*)(lwc + (ky * 6 + q) * G::WTAP);
+          const f32x4 xf = ((const f32x4*)lds)[xb[p] + xq_xtap<G>(q, ky) / 4];
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[kk], xf[kk], acc[p][q], 0, 0, 0);
+          if (ky * 3 + q < G::KP && (p < 2 || more)) issue_piece(n + 1, ky * 3 + q);   // a piece of product n + 1 behind each of the first taps
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+  for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
+  stage(a.Cbi - 1, std::false_type{});
+
+  // ---- the q halves exchange through LDS (free behind the barrier: nothing of the K loop is read or in flight any more):
+  // half 0 (A0, A1, A2) hands d = A1 - A2 over and takes s' = A3 + A4, half 1 (A3, A4, A5) the reverse; a tile is
+  // [16 registers / 4][64 lanes] float4, three tiles per wave
+  const int qhu = __builtin_amdgcn_readfirstlane(qh);
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {                                  // acc[p][0] = A0 | d', [1] = s | s', [2] = d | A5
+    if (qhu) {
+      const f32x16 sp = acc[p][0] + acc[p][1];
+      acc[p][0] = acc[p][0] - acc[p][1];
+      acc[p][1] = sp;
+    } else {
+      const f32x16 s = acc[p][1] + acc[p][2];
+      acc[p][2] = acc[p][1] - acc[p][2];
+      acc[p][1] = s;
+    }
+    asm volatile("" : "+v"(acc[p][0]), "+v"(acc[p][1]), "+v"(acc[p][2]));
+  }
+  __syncthreads();
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f32x16& tl = qhu ? acc[p][1] : acc[p][2];
+      const f32x4 v = {tl[4 * i], tl[4 * i + 1], tl[4 * i + 2], tl[4 * i + 3]};
+      *(f32x4*)(lds + ((wv * 3 + p) * 4 + i) * 256 + lane * 4) = v;
+    }
+  __syncthreads();
+  f32x16 got[3];
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const f32x4 v = *(const f32x4*)(lds + (((wv ^ 1) * 3 + p) * 4 + i) * 256 + lane * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) got[p][4 * i + e] = v[e];
+    }
+  // half 0: column 0 = (A0 + s) + s', column 2 = s + 4 s';  half 1: column 1 = d + 2 d', column 3 = (d + 8 d') + A5
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    f32x16 c0, c1;
+    if (qhu) {
+      c0 = got[p] + 2.f * acc[p][0];
+      c1 = (got[p] + 8.f * acc[p][0]) + acc[p][2];
+    } else {
+      c0 = (acc[p][0] + acc[p][1]) + got[p];
+      c1 = acc[p][1] + 4.f * got[p];
+    }
+    acc[p][0] = c0;
+    acc[p][1] = c1;
+    asm volatile("" : "+v"(acc[p][0]), "+v"(acc[p][1]));         // formed HERE, not sunk into the guarded stores below
+  }
+#pragma unroll
+  for (int z = 0; z < 2; ++z)
+#pragma unroll
+    for (int par = 0; par < 2; ++par) {
+      f32x16 o[1][1];
+      o[0][0] = acc[0][par] + acc[1 + z][par];
+      asm volatile("" : "+v"(o[0][0]));
+      const int ooff[1] = {ooff0 >= 0 ? ooff0 + (z * S * S + 2 * par + qh) * 8 : -1};
+      __builtin_amdgcn_sched_barrier(0);
+      conv_epilogue<1, 1>(a, o, nt, h, on, ooff, 2 * S);
+    }
+}
+
 // ---- 1x1x1 conv / Linear over voxels (flat voxel tiles, KC channel blocks per stage) ----
 // Replaces the skip_connection Conv3d(k=1) (model/MBAblocks.py:220-224) and every nn.Linear
 // of AttnBlock / Attention / Mlp applied to '(z h w) c' tokens (model/MBAblocks.py:465,
@@ -935,6 +1193,8 @@ int conv1_form(long vox, int ntile, int tile_variant) {
 
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant) {
   if (S == 4) return 1;                        // 4 x 4 planes: several patches per workgroup of the small tile
+  // x-quad: the large tile is 1024 voxels x 32 couts on eight waves, one workgroup per CU: taken where it still gives every CU one
+  if (form == CF_XQUAD) return tile_variant ? (tile_variant == 2 ? 2 : 1) : ((ovox / 1024) * 2 * ntile >= 256 ? 2 : 1);
   const long tiles = (form == CF_ZSKIP_UPS || form == CF_PAIR_UPS) ? 4L * ntile : ntile;
   const int variant = tile_variant ? tile_variant : (conv_fills_chip(ovox, tiles) ? 2 : 1);
   return variant == 2 ? 2 : 1;
@@ -1036,7 +1296,7 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     case CF_ZSKIP: case CF_PAIR:   // 3x3x3 pad 1 over two planes
       if (L.zmode != ZM_PAD1 || !z2) return hipErrorInvalidValue;
       break;
-    case CF_XPAIR:                 // ... with Winograd along x: planes of at least 8 x 8, plain epilogue
+    case CF_XPAIR: case CF_XQUAD:  // ... with Winograd along x: planes of at least 8 x 8, plain epilogue
       if (L.zmode != ZM_PAD1 || !z2 || L.x.H < 8 || up2) return hipErrorInvalidValue;
       break;
     case CF_ZSKIP_UPS: case CF_PAIR_UPS:   // 3x3x3 pad 1 of the nearest-x2 upsampled x, on the low-resolution x
@@ -1074,6 +1334,13 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
         constexpr int TW = decltype(tw)::value;
         return large ? launch_tiled<conv3d_zpair_ups<0, TW>, ZPUGeo<0, TW>>(a, 4, s)
                      : launch_tiled<conv3d_zpair_ups<1, TW>, ZPUGeo<1, TW>>(a, 4, s);
+      });
+    case CF_XQUAD:
+      a.ntile = (L.w.Cout + 31) / 32;                          // the kernel's cout tiles are of 32 (the pack holds 2 * ntile of them)
+      return with_tile_width<16>(S, [&](auto tw) {
+        constexpr int TW = decltype(tw)::value;
+        return large ? launch_tiled<conv3d_xquad<0, TW>, XQGeo<0, TW>, 64 * XQGeo<0, TW>::NW>(a, 1, s)
+                     : launch_tiled<conv3d_xquad<1, TW>, XQGeo<1, TW>, 64 * XQGeo<1, TW>::NW>(a, 1, s);
       });
     default:   // CF_XPAIR
       return with_tile_width<16>(S, [&](auto tw) {
@@ -1129,8 +1396,29 @@ static int xpair_frag_addrs(int what, int wv, int p, int ky, int q, int* out) {
   }
   return 0;
 }
+template <int HALF, int TW>
+static int xquad_frag_addrs(int what, int wv, int p, int ky, int q, int* out) {
+  using G = XQGeo<HALF, TW>;
+  if (wv >= G::NW || p < 0 || p > 2 || q < 0 || q >= (what == 2 ? 6 : 3) || ky < 0 || ky > (what == 2 ? 0 : 2)) return -1;
+  const int gt = wv >> 1, qh = wv & 1;
+  for (int lane = 0; lane < 64; ++lane) {
+    const int i32 = lane & 31, h = lane >> 5, tid = wv * 64 + lane;
+    int a = -1;
+    if (what == 0) a = 3 * qh * G::WTAP + conv_frag_off(i32, h, 32) + (ky * 6 + q) * G::WTAP;
+    else if (what == 1)
+      a = 2 * G::WSLOT + (p * 6 + 3 * qh) * G::XP * 8 +
+          conv_lane_of<G::TR, G::GW, G::HR * G::GW, G::GW, G::XP>(gt * 32 + xq_lane_group(TW, i32), h, 0, 0).xb + xq_xtap<G>(q, ky);
+    else if (tid < G::XITEMS)
+      a = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP) + (p * 6 + q) * G::XP * 8;
+    out[lane] = a < 0 ? -1 : a * 4;
+  }
+  return 0;
+}
 int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out) {
-  if (!out || kernel < 0 || kernel > 2 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > 3) return -1;
+  if (!out || kernel < 0 || kernel > 4 || kernel == 3 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > (kernel == 4 ? 7 : 3)) return -1;
+  if (kernel == 4 && tw == 8) return half ? xquad_frag_addrs<1, 8>(what, wv, p, ky, kx, out) : xquad_frag_addrs<0, 8>(what, wv, p, ky, kx, out);
+  if (kernel == 4 && tw == 16) return half ? xquad_frag_addrs<1, 16>(what, wv, p, ky, kx, out) : xquad_frag_addrs<0, 16>(what, wv, p, ky, kx, out);
+  if (kernel == 4) return -1;
 #define TM_FRAG(H, T)                                                                                              \
   if (half == H && tw == T) {                                                                                      \
     if (kernel == 0) return zpair_frag_addrs<ZPGeo<H, T>, H, T, false>(what, wv, p, ky, kx, sub, out);              \

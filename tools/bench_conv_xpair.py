@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Op-level timing of the fp32 3x3x3 pad-1 conv at Z = 2 in its two forms, the pair form (conv3d_zpair) against the x-pair form
-(conv3d_xpair), at the governing geometries of the fp32 step.  Per geometry ROUNDS rounds of CHUNK launches of each form,
-interleaved (pair, x-pair, pair, ..), every launch between two events of its own (tm_op_conv_pad1_time_f32); the first launch
-of a chunk is dropped.  Prints one JSON line per geometry: median, 10th and 90th percentile in microseconds of each form, and
-whether the x-pair median is below the pair form's by more than the larger of the two p90 - p10 spreads.
+"""Op-level timing of the fp32 3x3x3 pad-1 conv at Z = 2 in its three forms, the pair form (conv3d_zpair), the x-pair form
+(conv3d_xpair, F(2,3) along x) and the x-quad form (conv3d_xquad, F(4,3) along x), at the governing geometries of the fp32
+step.  Per geometry ROUNDS rounds of CHUNK launches of each form, interleaved (pair, x-pair, x-quad, pair, ..), every launch
+between two events of its own (tm_op_conv_pad1_time_f32); the first launch of a chunk is dropped.  Prints one JSON line per
+geometry: median, 10th and 90th percentile in microseconds of each form, and for each Winograd form whether its median is below
+the other two forms' by more than the largest of the p90 - p10 spreads.
 
     python3 tools/bench_conv_xpair.py [--rounds 5] [--chunk 21] [--tile 0]
 """
@@ -20,8 +21,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import teramind_amd  # noqa: E402,F401
 from teramind_amd import _lib  # noqa: E402
 
-# (N, Cin, Cout, S): the four encoder / decoder levels of configs[1] at b = 32, P = 1 and the widest decoder concat
-GEOMETRIES = [(128, 96, 64, 64), (128, 128, 128, 32), (128, 256, 256, 16), (128, 512, 512, 8), (32, 1253, 512, 8)]
+# (N, Cin, Cout, S): the four encoder / decoder levels of configs[1] at b = 32, P = 1, the widest decoder concat, the deepest
+# decoder's second conv and the shallowest decoder's
+GEOMETRIES = [(128, 96, 64, 64), (128, 128, 128, 32), (128, 256, 256, 16), (128, 512, 512, 8), (32, 1253, 512, 8),
+              (32, 512, 256, 16), (32, 160, 64, 64)]
+NAMES = {0: "pair", 1: "xpair", 2: "xquad"}
 
 
 def main():
@@ -40,19 +44,24 @@ def main():
         w = (torch.randn((Cout, Cin, 27)) / (27 * Cin) ** 0.5).contiguous()
         b = torch.randn((Cout,))
         ms = (C.c_float * a.chunk)()
-        t = {0: [], 1: []}
+        t = {f: [] for f in NAMES}
         for _ in range(a.rounds):
-            for form in (0, 1):
+            for form in NAMES:
                 rc = L.tm_op_conv_pad1_time_f32(_lib.ptr(x), C.c_void_p(w.data_ptr()), C.c_void_p(b.data_ptr()), _lib.ptr(y), N, Cin,
                                                 Cout, S, form, a.tile, a.chunk, ms, _lib.current_stream_ptr())
                 _lib.check(rc, "tm_op_conv_pad1_time_f32")
                 t[form] += [1e3 * v for v in list(ms)[1:]]
         q = {f: [float(np.percentile(t[f], p)) for p in (50, 10, 90)] for f in t}
-        spread = max(q[0][2] - q[0][1], q[1][2] - q[1][1])
-        print(json.dumps({"N": N, "Cin": Cin, "Cout": Cout, "S": S, "launches": len(t[0]),
-                          "pair_us": [round(v, 1) for v in q[0]], "xpair_us": [round(v, 1) for v in q[1]],
-                          "ratio": round(q[1][0] / q[0][0], 4), "spread_us": round(spread, 1),
-                          "wins": bool(q[0][0] - q[1][0] > spread)}), flush=True)
+        spread = max(q[f][2] - q[f][1] for f in q)
+        out = {"N": N, "Cin": Cin, "Cout": Cout, "S": S, "launches": len(t[0])}
+        for f, name in NAMES.items():
+            out[name + "_us"] = [round(v, 1) for v in q[f]]
+        out["xpair_ratio"] = round(q[1][0] / q[0][0], 4)
+        out["xquad_ratio"] = round(q[2][0] / min(q[0][0], q[1][0]), 4)
+        out["spread_us"] = round(spread, 1)
+        out["wins"] = bool(q[0][0] - q[1][0] > spread)
+        out["xquad_wins"] = bool(min(q[0][0], q[1][0]) - q[2][0] > spread)
+        print(json.dumps(out), flush=True)
 
 
 if __name__ == "__main__":

@@ -1,10 +1,10 @@
 // Stand-alone host check of the conv weight packers (no GPU): every form is packed for the segment lists (5, 16, 3) and (8) at
 // Cout 37 and 128 into buffers of exactly conv_pack_floats() floats -- built with -fsanitize=address,undefined a write past the
 // end aborts.  The forms that reach LDS by LDS-DMA (CF_PAIR, CF_PAIR_UPS, CF_XPAIR) must hold, tap for tap, the [64 cout][8 cin]
-// image permuted into [2 k-halves][64 cout][4 cin] (tm_conv_frag.h).  With -DTM_PARENT_PACK and a second copy of the packer,
-// from the build before the images changed and compiled with -Dtmk=tmk_parent, that is checked against ITS bytes, float for
-// float and as multisets of bit patterns, and every other form must be byte-identical; without it the run checks sizes, pad
-// slots and the sanitizers' silence.  Pad slots (couts past Cout, channels past a segment) must be zero.
+// image permuted into [2 k-halves][64 cout][4 cin] (tm_conv_frag.h); CF_XQUAD holds tiles of 32 couts, a tap being
+// [2 k-halves][32 cout][4 cin], and is checked against the F(4,3) filter transform evaluated here (the parent has no such form).  With -DTM_PARENT_PACK and a second copy of the packer,
+// from the parent commit and compiled with -Dtmk=tmk_parent, every form the parent has must be byte-identical to ITS pack;
+// without it the run checks sizes, pad slots and the sanitizers' silence.  Pad slots (couts past Cout, channels past a segment) must be zero.
 //   hipcc -O1 -g -std=c++17 -x hip --cuda-host-only -fsanitize=address,undefined -Itera-mind_amd/csrc -Iinclude \
 //         tools/conv_pack_check.cpp tera-mind_amd/csrc/tm_conv_pack.cpp -o conv_pack_check && ./conv_pack_check
 #include <stdio.h>
@@ -30,12 +30,12 @@ static int fails = 0;
 
 int main() {
   const int segs[2][3] = {{5, 16, 3}, {8, 0, 0}}, nsegs[2] = {3, 1}, couts[2] = {37, 128};
-  const int forms[] = {CF_1X1, CF_INPLANE, CF_PLANES3, CF_ZSKIP, CF_ZSKIP_UPS, CF_PAIR, CF_PAIR_UPS, CF_XPAIR};
-  const char* names[] = {"CF_1X1", "CF_INPLANE", "CF_PLANES3", "CF_ZSKIP", "CF_ZSKIP_UPS", "CF_PAIR", "CF_PAIR_UPS", "CF_XPAIR"};
+  const int forms[] = {CF_1X1, CF_INPLANE, CF_PLANES3, CF_ZSKIP, CF_ZSKIP_UPS, CF_PAIR, CF_PAIR_UPS, CF_XPAIR, CF_XQUAD};
+  const char* names[] = {"CF_1X1", "CF_INPLANE", "CF_PLANES3", "CF_ZSKIP", "CF_ZSKIP_UPS", "CF_PAIR", "CF_PAIR_UPS", "CF_XPAIR", "CF_XQUAD"};
   unsigned long long lcg = 88172645463325252ull;
   for (int si = 0; si < 2; ++si)
     for (int ci = 0; ci < 2; ++ci)
-      for (int fi = 0; fi < 8; ++fi) {
+      for (int fi = 0; fi < 9; ++fi) {
         const int form = forms[fi], Cout = couts[ci], nseg = nsegs[si];
         int Cin = 0, Cbi = 0;
         for (int s = 0; s < nseg; ++s) { Cin += segs[si][s]; Cbi += (segs[si][s] + 7) / 8; }
@@ -46,6 +46,44 @@ int main() {
         std::vector<float> pk(n, -7.f);
         conv_pack_host(form, w.data(), Cout, segs[si], nseg, pk.data());
         const bool halves = form == CF_PAIR || form == CF_PAIR_UPS || form == CF_XPAIR;
+        if (form == CF_XQUAD) {                                    // every slot: the transformed tap of its (cout, cin), or a zero pad
+          size_t pads = 0, nonzero = 0, wrong = 0;
+          const int n32 = (Cout + 63) / 64 * 2;
+          CHECK(n == (size_t)n32 * Cbi * 54 * 256, "CF_XQUAD pack size");
+          for (int nt = 0; nt < n32; ++nt) {
+            int cb = 0, ci0 = 0;
+            for (int s = 0; s < nseg; ci0 += segs[si][s], ++s)
+              for (int b = 0; b < (segs[si][s] + 7) / 8; ++b, ++cb)
+                for (int col = 0; col < 32; ++col)
+                  for (int c8 = 0; c8 < 8; ++c8) {
+                    const int co = nt * 32 + col, c = b * 8 + c8;
+                    const bool pad = co >= Cout || c >= segs[si][s];
+                    for (int r = 0; r < 9; ++r) {                  // r = product * 3 + ky
+                      float u[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                      if (!pad) {
+                        const float* f = &w[((size_t)co * Cin + ci0 + c) * 27];
+                        const int pr = r / 3, ky = r % 3;
+                        float g[3];
+                        for (int kx = 0; kx < 3; ++kx) {
+                          const float w0 = f[ky * 3 + kx], w1 = f[9 + ky * 3 + kx], w2 = f[18 + ky * 3 + kx];
+                          g[kx] = pr == 0 ? w1 : pr == 1 ? w2 - w1 : w0 - w1;
+                        }
+                        u[0] = g[0] / 4.f; u[1] = -((g[0] + g[1]) + g[2]) / 6.f; u[2] = -((g[0] - g[1]) + g[2]) / 6.f;
+                        u[3] = (g[0] / 24.f + g[1] / 12.f) + g[2] / 6.f; u[4] = (g[0] / 24.f - g[1] / 12.f) + g[2] / 6.f; u[5] = g[2];
+                      }
+                      for (int q = 0; q < 6; ++q) {
+                        const float v = pk[(((size_t)nt * Cbi + cb) * 54 + r * 6 + q) * 256 + conv_frag_off(col, c8 >> 2, 32) + (c8 & 3)];
+                        if (pad) { ++pads; unsigned b32; memcpy(&b32, &v, 4); CHECK(b32 == 0u, "CF_XQUAD pad slot not zero"); }
+                        else { nonzero += v != 0.f; wrong += memcmp(&v, &u[q], 4) != 0; }
+                      }
+                    }
+                  }
+          }
+          CHECK(wrong == 0, "CF_XQUAD: %zu slots are not the F(4,3) transform of their filter row", wrong);
+          printf("%-12s segs %-8s Cout %3d: %8zu floats, %7zu pad slots zero, %7zu real non-zero\n", names[fi], si ? "(8)" : "(5,16,3)",
+                 Cout, n, pads, nonzero);
+          continue;
+        }
         const int taps = conv_form_taps(form), ntile = (Cout + 63) / 64, groups = (int)(n / ((size_t)ntile * Cbi * taps * 512));
         // pad slots: cout past Cout or channel past its segment
         size_t nonzero = 0, pads = 0;
@@ -62,29 +100,14 @@ int main() {
                       else nonzero += v != 0.f;
                     }
           }
-        size_t moved = 0;
 #ifdef TM_PARENT_PACK
         CHECK(tmk_parent::conv_pack_floats(form, Cout, Cbi) == n, "%s pack size changed", names[fi]);
         std::vector<float> old(n, -9.f);
         tmk_parent::conv_pack_host(form, w.data(), Cout, segs[si], nseg, old.data());
-        if (!halves) CHECK(memcmp(old.data(), pk.data(), n * sizeof(float)) == 0, "%s bytes changed", names[fi]);
-        else {
-          for (size_t blk = 0; blk < n / 512; ++blk)
-            for (int col = 0; col < 64; ++col)
-              for (int c8 = 0; c8 < 8; ++c8) {
-                const size_t a = blk * 512 + col * 8 + c8, b = blk * 512 + conv_w_off(col, c8);
-                CHECK(memcmp(&old[a], &pk[b], 4) == 0, "%s block %zu cout %d cin %d: not the parent's float", names[fi], blk, col, c8);
-                moved += a != b;
-              }
-          std::vector<float> x(old), y(pk);                       // and as multisets of bit patterns
-          auto bits = [](float f) { unsigned u; memcpy(&u, &f, 4); return u; };
-          std::sort(x.begin(), x.end(), [&](float p, float q) { return bits(p) < bits(q); });
-          std::sort(y.begin(), y.end(), [&](float p, float q) { return bits(p) < bits(q); });
-          CHECK(memcmp(x.data(), y.data(), n * sizeof(float)) == 0, "%s is not a permutation of the parent's pack", names[fi]);
-        }
+        CHECK(memcmp(old.data(), pk.data(), n * sizeof(float)) == 0, "%s bytes changed", names[fi]);
 #endif
-        printf("%-12s segs %-8s Cout %3d: %8zu floats, %7zu pad slots zero, %7zu real non-zero, %7zu floats moved\n", names[fi],
-               si ? "(8)" : "(5,16,3)", Cout, n, pads, nonzero, moved);
+        printf("%-12s segs %-8s Cout %3d: %8zu floats, %7zu pad slots zero, %7zu real non-zero\n", names[fi],
+               si ? "(8)" : "(5,16,3)", Cout, n, pads, nonzero);
       }
   printf(fails ? "FAILED: %d checks\n" : "all checks passed\n", fails);
   return fails ? 1 : 0;
