@@ -472,10 +472,24 @@ int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias
  * multiple of 4), the form switched off (TM_CONV_XQUAD=0). */
 int tm_op_conv_xquad_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                          int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream);
+/* tm_op_conv_xquad_f32 with the schedule of conv3d_xquad forced: sched 0 = four barriers per cin block (all eighteen q-planes of
+ * a block staged in a phase of its own), 1 = the pipelined schedule (a ring of two sets of six q-planes staged under the
+ * products, three barriers).  Same pack, same order of sums: the two give identical bits.  tm_op_conv_xquad_f32 itself takes
+ * the launcher's choice per instantiation; TM_CONV_XQUAD_PIPE=0 (read once) keeps schedule 0 everywhere.  TM_ERR_ARG also for
+ * a sched outside 0 | 1. */
+int tm_op_conv_xquad_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                               int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, int sched, void* stream);
+/* The dynamic LDS (bytes) of conv3d_xquad in the large | small tile (half 0 | 1), tile width tw (8 | 16) and schedule sched
+ * (0 | 1); -1 if there is no such instantiation.  No device call. */
+int tm_conv_xquad_lds_bytes(int half, int tw, int sched);
 /* Timing hook (tools/bench_conv_xpair.py): that conv packed once for `form` (0 = the pair form, 1 = the x-pair form, 2 = the
  * x-quad form), then `iters` launches, each between two events of its own: ms_out[i] (HOST) = the time of launch i. */
 int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                              int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream);
+/* The same with the schedule of conv3d_xquad forced (form 2 only): sched 0 | 1 as in tm_op_conv_xquad_sched_f32, -1 = the
+ * launcher's choice, which is what tm_op_conv_pad1_time_f32 takes. */
+int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                   int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out, void* stream);
 
 /* The fp32 1x1x1 conv / Linear (conv1_mfma) in every form the model launches: y = res + gate_up * act(W x + b).
  * x_cb8: DEVICE [N][x_cbtot][Z][S][S][8]; the conv reads the channel-block slice [x_cb0, x_cb0 + ceil(Cin/8)) of it in place
@@ -500,7 +514,9 @@ int tm_conv1_form(long vox, int ntile, int tile_variant);
  * the output phase 2 py + px of kernel 1 (else 0); what 2: the staging store (ds_write_b128) into plane p of the thread's ky-th
  * item (x-pair: ky 0, kx = the q-plane).  out64[lane] = byte address in the workgroup's dynamic LDS, -1 for a lane that stores
  * nothing.  kernel 4 = conv3d_xquad (3 is no kernel and stays refused): tw 8 | 16, wave 0..7 (0..3 in the small tile), kx = the wave's q-th transform position
- * (0..2), in what 2 the q-plane (0..5).  Returns 0, or -1 if there is no such instantiation, fragment or item. */
+ * (0..2), in what 2 the q-plane (0..5).  kernel 5 = conv3d_xquad in its pipelined schedule: as 4, but the X planes are a ring of
+ * two sets of six and sub = the plane set (0 | 1) of an activation fragment or a staging store (product n of the running count
+ * reads set n & 1; sub 0 for a weight fragment).  Returns 0, or -1 if there is no such instantiation, fragment or item. */
 int tm_conv_frag_addrs(int kernel, int half, int tw, int what, int wave, int p, int ky, int kx, int sub, int* out64);
 
 /* 16-bit variant of the 3x3x3 pad-1 conv (Z == 2): x fp32 CB8 is rounded to `dtype` (TM_DTYPE_BF16 | TM_DTYPE_F16, RNE) on

@@ -95,6 +95,8 @@ struct ConvLaunch {
   int res_half = 0;      // k x 3 x 3 only: `res` lives at S/2 and is read at (z, y >> 1, x >> 1): the residual of a ResBlock(up=True)
                          // is the nearest-x2 upsampled block input (model/MBAblocks.py:254-258,297)
   int zmode = ZM_PAD1;   // the caller's statement of the z semantics; must agree with w.form (ignored for CF_1X1)
+  int xquad_sched = -1;  // CF_XQUAD only: 0 = the four-barrier schedule of conv3d_xquad, 1 = the pipelined one, -1 = the launcher's
+                         // choice per instantiation (TM_CONV_XQUAD_PIPE=0: the four-barrier schedule everywhere)
   // CF_PAIR, Cout == 64, the 128-voxel tile, no residual / gate / flags: fuse RMSNorm(C) * norm_w -> x (1 + scale) +
   // shift -> SiLU into the epilogue and write `a2` (the next conv's input) instead of y; y carries the geometry only
   int fuse_norm = 0;
@@ -112,8 +114,11 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant);
 // byte addresses in LDS of the 64 lanes of wave wv for one fragment read or staging store of conv3d_zpair (kernel 0),
 // conv3d_zpair_ups (1), conv3d_xpair (2), conv3d_xquad (4; 3 is no kernel: waves 0 .. 7 in the large tile, kx = the wave's q 0 .. 2, in a staging
-// store the q-plane 0 .. 5), instantiation <half, tw> (tm_kernels.hip); -1: no such thing; no device call
+// store the q-plane 0 .. 5), its pipelined schedule (5: as 4, `sub` = the plane set 0 | 1 of an X fragment or a staging store),
+// instantiation <half, tw> (tm_kernels.hip); -1: no such thing; no device call
 int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out);
+// the dynamic LDS of conv3d_xquad<half, tw> in schedule sched (0 | 1), bytes; -1: no such instantiation; no device call
+int conv_xquad_lds_bytes(int half, int tw, int sched);
 // which conv1_mfma instantiation a CF_1X1 launch takes (1 <1, 2>, 2 <2, 2>, 3 <2, 4>; 0 = refused); no device call
 int conv1_form(long vox, int ntile, int tile_variant);
 

@@ -831,7 +831,23 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
 // the first patch, the others the second (conv_lane_voxel's TW = 16 table), so each group reads sixteen consecutive rows.
 // Ring schedule and barriers are conv3d_xpair's: product n = 3 cb + p reads slot n & 1, the pieces of product n + 1 go out behind
 // its first taps, a wave retires its own with the vmcnt(0) in front of the next product's barrier.
-template <int HALF, int TW>
+//
+// PIPE = 1, the pipelined schedule (same pack, tiles, lane maps, accumulators and epilogue): the X planes are a ring of TWO SETS
+// of six q-planes, and no phase is left in which the matrix pipe must idle.  The products of a block run in the order X0, X1,
+// X0 + X1 (pack products 2, 1, 0: the accumulator families are independent, and inside one the order stays cin block, ky, k, so
+// no bit of any output changes); the running count n = 3 cb + i gives both the weight slot and the plane set, n & 1.  While
+// product n is multiplied, in its first taps (between a tap's fragment reads and its MFMAs, where the pieces of the weight ring
+// go out as well), the staging threads transform and store the planes of product n + 1 into the other set: X1 under X0's product; then X0 += X1 in place (no temporaries) and the sum under X1's, two planes per tap, after
+// which the registers take the loads of block cb + 1 (X0 first); X0(cb + 1) under the sum's.  The one barrier in front of each
+// product publishes its weight slot and its plane set: a wave arrives with lgkmcnt(0) for its own stores and the vmcnt that
+// covers its own pieces -- vmcnt(12) in front of the sum's product, where the twelve X loads issued behind the pieces may stay
+// in flight (every wave that loads issues exactly twelve: the addresses of items outside the plane are clamped, not branched
+// around), vmcnt(0) elsewhere.  Three barriers per cin block:
+//   [ pieces(0), X(0) -> registers, T(X0) -> set 0 ]   then per block   vmcnt | lgkmcnt(0) | B | P(X0), T(X1) | .. | B | P(X1),
+//   T(X0 + X1), X(cb + 1) -> registers | vmcnt(12) | lgkmcnt(0) | B | P(X0 + X1), T(X0(cb + 1))
+// LDS: 36 864 B of ring + 12 q-planes, not less than the exchange area behind the K loop (NW x 3 x 4 KiB): 98 304 B in both
+// large tiles (one workgroup per CU, as before), 64 512 B (<1,16>) and 67 584 B (<1,8>) in the small ones: two per CU.
+template <int HALF, int TW, int PIPE = 0>
 struct XQGeo {
   static constexpr int TW_ = TW;
   static constexpr int NW = HALF ? 4 : 8;                        // waves per workgroup
@@ -846,18 +862,42 @@ struct XQGeo {
   static constexpr int WTAP = 256;                               // floats of one tap of 32 couts
   static constexpr int WSLOT = 18 * WTAP;                        // floats of one product of a (cout tile, cin block)
   static constexpr int KP = (18 + NW - 1) / NW;                  // LDS-DMA pieces (one tap each) of a slot per wave, at most
-  static constexpr int LDS_BYTES = (2 * WSLOT + 18 * XP * 8) * 4;
+  static constexpr int XSET = 6 * XP * 8;                        // floats of the six q-planes of one product
+  static constexpr int NSET = PIPE ? 2 : 3;                      // sets in LDS: the ring of two | the three products of a block
+  static constexpr int XCH = NW * 3 * 1024;                      // floats of the exchange area behind the K loop
+  static constexpr int LDS_BYTES = (2 * WSLOT + NSET * XSET > XCH ? 2 * WSLOT + NSET * XSET : XCH) * 4;
   static_assert(2 * WSLOT * 4 <= 65536 && LDS_BYTES <= 160 * 1024, "LDS-DMA destinations below 64 KiB, the CU's LDS");
+  static_assert(!PIPE || !HALF || LDS_BYTES <= 80 * 1024, "two workgroups of the small tile per CU");
 };
+// plane q of the input transform from the six columns of a group (the one statement of T0 .. T5, for both schedules)
+template <class V>
+TM_HD V xq_transform(int q, const V (&d)[6]) {
+  switch (q) {
+    case 0: return (4.f * d[0] - 5.f * d[2]) + d[4];
+    case 1: return (d[3] + d[4]) - 4.f * (d[1] + d[2]);
+    case 2: return 4.f * (d[1] - d[2]) - (d[3] - d[4]);
+    case 3: return 2.f * (d[3] - d[1]) + (d[4] - d[2]);
+    case 4: return 2.f * (d[1] - d[3]) + (d[4] - d[2]);
+    default: return (4.f * d[1] - 5.f * d[3]) + d[5];
+  }
+}
 // the lane's group (0 .. 31 of the wave's tile) and the float offset of tap (ky, q) in a product slot
 TM_HD constexpr int xq_lane_group(int tw, int i32) { return tw == 8 ? conv_lane_voxel(16, i32) : i32; }
 // The constant part of conv3d_xquad's X fragment address (floats) inside a product's six planes: row ky of q-plane q.
 template <class G>
 TM_HD constexpr int xq_xtap(int q, int ky) { return q * G::XP * 8 + conv_frag_off(ky * G::GW, 0, G::XP); }
+// The base of a lane's X fragments (floats behind the weight ring) in plane set `set` (the product's own, or the ring's set of the
+// pipelined schedule) for q half qh, lxb = the lane's conv_lane_of offset; and of a staging item's slot in plane q of a set
+template <class G>
+TM_HD constexpr int xq_xfrag(int set, int qh, int lxb) { return set * G::XSET + 3 * qh * G::XP * 8 + lxb; }
+template <class G>
+TM_HD constexpr int xq_xstage(int set, int q, int item) {
+  return set * G::XSET + q * G::XP * 8 + conv_frag_off(conv_stage_row(item), conv_stage_half(item), G::XP);
+}
 
-template <int HALF, int TW>
+template <int HALF, int TW, int PIPE>
 __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) {
-  using G = XQGeo<HALF, TW>;
+  using G = XQGeo<HALF, TW, PIPE>;
   static_assert(G::XITEMS <= 64 * G::NW, "one staging item per thread");
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float* lw = lds;                                               // the weight ring; the X planes follow at float 2 * WSLOT
@@ -888,7 +928,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
     }
   }
   const long zplane = (long)S * S * 8;
-  int xw = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP);
+  int xw = 2 * G::WSLOT + xq_xstage<G>(0, 0, tid);
   asm volatile("" : "+v"(xw));
 
   // ---- per-lane fragment addresses ----
@@ -898,8 +938,8 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
   {
     const ConvLane l = conv_lane_of<G::TR, G::GW, G::HR * G::GW, G::GW, G::XP>(gt * 32 + xq_lane_group(TW, i32), h, 0, 0);
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {                                // one hidden base per product, in 16-byte slots
-      xb[p] = (2 * G::WSLOT + (p * 6 + 3 * qh) * G::XP * 8 + l.xb) / 4;
+    for (int p = 0; p < 3; ++p) {                                // one hidden base per product, in 16-byte slots (PIPE: [0], of set 0)
+      xb[p] = (2 * G::WSLOT + xq_xfrag<G>(p, qh, l.xb)) / 4;
       asm volatile("" : "+v"(xb[p]));
     }
     const int n = pg * G::NPB + l.ps;
@@ -936,16 +976,110 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
   };
   // the six transform planes of one product from its six columns
   auto put_t = [&](int p, const f32x4 (&d)[6]) __attribute__((always_inline)) {
-    float* o = lds + xw + p * 6 * G::XP * 8;
-    const f32x4 e42 = d[4] - d[2];
-    *(f32x4*)(o) = (4.f * d[0] - 5.f * d[2]) + d[4];
-    *(f32x4*)(o + G::XP * 8) = (d[3] + d[4]) - 4.f * (d[1] + d[2]);
-    *(f32x4*)(o + 2 * G::XP * 8) = 4.f * (d[1] - d[2]) - (d[3] - d[4]);
-    *(f32x4*)(o + 3 * G::XP * 8) = 2.f * (d[3] - d[1]) + e42;
-    *(f32x4*)(o + 4 * G::XP * 8) = 2.f * (d[1] - d[3]) + e42;
-    *(f32x4*)(o + 5 * G::XP * 8) = (4.f * d[1] - 5.f * d[3]) + d[5];
+    float* o = lds + xw + p * G::XSET;
+#pragma unroll
+    for (int q = 0; q < 6; ++q) *(f32x4*)(o + q * G::XP * 8) = xq_transform(q, d);
   };
 
+  if constexpr (PIPE) {
+  // ---- the pipelined schedule (header comment): product i of a block is pack product 2 - i, in slot and plane set n & 1 ----
+  const bool stg = tid < G::XITEMS;
+  const bool ldw = __builtin_amdgcn_readfirstlane(wv * 64 < G::XITEMS);   // this wave has staging items: it loads X
+  // every load is issued, whatever the item: exactly twelve per loading wave, which the counted vmcnt relies on
+  auto load_xc = [&](int cb) __attribute__((always_inline)) {
+    const float* xp = a.x + (long)cb * a.x_plane + (xoff >= 0 ? xoff : 0);
+#pragma unroll
+    for (int z = 0; z < 2; ++z) {                                // X0's six first: the next block's first product needs only them
+      const float* b = xp + z * zplane;
+      xr[z][0] = *(const f32x4*)(okl ? b - 8 : b);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) xr[z][1 + c] = *(const f32x4*)(b + 8 * c);
+      xr[z][5] = *(const f32x4*)(okr ? b + 32 : b);
+    }
+  };
+  // ... and the columns outside the plane become zero where the plane is first used, a product later: a select behind the load
+  // would wait for it on the spot
+  auto mask_x = [&](int z) __attribute__((always_inline)) {
+    xr[z][0] = okl ? xr[z][0] : zero4;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) xr[z][1 + c] = xoff >= 0 ? xr[z][1 + c] : zero4;
+    xr[z][5] = okr ? xr[z][5] : zero4;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) asm volatile("" : "+v"(xr[z][c]));   // all six HERE, in front of the product's pieces: a wait for a
+  };                                                                 // column at its first use further on would wait for those too
+  int xw4 = xw / 4;                                              // in 16-byte slots, as xb: the set is a run-time term, and behind a
+  asm volatile("" : "+v"(xw4));                                  // float index the store would lose its alignment and be split
+  auto put_q = [&](int q, const f32x4 (&d)[6], int set) __attribute__((always_inline)) {
+    ((f32x4*)lds)[xw4 + set * (G::XSET / 4) + q * G::XP * 2] = xq_transform(q, d);
+  };
+  constexpr int LOADTAP = G::KP > 3 ? G::KP - 1 : 2;             // the X loads go out behind the last piece and the last plane of the sum
+  static_assert(LOADTAP < 9, "inside the product");
+
+#pragma unroll
+  for (int k = 0; k < G::KP; ++k) lds_dma_piece<4, 18, G::NW>(lw_lds, 0, 2 * G::WSLOT, k, wvu, wvo, wrs);   // product 0: X0's of block 0
+  if (ldw) load_xc(0);
+  else {
+#pragma unroll
+    for (int c = 0; c < 12; ++c) xr[c / 6][c % 6] = zero4;
+  }
+  mask_x(0);
+  if (stg) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) put_q(q, xr[0], 0);
+  }
+  auto block = [&](int cb, auto more_c) __attribute__((always_inline)) {
+    constexpr bool more = decltype(more_c)::value;
+    __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const int n = cb * 3 + i, par = n & 1;
+      const int p = 2 - i;                                       // pack product and accumulator family: X0, X1, X0 + X1
+      const bool follows = i < 2 || more;                        // product n + 1 exists: pack product (i == 2 ? 2 of the next block : p - 1)
+      // this wave's pieces of product n landed (the X loads issued behind them may stay in flight), its planes of it stored;
+      // behind the barrier everybody's are visible, and slot and set of product n - 1 are free
+      if (i == 2 && more && ldw) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_waitcnt(0xC07F);                        // lgkmcnt(0) only
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_barrier();
+      asm volatile("" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      const float* lwc = lw + par * G::WSLOT + wb;
+      const int xbn = xb[0] + par * (G::XSET / 4);
+      const int nsrc = (i == 2 ? cb * 3 + 5 : cb * 3 + p - 1) * G::WSLOT;
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {                            // (q counts from the wave's 3 qh: in both bases)
+          const int tap = ky * 3 + q;
+          const f32x4 wf = *(const f32x4*)(lwc + (ky * 6 + q) * G::WTAP);
+          const f32x4 xf = ((const f32x4*)lds)[xbn + xq_xtap<G>(q, ky) / 4];
+          // between the tap's fragment reads and its MFMAs (behind the MFMAs the stores and the pieces held the next tap's reads
+          // back until those had issued: 2 - 6 % slower at the op level, profiles/fp32_xquad_pipe.txt section 2)
+          if (follows) {
+            if (tap == 0 && i != 1) mask_x(i == 0 ? 1 : 0);      // X1 of this block | X0 of the next, loaded a product ago or more
+            if (i == 1) {                                        // X0 + X1 in place, two planes in each of the first three taps
+              if (tap == 0) {
+#pragma unroll
+                for (int c = 0; c < 6; ++c) xr[0][c] = xr[0][c] + xr[1][c];
+              }
+              if (tap < 3 && stg) { put_q(2 * tap, xr[0], par ^ 1); put_q(2 * tap + 1, xr[0], par ^ 1); }
+            } else if (tap < 6 && stg) {
+              put_q(tap, i == 0 ? xr[1] : xr[0], par ^ 1);       // X1 of this block | X0 of the next
+            }
+            if (tap < G::KP) lds_dma_piece<4, 18, G::NW>(lw_lds, (par ^ 1) * G::WSLOT, nsrc, tap, wvu, wvo, wrs);
+            if (i == 1 && more && tap == LOADTAP && ldw) load_xc(cb + 1);
+          }
+#pragma unroll
+          for (int kk = 0; kk < 4; ++kk) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[kk], xf[kk], acc[p][q], 0, 0, 0);
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+  };
+  for (int cb = 0; cb + 1 < a.Cbi; ++cb) block(cb, std::true_type{});
+  block(a.Cbi - 1, std::false_type{});
+  } else {
   load_x(0);
 #pragma unroll
   for (int k = 0; k < G::KP; ++k) issue_piece(0, k);
@@ -997,6 +1131,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
   };
   for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
   stage(a.Cbi - 1, std::false_type{});
+  }
 
   // ---- the q halves exchange through LDS (free behind the barrier: nothing of the K loop is read or in flight any more):
   // half 0 (A0, A1, A2) hands d = A1 - A2 over and takes s' = A3 + A4, half 1 (A3, A4, A5) the reverse; a tile is
@@ -1200,6 +1335,17 @@ int conv_tile(int form, long ovox, int ntile, int S, int tile_variant) {
   return variant == 2 ? 2 : 1;
 }
 
+// The schedule of conv3d_xquad a launch takes where the caller forces none: the pipelined one (PIPE = 1) in the instantiations
+// <half, tw> where it won at the op level (profiles/fp32_xquad_pipe.txt); TM_CONV_XQUAD_PIPE=0 (read once) keeps the
+// four-barrier schedule everywhere.  The form and the pack are the same in both, so conv_pick_form does not see the switch.
+static bool xquad_pipe_default(bool half, int tw) {
+  static const bool on = [] {
+    const char* v = getenv("TM_CONV_XQUAD_PIPE");
+    return !(v && atoi(v) == 0);
+  }();
+  return on && !half && tw == 16;              // <0, 16> alone: <0, 8> ties or loses by 2 %, the small tiles lose 13 - 16 %
+}
+
 // One k x 3 x 3 launch: KERN over the tiles of geometry G (TW x TR voxels of NPB patches, LDS_BYTES of dynamic LDS), `factor`
 // workgroups per (patch group, tile, cout tile): output planes and / or the four phases.
 template <void (*KERN)(ConvArgs), class G, int BLOCK = 256>
@@ -1337,10 +1483,14 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
       });
     case CF_XQUAD:
       a.ntile = (L.w.Cout + 31) / 32;                          // the kernel's cout tiles are of 32 (the pack holds 2 * ntile of them)
+      if (L.xquad_sched < -1 || L.xquad_sched > 1) return hipErrorInvalidValue;
       return with_tile_width<16>(S, [&](auto tw) {
         constexpr int TW = decltype(tw)::value;
-        return large ? launch_tiled<conv3d_xquad<0, TW>, XQGeo<0, TW>, 64 * XQGeo<0, TW>::NW>(a, 1, s)
-                     : launch_tiled<conv3d_xquad<1, TW>, XQGeo<1, TW>, 64 * XQGeo<1, TW>::NW>(a, 1, s);
+        if (L.xquad_sched < 0 ? xquad_pipe_default(!large, TW) : L.xquad_sched == 1)
+          return large ? launch_tiled<conv3d_xquad<0, TW, 1>, XQGeo<0, TW, 1>, 64 * XQGeo<0, TW, 1>::NW>(a, 1, s)
+                       : launch_tiled<conv3d_xquad<1, TW, 1>, XQGeo<1, TW, 1>, 64 * XQGeo<1, TW, 1>::NW>(a, 1, s);
+        return large ? launch_tiled<conv3d_xquad<0, TW, 0>, XQGeo<0, TW, 0>, 64 * XQGeo<0, TW, 0>::NW>(a, 1, s)
+                     : launch_tiled<conv3d_xquad<1, TW, 0>, XQGeo<1, TW, 0>, 64 * XQGeo<1, TW, 0>::NW>(a, 1, s);
       });
     default:   // CF_XPAIR
       return with_tile_width<16>(S, [&](auto tw) {
@@ -1396,29 +1546,42 @@ static int xpair_frag_addrs(int what, int wv, int p, int ky, int q, int* out) {
   }
   return 0;
 }
-template <int HALF, int TW>
-static int xquad_frag_addrs(int what, int wv, int p, int ky, int q, int* out) {
-  using G = XQGeo<HALF, TW>;
+// set: the plane set of an X fragment or a staging store: the product's own in the four-barrier schedule, the ring's set (0 | 1)
+// in the pipelined one
+template <int HALF, int TW, int PIPE>
+static int xquad_frag_addrs(int what, int wv, int p, int ky, int q, int set, int* out) {
+  using G = XQGeo<HALF, TW, PIPE>;
   if (wv >= G::NW || p < 0 || p > 2 || q < 0 || q >= (what == 2 ? 6 : 3) || ky < 0 || ky > (what == 2 ? 0 : 2)) return -1;
+  if (set < 0 || set >= G::NSET) return -1;
   const int gt = wv >> 1, qh = wv & 1;
   for (int lane = 0; lane < 64; ++lane) {
     const int i32 = lane & 31, h = lane >> 5, tid = wv * 64 + lane;
     int a = -1;
     if (what == 0) a = 3 * qh * G::WTAP + conv_frag_off(i32, h, 32) + (ky * 6 + q) * G::WTAP;
     else if (what == 1)
-      a = 2 * G::WSLOT + (p * 6 + 3 * qh) * G::XP * 8 +
-          conv_lane_of<G::TR, G::GW, G::HR * G::GW, G::GW, G::XP>(gt * 32 + xq_lane_group(TW, i32), h, 0, 0).xb + xq_xtap<G>(q, ky);
+      a = 2 * G::WSLOT + xq_xtap<G>(q, ky) +
+          xq_xfrag<G>(set, qh, conv_lane_of<G::TR, G::GW, G::HR * G::GW, G::GW, G::XP>(gt * 32 + xq_lane_group(TW, i32), h, 0, 0).xb);
     else if (tid < G::XITEMS)
-      a = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP) + (p * 6 + q) * G::XP * 8;
+      a = 2 * G::WSLOT + xq_xstage<G>(set, q, tid);
     out[lane] = a < 0 ? -1 : a * 4;
   }
   return 0;
 }
+int conv_xquad_lds_bytes(int half, int tw, int sched) {
+  if (half < 0 || half > 1 || (tw != 8 && tw != 16) || sched < 0 || sched > 1) return -1;
+  if (sched) return half ? (tw == 8 ? XQGeo<1, 8, 1>::LDS_BYTES : XQGeo<1, 16, 1>::LDS_BYTES) : (tw == 8 ? XQGeo<0, 8, 1>::LDS_BYTES : XQGeo<0, 16, 1>::LDS_BYTES);
+  return half ? (tw == 8 ? XQGeo<1, 8, 0>::LDS_BYTES : XQGeo<1, 16, 0>::LDS_BYTES) : (tw == 8 ? XQGeo<0, 8, 0>::LDS_BYTES : XQGeo<0, 16, 0>::LDS_BYTES);
+}
 int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out) {
-  if (!out || kernel < 0 || kernel > 4 || kernel == 3 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > (kernel == 4 ? 7 : 3)) return -1;
-  if (kernel == 4 && tw == 8) return half ? xquad_frag_addrs<1, 8>(what, wv, p, ky, kx, out) : xquad_frag_addrs<0, 8>(what, wv, p, ky, kx, out);
-  if (kernel == 4 && tw == 16) return half ? xquad_frag_addrs<1, 16>(what, wv, p, ky, kx, out) : xquad_frag_addrs<0, 16>(what, wv, p, ky, kx, out);
-  if (kernel == 4) return -1;
+  const bool xq = kernel == 4 || kernel == 5;
+  if (!out || kernel < 0 || kernel > 5 || kernel == 3 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > (xq ? 7 : 3)) return -1;
+  if (kernel == 4 && tw == 8) return half ? xquad_frag_addrs<1, 8, 0>(what, wv, p, ky, kx, p, out) : xquad_frag_addrs<0, 8, 0>(what, wv, p, ky, kx, p, out);
+  if (kernel == 4 && tw == 16) return half ? xquad_frag_addrs<1, 16, 0>(what, wv, p, ky, kx, p, out) : xquad_frag_addrs<0, 16, 0>(what, wv, p, ky, kx, p, out);
+  // the pipelined schedule: sub = the plane set (0 for a weight fragment: slot 0 of the ring)
+  if (kernel == 5 && what == 0 && sub != 0) return -1;
+  if (kernel == 5 && tw == 8) return half ? xquad_frag_addrs<1, 8, 1>(what, wv, p, ky, kx, sub, out) : xquad_frag_addrs<0, 8, 1>(what, wv, p, ky, kx, sub, out);
+  if (kernel == 5 && tw == 16) return half ? xquad_frag_addrs<1, 16, 1>(what, wv, p, ky, kx, sub, out) : xquad_frag_addrs<0, 16, 1>(what, wv, p, ky, kx, sub, out);
+  if (xq) return -1;
 #define TM_FRAG(H, T)                                                                                              \
   if (half == H && tw == T) {                                                                                      \
     if (kernel == 0) return zpair_frag_addrs<ZPGeo<H, T>, H, T, false>(what, wv, p, ky, kx, sub, out);              \

@@ -306,31 +306,44 @@ static int xquad_args(const void* x, const void* w, const void* b, const void* y
     return fail(TM_ERR_ARG, "the x-quad form is switched off (TM_CONV_XQUAD=0)");
   return TM_OK;
 }
-extern "C" int tm_op_conv_xquad_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
-                                    int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream) {
+static int xquad_op(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8, int res_half, int N,
+                    int Cin, int Cout, int Z, int S, int tile_variant, int sched, void* stream) {
   if (const int rc = xquad_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
   if (res_half && !res_cb8) return fail(TM_ERR_ARG, "res_half needs a residual");
   ConvOp op;
   if (const int rc = conv_op(op, CF_XQUAD, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, Z, S, Z, S, ZM_PAD1, tile_variant, res_cb8,
                              res_half))
     return rc;
+  op.L.xquad_sched = sched;
   const int rc = finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_xquad (fp32)");
   return rc ? rc : conv_tile(CF_XQUAD, (long)N * Z * S * S, op.L.w.ntile, S, tile_variant);
+}
+extern "C" int tm_op_conv_xquad_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                                    int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream) {
+  return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, -1, stream);
+}
+// The same with the schedule of conv3d_xquad forced: 0 = the four-barrier schedule, 1 = the pipelined one (same pack, same bits).
+extern "C" int tm_op_conv_xquad_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                                          int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, int sched, void* stream) {
+  if (sched != 0 && sched != 1) return fail(TM_ERR_ARG, "sched must be 0 (four barriers) or 1 (pipelined) (got %d)", sched);
+  return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, sched, stream);
 }
 
 // Timing hook (tools/bench_conv_xpair.py): the 3x3x3 pad-1 conv at Z == 2 packed once for `form` (0 = the pair form, 1 = the
 // x-pair form, 2 = the x-quad form), then `iters` launches, each between two events of its own; ms_out[i] (host) = the time of
-// launch i.
-extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                                        int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream) {
+// launch i.  sched: the schedule of conv3d_xquad (form 2 only): -1 = the launcher's choice, 0 | 1 forced.
+static int pad1_time(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin, int Cout, int S, int form,
+                     int tile_variant, int sched, int iters, float* ms_out, void* stream) {
   if (const int rc = form == 2 ? xquad_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant)
                                : xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant))
     return rc;
   if (form < 0 || form > 2 || iters < 1 || !ms_out) return fail(TM_ERR_ARG, "form must be 0, 1 or 2, iters >= 1, ms_out non-null");
+  if (sched < -1 || sched > 1 || (sched >= 0 && form != 2)) return fail(TM_ERR_ARG, "sched must be -1, or 0 | 1 with form 2 (got %d)", sched);
   const int cf = conv_pick_form(3, ZM_PAD1, 2, true, form == 2 ? ROLE_OP_XQUAD : form ? ROLE_OP_XPAIR : ROLE_OP);
   if (!form && cf != CF_PAIR) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
   ConvOp op;
   if (const int rc = conv_op(op, cf, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, 2, S, 2, S, ZM_PAD1, tile_variant)) return rc;
+  op.L.xquad_sched = sched;
   hipEvent_t e0 = op.tmp.event(), e1 = op.tmp.event();
   if (op.tmp.err) return op.tmp.report();
   hipStream_t st = (hipStream_t)stream;
@@ -343,11 +356,21 @@ extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, c
   }
   return finish(st, hipSuccess, "conv_pad1_time (fp32)");
 }
+extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                        int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream) {
+  return pad1_time(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, form, tile_variant, -1, iters, ms_out, stream);
+}
+extern "C" int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                              int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out,
+                                              void* stream) {
+  return pad1_time(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, form, tile_variant, sched, iters, ms_out, stream);
+}
 
 // power of two >= 2: what a half-resolution gate needs of S (read at (z, y >> 1, x >> 1))
 static bool half_gate_ok(int S) { return S >= 2 && (S & (S - 1)) == 0; }
 
 extern "C" int tm_conv1_form(long vox, int ntile, int tile_variant) { return conv1_form(vox, ntile, tile_variant); }
+extern "C" int tm_conv_xquad_lds_bytes(int half, int tw, int sched) { return conv_xquad_lds_bytes(half, tw, sched); }
 extern "C" int tm_conv_frag_addrs(int kernel, int half, int tw, int what, int wave, int p, int ky, int kx, int sub, int* out64) {
   return conv_frag_addrs(kernel, half, tw, what, wave, p, ky, kx, sub, out64);
 }
