@@ -745,21 +745,24 @@ int tm_op_conv_wgrad(const void* x_cb8, const void* dy_cb8, void* dw_host, void*
  *   role 1: the pack tm_op_conv_dgrad builds: the filter flipped in z, y, x with cin <-> cout transposed. */
 long tm_conv_pack_floats(int Cout, int Cin, int ksize, int Z, int role);      /* floats of one pack; -1: bad argument */
 int tm_op_conv_pack_dev(const void* w_dev, void* pack_dev, int Cout, int Cin, int ksize, int Z, int role, void* stream);
-/* tm_op_conv_mfma(..., zmode 0, up2 0, variant 0) on a role-0 pack; bias_dev [Cout] DEVICE */
+/* tm_op_conv_mfma(..., zmode 0, up2 0, variant 0) on a role-0 pack; bias_dev [Cout] DEVICE.  Z 1 .. 4 or 8 here, in the data gradient
+ * and in the weight gradient below (Z = 8: rna_slc 16); 5, 6, 7 are refused before any launch. */
 int tm_op_conv_mfma_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout,
                            int Z, int S, int ksize, void* stream);
-/* tm_op_conv_dgrad on a role-1 pack */
+/* tm_op_conv_dgrad on a role-1 pack; Z 1 .. 4 or 8 */
 int tm_op_conv_dgrad_packed(const void* dy_cb8, const void* pack_dev, void* dx_cb8, int N, int Cin, int Cout, int Z, int S,
                             int ksize, void* stream);
 /* dL/dw [Cout][Cin][k^3] and dL/dbias [Cout] (may be NULL) to DEVICE pointers, on the fp32 MFMA pipe; accumulate 1 adds into what
- * is there.  Z 1 .. 4, square S x S planes.  Partial sums over chunks of the voxel range are added in chunk order (no atomics);
- * the chunk count depends on (N, Z, S, Cin, Cout) only, so every run on every device gives the same bits. */
+ * is there.  Z 1 .. 4 or 8, square S x S planes: up to Z = 4 a spatial tile holds every z plane; Z = 8 runs the slab form (z tiled
+ * in slabs of 4 output planes, 6 staged input planes).  Partial sums over chunks of the tile list are added in chunk order (no
+ * atomics); the chunk count depends on (N, Z, S, Cin, Cout) only, so every run on every device gives the same bits. */
 int tm_op_conv_wgrad_dev(const void* x_cb8, const void* dy_cb8, void* dw_dev, void* db_dev_or_null, int accumulate, int N,
                          int Cin, int Cout, int Z, int S, int ksize, void* stream);
 
 /* Timing hook (tools/bench_train.py): the weight gradient of one layer on random device data, engine 0 = the VALU kernel of
  * tm_op_conv_wgrad, 1 = the MFMA kernel of tm_op_conv_wgrad_dev (with its chunk reduction).  After one warm-up launch,
- * ms_per_launch_host[r], r < reps, is the time per launch of `iters` launches between two events. */
+ * ms_per_launch_host[r], r < reps, is the time per launch of `iters` launches between two events.  Z as tm_op_conv_wgrad_dev for
+ * engine 1, 1 .. 4 for engine 0. */
 int tm_op_conv_wgrad_time(int N, int Cin, int Cout, int Z, int S, int ksize, int engine, int iters, int reps,
                           float* ms_per_launch_host, void* stream);
 
@@ -832,7 +835,8 @@ int tm_op_adam(void* p_dev, const void* g_dev, void* m_dev, void* v_dev, long n,
 int tm_op_rank_sum(const void* parts_dev, void* out_dev, int W, long n, void* stream);
 
 /* Timing hook (tools/bench_rank_sum.py): tm_op_rank_sum's kernel on random device data.  After one warm-up launch,
- * ms_per_launch_host[r], r < reps, is the time per launch of `iters` launches between two events. */
+ * ms_per_launch_host[r], r < reps, is the time per launch of `iters` launches between two events.  Z as tm_op_conv_wgrad_dev for
+ * engine 1, 1 .. 4 for engine 0. */
 int tm_op_rank_sum_time(int W, long n, int iters, int reps, float* ms_per_launch_host, void* stream);
 
 #ifdef __cplusplus

@@ -375,7 +375,8 @@ hipError_t launch_prep_bwd(const float* x, long x_ns, const float* g, long g_ns,
 size_t prep_bwd_scratch_floats(int N, int Cb, int Z, int S, bool with_mod);
 hipError_t launch_conv_wgrad(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, hipStream_t s);
 hipError_t launch_chan_sum(const TV& x, float* out, int C, hipStream_t s, int accumulate = 0);
-// the same dW on the matrix pipe, to a device pointer; scratch: conv_wgrad_scratch_floats(...) floats (0: none needed)
+// the same dW on the matrix pipe, to a device pointer (Z 1 .. 4, or 8: the z-slab form); scratch: conv_wgrad_scratch_floats(...) floats
+// (0: none needed)
 hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, int accumulate, float* scratch,
                                   hipStream_t s);
 int conv_wgrad_chunks(int N, int Z, int S, int Cin, int Cout, int* per_out);

@@ -1336,7 +1336,7 @@ static int conv_packed(const void* x_cb8, const void* pack_dev, const void* bias
 static int resident_geo(int N, int Cin, int Cout, int Z, int S, int ksize) {
   if (ksize != 1 && ksize != 3) return fail(TM_ERR_ARG, "ksize must be 1 or 3");
   if (N < 1 || Cin < 1 || Cout < 1 || S < 1) return fail(TM_ERR_ARG, "N, Cin, Cout and S must be positive");
-  if (Z < 1 || Z > 4) return fail(TM_ERR_ARG, "Z must be 1 .. 4");
+  if (Z < 1 || (Z > 4 && Z != 8)) return fail(TM_ERR_ARG, "Z must be 1 .. 4 or 8 (got %d)", Z);
   return TM_OK;
 }
 extern "C" int tm_op_conv_mfma_packed(const void* x_cb8, const void* pack_dev, const void* bias_dev, void* y_cb8, int N, int Cin, int Cout,
@@ -1635,6 +1635,7 @@ extern "C" int tm_op_conv_wgrad_time(int N, int Cin, int Cout, int Z, int S, int
                                      float* ms_per_launch_host, void* stream) {
   if (!ms_per_launch_host || iters < 1 || reps < 1 || (engine != 0 && engine != 1)) return fail(TM_ERR_ARG, "bad argument");
   if (int rc = resident_geo(N, Cin, Cout, Z, S, ksize)) return rc;
+  if (!engine && Z > 4) return fail(TM_ERR_ARG, "engine 0 (the VALU kernel): Z must be 1 .. 4 (got %d)", Z);
   const int taps = ksize == 1 ? 1 : 27;
   hipStream_t st = (hipStream_t)stream;
   TV x = cb8_view(nullptr, N, Cin, Z, S, S), dy = cb8_view(nullptr, N, Cout, Z, S, S);

@@ -488,6 +488,155 @@ __global__ __launch_bounds__(256) void conv_wgrad_mfma_kernel(WgradMfmaArgs a) {
   }
 }
 
+// The store of conv_wgrad_mfma_kernel as a function, for the slab form below (that kernel keeps its own text, so that its Z <= 4 code
+// objects stay what they were): the 1x1x1 form sums its four waves through LDS in the order 0, 1, 2, 3, then the tile goes
+// to dW (chunks == 1: written or added) or to this chunk's partial.  xs: the kernel's X staging array, free by now (6912 floats for 27
+// taps, 4096 for one).
+template <int TAPS, int NA>
+__device__ __forceinline__ void wgrad_mfma_store(const WgradMfmaArgs& a, f32x16 (&acc)[NA], float* xs, int tid, int lane, int c, int h, int q) {
+  if (TAPS == 1) {
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 16; ++r) xs[(q * 16 + r) * 64 + lane] = acc[0][r];
+    __syncthreads();
+    if (q == 0) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[0][r] = ((xs[r * 64 + lane] + xs[(16 + r) * 64 + lane]) + xs[(32 + r) * 64 + lane]) + xs[(48 + r) * 64 + lane];
+    }
+  }
+  // D register r of a lane: row (cout) 8 (r / 4) + 4 h + r % 4, column (cin) c
+  const int ic = blockIdx.y * 32 + c;
+  float* out = a.out + (gridDim.z > 1 ? (long)blockIdx.z * a.Cout * a.Cin * TAPS : 0);
+  const bool add = gridDim.z == 1 && a.accumulate;
+  if (TAPS == 27) {
+    // 27-tap form: through LDS, 8 cout rows at a time, so that a row of the tile leaves as one run of (cins of the tile) x 27
+    // consecutive floats and not as 4-byte stores 108 bytes apart.  xs [8 rows][32 cin][27 taps]: 6912 floats.
+    const int ic0 = blockIdx.y * 32, run = min(32, a.Cin - ic0) * 27;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < NA; ++i) {
+        const int t = q + 4 * i;
+        if (t < 27) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) xs[((4 * h + k) * 32 + c) * 27 + t] = acc[i][4 * g + k];
+        }
+      }
+      __syncthreads();
+      for (int row = 0; row < 8; ++row) {
+        const int oc = blockIdx.x * 32 + 8 * g + row;
+        if (oc >= a.Cout) break;
+        float* d = out + ((long)oc * a.Cin + ic0) * 27;
+        for (int e = tid; e < run; e += 256) d[e] = add ? d[e] + xs[row * 864 + e] : xs[row * 864 + e];
+      }
+    }
+  } else if (ic < a.Cin && q == 0) {
+#pragma unroll
+    for (int i = 0; i < NA; ++i) {
+      const int t = TAPS == 27 ? q + 4 * i : 0;
+      if (t >= TAPS) continue;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int oc = blockIdx.x * 32 + 8 * (r / 4) + 4 * h + (r % 4);
+        if (oc < a.Cout) {
+          float* d = out + ((long)oc * a.Cin + ic) * TAPS + t;
+          *d = add ? *d + acc[i][r] : acc[i][r];
+        }
+      }
+    }
+  }
+}
+
+// The Z = 8 form: z is a tiled dimension.  The tile list is (n, z slab, ty, tx); a slab owns TZ = 4 output planes z0 .. z0 + 3, and the
+// 27-tap form stages those 4 dY planes and the 6 X planes z0 - 1 .. z0 + 4 (planes outside [0, Z) are not read, and a (tap, z) pair
+// whose X plane lies there is skipped wave-uniformly as above: no MFMA on zeros).  The 1x1x1 form has no halo in any axis: its slab is
+// the voxel range of 4 planes.  Wave -> tap split, accumulators, chunking over the tile list and the store are those of the kernel
+// above.  LDS: TH x TW = 4 x 4: 8 KB dY + 27 KB X;  4 x 8 (S >= 8): 16 KB dY + 45 KB X (6 x 6 x 10 voxels x 32 channels).
+template <int TAPS, int TH, int TW>
+__global__ __launch_bounds__(256) void conv_wgrad_mfma_slab_kernel(WgradMfmaArgs a) {
+  constexpr int TZ = 4, HALO = TAPS == 27 ? 1 : 0, XH = TH + 2 * HALO, XW = TW + 2 * HALO, XP = TZ + 2 * HALO, NA = TAPS == 27 ? 7 : 1;
+  constexpr int NXS = XP * XH * XW * 32, NST = TAPS == 27 ? 6912 : 4096;        // NST: what wgrad_mfma_store needs of xs
+  __shared__ __attribute__((aligned(16))) float ys[TZ * TH * TW * 32];          // [zl][TH][TW][32 cout]
+  __shared__ __attribute__((aligned(16))) float xs[NXS > NST ? NXS : NST];      // [zp][XH][XW][32 cin], plane zp = z - z0 + HALO
+  const int tid = threadIdx.x, lane = tid & 63, c = lane & 31, h = lane >> 5;
+  const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int S = a.S, Z = a.Z;
+  const long plane = (long)Z * S * S * 8;
+  const int tiy = (S + TH - 1) / TH, tix = (S + TW - 1) / TW, slabs = (Z + TZ - 1) / TZ;
+  f32x16 acc[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
+  const int t0 = blockIdx.z * a.per, t1 = min(t0 + a.per, a.tiles);
+  for (int tl = t0; tl < t1; ++tl) {
+    int rem = tl;
+    const int tx = rem % tix; rem /= tix;
+    const int ty = rem % tiy; rem /= tiy;
+    const int z0 = (rem % slabs) * TZ, n = rem / slabs;
+    __syncthreads();
+    for (int i = tid; i < XP * XH * XW * 4; i += 256) {
+      const int cbl = i & 3;
+      int r = i >> 2;
+      const int hx = r % XW; r /= XW;
+      const int hy = r % XH;
+      const int zp = r / XH;
+      const int z = z0 + zp - HALO, y = ty * TH + hy - HALO, x = tx * TW + hx - HALO, cb = blockIdx.y * 4 + cbl;
+      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+      if (cb < a.Cbi && z >= 0 && z < Z && y >= 0 && y < S && x >= 0 && x < S) {
+        const float* p = a.x + (long)n * a.x_ns + (long)cb * plane + ((long)(z * S + y) * S + x) * 8;
+        v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);
+      }
+      float* d = xs + ((zp * XH + hy) * XW + hx) * 32 + cbl * 8;
+      *(f32x4*)d = v0; *(f32x4*)(d + 4) = v1;
+    }
+    for (int i = tid; i < TZ * TH * TW * 4; i += 256) {
+      const int cbl = i & 3;
+      int r = i >> 2;
+      const int lx = r % TW; r /= TW;
+      const int ly = r % TH;
+      const int zl = r / TH;
+      const int z = z0 + zl, y = ty * TH + ly, x = tx * TW + lx, cb = blockIdx.x * 4 + cbl;
+      f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
+      if (cb < a.Cbo && z < Z && y < S && x < S) {
+        const float* p = a.dy + (long)n * a.dy_ns + (long)cb * plane + ((long)(z * S + y) * S + x) * 8;
+        v0 = *(const f32x4*)p; v1 = *(const f32x4*)(p + 4);
+      }
+      float* d = ys + ((zl * TH + ly) * TW + lx) * 32 + cbl * 8;
+      *(f32x4*)d = v0; *(f32x4*)(d + 4) = v1;
+    }
+    __syncthreads();
+    if (TAPS == 27) {
+      for (int zl = 0; zl < TZ; ++zl) {
+        const int z = z0 + zl;
+        if (z >= Z) break;
+        for (int ly = 0; ly < TH; ++ly)
+#pragma unroll
+          for (int px = 0; px < TW / 2; ++px) {
+            const int lx = 2 * px + h;
+            const float av = ys[((zl * TH + ly) * TW + lx) * 32 + c];
+            const float* xb = xs + (((zl + 1) * XH + ly) * XW + lx) * 32 + c;      // X plane z of the slab image, tap (1, 0, 0)
+#pragma unroll
+            for (int i = 0; i < NA; ++i) {
+              const int t = q + 4 * i, kz = t / 9, ky = (t / 3) % 3, kx = t % 3, zi = z + kz - 1;
+              if (t < 27 && zi >= 0 && zi < Z)
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xb[(((kz - 1) * XH + ky) * XW + kx) * 32], acc[i], 0, 0, 0);
+            }
+          }
+      }
+    } else {
+      // voxel pair j of the slab tile belongs to wave j % 4; no halo: dY and X voxel v share the index
+      for (int j = q; j < TZ * TH * TW / 2; j += 4) {
+        const int v = 2 * j + h;
+        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(ys[v * 32 + c], xs[v * 32 + c], acc[0], 0, 0, 0);
+      }
+    }
+  }
+  wgrad_mfma_store<TAPS, NA>(a, acc, xs, tid, lane, c, h, q);
+}
+
+
 __global__ __launch_bounds__(256) void conv_wgrad_reduce_kernel(const float* part, long nw, int chunks, float* dw, int accumulate) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= nw) return;
@@ -501,14 +650,20 @@ static void wgrad_tile(int Z, int S, int& th, int& tw) {
   tw = S >= 8 ? 8 : 4;
   th = (S >= 8 && Z <= 2) ? 8 : 4;
 }
+// The tile list: (n, ty, tx) with every z plane in the tile up to Z = 4; at Z = 8 (the slab form) (n, z slab of 4 planes, ty, tx) with
+// the 4 x 8 in-plane tile from S = 8 on (61 KB of LDS, two workgroups per CU) and 4 x 4 below.  Returns the number of tiles.
+static int wgrad_tiles(int N, int Z, int S, int& th, int& tw) {
+  wgrad_tile(Z, S, th, tw);
+  if (Z > 4) th = 4;
+  return N * ((Z + 3) / 4) * ((S + th - 1) / th) * ((S + tw - 1) / tw);
+}
 // Chunks of the voxel range: about 1024 workgroups in all, at most one chunk per spatial tile, at most 256, and at most 16 Mi
 // floats (64 MB) of 27-tap partials, so that a narrow layer (64 -> 64: a 442 KB dW) does not spend its time writing and
 // re-reading copies of dW and the partials stay within the 256 MB last-level cache.  A function of the layer geometry only,
 // never of the device: the summation order, and with it every bit of dW, is the same on every box.
 int conv_wgrad_chunks(int N, int Z, int S, int Cin, int Cout, int* per_out) {
   int th, tw;
-  wgrad_tile(Z, S, th, tw);
-  const int tiles = N * ((S + th - 1) / th) * ((S + tw - 1) / tw);
+  const int tiles = wgrad_tiles(N, Z, S, th, tw);
   const long ct = (long)((Cout + 31) / 32) * ((Cin + 31) / 32);
   const long cap = (16L << 20) / ((long)Cout * Cin * 27);
   int chunks = (int)std::max<long>(1, std::min<long>(std::min<long>(std::min<long>(256, tiles), 1024 / ct), cap));
@@ -524,23 +679,27 @@ size_t conv_wgrad_scratch_floats(int N, int Z, int S, int Cin, int Cout, int tap
 hipError_t launch_conv_wgrad_mfma(const TV& x, const TV& dy, float* dw, int Cin, int Cout, int taps, int accumulate, float* scratch,
                                   hipStream_t s) {
   const int S = x.H, Z = x.Z;
-  if ((taps != 27 && taps != 1) || x.Z != dy.Z || x.H != dy.H || x.N != dy.N || Z < 1 || Z > 4 || x.H != x.W || dy.H != dy.W || S < 1 ||
+  if ((taps != 27 && taps != 1) || x.Z != dy.Z || x.H != dy.H || x.N != dy.N || Z < 1 || (Z > 4 && Z != 8) || x.H != x.W || dy.H != dy.W || S < 1 ||
       x.N < 1 || Cin < 1 || Cout < 1 || x.Cb != (Cin + 7) / 8 || dy.Cb != (Cout + 7) / 8)
     return hipErrorInvalidValue;
   int th, tw, per;
-  wgrad_tile(Z, S, th, tw);
+  const int tiles = wgrad_tiles(x.N, Z, S, th, tw);
   const int chunks = conv_wgrad_chunks(x.N, Z, S, Cin, Cout, &per);
   if (chunks > 1 && !scratch) return hipErrorInvalidValue;
-  WgradMfmaArgs a{x.p, x.nstride, x.Cb, dy.p, dy.nstride, dy.Cb, chunks > 1 ? scratch : dw, x.N, Z, S, Cout, Cin,
-                  x.N * ((S + th - 1) / th) * ((S + tw - 1) / tw), per, accumulate};
+  WgradMfmaArgs a{x.p, x.nstride, x.Cb, dy.p, dy.nstride, dy.Cb, chunks > 1 ? scratch : dw, x.N, Z, S, Cout, Cin, tiles, per, accumulate};
   const dim3 grid((unsigned)((Cout + 31) / 32), (unsigned)((Cin + 31) / 32), (unsigned)chunks);
 #define TM_WGRAD(TAPS, TH, TW) hipLaunchKernelGGL((conv_wgrad_mfma_kernel<TAPS, TH, TW>), grid, dim3(256), 0, s, a)
-  if (taps == 27) {
+#define TM_WGRAD_SLAB(TAPS, TH, TW) hipLaunchKernelGGL((conv_wgrad_mfma_slab_kernel<TAPS, TH, TW>), grid, dim3(256), 0, s, a)
+  if (Z > 4) {
+    if (taps == 27) { if (tw == 8) TM_WGRAD_SLAB(27, 4, 8); else TM_WGRAD_SLAB(27, 4, 4); }
+    else { if (tw == 8) TM_WGRAD_SLAB(1, 4, 8); else TM_WGRAD_SLAB(1, 4, 4); }
+  } else if (taps == 27) {
     if (th == 8) TM_WGRAD(27, 8, 8); else if (tw == 8) TM_WGRAD(27, 4, 8); else TM_WGRAD(27, 4, 4);
   } else {
     if (th == 8) TM_WGRAD(1, 8, 8); else if (tw == 8) TM_WGRAD(1, 4, 8); else TM_WGRAD(1, 4, 4);
   }
 #undef TM_WGRAD
+#undef TM_WGRAD_SLAB
   if (chunks > 1) {
     const long nw = (long)Cout * Cin * taps;
     hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, scratch, nw, chunks, dw, accumulate);

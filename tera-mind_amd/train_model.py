@@ -7,7 +7,8 @@ model/unet_ours.py).  Here `UNetTrain.forward` records a tape of ops, each with 
 
     conv3 / conv1     the conv engine (train_conv.py): forward | data gradient (same kernel, transposed + flipped weights), weight gradient
                       ((1,3,3) and the down_z (kz,3,3) kernels run embedded in the 3x3x3 'same' conv, sliced afterwards; down_z at
-                      kz = 5 (rna_slc 8) is training.DownZTrain: its z taps as five shifted in-plane convs)
+                      kz = 5 (rna_slc 8) and kz = 9 (rna_slc 16, Z = 8: resident engine only) is training.DownZTrain: its z taps as
+                      shifted in-plane convs)
     SiLU(RMSNorm * w [* (1 + scale) + shift])   tm_op_prep_train | tm_op_prep_bwd     (ResBlock in / out layers, the head)
     nearest x2 / AvgPool(1,2,2)                 tm_op_resample   | the other mode, x 4 or / 4 (training.ew 7 / 8)
     AttnBlock with gene cross-attention         training.AttnBlockTrain (modulate(norm), windowed attention core, MLP, gates)
@@ -135,9 +136,14 @@ class UNetTrain:
             raise NotImplementedError("UNetTrain: rna_slc 1 at patch size 32 has patches of 16 voxels at the lowest level (Z = 1, S = 4); the "
                                       "ResBlock norm backward sums the per-image scale / shift gradients of at most two images per "
                                       "64-voxel workgroup, so an image needs 32 voxels or more")
-        if cfg.down_z_kernel not in (1, 3, 5):
-            raise NotImplementedError(f"UNetTrain: rna_slc {cfg.rna_slc} runs its convs at Z = {cfg.z_size}; the conv gradients (both weight-"
-                                      "gradient kernels, the device pack, the data gradient) take Z <= 4 (rna_slc 1, 4, 8)")
+        if cfg.z_size > 4 and not self.resident:
+            raise NotImplementedError(f"UNetTrain: rna_slc {cfg.rna_slc} runs its convs at Z = {cfg.z_size}; the host-weight engine's weight "
+                                      "gradient (conv_wgrad_kernel) takes Z <= 4 (rna_slc 1, 4, 8): that is this engine's limit, rna_slc "
+                                      f"{cfg.rna_slc} trains with resident=True")
+        if cfg.z_size > 4 and cfg.patch_size != 64:
+            raise NotImplementedError(f"UNetTrain: rna_slc {cfg.rna_slc} trains at patch size 64 only: at patch size {cfg.patch_size} no "
+                                      "gradient of the step has been compared with the reference's backward (the fixture, "
+                                      "tests/golden/train_grad_slc16_ref.npz, holds patch size 64)")
 
     # ------------------------------------------------------------------------------------------------------------------
     # plumbing
@@ -294,7 +300,10 @@ class UNetTrain:
         return out
 
     def attn_block(self, x: _V, cond: _V, pfx: str) -> _V:
-        blk = AttnBlockTrain({k[len(pfx) + 1:]: v for k, v in self.W.items() if k.startswith(pfx + ".")}, self.dev)
+        # Z = 8 (rna_slc 16, resident only): the block's Linears run on this net's engine, whose weight gradient takes Z = 8; up to Z = 4
+        # they stay on the block's own host-weight engine in both modes
+        eng = self.convs if self.cfg.z_size > 4 else None
+        blk = AttnBlockTrain({k[len(pfx) + 1:]: v for k, v in self.W.items() if k.startswith(pfx + ".")}, self.dev, engine=eng, key=pfx)
         out = _V(blk.forward_cb(x.t, cond.t), x.C)
 
         def bwd():
@@ -440,7 +449,8 @@ class UNetTrain:
         return out
 
     def down_z(self, x: _V, key: str) -> _V:
-        """The (kz,3,3) conv without z padding at kz > 3 (rna_slc 8: kz = 5): training.DownZTrain on this net's engine and weights."""
+        """The (kz,3,3) conv without z padding at kz > 3 (rna_slc 8: kz = 5; rna_slc 16: kz = 9, resident engine): training.DownZTrain on
+        this net's engine and weights."""
         kw, kb = key + ".weight", key + ".bias"
         w, b = self._wc(kw), self._wc(kb)
         # host weights are replaced, never written in place (AdamTrainer.step): the block and its embedded filters hold as long as W[kw] /
@@ -472,7 +482,7 @@ class UNetTrain:
         D = zs * gh * gw
         tok = self.gene_attention(rna_h.reshape(n * G, D), n, G, D)
         x = self.rows_to_cb8(tok, (n, G, zs, gh, gw), G)
-        x = self.down_z(x, "rna_blocks.0.0.down_z") if cfg.down_z_kernel == 5 else self.conv(x, "rna_blocks.0.0.down_z")
+        x = self.down_z(x, "rna_blocks.0.0.down_z") if cfg.down_z_kernel > 3 else self.conv(x, "rna_blocks.0.0.down_z")
         if cfg.down_z_kernel == 3:
             x = self.zslice(x, 1, zs - 1)                                  # padding 0 along z: the interior planes of the 'same' conv
         out = [self.resample(x, 1)]

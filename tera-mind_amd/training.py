@@ -143,7 +143,8 @@ class DownZTrain:
         dw[:, :, dz]   = the middle z plane of the 3x3x3 weight gradient of x[:, :, dz:dz + Zo] against dy;  db = sum dy
 
     every term an in-plane conv embedded in the middle z slice of the 3x3x3 'same' conv at Zo planes, summed in dz order
-    (ew op 6), so the result is deterministic.  Zo <= 4 (the weight-gradient kernels stage four planes).
+    (ew op 6), so the result is deterministic.  Zo = 1 .. 4 on either engine; Zo = 8 (kz = 9 on 16 planes, rna_slc 16) on the
+    resident engine only: its weight gradient has the z-slab form, the host engine's kernel stages four planes at most.
     Untuned: every tap after the first is a conv into a second buffer plus a separate add launch (the backward also copies
     the z slice of dx out and back per tap) where an accumulating epilogue would do; the conv runs once per step.
 
@@ -168,8 +169,10 @@ class DownZTrain:
         """CB8 in, CB8 out: x_cb [N, ceil(Ci/8), Zi, S, S, 8] -> [N, ceil(Co/8), Zi - kz + 1, S, S, 8]."""
         N, _, Zi, S, _, _ = x_cb.shape
         Zo = Zi - self.kz + 1
-        if not 1 <= Zo <= 4:
-            raise ValueError(f"DownZTrain: {Zi} planes under a depth-{self.kz} kernel leave {Zo}; 1 .. 4 are supported")
+        if not (1 <= Zo <= 4 or (Zo == 8 and self.convs.resident)):
+            raise ValueError(f"DownZTrain: {Zi} planes under a depth-{self.kz} kernel leave {Zo} on the "
+                             f"{'resident' if self.convs.resident else 'host-weight'} engine; 1 .. 4 planes are supported on either engine, "
+                             "8 on the resident engine only (resident=True)")
         zero_b = torch.zeros((self.co,), dtype=torch.float32, device=self.b.device)
         xs = []
         y = torch.zeros((N, (self.co + 7) // 8, Zo, S, S, 8), dtype=torch.float32, device=self.dev)
@@ -221,11 +224,15 @@ class AttnBlockTrain:
     conv_wgrad_kernel; modulate(norm) on prep_kernel / modnorm_bwd_kernel; the windowed attention core on attn_short_kernel (windows of 4 - 16 tokens),
     attn_train_kernel (32 - 128 tokens) or the key-blocked attn_long_* kernels (256 / 512 tokens);
     the gates and activations on ew_kernel (csrc/tm_train.hip).  Channel chunks / concatenations of the CB8 tensors are torch
-    slices on the device (C a multiple of 8)."""
+    slices on the device (C a multiple of 8).
+
+    `engine`, `key`: the conv engine the Linears run on (default: a HostConvs of its own, Z <= 4) and the prefix of their ids in its pack
+    cache.  On a resident engine (the only one that takes Z = 8) the Linear weights and biases are read from the device and the weight
+    gradients stay there."""
 
     LIN = ("attn.q", "attn.k", "attn.v", "attn.proj", "mlp.fc1", "mlp.fc2", "adaLN_modulation.1")
 
-    def __init__(self, params: Dict[str, torch.Tensor], device="cuda:0"):
+    def __init__(self, params: Dict[str, torch.Tensor], device="cuda:0", engine=None, key="attn"):
         self.p = {k: _host(v) for k, v in params.items()}
         self.dev = torch.device(device)
         self.C = self.p["attn.q.weight"].shape[0]
@@ -233,8 +240,11 @@ class AttnBlockTrain:
         self.hid = self.p["mlp.fc1.weight"].shape[0]
         if self.C % 8:
             raise ValueError("AttnBlockTrain: hidden size must be a multiple of 8")
-        self.convs = HostConvs(self.dev)
-        self.f = {k: self.convs.filter(k, self.p[k + ".weight"]) for k in self.LIN}
+        self.convs = engine if engine is not None else HostConvs(self.dev)
+        put = (lambda t: t.to(self.dev)) if self.convs.resident else (lambda t: t)          # where the engine reads weights and biases
+        self.lw = {k: put(self.p[k + ".weight"]) for k in self.LIN}
+        self.lb = {k: put(self.p[k + ".bias"]) for k in self.LIN}
+        self.f = {k: self.convs.filter(k if engine is None else f"{key}.{k}", self.lw[k]) for k in self.LIN}
         self._saved = None
 
     # -- pieces ---------------------------------------------------------------------------------
@@ -242,7 +252,7 @@ class AttnBlockTrain:
         return self._saved["shape"]
 
     def _lin(self, x_cb, name):
-        return self.convs.conv(x_cb, self.f[name], self.p[name + ".bias"])
+        return self.convs.conv(x_cb, self.f[name], self.lb[name])
 
     def _lin_bwd(self, x_cb, dy_cb, name, grads):
         grads[name + ".weight"], grads[name + ".bias"] = self.convs.wgrad(x_cb, dy_cb, self.f[name])

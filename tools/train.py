@@ -29,7 +29,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--batch_size", "-b", type=int, default=32)
     ap.add_argument("--patch_size", "-ps", type=int, default=64)
-    ap.add_argument("--rna_slc", type=int, choices=(1, 4, 8), default=4, help="UNetTrain covers rna_slc 1 (patch 64, 128), 4 and 8")
+    ap.add_argument("--rna_slc", type=int, choices=(1, 4, 8, 16), default=4, help="UNetTrain covers rna_slc 1 (patch 64, 128), 4, 8 and, "
+                    "with --resident at patch size 64, 16")
     ap.add_argument("--mouse", default="638850", choices=["609882", "609889", "638850"])
     ap.add_argument("--stain", default="all", choices=["DAPI", "PolyT", "all"])
     ap.add_argument("--data", required=True, help="directory of gene .npz tiles (images: the same paths with gene -> img, .npz -> .zip)")
@@ -46,6 +47,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1, help="data-parallel ranks, one process per GPU")
     ap.add_argument("--rehearse", action="store_true", help="--gpus N on a one-GPU box: every rank on cuda:0, gloo instead of RCCL")
     a = ap.parse_args()
+    if a.rna_slc == 16 and not a.resident:
+        ap.error("--rna_slc 16 needs --resident: its convs run at Z = 8, and the host-weight engine's weight gradient takes Z <= 4")
     if a.gpus > 1 and not launch.launched_as_rank():
         sys.exit(launch.spawn_ranks(a.gpus, [os.path.abspath(__file__)] + sys.argv[1:]))
     train(a)
