@@ -381,6 +381,35 @@ int tm_ssim_planes(const void* x, const void* y, int dtype, int P, int H, int W,
 int tm_avgpool2_pad(const void* src, int dtype, int P, int H, int W, int64_t src_pitch, int64_t src_plane, void* dst,
                     int64_t dst_pitch, int64_t dst_plane, void* stream);
 
+/* tm_ssim_volumes: the 3-D window of `_ssim` on a 5-D input (conv3d along depth, rows and columns).  For each of the V volume
+ * pairs x[v], y[v] of [D][H][W] (volume v at x + v * x_vol, plane z at + z * x_depth, row r at + r * x_pitch; all in bytes; the
+ * depth stride is its own argument so that one stain of an '(s c)'-ordered mosaic, every n_stain-th plane, is read in place):
+ *   out[v][0] = sum of ssim_map, out[v][1] = sum of cs_map over the (D - n + 1)(H - n + 1)(W - n + 1) valid region: the
+ *               separable valid filter of x, y, x^2, y^2, x y with the n taps of win_host (float32, host; n odd, 3 .. 11;
+ *               shorter windows run as 11 taps with zeros behind) along columns, rows and depth
+ *   out[v][2] = sum of (x - y)^2 over the whole volume; for uint8 the exact integer
+ *   out is double [V][3] on the device.  The filters and maps are fp32; the second moments are formed about one voxel value
+ *   per image and 16 x 16 in-plane tile (the tile's first voxel of plane 0) and corrected with S = (sum of the taps)^3 and
+ *   1 - S, formed in double; a lane owns 1 output per plane, so it adds none of its outputs in fp32: every output goes to an
+ *   fp64 sum, in a fixed tree: no atomics, two calls give the same bits.  Asynchronous on `stream`; the per-tile partials are stream-ordered.
+ *   TM_ERR_ARG with a text before any device call: a null pointer, an unknown dtype, n even or outside 3 .. 11 (a lane keeps
+ *   the depth window of every output in registers: longer windows do not fit), D, H or W below n, V outside 1 .. 65535, a
+ *   pitch below the row, a depth stride below the extent of one plane ((H - 1) pitch + the row), a misaligned float32
+ *   operand (pointer, pitch, depth and volume strides are multiples of 4). */
+int tm_ssim_volumes(const void* x, const void* y, int dtype, int V, int D, int H, int W, int64_t x_pitch, int64_t x_depth,
+                    int64_t x_vol, int64_t y_pitch, int64_t y_depth, int64_t y_vol, const float* win_host, int n, float C1,
+                    float C2, double* out, void* stream);
+
+/* tm_avgpool2_pad3: one 5-D MS-SSIM level, F.avg_pool3d(kernel 2, stride 2, padding (D % 2, H % 2, W % 2)):
+ *   dst float32 [V][ceil(D / 2)][ceil(H / 2)][ceil(W / 2)], window (k, i, j) = planes 2 k - D % 2 .., rows 2 i - H % 2 ..,
+ *   columns 2 j - W % 2 .. of src, a plane, row or column -1 being the zero pad, which is counted: the divisor is 8 (D = 1
+ *   pools to one plane of the in-plane sums / 8).  The eight values are added from 0 in the order plane, then row, then
+ *   column (v000, v001, v010, v011, v100, ..., the last index the column) and the sum is multiplied by 0.125; on 8-bit data
+ *   every level is exact.  src uint8 or float32 by `dtype`.  Asynchronous on `stream`.  TM_ERR_ARG before any device call as
+ *   for tm_ssim_volumes (the destination is held to the float32 rules). */
+int tm_avgpool2_pad3(const void* src, int dtype, int V, int D, int H, int W, int64_t src_pitch, int64_t src_depth,
+                     int64_t src_vol, void* dst, int64_t dst_pitch, int64_t dst_depth, int64_t dst_vol, void* stream);
+
 /* Measurement hooks (bench.py): while enabled, every launch of the dominant kernel
  * (conv3d_mfma<2,..> in fp32, conv27_bf16 / conv27_f16 in the 16-bit modes: the 3x3x3 implicit-GEMM conv) inside tm_unet_forward is bracketed by two
  * hipEvents recorded on the forward's stream.  tm_profile_collect synchronises on the last

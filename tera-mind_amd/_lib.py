@@ -90,6 +90,8 @@ SIGNATURES = {
     "tm_jpeg_tables": (c_int, [c_int, c_void_p, c_size_t, C.POINTER(c_size_t)]),
     "tm_ssim_planes": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [C.c_int64] * 4 + [C.POINTER(c_float), c_int, c_float, c_float, c_void_p, c_void_p]),
     "tm_avgpool2_pad": (c_int, [c_void_p] + [c_int] * 4 + [C.c_int64] * 2 + [c_void_p] + [C.c_int64] * 2 + [c_void_p]),
+    "tm_ssim_volumes": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [C.c_int64] * 6 + [C.POINTER(c_float), c_int, c_float, c_float, c_void_p, c_void_p]),
+    "tm_avgpool2_pad3": (c_int, [c_void_p] + [c_int] * 5 + [C.c_int64] * 3 + [c_void_p] + [C.c_int64] * 3 + [c_void_p]),
     "tm_profile_enable": (c_int, [c_void_p, c_int]),
     "tm_profile_collect": (c_int, [c_void_p, C.POINTER(TmProfStats)]),
     "tm_op_to_cb8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -492,6 +492,22 @@ hipError_t launch_ssim_planes(const void* x, const void* y, bool is_f32, int P, 
 // dst fp32 [P][ceil(H / 2)][ceil(W / 2)] = avg_pool2d(kernel 2, stride 2, padding (H % 2, W % 2)) with the pad counted
 hipError_t launch_avgpool2_pad(const void* src, bool is_f32, int P, int H, int W, long spitch, long splane, void* dst, long dpitch,
                                long dplane, hipStream_t s);
+// SSIM statistics of V volume pairs (the 3-D window): SSIM3_TW x SSIM3_TH tiles of the valid in-plane output, one workgroup
+// each, marching along the depth with the SSIM3_TAPS - 1 open windows of its output held in registers
+constexpr int SSIM3_TW = 16, SSIM3_TH = 16, SSIM3_TAPS = 11;
+struct Ssim3Taps {
+  float w[SSIM3_TAPS];                         // the n taps, zeros behind
+  float sum, one_minus_sum;                    // S = (sum of the taps)^3, the weight of the n^3 window, and 1 - S: from double, rounded once
+  int n;
+};
+size_t ssim3_partial_doubles(int V, int H, int W, int n);
+// out[v][3] in fp64; pitches, depth strides (plane to plane) and volume strides in bytes
+hipError_t launch_ssim_volumes(const void* x, const void* y, bool is_f32, int V, int D, int H, int W, long xpitch, long xdepth, long xvol,
+                               long ypitch, long ydepth, long yvol, const Ssim3Taps& taps, float C1, float C2, double* partials,
+                               double* out, hipStream_t s);
+// dst fp32 [V][ceil(D / 2)][ceil(H / 2)][ceil(W / 2)] = avg_pool3d(kernel 2, stride 2, padding (D % 2, H % 2, W % 2)), the pad counted
+hipError_t launch_avgpool2_pad3(const void* src, bool is_f32, int V, int D, int H, int W, long spitch, long sdepth, long svol, void* dst,
+                                long dpitch, long ddepth, long dvol, hipStream_t s);
 
 // ---- host helpers of the C-ABI units (tm_model.hip, tm_ops.hip, tm_io.hip) ---------------
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // sets the tm_last_error() text, returns code

@@ -1621,6 +1621,63 @@ extern "C" int tm_avgpool2_pad(const void* src, int dtype, int P, int H, int W, 
   return TM_OK;
 }
 
+// SSIM / PSNR sums of volume pairs, the 3-D window (tm_metrics.hip); enqueues only
+static int vol_geometry(const char* fn, const char* what, const void* p, int dtype, int H, int W, int64_t pitch, int64_t depth, int64_t vol) {
+  const int64_t esz = dtype == TM_PIX_F32 ? 4 : 1;
+  if (int rc = pix_geometry(fn, what, p, dtype, W, pitch, vol)) return rc;
+  const int64_t extent = (int64_t)(H - 1) * pitch + (int64_t)W * esz;
+  if (depth < extent)
+    return fail(TM_ERR_ARG, "%s: %s depth stride %lld below the extent of one plane, %lld bytes", fn, what, (long long)depth, (long long)extent);
+  if (esz == 4 && (depth & 3)) return fail(TM_ERR_ARG, "%s: float32 %s depth stride must be a multiple of 4 bytes", fn, what);
+  return TM_OK;
+}
+extern "C" int tm_ssim_volumes(const void* x, const void* y, int dtype, int V, int D, int H, int W, int64_t x_pitch, int64_t x_depth,
+                               int64_t x_vol, int64_t y_pitch, int64_t y_depth, int64_t y_vol, const float* win_host, int n, float C1,
+                               float C2, double* out, void* stream) {
+  const char* fn = "tm_ssim_volumes";
+  if (!x || !y || !win_host || !out) return fail(TM_ERR_ARG, "%s: null x / y / window / out pointer", fn);
+  if (dtype != TM_PIX_U8 && dtype != TM_PIX_F32) return fail(TM_ERR_ARG, "%s: dtype %d is neither TM_PIX_U8 nor TM_PIX_F32", fn, dtype);
+  if (n < 3 || n > SSIM3_TAPS || !(n & 1))
+    return fail(TM_ERR_ARG, "%s: window of %d taps (odd, 3 .. %d: a lane keeps the depth window of every output in registers)", fn, n,
+                SSIM3_TAPS);
+  if (V < 1 || V > 65535) return fail(TM_ERR_ARG, "%s: V = %d outside 1 .. 65535", fn, V);
+  if (D < n || H < n || W < n) return fail(TM_ERR_ARG, "%s: volume %d x %d x %d below the window of %d taps", fn, D, H, W, n);
+  if ((H - n) / SSIM3_TH >= 65535) return fail(TM_ERR_ARG, "%s: H = %d takes more than 65535 tile rows", fn, H);
+  if (int rc = vol_geometry(fn, "x", x, dtype, H, W, x_pitch, x_depth, x_vol)) return rc;
+  if (int rc = vol_geometry(fn, "y", y, dtype, H, W, y_pitch, y_depth, y_vol)) return rc;
+  if (x_pitch > ((int64_t)1 << 26) || y_pitch > ((int64_t)1 << 26))   // a tile's 26 rows are addressed with 32-bit offsets
+    return fail(TM_ERR_ARG, "%s: pitch %lld above 2^26 bytes", fn, (long long)(x_pitch > y_pitch ? x_pitch : y_pitch));
+  Ssim3Taps taps = {};
+  double sum = 0.0;
+  for (int t = 0; t < n; ++t) { taps.w[t] = win_host[t]; sum += (double)win_host[t]; }
+  const double s3 = sum * sum * sum;                                 // the n x n x n window weighs (sum)^3
+  taps.sum = (float)s3; taps.one_minus_sum = (float)(1.0 - s3); taps.n = n;
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp(st);
+  double* partials = (double*)tmp.ordered_floats(2 * ssim3_partial_doubles(V, H, W, n), false);
+  if (tmp.err) return tmp.report();
+  HIP_TRY(launch_ssim_volumes(x, y, dtype == TM_PIX_F32, V, D, H, W, (long)x_pitch, (long)x_depth, (long)x_vol, (long)y_pitch, (long)y_depth,
+                              (long)y_vol, taps, C1, C2, partials, out, st));
+  return TM_OK;
+}
+
+// One 5-D MS-SSIM level (tm_metrics.hip); enqueues only
+extern "C" int tm_avgpool2_pad3(const void* src, int dtype, int V, int D, int H, int W, int64_t src_pitch, int64_t src_depth, int64_t src_vol,
+                                void* dst, int64_t dst_pitch, int64_t dst_depth, int64_t dst_vol, void* stream) {
+  const char* fn = "tm_avgpool2_pad3";
+  if (!src || !dst) return fail(TM_ERR_ARG, "%s: null source / destination", fn);
+  if (dtype != TM_PIX_U8 && dtype != TM_PIX_F32) return fail(TM_ERR_ARG, "%s: dtype %d is neither TM_PIX_U8 nor TM_PIX_F32", fn, dtype);
+  if (V < 1 || V > 65535) return fail(TM_ERR_ARG, "%s: V = %d outside 1 .. 65535", fn, V);
+  if (D < 1 || H < 1 || W < 1) return fail(TM_ERR_ARG, "%s: D, H and W must be positive, got %d x %d x %d", fn, D, H, W);
+  const int64_t outs = (int64_t)((D + 1) / 2) * ((H + 1) / 2) * ((W + 1) / 2);
+  if (outs > ((int64_t)1 << 38)) return fail(TM_ERR_ARG, "%s: %lld outputs per volume exceed one launch (2^38)", fn, (long long)outs);
+  if (int rc = vol_geometry(fn, "source", src, dtype, H, W, src_pitch, src_depth, src_vol)) return rc;
+  if (int rc = vol_geometry(fn, "destination", dst, TM_PIX_F32, (H + 1) / 2, (W + 1) / 2, dst_pitch, dst_depth, dst_vol)) return rc;
+  HIP_TRY(launch_avgpool2_pad3(src, dtype == TM_PIX_F32, V, D, H, W, (long)src_pitch, (long)src_depth, (long)src_vol, dst, (long)dst_pitch,
+                               (long)dst_depth, (long)dst_vol, (hipStream_t)stream));
+  return TM_OK;
+}
+
 // Timing hook of the conv weight gradient on random device data (uniform in [-1, 1)): engine 0 = conv_wgrad_kernel (VALU),
 // 1 = conv_wgrad_mfma_kernel + its chunk reduction.  One warm-up launch, then `reps` measurements of `iters` launches between two
 // events each: ms_per_launch_host[r] = milliseconds per launch of repetition r (their spread is the noise of identical calls).
