@@ -353,6 +353,41 @@ int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pitch, int qua
  * tm_jpeg_encode_tiles (which reads the same table statements).  buf == NULL: only *out_bytes is set.  Host only. */
 int tm_jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
 
+/* ---- colour composite export: two stains in one image, as utils/vis_mba.py:193-195 stacks [0, PolyT, DAPI] and
+ * onto_overlay (:118-179) brightens it and blends an ontology image over it.
+ *
+ * The composite of pixel (y, x) of a level [H][W], from three planar uint8 device planes planes[0 .. 2] = R, G, B with their
+ * own pitches[] in bytes (a null plane is all zeros; not all three may be null):
+ *   brightness  v <- min(255, trunc(float32(bright) * float32(v))) per channel, skipped when bright == 1 (bright >= 0, finite)
+ *   overlay     optional uint8 [oh][ow][3] device image, alpha 0 .. 255: ov = overlay[(y oh) / H][(x ow) / W] (integer
+ *               division: nearest sampling by the level's own size); where any channel of ov is non-zero
+ *               v_c <- (ov_c alpha + v_c (255 - alpha) + 127) / 255, elsewhere v is unchanged.  H oh and W ow below 2^31.
+ * in that order.  The blend rounding is this library's own (equality with libvips' composite is not pinned).
+ *
+ * tm_rgb_compose: the composite of the whole level as interleaved uint8 dst [H][W][3] device, dst_pitch >= 3 W bytes.
+ *   Asynchronous on `stream`. */
+int tm_rgb_compose(const void* const* planes, const int64_t* pitches, int H, int W, float bright, const void* overlay, int oh, int ow,
+                   int alpha, void* dst, int64_t dst_pitch, void* stream);
+
+/* tm_jpeg_encode_tiles_rgb: tm_jpeg_encode_tiles for the composite, which is formed in the block load (no RGB image of the
+ *   level is stored).  Baseline JPEG, three components Y Cb Cr all sampled 1 x 1 (4:4:4), one interleaved scan per 256 x 256
+ *   tile, MCU = 8 x 8 pixels = one Y, one Cb, one Cr block; colour conversion in libjpeg's fixed point:
+ *     Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *     Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16
+ *     Cr = ( 32768 R - 27439 G -  5329 B + (128 << 16) + 32767) >> 16
+ *   Y on quantiser 0 (K.1) and Huffman tables 0 / 0 (K.3, K.5); Cb and Cr on quantiser 1 (K.2, scaled and clipped like K.1)
+ *   and tables 1 / 1 (K.4, K.6); DC predicted per component.  The bytes are those libjpeg writes for the tile with
+ *   4:4:4 sampling.  slots / slot_bytes / need / packed / offsets / stream exactly as in tm_jpeg_encode_tiles; the bit
+ *   buffers are three times as large (at most 512 x 623 KB of stream-ordered scratch). */
+int tm_jpeg_encode_tiles_rgb(const void* const* planes, const int64_t* pitches, int H, int W, float bright, const void* overlay,
+                             int oh, int ow, int alpha, int quality, int tile0, int ntiles, void* slots, int64_t slot_bytes,
+                             int32_t* need, void* packed, int64_t* offsets, void* stream);
+
+/* The tables-only datastream SOI DQT(0) DQT(1) DHT(DC 0) DHT(AC 0) DHT(DC 1) DHT(AC 1) EOI for `quality` (the segments and
+ * the order libjpeg writes): the JPEGTables tag of tiles encoded by tm_jpeg_encode_tiles_rgb.  buf == NULL: only
+ * *out_bytes is set.  Host only. */
+int tm_jpeg_tables_rgb(int quality, void* buf, size_t cap, size_t* out_bytes);
+
 /* ---- ROI evaluation ("evaluation"): the measures of utils/metrics.py:201-541 for a generated / real plane pair ----
  * Pixels are uint8 or float32, chosen by `dtype`; pitches and plane strides are in bytes.  uint8 pointers need no alignment;
  * float32 pointers, pitches and strides are multiples of 4. */

@@ -424,6 +424,24 @@ size_t jpeg_scratch_bytes(int ntiles);
 hipError_t launch_jpeg_tiles(const uint8_t* plane, int H, int W, long pitch, int quality, int tile0, int ntiles, uint32_t* scratch,
                              uint8_t* slots, long slot_bytes, int32_t* need, uint8_t* packed, int64_t* offsets, hipStream_t s);
 int jpeg_tables(int quality, void* buf, size_t cap, size_t* out_bytes);
+// Colour composite of three planar uint8 planes as R, G, B (a null plane is all zeros): brightness, then an optional
+// interleaved uint8 [oh][ow][3] overlay sampled nearest by the level's own H and W and blended with alpha / 255 where it is
+// not black.  H oh and W ow must stay below 2^31 (32-bit index arithmetic in the kernels).
+struct RgbSrc {
+  const uint8_t* p[3];
+  long pitch[3];
+  int H, W;
+  float bright;
+  const uint8_t* ov;
+  int oh, ow, alpha;
+};
+// the composite as interleaved [H][W][3]
+hipError_t launch_rgb_compose(const RgbSrc& src, uint8_t* dst, long dpitch, hipStream_t s);
+// launch_jpeg_tiles for the composite: 4:4:4 YCbCr scans, Y Cb Cr interleaved per 8 x 8 MCU; jpeg_rgb_scratch_bytes(ntiles) of scratch
+size_t jpeg_rgb_scratch_bytes(int ntiles);
+hipError_t launch_jpeg_tiles_rgb(const RgbSrc& src, int quality, int tile0, int ntiles, uint32_t* scratch, uint8_t* slots,
+                                 long slot_bytes, int32_t* need, uint8_t* packed, int64_t* offsets, hipStream_t s);
+int jpeg_tables_rgb(int quality, void* buf, size_t cap, size_t* out_bytes);
 
 // ---- Blosc-lz4 frames (tm_blosc.hip) --------------------------------------------------------
 constexpr int BLOSC_ENC_MIN_BLOCK = 256, BLOSC_ENC_MAX_BLOCK = 65536;

@@ -1390,6 +1390,65 @@ extern "C" int tm_jpeg_encode_tiles(const void* plane, int H, int W, int64_t pit
   return TM_OK;
 }
 
+// The colour composite (tm_export.hip): the checks of the source that tm_rgb_compose and tm_jpeg_encode_tiles_rgb share
+static int rgb_source(const char* fn, const void* const* planes, const int64_t* pitches, int H, int W, float bright, const void* overlay,
+                      int oh, int ow, int alpha, RgbSrc* src) {
+  if (!planes || !pitches) return fail(TM_ERR_ARG, "%s: null planes / pitches array", fn);
+  if (!planes[0] && !planes[1] && !planes[2]) return fail(TM_ERR_ARG, "%s: all three planes are null", fn);
+  if (H < 1 || W < 1) return fail(TM_ERR_ARG, "%s: H and W must be positive, got %d x %d", fn, H, W);
+  for (int c = 0; c < 3; ++c)
+    if (planes[c] && pitches[c] < W) return fail(TM_ERR_ARG, "%s: pitch %lld of plane %d below W %d", fn, (long long)pitches[c], c, W);
+  if (!(bright >= 0.f) || bright > 3.0e38f) return fail(TM_ERR_ARG, "%s: bright must be finite and not negative, got %g", fn, (double)bright);
+  if (overlay) {
+    if (oh < 1 || ow < 1) return fail(TM_ERR_ARG, "%s: overlay size must be positive, got %d x %d", fn, oh, ow);
+    if (alpha < 0 || alpha > 255) return fail(TM_ERR_ARG, "%s: alpha %d outside 0 .. 255", fn, alpha);
+    if ((long)H * oh >= (1L << 31) || (long)W * ow >= (1L << 31))
+      return fail(TM_ERR_ARG, "%s: overlay %d x %d on a %d x %d level: H oh and W ow must stay below 2^31", fn, oh, ow, H, W);
+  }
+  for (int c = 0; c < 3; ++c) {
+    src->p[c] = (const uint8_t*)planes[c];
+    src->pitch[c] = planes[c] ? (long)pitches[c] : 0;
+  }
+  src->H = H;
+  src->W = W;
+  src->bright = bright;
+  src->ov = (const uint8_t*)overlay;
+  src->oh = overlay ? oh : 0;
+  src->ow = overlay ? ow : 0;
+  src->alpha = overlay ? alpha : 0;
+  return TM_OK;
+}
+extern "C" int tm_rgb_compose(const void* const* planes, const int64_t* pitches, int H, int W, float bright, const void* overlay, int oh,
+                              int ow, int alpha, void* dst, int64_t dst_pitch, void* stream) {
+  const char* fn = "tm_rgb_compose";
+  RgbSrc src;
+  if (int rc = rgb_source(fn, planes, pitches, H, W, bright, overlay, oh, ow, alpha, &src)) return rc;
+  if (!dst) return fail(TM_ERR_ARG, "%s: null destination", fn);
+  if (dst_pitch < 3 * (int64_t)W) return fail(TM_ERR_ARG, "%s: destination pitch %lld below 3 W = %lld", fn, (long long)dst_pitch, 3LL * W);
+  HIP_TRY(launch_rgb_compose(src, (uint8_t*)dst, (long)dst_pitch, (hipStream_t)stream));
+  return TM_OK;
+}
+extern "C" int tm_jpeg_encode_tiles_rgb(const void* const* planes, const int64_t* pitches, int H, int W, float bright, const void* overlay,
+                                        int oh, int ow, int alpha, int quality, int tile0, int ntiles, void* slots, int64_t slot_bytes,
+                                        int32_t* need, void* packed, int64_t* offsets, void* stream) {
+  const char* fn = "tm_jpeg_encode_tiles_rgb";
+  RgbSrc src;
+  if (int rc = rgb_source(fn, planes, pitches, H, W, bright, overlay, oh, ow, alpha, &src)) return rc;
+  if (!slots || !need) return fail(TM_ERR_ARG, "%s: null slots / need pointer", fn);
+  if (!packed != !offsets) return fail(TM_ERR_ARG, "%s: packed and offsets go together (both or neither)", fn);
+  if (quality < 1 || quality > 100) return fail(TM_ERR_ARG, "%s: quality %d outside 1 .. 100", fn, quality);
+  const long grid = (long)((H + 255) / 256) * ((W + 255) / 256);
+  if (tile0 < 0 || ntiles < 1 || (long)tile0 + ntiles > grid)
+    return fail(TM_ERR_ARG, "%s: tiles [%d, %d + %d) outside the grid of %ld", fn, tile0, tile0, ntiles, grid);
+  if (slot_bytes < 1) return fail(TM_ERR_ARG, "%s: slot_bytes must be positive", fn);
+  hipStream_t st = (hipStream_t)stream;
+  DevTmp tmp(st);
+  uint32_t* scratch = (uint32_t*)tmp.ordered_floats(jpeg_rgb_scratch_bytes(ntiles) / sizeof(float), false);
+  if (tmp.err) return tmp.report();
+  HIP_TRY(launch_jpeg_tiles_rgb(src, quality, tile0, ntiles, scratch, (uint8_t*)slots, (long)slot_bytes, need, (uint8_t*)packed, offsets, st));
+  return TM_OK;
+}
+
 // Blosc-lz4 frames (tm_blosc.hip); enqueue only, the stream slots and length tables are stream-ordered scratch
 static int blosc_args(const char* fn, size_t nbytes, int typesize, int blocksize, BloscGeo* g) {
   if (nbytes < 1) return fail(TM_ERR_ARG, "%s: nothing to compress (nbytes = 0)", fn);

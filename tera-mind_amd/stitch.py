@@ -7,7 +7,9 @@ tensor.  `save_slices` writes it with PIL as plain TIFF / JPEG (small ROIs); `sa
 reference's product, one tiled pyramidal OME-TIFF (BigTIFF, 256 x 256 JPEG tiles) per slice, with the level
 reductions and the JPEG tile scans computed on the GPU (ometiff.py).  Pinned there: the JPEG bytes equal
 libjpeg's and Pillow / libtiff reads the container back; not pinned: byte equality with a libvips-written file,
-libvips' level sizes at odd dimensions, QuPath / Bio-Formats (never run).  Output index `sl = s * n_stain + c` (slice-major, stain-minor), as the reference's
+libvips' level sizes at odd dimensions, QuPath / Bio-Formats (never run).  `save_composites_pyramid` writes the two stains
+of a slice as one colour pyramid (PolyT green, DAPI blue, utils/vis_mba.py:193-195), optionally brightened and with an
+ontology overlay as onto_overlay does; the composite is formed inside the colour JPEG kernel.  Output index `sl = s * n_stain + c` (slice-major, stain-minor), as the reference's
 per-slice directories are numbered.
 """
 import os
@@ -150,6 +152,88 @@ def save_slices_pyramid(state, odir, slc: int = 50, slices: Optional[Sequence[in
         if page is not None:
             from PIL import Image
             Image.fromarray(levels[page].cpu().numpy(), mode="L").save(os.path.join(str(odir), f"all_{sl}.jpg"))
+
+
+REGIONS = ("all", "half", "rhalf", "thalf", "bhalf", "quarter", "3quarter")
+
+
+def overlay_region(overlay: np.ndarray, region: str = "all") -> np.ndarray:
+    """The part of an [h, w, 3] overlay that `region` keeps, the rest black (= not blended), as onto_overlay selects it
+    (utils/vis_mba.py:142-161): half / rhalf = left / right, thalf / bhalf = top / bottom, quarter = top left, 3quarter = all
+    but top right."""
+    if region not in REGIONS:
+        raise ValueError(f"region must be one of {', '.join(REGIONS)}, got {region!r}")
+    ov = np.ascontiguousarray(overlay)
+    if ov.dtype != np.uint8 or ov.ndim != 3 or ov.shape[2] != 3:
+        raise ValueError(f"the overlay is a uint8 [h, w, 3] image, got {ov.dtype} {ov.shape}")
+    h, w = ov.shape[:2]
+    keep = np.zeros((h, w), dtype=bool)
+    if region == "all":
+        keep[:] = True
+    elif region == "half":
+        keep[:, :w // 2] = True
+    elif region == "rhalf":
+        keep[:, w // 2:] = True
+    elif region == "thalf":
+        keep[:h // 2] = True
+    elif region == "bhalf":
+        keep[h // 2:] = True
+    elif region == "quarter":
+        keep[:h // 2, :w // 2] = True
+    else:
+        keep[:] = True
+        keep[:h // 2, w // 2:] = False
+    return ov * keep[:, :, None].astype(np.uint8)
+
+
+def save_composites_pyramid(state, odir, slc: int = 50, slices: Optional[Sequence[int]] = None, quality: int = 75,
+                            page: Optional[int] = None, bright: float = 1.0, overlay=None, alpha: int = 100,
+                            region: str = "all", device=None):
+    """'{odir}/rgb_{s}.tif' per slice s: the two stains of the slice as one colour image, R = 0, G = PolyT (c = 1),
+    B = DAPI (c = 0) (utils/vis_mba.py:193-195), as a tiled pyramidal OME-TIFF of YCbCr JPEG pages (ometiff.write_pyramid_rgb).
+    state: the resident float [(c s), H, W] state or a uint8 [(s c), H, W] mosaic of all `slc` slices; only the two planes of
+    one slice are converted / uploaded at a time.  slices: slice indices (default all).  bright, overlay ([h, w, 3] uint8 array
+    or an image path), alpha, region: onto_overlay's brightening and ontology overlay (overlay_region keeps `region` of it);
+    they are applied per level on the GPU.  page: also write that level's composite as 'rgb_{s}.jpg' through Pillow."""
+    os.makedirs(str(odir), exist_ok=True)
+    if isinstance(state, np.ndarray):
+        state = torch.from_numpy(state)
+    is_u8 = state.dtype == torch.uint8
+    dev = torch.device(device) if device is not None else (state.device if state.is_cuda else torch.device("cuda"))
+    cs = state.shape[0]
+    if cs % slc:
+        raise ValueError(f"{cs} state planes are no multiple of slc = {slc}")
+    n_stain = cs // slc
+    if n_stain < 2:
+        raise ValueError(f"a composite shows two stains (PolyT green, DAPI blue); this state has {n_stain} per slice "
+                         f"({cs} planes, slc = {slc}): use save_slices_pyramid for grey pages")
+    if region not in REGIONS:
+        raise ValueError(f"region must be one of {', '.join(REGIONS)}, got {region!r}")
+    ov = None
+    if overlay is not None:
+        if isinstance(overlay, torch.Tensor):
+            overlay = overlay.cpu().numpy()
+        elif not isinstance(overlay, np.ndarray):
+            from PIL import Image
+            with Image.open(str(overlay)) as im:
+                overlay = np.asarray(im.convert("RGB"))
+        ov = torch.from_numpy(overlay_region(overlay, region)).to(dev)
+    picks = list(range(slc)) if slices is None else list(slices)
+    if any(not 0 <= s < slc for s in picks):
+        raise ValueError(f"slices are indices 0 .. {slc - 1}, got {picks}")
+    bufs = ometiff.JpegBatches(dev, ometiff.BATCH_TILES, 3 * ometiff.SLOT_BYTES)
+    for s in picks:
+        pair = []
+        for c in (1, 0):                                           # green = PolyT, blue = DAPI
+            if is_u8:
+                pair.append(state[s * n_stain + c].to(dev).contiguous())
+            else:
+                pair.append(to_uint8(state[c * slc + s].to(dev)).contiguous())
+        levels = ometiff.write_pyramid_rgb(os.path.join(str(odir), f"rgb_{s}.tif"), (None, pair[0], pair[1]), quality, bright, ov,
+                                           alpha, buffers=bufs)
+        if page is not None:
+            from PIL import Image
+            Image.fromarray(levels[page].compose().cpu().numpy(), mode="RGB").save(os.path.join(str(odir), f"rgb_{s}.jpg"))
 
 
 # ---- attention read-out tiles (infer_attn.py:9-39) -----------------------------------------------------------

@@ -12,6 +12,11 @@ Kernel times come from a run of their own:
     python tools/bench_export.py --summarize OUT
 --profile exports each plane 1 + --reps times and writes OUT/export_meta.json (dispatches per export, pixels, scan bytes);
 --summarize joins it with the kernel trace: per kernel the time per plane, the bytes its algorithm moves and pixels per second.
+
+--rgb: the same for the colour composite export of a plane pair (`stitch.save_composites_pyramid`: PolyT green, DAPI blue,
+YCbCr 4:4:4 tiles) against Pillow encoding the same composite tiles with `subsampling=0` on the host; the files of the two
+routes must be identical.  With --profile / --summarize it records and reports the colour tile kernel against three grey
+encodes (`tm_jpeg_encode_tiles`) of planes of that size, which is the number of 8 x 8 blocks the colour kernel processes.
 """
 import argparse
 import csv
@@ -74,23 +79,72 @@ def gpu_export(state, odir):
     torch.cuda.synchronize()
 
 
-def end_to_end(reps, out):
+def synthetic_pair(n, device):
+    """A two-stain state [(c s) = 2, n, n] of one slice: two different planes of synthetic_state's kind."""
+    import torch
+    return torch.cat([synthetic_state(n, device), synthetic_state(n + 1, device)[:, :n, :n]])
+
+
+def host_export_rgb(state, path):
+    """The colour baseline: both planes downloaded, each reduced with numpy, every level's tiles stacked [0, PolyT, DAPI] and
+    encoded with Pillow at 4:4:4 on the host into the same container."""
+    import numpy as np
+    from PIL import Image
+    from teramind_amd import ometiff, stitch
+
+    def pyramid(a):
+        levels = [a]
+        for _ in ometiff.pyramid_sizes(*a.shape)[1:]:
+            s = levels[-1]
+            h, w = s.shape
+            ys, xs = np.minimum(np.arange(2 * ((h + 1) // 2)), h - 1), np.minimum(np.arange(2 * ((w + 1) // 2)), w - 1)
+            b = s[np.ix_(ys, xs)].astype(np.uint16)
+            levels.append(((b[0::2, 0::2] + b[0::2, 1::2] + b[1::2, 0::2] + b[1::2, 1::2] + 2) >> 2).astype(np.uint8))
+        return levels
+    dapi, polyt = pyramid(stitch.to_uint8(state[0]).cpu().numpy()), pyramid(stitch.to_uint8(state[1]).cpu().numpy())
+
+    def tiles(lv, h, w):
+        for y0 in range(0, h, 256):
+            for x0 in range(0, w, 256):
+                ys, xs = np.minimum(np.arange(y0, y0 + 256), h - 1), np.minimum(np.arange(x0, x0 + 256), w - 1)
+                g, b = polyt[lv][np.ix_(ys, xs)], dapi[lv][np.ix_(ys, xs)]
+                buf = io.BytesIO()
+                Image.fromarray(np.stack([np.zeros_like(g), g, b], -1), mode="RGB").save(buf, format="JPEG", quality=QUALITY, subsampling=0)
+                d = buf.getvalue()
+                i = d.index(b"\xff\xda")
+                yield ometiff.jpeg_tile_stream_rgb(d[i + 2 + int.from_bytes(d[i + 2:i + 4], "big"):-2])
+    ometiff.write_tiles(path, state.shape[1], state.shape[2], tiles, "jpeg", ometiff.jpeg_tables_rgb(QUALITY), samples=3)
+
+
+def gpu_export_rgb(state, odir):
+    import torch
+    from teramind_amd import stitch
+    stitch.save_composites_pyramid(state, odir, slc=1, quality=QUALITY)
+    torch.cuda.synchronize()
+
+
+def end_to_end(reps, out, rgb=False):
     import torch
     import teramind_amd  # noqa: F401
     assert torch.cuda.is_available(), "bench_export needs a GPU"
-    res = {"what": "pyramidal OME-TIFF export, seconds per plane, profiler off", "quality": QUALITY, "reps": reps, "planes": []}
+    what = "colour composite (plane pair)" if rgb else "pyramidal OME-TIFF"
+    unit = "plane pair" if rgb else "plane"
+    res = {"what": f"{what} export, seconds per {unit}, profiler off", "quality": QUALITY, "reps": reps, "planes": []}
+    gpu_route, host_route, name = (gpu_export_rgb, host_export_rgb, "rgb_0.tif") if rgb else (gpu_export, host_export, "all_0.tif")
     with tempfile.TemporaryDirectory() as tmp:
         for n in SIZES:
-            state = synthetic_state(n, "cuda:0")
-            gpu_export(state, os.path.join(tmp, "g"))                       # warm-up of both routes
-            host_export(state, os.path.join(tmp, "h.tif"))
-            same = open(os.path.join(tmp, "g", "all_0.tif"), "rb").read() == open(os.path.join(tmp, "h.tif"), "rb").read()
+            state = synthetic_pair(n, "cuda:0") if rgb else synthetic_state(n, "cuda:0")
+            gpu_route(state, os.path.join(tmp, "g"))                       # warm-up of both routes
+            host_route(state, os.path.join(tmp, "h.tif"))
+            same = open(os.path.join(tmp, "g", name), "rb").read() == open(os.path.join(tmp, "h.tif"), "rb").read()
+            if rgb and not same:
+                sys.exit(f"{n} x {n}: the GPU route and the host route wrote different files")
             tg, th = [], []
             for _ in range(reps):                                           # alternated
                 t0 = time.perf_counter()
-                gpu_export(state, os.path.join(tmp, "g"))
+                gpu_route(state, os.path.join(tmp, "g"))
                 t1 = time.perf_counter()
-                host_export(state, os.path.join(tmp, "h.tif"))
+                host_route(state, os.path.join(tmp, "h.tif"))
                 t2 = time.perf_counter()
                 tg.append(t1 - t0)
                 th.append(t2 - t1)
@@ -138,6 +192,56 @@ def profile(out_dir, reps):
         json.dump(meta, f)
 
 
+def profile_rgb(out_dir, reps):
+    """Under rocprofv3: per size the colour export of a plane pair 1 + reps times, then the grey export of one plane 1 + 3
+    times.  Three grey planes are the 8 x 8 blocks one colour export transforms and codes."""
+    import torch
+    import teramind_amd  # noqa: F401
+    from teramind_amd import ometiff
+    assert torch.cuda.is_available(), "bench_export needs a GPU"
+    meta = {"exports": 1 + reps, "grey_exports": 1 + 3, "planes": []}
+    with tempfile.TemporaryDirectory() as tmp:
+        for n in SIZES:
+            state = synthetic_pair(n, "cuda:0")
+            for _ in range(1 + reps):
+                gpu_export_rgb(state, os.path.join(tmp, "g"))
+            for _ in range(1 + 3):
+                gpu_export(state[:1], os.path.join(tmp, "g"))
+            tiles = [((h + 255) // 256) * ((w + 255) // 256) for h, w in ometiff.pyramid_sizes(n, n)]
+            meta["planes"].append({"n": n, "tiles": sum(tiles),
+                                   "batches": sum((t + ometiff.BATCH_TILES - 1) // ometiff.BATCH_TILES for t in tiles)})
+            del state
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "export_rgb_meta.json"), "w") as f:
+        json.dump(meta, f)
+
+
+def summarize_rgb(d):
+    """Colour kernel time per export against three grey encodes of the same size, from the trace of profile_rgb."""
+    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        sys.exit(f"no kernel trace under {d}")
+    meta = json.load(open(os.path.join(d, "export_rgb_meta.json")))
+    per = {"jpeg_tile_rgb_kernel": [], "jpeg_tile_kernel": []}
+    for row in csv.DictReader(open(files[0])):
+        name = row["Kernel_Name"].split("(")[0].replace("tmk::", "").replace("void ", "")
+        if name in per:
+            per[name].append((int(row["Start_Timestamp"]), (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3))
+    for name in per:
+        per[name].sort()
+    print("tile encoder kernel time per export (rocprofv3 --kernel-trace; warm-up export dropped)")
+    print(f"{'plane':>6s} {'tiles':>6s} {'colour us (median)':>19s} {'spread':>8s} {'3 x grey us':>12s} {'colour / 3 grey':>16s} {'Mblocks/s colour':>17s}")
+    used_c = used_g = 0
+    for pl in meta["planes"]:
+        k = pl["batches"]
+        col = [sum(c[1] for c in per["jpeg_tile_rgb_kernel"][used_c + e * k: used_c + (e + 1) * k]) for e in range(meta["exports"])][1:]
+        gre = [sum(c[1] for c in per["jpeg_tile_kernel"][used_g + e * k: used_g + (e + 1) * k]) for e in range(meta["grey_exports"])][1:]
+        used_c += meta["exports"] * k
+        used_g += meta["grey_exports"] * k
+        cm, g3 = statistics.median(col), sum(gre)
+        print(f"{pl['n']:6d} {pl['tiles']:6d} {cm:19.1f} {max(col) - min(col):8.1f} {g3:12.1f} {cm / g3:16.2f} {3072 * pl['tiles'] / cm:17.1f}")
+
+
 def summarize(d):
     files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
     if not files:
@@ -180,10 +284,12 @@ if __name__ == "__main__":
     ap.add_argument("--out", default=None, help="end-to-end mode: also write the JSON line here")
     ap.add_argument("--profile", default=None, metavar="DIR", help="run the exports only (under rocprofv3) and write DIR/export_meta.json")
     ap.add_argument("--summarize", default=None, metavar="DIR")
+    ap.add_argument("--rgb", action="store_true", help="the colour composite export of a plane pair (stitch.save_composites_pyramid) "
+                    "against Pillow at 4:4:4 on the host; with --profile / --summarize: the colour tile kernel against three grey encodes")
     a = ap.parse_args()
     if a.summarize:
-        summarize(a.summarize)
+        (summarize_rgb if a.rgb else summarize)(a.summarize)
     elif a.profile:
-        profile(a.profile, a.reps)
+        (profile_rgb if a.rgb else profile)(a.profile, a.reps)
     else:
-        end_to_end(a.reps, a.out)
+        end_to_end(a.reps, a.out, a.rgb)

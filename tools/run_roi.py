@@ -118,6 +118,18 @@ def worker(args):
             else:
                 raise SystemExit("--pyramid with several ranks needs the tile files (drop --no_tile_files)")
             pyr_s = round(time.perf_counter() - t4, 2)
+        comp_s = None
+        if args.composite:                      # PolyT green / DAPI blue per slice (utils/vis_mba.py:193-195), colour pages
+            t5 = time.perf_counter()
+            kw = dict(quality=args.quality, page=args.page, bright=args.bright, overlay=args.overlay, alpha=args.alpha, region=args.region)
+            if world == 1:
+                stitch.save_composites_pyramid(st, os.path.join(out_dir, "gen_composite"), 50, **kw)
+            elif d is not None:
+                full = stitch.stitch_dir(d, 256, 256, args.hnm, args.wnm, 50)
+                stitch.save_composites_pyramid(full, os.path.join(out_dir, "gen_composite"), 50, **kw)
+            else:
+                raise SystemExit("--composite with several ranks needs the tile files (drop --no_tile_files)")
+            comp_s = round(time.perf_counter() - t5, 2)
         tiles = args.hnm * args.wnm
         T = max(1, steps_done - first)          # steps run by this process
         per_step = per_step or [0.0]
@@ -131,7 +143,7 @@ def worker(args):
                           "interior_patch_steps_per_s": round(400 * tiles * T / sweep_s, 1),
                           "first_step_s": round(per_step[0], 2), "last_step_s": round(per_step[-1], 2),
                           "exchange_ms_per_step": round(res["exchange_ms_per_step"], 3),
-                          "save_and_stitch_s": round(io_s, 2), "pyramid_export_s": pyr_s, "stitch_from_files_equals_resident": same,
+                          "save_and_stitch_s": round(io_s, 2), "pyramid_export_s": pyr_s, "composite_export_s": comp_s, "stitch_from_files_equals_resident": same,
                           "state_finite": bool(torch.isfinite(st.float()).all()), "state_absmax": float(st.float().abs().max()),
                           "state_std": float(st.float().std())}), flush=True)
     if world > 1:
@@ -176,7 +188,15 @@ def main():
     ap.add_argument("--pyramid", action="store_true",
                     help="also export every plane as '<out_dir>/gen_pyramid/all_{sl}.tif': tiled pyramidal OME-TIFF with JPEG tiles")
     ap.add_argument("--page", type=int, default=None, help="with --pyramid: also write that pyramid level as all_{sl}.jpg")
-    ap.add_argument("--quality", type=int, default=75, help="with --pyramid: JPEG quality 1 .. 100")
+    ap.add_argument("--quality", type=int, default=75, help="with --pyramid / --composite: JPEG quality 1 .. 100")
+    ap.add_argument("--composite", action="store_true",
+                    help="also export every slice as '<out_dir>/gen_composite/rgb_{s}.tif': PolyT green / DAPI blue colour pyramid "
+                         "(--page and --quality apply)")
+    ap.add_argument("--bright", type=float, default=1.0, help="with --composite: brightness factor (ImageEnhance.Brightness)")
+    ap.add_argument("--overlay", default=None, metavar="PNG", help="with --composite: ontology image blended over every level")
+    ap.add_argument("--alpha", type=int, default=100, help="with --overlay: its weight, 0 .. 255")
+    ap.add_argument("--region", default="all", choices=["all", "half", "rhalf", "thalf", "bhalf", "quarter", "3quarter"],
+                    help="with --overlay: the part of it that is blended")
     args = ap.parse_args()
     if args.save_steps and not args.out_dir:
         ap.error("--save_steps needs --out_dir")
