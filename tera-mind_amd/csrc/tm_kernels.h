@@ -96,7 +96,7 @@ struct ConvLaunch {
                          // is the nearest-x2 upsampled block input (model/MBAblocks.py:254-258,297)
   int zmode = ZM_PAD1;   // the caller's statement of the z semantics; must agree with w.form (ignored for CF_1X1)
   int xquad_sched = -1;  // CF_XQUAD only: 0 = the four-barrier schedule of conv3d_xquad, 1 = the pipelined one, -1 = the launcher's
-                         // choice per instantiation (TM_CONV_XQUAD_PIPE=0: the four-barrier schedule everywhere)
+                         // choice per instantiation and launch size (TM_CONV_XQUAD_PIPE=0: the four-barrier schedule everywhere)
   // CF_PAIR, Cout == 64, the 128-voxel tile, no residual / gate / flags: fuse RMSNorm(C) * norm_w -> x (1 + scale) +
   // shift -> SiLU into the epilogue and write `a2` (the next conv's input) instead of y; y carries the geometry only
   int fuse_norm = 0;
@@ -109,8 +109,9 @@ struct ConvLaunch {
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
 // The tile of a k x 3 x 3 launch of `ovox` output voxels (N * Z * S * S of the launched plane): 2 = the large tile (256 voxels; 128
 // in the pair and x-pair forms), 1 = the small one.  tile_variant 0 chooses by launch size (conv_fills_chip), 1 / 2 force it; a 4 x 4
-// plane has the small tile only.  The one statement of the rule, for the launcher and for whoever must know the tile beforehand
-// (the fused mid-section exists in the large tile only).  No device call.
+// plane has the small tile only; the x-quad form takes its large tile from 256 large workgroups on, except at S >= 64 from 2048 on.
+// The one statement of the rule, for the launcher and for whoever must know the tile beforehand (the fused mid-section exists in
+// the large tile only).  No device call.
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant);
 // byte addresses in LDS of the 64 lanes of wave wv for one fragment read or staging store of conv3d_zpair (kernel 0),
 // conv3d_zpair_ups (1), conv3d_xpair (2), conv3d_xquad (4; 3 is no kernel: waves 0 .. 7 in the large tile, kx = the wave's q 0 .. 2, in a staging

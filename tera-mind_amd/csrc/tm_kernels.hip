@@ -847,6 +847,20 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
 //   T(X0 + X1), X(cb + 1) -> registers | vmcnt(12) | lgkmcnt(0) | B | P(X0 + X1), T(X0(cb + 1))
 // LDS: 36 864 B of ring + 12 q-planes, not less than the exchange area behind the K loop (NW x 3 x 4 KiB): 98 304 B in both
 // large tiles (one workgroup per CU, as before), 64 512 B (<1,16>) and 67 584 B (<1,8>) in the small ones: two per CU.
+//
+// THE TAIL (both schedules, all tiles; nothing of the large tile's tail is covered by another workgroup, so it is kept short).
+// The kernel has an epilogue of its own with conv_epilogue's arithmetic in its order -- (acc + bias) -> GELU flag -> res + -- and
+// its addresses, res_half's (z, y >> 1, x >> 1) included; a gate is refused by the launcher.  Behind the K loop, where the X and
+// fragment registers are dead, a wave requests the four bias quads and the eight residual quads of its z = 0 outputs, then
+// passes the exchange (each half names the tile it sends acc[p][2], so that it is dead behind the send in both halves), whose
+// barriers are bare s_barriers with lgkmcnt(0) alone: no wait for the loads in flight.  The z = 1 quads of column pair 0 go out
+// behind the sends into the sent tiles' registers, those of pair 1 behind the columns into the received tiles': all sixteen are
+// requested before the first output is formed (144 accumulator + 48 received + 64 residual registers would not fit at once).
+// The requests are unconditional -- a lane without a voxel or a cout block reads element 0 of the tensor, a launch without a
+// residual element 0 of the bias -- so the tail is one straight line and every wait is the counted vmcnt of its own quad.  An
+// address is a per-lane term (patch, row, group, q half, k half) plus a uniform one (cout block, plane, column pair).  The
+// outputs are formed for every lane in the residual's registers; the sixteen guarded stores follow and wait for nothing
+// (profiles/fp32_xquad_tail.txt: the stamps of the tail, and the groupings of the requests that spill).
 template <int HALF, int TW, int PIPE = 0>
 struct XQGeo {
   static constexpr int TW_ = TW;
@@ -1137,12 +1151,39 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
   // half 0 (A0, A1, A2) hands d = A1 - A2 over and takes s' = A3 + A4, half 1 (A3, A4, A5) the reverse; a tile is
   // [16 registers / 4][64 lanes] float4, three tiles per wave
   const int qhu = __builtin_amdgcn_readfirstlane(qh);
+  // ---- the tail's loads go out HERE, ahead of the exchange (header comment): bias, and the residual of the z = 0 outputs.  An
+  // address is one per-lane term plus one uniform term (cout block, plane z, column pair); with res_half, (z, y >> 1, x >> 1) of
+  // x = 4 c + 2 par + qh is half_res_off of column 4 c plus z (S / 2)^2 + par voxels
+  const bool okv = ooff0 >= 0;
+  const long yl = okv ? (long)on[0] * a.y_nstride + ooff0 + qh * 8 + 4 * h : 0;
+  const long rl = okv ? (long)on[0] * a.res_nstride + (a.res_ls ? half_res_off(ooff0, a.res_ls) : ooff0 + qh * 8) + 4 * h : 0;
+  const long rplane = a.res_ls ? a.y_plane >> 2 : a.y_plane;
+  const int rz = a.res_ls ? S * S * 2 : S * S * 8, rp = a.res_ls ? 8 : 16;
+  const float* rsrc = a.res ? a.res : a.bias;                    // no residual: the same sixteen requests, of the bias' element 0 (cached),
+                                                                 // so that one straight-line tail serves both and every wait is counted
+  f32x4 bv[4], rv[2][2][4];                                      // rv[z][par][g]: column 2 par + qh of plane z, cout block 4 nt + g
 #pragma unroll
-  for (int p = 0; p < 3; ++p) {                                  // acc[p][0] = A0 | d', [1] = s | s', [2] = d | A5
-    if (qhu) {
+  for (int g = 0; g < 4; ++g) {
+    const int cob = nt * 4 + g;
+    bv[g] = *(const f32x4*)(a.bias + (long)(cob < a.Cob ? cob : 0) * 8 + 4 * h);
+  }
+  auto load_res = [&](int z, int par) __attribute__((always_inline)) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int cob = nt * 4 + g;
+      const long uni = (long)cob * rplane + z * rz + par * rp;
+      rv[z][par][g] = *(const f32x4*)(rsrc + (cob < a.Cob && okv && a.res ? rl + uni : 0));
+    }
+  };
+  load_res(0, 0);
+  load_res(0, 1);
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {                                  // acc[p][0] = A0 | d', [1] = s | A5, [2] = d | s': the tile it sends,
+    if (qhu) {                                                   // dead behind the send in BOTH halves (registers for the residual)
       const f32x16 sp = acc[p][0] + acc[p][1];
       acc[p][0] = acc[p][0] - acc[p][1];
-      acc[p][1] = sp;
+      acc[p][1] = acc[p][2];
+      acc[p][2] = sp;
     } else {
       const f32x16 s = acc[p][1] + acc[p][2];
       acc[p][2] = acc[p][1] - acc[p][2];
@@ -1150,16 +1191,26 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
     }
     asm volatile("" : "+v"(acc[p][0]), "+v"(acc[p][1]), "+v"(acc[p][2]));
   }
-  __syncthreads();
+  // every wave is through the K loop (its fragment reads have fed their MFMAs, no piece is in flight behind the last block)
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const f32x16& tl = qhu ? acc[p][1] : acc[p][2];
+      const f32x16& tl = acc[p][2];
       const f32x4 v = {tl[4 * i], tl[4 * i + 1], tl[4 * i + 2], tl[4 * i + 3]};
       *(f32x4*)(lds + ((wv * 3 + p) * 4 + i) * 256 + lane * 4) = v;
     }
-  __syncthreads();
+  load_res(1, 0);                                                // into the sent tiles' registers
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0xC07F);                            // lgkmcnt(0) only: this wave's tiles are in LDS
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
   f32x16 got[3];
 #pragma unroll
   for (int p = 0; p < 3; ++p)
@@ -1175,7 +1226,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
     f32x16 c0, c1;
     if (qhu) {
       c0 = got[p] + 2.f * acc[p][0];
-      c1 = (got[p] + 8.f * acc[p][0]) + acc[p][2];
+      c1 = (got[p] + 8.f * acc[p][0]) + acc[p][1];
     } else {
       c0 = (acc[p][0] + acc[p][1]) + got[p];
       c1 = acc[p][1] + 4.f * got[p];
@@ -1184,17 +1235,41 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
     acc[p][1] = c1;
     asm volatile("" : "+v"(acc[p][0]), "+v"(acc[p][1]));         // formed HERE, not sunk into the guarded stores below
   }
+  load_res(1, 1);                                                // into got's: all sixteen quads are requested before the first output
+  // conv_epilogue's arithmetic in its order, (acc + bias) -> GELU -> res +, formed for every lane in the residual's registers (the
+  // waits for the loads stand in code every lane runs, counted per quad), then the sixteen stores, which wait for nothing
 #pragma unroll
   for (int z = 0; z < 2; ++z)
 #pragma unroll
     for (int par = 0; par < 2; ++par) {
-      f32x16 o[1][1];
-      o[0][0] = acc[0][par] + acc[1 + z][par];
-      asm volatile("" : "+v"(o[0][0]));
-      const int ooff[1] = {ooff0 >= 0 ? ooff0 + (z * S * S + 2 * par + qh) * 8 : -1};
-      __builtin_amdgcn_sched_barrier(0);
-      conv_epilogue<1, 1>(a, o, nt, h, on, ooff, 2 * S);
+      f32x16 o = acc[0][par] + acc[1 + z][par];
+      asm volatile("" : "+v"(o));
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        f32x4 v;
+        v[0] = o[4 * g + 0] + bv[g][0];
+        v[1] = o[4 * g + 1] + bv[g][1];
+        v[2] = o[4 * g + 2] + bv[g][2];
+        v[3] = o[4 * g + 3] + bv[g][3];
+        if (a.flags & EPI_GELU) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] = gelu_tanh_hw(v[j]);
+        }
+        if (a.res) v = rv[z][par][g] + v;
+        rv[z][par][g] = v;
+        asm volatile("" : "+v"(rv[z][par][g]));                  // formed HERE: sunk into the guarded stores, its wait would count them
+      }
     }
+#pragma unroll
+  for (int z = 0; z < 2; ++z)
+#pragma unroll
+    for (int par = 0; par < 2; ++par)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int cob = nt * 4 + g;
+        const long uni = (long)cob * a.y_plane + z * (S * S * 8) + par * 16;
+        if (cob < a.Cob && okv) *(f32x4*)(a.y + yl + uni) = rv[z][par][g];
+      }
 }
 
 // ---- 1x1x1 conv / Linear over voxels (flat voxel tiles, KC channel blocks per stage) ----
@@ -1326,24 +1401,36 @@ int conv1_form(long vox, int ntile, int tile_variant) {
   return variant == 2 ? 2 : 1;
 }
 
+// The workgroups an x-quad launch of `ovox` output voxels and `ntile` 64-cout tiles would have in its large tile, and whether it is
+// one of the launches in which the small tile is the faster one: planes of 64 x 64 and up with eight large workgroups per CU or
+// more (what was measured: the S = 64 levels at 128 patches, whose K loops of 8 and 12 cin blocks are the shortest of the step)
+static long xquad_large_wgs(long ovox, int ntile) { return (ovox / 1024) * 2 * ntile; }
+static bool xquad_many_wgs(long ovox, int ntile, int S) { return S >= 64 && xquad_large_wgs(ovox, ntile) >= 2048; }
+
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant) {
   if (S == 4) return 1;                        // 4 x 4 planes: several patches per workgroup of the small tile
-  // x-quad: the large tile is 1024 voxels x 32 couts on eight waves, one workgroup per CU: taken where it still gives every CU one
-  if (form == CF_XQUAD) return tile_variant ? (tile_variant == 2 ? 2 : 1) : ((ovox / 1024) * 2 * ntile >= 256 ? 2 : 1);
+  // x-quad: the large tile is 1024 voxels x 32 couts on eight waves, one workgroup per CU, whose head and tail nothing covers: taken
+  // where it still gives every CU one workgroup, except at S >= 64 from 2048 large workgroups on (the S = 64 levels at 128
+  // patches): there the small tile, two workgroups per CU that cover each other's head and tail, wins by 6 - 7 % at the op
+  // level; at 512 workgroups of S = 64 and at 1024 of S = 32 the two tie (profiles/fp32_xquad_tail.txt section 3)
+  if (form == CF_XQUAD)
+    return tile_variant ? (tile_variant == 2 ? 2 : 1) : (xquad_large_wgs(ovox, ntile) >= 256 && !xquad_many_wgs(ovox, ntile, S) ? 2 : 1);
   const long tiles = (form == CF_ZSKIP_UPS || form == CF_PAIR_UPS) ? 4L * ntile : ntile;
   const int variant = tile_variant ? tile_variant : (conv_fills_chip(ovox, tiles) ? 2 : 1);
   return variant == 2 ? 2 : 1;
 }
 
 // The schedule of conv3d_xquad a launch takes where the caller forces none: the pipelined one (PIPE = 1) in the instantiations
-// <half, tw> where it won at the op level (profiles/fp32_xquad_pipe.txt); TM_CONV_XQUAD_PIPE=0 (read once) keeps the
-// four-barrier schedule everywhere.  The form and the pack are the same in both, so conv_pick_form does not see the switch.
-static bool xquad_pipe_default(bool half, int tw) {
+// <half, tw> where it won at the op level (profiles/fp32_xquad_pipe.txt), and in the small tile <1, 16> of a launch that takes it
+// for its many workgroups (`many`: xquad_many_wgs), where only the pipelined schedule beats the large tile by the rule
+// (profiles/fp32_xquad_tail.txt section 3); TM_CONV_XQUAD_PIPE=0 (read once) keeps the four-barrier schedule everywhere.  The
+// form and the pack are the same in both, so conv_pick_form does not see the switch.
+static bool xquad_pipe_default(bool half, int tw, bool many) {
   static const bool on = [] {
     const char* v = getenv("TM_CONV_XQUAD_PIPE");
     return !(v && atoi(v) == 0);
   }();
-  return on && !half && tw == 16;              // <0, 16> alone: <0, 8> ties or loses by 2 %, the small tiles lose 13 - 16 %
+  return on && tw == 16 && (!half || many);    // <0, 8> ties or loses by 2 %, the small tiles of the small launches lose 6 - 16 %
 }
 
 // One k x 3 x 3 launch: KERN over the tiles of geometry G (TW x TR voxels of NPB patches, LDS_BYTES of dynamic LDS), `factor`
@@ -1444,6 +1531,7 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
       break;
     case CF_XPAIR: case CF_XQUAD:  // ... with Winograd along x: planes of at least 8 x 8, plain epilogue
       if (L.zmode != ZM_PAD1 || !z2 || L.x.H < 8 || up2) return hipErrorInvalidValue;
+      if (form == CF_XQUAD && L.gate) return hipErrorInvalidValue;   // its own epilogue: bias, GELU flag and residual, no gate
       break;
     case CF_ZSKIP_UPS: case CF_PAIR_UPS:   // 3x3x3 pad 1 of the nearest-x2 upsampled x, on the low-resolution x
       if (L.zmode != ZM_UPS || !z2 || up2 || L.res || L.gate) return hipErrorInvalidValue;
@@ -1486,7 +1574,7 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
       if (L.xquad_sched < -1 || L.xquad_sched > 1) return hipErrorInvalidValue;
       return with_tile_width<16>(S, [&](auto tw) {
         constexpr int TW = decltype(tw)::value;
-        if (L.xquad_sched < 0 ? xquad_pipe_default(!large, TW) : L.xquad_sched == 1)
+        if (L.xquad_sched < 0 ? xquad_pipe_default(!large, TW, xquad_many_wgs((long)a.N * a.Z * a.S * a.S, L.w.ntile, S)) : L.xquad_sched == 1)
           return large ? launch_tiled<conv3d_xquad<0, TW, 1>, XQGeo<0, TW, 1>, 64 * XQGeo<0, TW, 1>::NW>(a, 1, s)
                        : launch_tiled<conv3d_xquad<1, TW, 1>, XQGeo<1, TW, 1>, 64 * XQGeo<1, TW, 1>::NW>(a, 1, s);
         return large ? launch_tiled<conv3d_xquad<0, TW, 0>, XQGeo<0, TW, 0>, 64 * XQGeo<0, TW, 0>::NW>(a, 1, s)
