@@ -452,8 +452,9 @@ int tm_avgpool2_pad3(const void* src, int dtype, int V, int D, int H, int W, int
  *   nominal_flops  = 2*Cin*Cout*27*voxels per launch (dense-conv convention; what
  *                    torch.utils.flop_counter counts for the reference's Conv3d)
  *   executed_flops = the MFMA FLOPs actually issued: for z_size 2, fp32, 1/2 of that (pair form: three in-plane products per
- *                    plane pair, 27 of the nominal 54 taps; 2/3 with TM_CONV_ZPAIR=0 and in the 16-bit modes, where only the
- *                    always-zero z tap is skipped), 1/3 for z_size 1 (centre slice only), all of it for z_size 4 / 8
+ *                    plane pair, 27 of the nominal 54 taps; 1/4 for a launch in the x-quad form, 54 tap-products per eight
+ *                    outputs; 2/3 with TM_CONV_ZPAIR=0 and in the 16-bit modes, where only the always-zero z tap is
+ *                    skipped), 1/3 for z_size 1 (centre slice only), all of it for z_size 4 / 8
  *   alg_bytes      = input + packed weights + output bytes, each counted once per launch */
 typedef struct tm_prof_stats {
   uint64_t launches;
@@ -522,18 +523,12 @@ int tm_op_conv_zpair_fused_f32(const void* x_cb8, const void* w_host, const void
 int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                             int Cout, int Z, int S, int tile_variant, void* stream);
 
-/* The fp32 3x3x3 pad-1 conv at Z == 2 in its x-pair form (conv3d_xpair: the pair form in z composed with Winograd F(2,3) along
- * x, 36 tap-products per four outputs).  x CB8 DEVICE [N][ceil(Cin/8)][2][S][S][8]; w [Cout][Cin][27], bias [Cout] HOST; y CB8
+/* The fp32 3x3x3 pad-1 conv at Z == 2 in its x-quad form (conv3d_xquad: the pair form in z composed with Winograd F(4,3) along
+ * x, 54 tap-products per eight outputs).  x CB8 DEVICE [N][ceil(Cin/8)][2][S][S][8]; w [Cout][Cin][27], bias [Cout] HOST; y CB8
  * DEVICE; res_cb8 (nullable): y's geometry, or S / 2 in-plane with res_half != 0 (read at (z, y >> 1, x >> 1)).  tile_variant:
- * 0 = by launch size, 1 | 2 = the 64- | 128-voxel tile.  Returns the tile launched (1 | 2) on success.  TM_ERR_ARG before any
- * device call: Z != 2, S outside {8, .., 128}, the form switched off (TM_CONV_XPAIR=0).  tm_op_conv_mfma with zmode 0 stays
- * the pair form of the same conv. */
-int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
-                         int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream);
-/* The same conv in its x-quad form (conv3d_xquad: the pair form in z composed with Winograd F(4,3) along x, 54 tap-products per
- * eight outputs), arguments as tm_op_conv_xpair_f32.  tile_variant 1 | 2 = 64 | 128 four-column groups per workgroup.  Returns the
- * tile launched (1 | 2).  TM_ERR_ARG before any device call: Z != 2, S outside {8, .., 128} (so S = 4 and every S that is no
- * multiple of 4), the form switched off (TM_CONV_XQUAD=0). */
+ * 0 = by launch size, 1 | 2 = 64 | 128 four-column groups per workgroup.  Returns the tile launched (1 | 2) on success.
+ * TM_ERR_ARG before any device call: Z != 2, S outside {8, .., 128} (so S = 4 and every S that is no multiple of 4), the form
+ * switched off (TM_CONV_XQUAD=0).  tm_op_conv_mfma with zmode 0 stays the pair form of the same conv. */
 int tm_op_conv_xquad_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                          int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream);
 /* tm_op_conv_xquad_f32 with the schedule of conv3d_xquad forced: sched 0 = four barriers per cin block (all eighteen q-planes of
@@ -546,12 +541,10 @@ int tm_op_conv_xquad_sched_f32(const void* x_cb8, const void* w_host, const void
 /* The dynamic LDS (bytes) of conv3d_xquad in the large | small tile (half 0 | 1), tile width tw (8 | 16) and schedule sched
  * (0 | 1); -1 if there is no such instantiation.  No device call. */
 int tm_conv_xquad_lds_bytes(int half, int tw, int sched);
-/* Timing hook (tools/bench_conv_xpair.py): that conv packed once for `form` (0 = the pair form, 1 = the x-pair form, 2 = the
- * x-quad form), then `iters` launches, each between two events of its own: ms_out[i] (HOST) = the time of launch i. */
-int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                             int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream);
-/* The same with the schedule of conv3d_xquad forced (form 2 only): sched 0 | 1 as in tm_op_conv_xquad_sched_f32, -1 = the
- * launcher's choice, which is what tm_op_conv_pad1_time_f32 takes. */
+/* Timing hook (tools/bench_conv_xquad.py): that conv packed once for `form` (0 = the pair form, 2 = the x-quad form; any other
+ * value, 1 included, is TM_ERR_ARG), then `iters` launches, each between two events of its own: ms_out[i] (HOST) = the time of
+ * launch i.  sched: the schedule of conv3d_xquad (form 2 only), 0 | 1 as in tm_op_conv_xquad_sched_f32, -1 = the launcher's
+ * choice. */
 int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                                    int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out, void* stream);
 
@@ -572,15 +565,15 @@ int tm_op_conv1_f32(const void* x_cb8, const void* w_host, const void* bias_host
 int tm_conv1_form(long vox, int ntile, int tile_variant);
 
 /* Where the lanes of the fp32 LDS-DMA conv kernels address LDS (no device call; for bank-conflict models of the operand images).
- * kernel 0 = conv3d_zpair, 1 = conv3d_zpair_ups, 2 = conv3d_xpair; half 0 | 1 = the large | small tile; tw = tile width (4 | 8 |
- * 16 | 32; x-pair 8 | 16); wave 0..3.  what 0: the weight fragment (ds_read_b128) of product p (0..2), window row ky, column kx
- * (x-pair: the wave's q-th transform position) and 32-cout sub-tile sub; what 1: the activation fragment of (p, ky, kx), sub =
- * the output phase 2 py + px of kernel 1 (else 0); what 2: the staging store (ds_write_b128) into plane p of the thread's ky-th
- * item (x-pair: ky 0, kx = the q-plane).  out64[lane] = byte address in the workgroup's dynamic LDS, -1 for a lane that stores
- * nothing.  kernel 4 = conv3d_xquad (3 is no kernel and stays refused): tw 8 | 16, wave 0..7 (0..3 in the small tile), kx = the wave's q-th transform position
- * (0..2), in what 2 the q-plane (0..5).  kernel 5 = conv3d_xquad in its pipelined schedule: as 4, but the X planes are a ring of
- * two sets of six and sub = the plane set (0 | 1) of an activation fragment or a staging store (product n of the running count
- * reads set n & 1; sub 0 for a weight fragment).  Returns 0, or -1 if there is no such instantiation, fragment or item. */
+ * kernel 0 = conv3d_zpair, 1 = conv3d_zpair_ups; half 0 | 1 = the large | small tile; tw = tile width (4 | 8 | 16 | 32); wave
+ * 0..3.  what 0: the weight fragment (ds_read_b128) of product p (0..2), window row ky, column kx and 32-cout sub-tile sub; what
+ * 1: the activation fragment of (p, ky, kx), sub = the output phase 2 py + px of kernel 1 (else 0); what 2: the staging store
+ * (ds_write_b128) into plane p of the thread's ky-th item.  out64[lane] = byte address in the workgroup's dynamic LDS, -1 for a
+ * lane that stores nothing.  kernel 4 = conv3d_xquad (2 and 3 are no kernels and stay refused): tw 8 | 16, wave 0..7 (0..3 in
+ * the small tile), kx = the wave's q-th transform position (0..2), in what 2 ky 0 and kx = the q-plane (0..5).  kernel 5 =
+ * conv3d_xquad in its pipelined schedule: as 4, but the X planes are a ring of two sets of six and sub = the plane set (0 | 1) of
+ * an activation fragment or a staging store (product n of the running count reads set n & 1; sub 0 for a weight fragment).
+ * Returns 0, or -1 if there is no such instantiation, fragment or item. */
 int tm_conv_frag_addrs(int kernel, int half, int tw, int what, int wave, int p, int ky, int kx, int sub, int* out64);
 
 /* 16-bit variant of the 3x3x3 pad-1 conv (Z == 2): x fp32 CB8 is rounded to `dtype` (TM_DTYPE_BF16 | TM_DTYPE_F16, RNE) on

@@ -112,11 +112,9 @@ SIGNATURES = {
     "tm_op_conv27_fused_z": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_void_p]),
     "tm_op_conv_zpair_fused_f32": (c_int, [c_void_p] * 10 + [c_int] * 7 + [c_void_p]),
     "tm_op_conv_ups_pair_f32": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p]),
-    "tm_op_conv_xpair_f32": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     "tm_op_conv_xquad_f32": (c_int, [c_void_p] * 5 + [c_int] * 7 + [c_void_p]),
     "tm_op_conv_xquad_sched_f32": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "tm_conv_xquad_lds_bytes": (c_int, [c_int] * 3),
-    "tm_op_conv_pad1_time_f32": (c_int, [c_void_p] * 4 + [c_int] * 7 + [C.POINTER(c_float), c_void_p]),
     "tm_op_conv_pad1_time_sched_f32": (c_int, [c_void_p] * 4 + [c_int] * 8 + [C.POINTER(c_float), c_void_p]),
     "tm_op_conv27_time":(c_int, [c_int] * 10 + [c_void_p, c_void_p]),
     "tm_op_conv1_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4),

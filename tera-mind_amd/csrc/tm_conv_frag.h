@@ -1,16 +1,17 @@
-// The LDS operand images of the fp32 LDS-DMA conv kernels (conv3d_zpair, conv3d_zpair_ups, conv3d_xpair) as plain functions:
+// The LDS operand images of the fp32 LDS-DMA conv kernels (conv3d_zpair, conv3d_zpair_ups, conv3d_xquad) as plain functions:
 // where a lane reads its MFMA fragments and where a staging thread stores.  Shared by the kernels, the weight packers (the
 // pack IS the LDS image: LDS-DMA copies it linearly) and the host entry point tm_conv_frag_addrs, which hands the addresses
 // to the bank model of tests/test_conv_frag_banks.py.  No device builtins in here.
 //
 // An operand fragment is the 16 bytes (4 of the 8 channels of a block: k-half h = lane >> 5) of one row (a cout, a voxel or an
-// x-pair position).  `ds_read_b128` is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
+// x-quad group position).  `ds_read_b128` is served in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
 // same of lanes 32-63 -- and a group takes one LDS cycle only if its sixteen 16-byte slots differ mod 16 (256 bytes = all 64
 // banks).  All lanes of a group share h.  An image of [row][8 floats] puts row r, half h at slot 2 r + h: a group lands on eight
 // slots, each of them twice.  The images below keep the two k-halves as two arrays of 16-byte slots, [2 halves][rows][4 floats]:
 // a group whose rows differ mod 16 is conflict-free, whatever the constant (tap, plane, window) offset.
 //   weights  the 64 couts of a tap: a group's lanes are rows i32 (mod 32) themselves, {0-3, 12-15, 20-27} = all residues.
-//   x-pair   the q-planes have no x halo: a wave's 32 pair positions are consecutive rows.
+//   x-quad   the q-planes have no x halo: a wave's 32 group positions are consecutive rows (TW = 16), or two runs of sixteen in
+//            two patches, one run per group of lanes (TW = 8).
 //   z-pair   rows are halo positions (tile row * pitch + column), so the rows of a group depend on the tile width:
 //            TW = 32  a wave is one tile row: consecutive.
 //            TW = 16  two rows of 16 at pitch 18: a row is conflict-free in itself, so lanes are mapped group -> row.

@@ -14,7 +14,6 @@ int conv_form_taps(int form) {
     case CF_1X1: return 1;
     case CF_INPLANE: return 9;
     case CF_ZSKIP_UPS: case CF_PAIR_UPS: return 12;
-    case CF_XPAIR: return 36;
     case CF_XQUAD: return 54;
     default: return 27;
   }
@@ -34,8 +33,7 @@ static bool switch_on(const char* name) {        // an A/B switch: on unless the
   return !(v && atoi(v) == 0);
 }
 int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse_mid) {
-  static const bool zpair_on = switch_on("TM_CONV_ZPAIR"), xpair_on = switch_on("TM_CONV_XPAIR"),
-                    xmid_on = switch_on("TM_CONV_XPAIR_MID"), fuse_on = switch_on("TM_CONV_FUSE_MID"),
+  static const bool zpair_on = switch_on("TM_CONV_ZPAIR"), fuse_on = switch_on("TM_CONV_FUSE_MID"),
                     xquad_on = switch_on("TM_CONV_XQUAD");
   if (fuse_mid) *fuse_mid = false;
   if (ksize == 1) return CF_1X1;
@@ -44,18 +42,14 @@ int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse
   const bool pair = Z == 2 && zpair_on;
   if (zmode == ZM_UPS) return ((role & ROLE_OP_PAIR_UPS) || ((role & ROLE_RES) && pair)) ? CF_PAIR_UPS : CF_ZSKIP_UPS;
   if (Z != 2) return (Z == 1 && (role & ROLE_RES)) ? CF_INPLANE : CF_PLANES3;
-  if ((role & ROLE_OP_XPAIR) && xpair_on) return CF_XPAIR;
   if ((role & ROLE_OP_XQUAD) && xquad_on) return CF_XQUAD;
   if (!pair) return CF_ZSKIP;
-  // c1 of a 64-channel block: the pair form fuses the mid norm into its epilogue, an x-pair wave holds 32 of the 64 channels and
-  // leaves the norm to the separate pass.  Measured per step (profiles/fp32_xpair.txt), x-pair + separate pass is the faster by
-  // 0.58 ms over the six launches, so these layers move too; TM_CONV_XPAIR_MID=0 keeps them fused
-  const bool fuses = (role & ROLE_C1_64) && fuse_on;
-  const bool xp = (role & ROLE_RES) && !(role & ROLE_DEEP) && xpair_on && deep8 && (!fuses || xmid_on);
-  if (fuse_mid) *fuse_mid = fuses && !xp;
-  // the x-pair layers move on to the x-quad form (F(4,3) along x, 0.75 of the x-pair's MFMAs); TM_CONV_XQUAD=0 keeps them
-  if (xp && xquad_on) return CF_XQUAD;
-  return xp ? CF_XPAIR : CF_PAIR;
+  // a ResBlock conv above the deepest decoder level, on planes of at least 8 x 8, runs in the x-quad form (F(4,3) along x, half
+  // the pair form's MFMAs); TM_CONV_XQUAD=0 leaves it on the pair form.  c1 of a 64-channel block: the pair form fuses the mid
+  // norm into its epilogue; an x-quad workgroup holds 32 of the 64 channels and leaves the norm to the separate pass
+  const bool xq = (role & ROLE_RES) && !(role & ROLE_DEEP) && deep8 && xquad_on;
+  if (fuse_mid) *fuse_mid = (role & ROLE_C1_64) && fuse_on && !xq;
+  return xq ? CF_XQUAD : CF_PAIR;
 }
 
 // ---- packers ----
@@ -116,21 +110,6 @@ static std::vector<float> z_diff(const float* w, size_t n, int k) {
     }
   return o;
 }
-// F(2,3) filter transform of the three kx taps g0, g1, g2 of every (product, ky) row: U0 = g0, U1 = ((g0 + g1) + g2) / 2,
-// U2 = ((g0 - g1) + g2) / 2, U3 = g2.  [n][9 rows][3] -> [n][9 rows][4]
-static std::vector<float> f23_rows(const float* w, size_t n) {
-  std::vector<float> o(n * 36);
-  for (size_t r = 0; r < n * 9; ++r) {
-    const float* g = w + r * 3;
-    float* u = o.data() + r * 4;
-    u[0] = g[0];
-    u[1] = ((g[0] + g[1]) + g[2]) * 0.5f;
-    u[2] = ((g[0] - g[1]) + g[2]) * 0.5f;
-    u[3] = g[2];
-  }
-  return o;
-}
-
 // F(4,3) filter transform of the three kx taps of every (product, ky) row: U0 = g0 / 4, U1 = -((g0 + g1) + g2) / 6,
 // U2 = -((g0 - g1) + g2) / 6, U3 = (g0 / 24 + g1 / 12) + g2 / 6, U4 = (g0 / 24 - g1 / 12) + g2 / 6, U5 = g2.  Divisions, not
 // rounded reciprocals: weights that are multiples of 24 transform exactly.  [n][9 rows][3] -> [n][9 rows][6]
@@ -177,8 +156,6 @@ void conv_pack_host(int form, const float* w, int Cout, const int* seg_c, int ns
     pack_taps32(f43_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, out);
   } else if (form == CF_PAIR) {
     pack_taps(z_diff(w, n, 9).data(), Cout, seg_c, nseg, 27, out, true);
-  } else if (form == CF_XPAIR) {
-    pack_taps(f23_rows(z_diff(w, n, 9).data(), n).data(), Cout, seg_c, nseg, 36, out, true);
   } else if (form_ups(form)) {               // [phase = 2 py + px][the 12-tap pack of that phase's weights]
     const size_t per = conv_pack_floats(form, Cout, Cbi) / 4;
     for (int ph = 0; ph < 4; ++ph) {

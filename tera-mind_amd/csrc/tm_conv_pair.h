@@ -1,5 +1,5 @@
 // Scaffolding shared by the fp32 k x 3 x 3 MFMA conv kernels of tm_kernels.hip (conv3d_mfma, conv3d_zpair, conv3d_zpair_ups,
-// conv3d_xpair): what they have in common around their K loops.  The K loops, ring schedules, barriers, waits and register pins
+// conv3d_xquad): what they have in common around their K loops.  The K loops, ring schedules, barriers, waits and register pins
 // stay in the kernels, and so do the halo staging, the two-plane load, the stage head and the plane-sum tail of the two z-pair
 // kernels: moved into functions here they changed the compiler's wait counts and the instruction order of the K loop
 // (profiles/conv_family_refactor.txt).

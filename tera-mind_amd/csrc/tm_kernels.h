@@ -47,7 +47,6 @@ enum ConvForm {
   CF_ZSKIP_UPS,      // z-skip of the nearest-x2 upsampled input: 4 phases x 12 phase-sum taps (conv3d_mfma<2, .., true>)
   CF_PAIR,           // pair form at Z == 2: W1, W2 - W1, W0 - W1, 27 taps (conv3d_zpair)
   CF_PAIR_UPS,       // pair form of the upsampled input: the z difference of the phase sums, 4 x 12 taps (conv3d_zpair_ups)
-  CF_XPAIR,          // pair form in z with Winograd F(2,3) along x: 36 transformed taps (conv3d_xpair)
   CF_XQUAD,          // pair form in z with Winograd F(4,3) along x: 54 transformed taps, 32-cout tiles (conv3d_xquad)
 };
 struct ConvW {
@@ -56,19 +55,19 @@ struct ConvW {
   int Cout = 0, Cbi = 0, taps = 0, ntile = 0;     // taps = conv_form_taps(form): set by conv_w only
   int form = CF_1X1;
 };
-int conv_form_taps(int form);                            // taps per (cout tile, cin block) of the pack: 1 / 9 / 27 / 12 / 36 / 54
+int conv_form_taps(int form);                            // taps per (cout tile, cin block) of the pack: 1 / 9 / 27 / 12 / 54
 size_t conv_pack_floats(int form, int Cout, int Cbi);    // floats of the whole pack (the upsampled forms hold four phases)
 ConvW conv_w(int form, int Cout, int Cbi);               // the weight geometry of a form; w / bias are left for the caller
 // Which form a conv runs in, from what its caller knows: the kernel size (1 or 3), the z semantics (ZM_*), the input planes Z,
-// whether the model's deepest plane is at least 8 x 8 (the x-pair kernel has no 4 x 4 tile) and the role of the layer.  The one
-// reader of the A/B switches TM_CONV_ZPAIR, TM_CONV_XPAIR, TM_CONV_XQUAD, TM_CONV_XPAIR_MID and TM_CONV_FUSE_MID (each read once; =0 switches
-// the form off, for timing in separate processes only).  *fuse_mid (nullable): the layer runs the ResBlock mid-section in its
-// epilogue wherever a launch takes the 128-voxel tile.
-enum { ROLE_OP = 0,             // single-operator hooks and the training tape: pair form at Z == 2, never x-pair
-       ROLE_RES = 1,            // a ResBlock 3x3x3 conv of the executor: centre slice at Z == 1, x-quad (x-pair under TM_CONV_XQUAD=0) at Z == 2
+// whether the model's deepest plane is at least 8 x 8 (the x-quad kernel has no 4 x 4 tile) and the role of the layer.  The one
+// reader of the A/B switches TM_CONV_ZPAIR, TM_CONV_XQUAD and TM_CONV_FUSE_MID (each read once; =0 switches the form off, for
+// timing in separate processes only: TM_CONV_XQUAD=0 leaves its layers on the pair form).  *fuse_mid (nullable): the layer runs
+// the ResBlock mid-section in its epilogue wherever a launch takes the 128-voxel tile.
+enum { ROLE_OP = 0,             // single-operator hooks and the training tape: pair form at Z == 2, never x-quad
+       ROLE_RES = 1,            // a ResBlock 3x3x3 conv of the executor: centre slice at Z == 1; at Z == 2 x-quad, or pair
+                                //   (TM_CONV_XQUAD=0)
        ROLE_DEEP = 2,           // + a decoder block of the deepest level: stays on the pair form (profiles/fp32_xpair.txt)
-       ROLE_C1_64 = 4,          // + the first conv of a 64-channel block: pair form with the fused mid-section, or x-pair
-       ROLE_OP_XPAIR = 8,       // the hooks of the x-pair form: under TM_CONV_XPAIR alone
+       ROLE_C1_64 = 4,          // + the first conv of a 64-channel block: on the pair form it runs the fused mid-section
        ROLE_OP_PAIR_UPS = 16,   // the hook of the upsampled pair form: under no switch
        ROLE_OP_XQUAD = 32 };    // the hooks of the x-quad form: under TM_CONV_XQUAD alone
 int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse_mid = nullptr);
@@ -108,14 +107,14 @@ struct ConvLaunch {
 };
 hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
 // The tile of a k x 3 x 3 launch of `ovox` output voxels (N * Z * S * S of the launched plane): 2 = the large tile (256 voxels; 128
-// in the pair and x-pair forms), 1 = the small one.  tile_variant 0 chooses by launch size (conv_fills_chip), 1 / 2 force it; a 4 x 4
-// plane has the small tile only; the x-quad form takes its large tile from 256 large workgroups on, except at S >= 64 from 2048 on.
-// The one statement of the rule, for the launcher and for whoever must know the tile beforehand (the fused mid-section exists in
-// the large tile only).  No device call.
+// in the pair forms, 128 four-column groups in the x-quad form), 1 = the small one.  tile_variant 0 chooses by launch size
+// (conv_fills_chip), 1 / 2 force it; a 4 x 4 plane has the small tile only; the x-quad form takes its large tile from 256 large
+// workgroups on, except at S >= 64 from 2048 on.  The one statement of the rule, for the launcher and for whoever must know the
+// tile beforehand (the fused mid-section exists in the large tile only).  No device call.
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant);
 // byte addresses in LDS of the 64 lanes of wave wv for one fragment read or staging store of conv3d_zpair (kernel 0),
-// conv3d_zpair_ups (1), conv3d_xpair (2), conv3d_xquad (4; 3 is no kernel: waves 0 .. 7 in the large tile, kx = the wave's q 0 .. 2, in a staging
-// store the q-plane 0 .. 5), its pipelined schedule (5: as 4, `sub` = the plane set 0 | 1 of an X fragment or a staging store),
+// conv3d_zpair_ups (1), conv3d_xquad (4; 2 and 3 are no kernels: waves 0 .. 7 in the large tile, kx = the wave's q 0 .. 2, in a
+// staging store the q-plane 0 .. 5), its pipelined schedule (5: as 4, `sub` = the plane set 0 | 1 of an X fragment or a staging store),
 // instantiation <half, tw> (tm_kernels.hip); -1: no such thing; no device call
 int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out);
 // the dynamic LDS of conv3d_xquad<half, tw> in schedule sched (0 | 1), bytes; -1: no such instantiation; no device call

@@ -542,268 +542,6 @@ __global__ __launch_bounds__(256, 2) void conv3d_zpair_ups(ConvArgs a) {
   conv_epilogue<1, NC>(a, o, nte, h, on, ooff1, 0);
 }
 
-// ---- x-pair form of the 3x3x3 pad-1 conv at Z == 2 (fp32): the pair form in z composed with Winograd F(2,3) along x ----
-// The 1-D identity F(2,3) gives two neighbouring outputs of a 3-tap filter g with four products instead of six: with d0..d3 the
-// inputs at columns 2j - 1 .. 2j + 2,
-//   T0 = d0 - d2   T1 = d1 + d2   T2 = d2 - d1   T3 = d1 - d3          (formed while staging)
-//   U0 = g0   U1 = (g0 + g1 + g2) / 2   U2 = (g0 - g1 + g2) / 2   U3 = g2   (formed at pack time, conv_pack_host, CF_XPAIR)
-//   out[2j] = U0 T0 + U1 T1 + U2 T2        out[2j + 1] = U1 T1 - U2 T2 - U3 T3.
-// It is linear in the weights, so it applies to each of the three z products of the pair form (V = W1, W2 - W1, W0 - W1 on
-// Xs = X0 + X1, X1, X0): per (product, ky) four transform positions per x-pair replace three taps per voxel, 36 tap-products
-// per four outputs (9 per output against the pair form's 13.5).  A_q(p) = sum over cin, ky of U_q(p)[ky] T_q(p)[y + ky - 1][j]
-// is accumulated on the MFMA exactly as a tap is; the epilogue forms, per product, even = (A0 + A1) + A2 and odd = (A1 - A2) -
-// A3, then Y0 = P(1) + P(2), Y1 = P(1) + P(3) per column parity and runs the common epilogue on each (plane, parity).
-// One workgroup (256 threads) owns MP x-pairs (2 MP in-plane voxels), both output planes and 64 couts.  HALF = 0: 64 pairs, a wave
-// owns 32 x-pairs x 32 couts with all four q (3 x 4 accumulators; waves 0/1 and 2/3 are the two pair tiles, wave & 1 the cout
-// half).  HALF = 1 (small launches, which do not fill the chip: the time is a wave's own work): 32 pairs, and the four waves
-// split a 32-pair x 32-cout tile by q -- waves 0/1 accumulate A0, A1, waves 2/3 A2, A3 (3 x 2 accumulators, half the MFMAs per
-// wave); after the K loop the q halves swap the one tile per product the other needs through LDS (A1 one way, A2 the other),
-// then waves 0/1 finish the even columns and waves 2/3 the odd ones.  Every output sees one order of sums in both -- cin
-// block, product, ky, k inside an accumulator, then the fixed output transform -- so the two tiles give identical bits.
-// LDS: per product four q-planes of XP = NPB x HR x TW/2 pair positions (no x halo: the transform consumed it), each two k-half
-// arrays [2][XP][4] (tm_conv_frag.h; the weights of a tap likewise [2][64 couts][4]), fragment addresses contiguous in the pair
-// index: a wave's 32 positions are consecutive rows, so every 16-lane group of a fragment read meets sixteen different slots;
-// weights are a ring of two PRODUCT slots (12 taps x 512 floats, the (ky, q) of one
-// product) filled by LDS-DMA as in conv3d_zpair_ups: product n = 3 cb + p reads slot n & 1, the pieces of product n + 1 go out
-// behind its first taps into the slot every wave left at the barrier in front of product n, and a wave retires its own with the
-// vmcnt(0) in front of the next product's barrier.  A cin block costs four barriers:
-//   vmcnt(0) | B0 | T(cb) -> LDS | B1 | P1, X(cb + 1) -> registers | vmcnt(0) | B2 | P2 | vmcnt(0) | B3 | P3
-// HALF = 0: 2 x 24 576 B + 3 x 4 x 80 x 32 B = 79 872 B: two workgroups per CU.
-template <int HALF, int TW>
-struct XPGeo {
-  static constexpr int TW_ = TW;
-  static constexpr int NW = 4;                                   // waves per workgroup
-  static constexpr int NQ = HALF ? 2 : 4;                        // transform positions q a wave accumulates
-  static constexpr int MP = HALF ? 32 : 64;                      // x-pairs per workgroup
-  static constexpr int PWD = TW / 2;                             // pairs per tile row
-  static constexpr int TR = (MP / PWD < TW) ? (MP / PWD) : TW;   // tile rows
-  static constexpr int NPB = MP / (TR * PWD);                    // patches per workgroup
-  static constexpr int HR = TR + 2;
-  static constexpr int XP = NPB * HR * PWD;                      // pair positions of one q-plane (y halo only)
-  static constexpr int XITEMS = XP * 2;                          // staging items: (position, half block), one per thread
-  static_assert(XP % 8 == 0, "whole groups of eight staging items (tm_conv_frag.h)");
-  static constexpr int WSLOT = 12 * 512;                         // floats of one product of a (cout tile, cin block)
-  static constexpr int KP = 24 / NW;                             // LDS-DMA pieces (256 floats) of a slot per wave
-  static constexpr int LDS_BYTES = (2 * WSLOT + 12 * XP * 8) * 4;
-};
-// The constant part of conv3d_xpair's X fragment address (floats): row ky of q-plane (p, q).  Shared with tm_conv_frag_addrs.
-template <class G>
-TM_HD constexpr int xp_xtap(int p, int q, int ky) { return (p * 4 + q) * G::XP * 8 + conv_frag_off(ky * G::PWD, 0, G::XP); }
-
-template <int HALF, int TW>
-__global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
-  using G = XPGeo<HALF, TW>;
-  static_assert(G::XITEMS <= 64 * G::NW, "one staging item per thread");
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* lw = lds;                                               // [2][12][2 k-halves][64][4]: the LDS-DMA destinations stay below 64 KiB
-  // the X planes [3 products][4 q][2 k-halves][XP][4] follow at float 2 * WSLOT, up to byte 79 872 (addressed through xw / xb below)
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wv = tid >> 6;
-  const int i32 = lane & 31, h = lane >> 5;
-
-  const int S = a.S;
-  const ConvTile t = conv_tile_of<TW, G::TR, false, false>(a);
-  const int nt = t.nt, pg = t.pg, tr = t.tr, tc = t.tc;
-
-  // ---- staging descriptor: this thread's (row, x-pair, half block); xoff addresses column 2j of plane 0 ----
-  long xoff = -1;
-  bool okl = false, okr = false;                                 // columns 2j - 1 and 2j + 2 lie inside the plane
-  if (tid < G::XITEMS) {
-    const int half = conv_stage_half(tid);
-    int v = conv_stage_row(tid);
-    const int j = v % G::PWD; v /= G::PWD;
-    const int hr = v % G::HR;
-    const int ps = v / G::HR;
-    const int n = pg * G::NPB + ps;
-    const int y = tr * G::TR + hr - 1, x = tc * TW + 2 * j;
-    if (n < a.N && y >= 0 && y < S) {
-      xoff = (long)n * a.x_nstride + ((long)y * S + x) * 8 + half * 4;
-      okl = x > 0;
-      okr = x + 2 < S;
-    }
-  }
-  const long zplane = (long)S * S * 8;
-  // this item's slot of a q-plane (base hidden as xb's below)
-  int xw = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP);
-  asm volatile("" : "+v"(xw));
-
-  // ---- per-lane fragment addresses ----
-  const int pt = HALF ? 0 : (wv >> 1);                           // 32-pair tile of this wave
-  const int ch = wv & 1;                                         // its 32-cout half
-  const int q0 = HALF ? (wv >> 1) * 2 : 0;                       // its first q
-  int xb, on[1], ooff0;                                          // ooff0: the even column of plane 0 (or -1)
-  {
-    const ConvLane l = conv_lane_of<G::TR, G::PWD, G::HR * G::PWD, G::PWD, G::XP>(pt * 32 + i32, h, 0, 0);
-    // lx's offset is part of the lane's base and hidden from the compiler, so that the (product, q, ky) of a fragment is a
-    // 16-bit ds_read offset of ONE register (folded into the constant it would pass 64 KiB and take a register per plane)
-    // xb counts 16-byte slots: as a float index the hidden base hid the alignment as well, and the compiler split every X
-    // fragment read into two ds_read2_b32 (dword banking: 4-way conflicts on the k-half image, 8-way on [row][8])
-    xb = (2 * G::WSLOT + q0 * G::XP * 8 + l.xb) / 4;
-    asm volatile("" : "+v"(xb));
-    const int n = pg * G::NPB + l.ps;
-    on[0] = n;
-    const int y = tr * G::TR + l.r, x = tc * TW + 2 * l.c;
-    ooff0 = n < a.N ? (y * S + x) * 8 : -1;
-  }
-  const int wb = q0 * 512 + conv_w_off(ch * 32 + i32, 4 * h);
-
-  f32x16 acc[3][G::NQ];
-  clear_acc(acc);
-
-  const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
-  const rsrc_words wrs = weight_rsrc<true>(a.w + (long)nt * a.Cbi * 3 * G::WSLOT, a.Cbi * 3 * G::WSLOT * 4);
-  const int wvo = lane * 16;
-  const int wvu = __builtin_amdgcn_readfirstlane(wv);
-  // piece k (0 .. KP - 1) of this wave of product n: 256 floats at j = NW k + wave of the product's 24
-  // (s_nop 4: the source offset may come straight from the SALU, five wait states ahead of a VMEM read of it)
-  auto issue_piece = [&](int n, int k) __attribute__((always_inline)) {
-    lds_dma_piece<4, 4 * G::KP>(lw_lds, (n & 1) * G::WSLOT, n * G::WSLOT, k, wvu, wvo, wrs);
-  };
-
-  f32x4 xr[2][4];                                                // [plane][column 2j - 1 .. 2j + 2]
-  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-  auto load_x = [&](int cb) {
-    const float* xp = a.x + (long)cb * a.x_plane;
-#pragma unroll
-    for (int z = 0; z < 2; ++z) {
-      const float* b = xp + xoff + z * zplane;
-      xr[z][0] = okl ? *(const f32x4*)(b - 8) : zero4;
-      xr[z][1] = xoff >= 0 ? *(const f32x4*)(b) : zero4;
-      xr[z][2] = xoff >= 0 ? *(const f32x4*)(b + 8) : zero4;
-      xr[z][3] = okr ? *(const f32x4*)(b + 16) : zero4;
-    }
-  };
-  // the four transform planes of one product from its four columns
-  auto put_t = [&](int p, const f32x4& d0, const f32x4& d1, const f32x4& d2, const f32x4& d3) __attribute__((always_inline)) {
-    float* d = lds + xw + p * 4 * G::XP * 8;
-    *(f32x4*)(d) = d0 - d2;
-    *(f32x4*)(d + G::XP * 8) = d1 + d2;
-    *(f32x4*)(d + 2 * G::XP * 8) = d2 - d1;
-    *(f32x4*)(d + 3 * G::XP * 8) = d1 - d3;
-  };
-
-  load_x(0);
-#pragma unroll
-  for (int k = 0; k < G::KP; ++k) issue_piece(0, k);
-  // one cin block; MORE = another block follows (the last block is its own instantiation: no branch around a piece)
-  auto stage = [&](int cb, auto more_c) __attribute__((always_inline)) {
-    constexpr bool more = decltype(more_c)::value;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // X(cb) in registers; this wave's pieces of product 3 cb landed
-    __builtin_amdgcn_s_barrier();                                // B0: every wave is through block cb - 1: lx and the other slot are free
-    asm volatile("" ::: "memory");
-    if (tid < G::XITEMS) {
-      put_t(2, xr[0][0], xr[0][1], xr[0][2], xr[0][3]);         // X0 first: its registers then take X0 + X1 (no temporaries)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) xr[0][c] = xr[0][c] + xr[1][c];
-      put_t(0, xr[0][0], xr[0][1], xr[0][2], xr[0][3]);
-      put_t(1, xr[1][0], xr[1][1], xr[1][2], xr[1][3]);
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                          // lgkmcnt(0) only
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();                                // B1
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (more) load_x(cb + 1);
-
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      const int n = cb * 3 + p;
-      if (p > 0) {                                               // B2, B3: this wave's pieces of product n landed, everybody's are visible
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // behind the barrier, and the slot of product n - 1 is free
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const float* lwc = lw + (n & 1) * G::WSLOT + wb;
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky) {
-#pragma unroll
-        for (int q = 0; q < G::NQ; ++q) {                        // (q counts from the wave's q0: in both bases)
-          const int tap = ky * 4 + q;
-          const f32x4 wf = *(const f32x4*)(lwc + tap * 512);
-          const f32x4 xf = ((const f32x4*)lds)[xb + xp_xtap<G>(p, q, ky) / 4];
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) acc[p][q] = __builtin_amdgcn_mfma_f32_32x32x2f32(wf[kk], xf[kk], acc[p][q], 0, 0, 0);
-          if (ky * G::NQ + q < G::KP && (p < 2 || more)) issue_piece(n + 1, ky * G::NQ + q);   // a piece of product n + 1 behind each of the first six taps
-        }
-      }
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-  for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
-  stage(a.Cbi - 1, std::false_type{});
-  // output transform per product, then the plane sums: one epilogue per (plane, column parity) with that parity's offsets
-  // (in place: tile 0 of a product becomes its even column, tile 1 its odd one, so the other two die before the first store)
-  const int nte = 2 * nt + ch;                                   // conv_epilogue counts cout blocks in units of its own tile
-  if constexpr (HALF) {
-    // the q halves swap through LDS (free behind the barrier: nothing of the K loop is read or in flight any more): waves 0/1
-    // hand A1(p) over and take A2(p), waves 2/3 the reverse; a tile is [16 registers / 4][64 lanes] float4
-    const int qh = __builtin_amdgcn_readfirstlane(wv >> 1);
-    __syncthreads();
-    auto hand_over = [&](const f32x16& t, int p) __attribute__((always_inline)) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f32x4 v = {t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]};
-        *(f32x4*)(lds + ((wv * 3 + p) * 4 + i) * 256 + lane * 4) = v;
-      }
-    };
-    if (qh) {
-#pragma unroll
-      for (int p = 0; p < 3; ++p) hand_over(acc[p][0], p);
-    } else {
-#pragma unroll
-      for (int p = 0; p < 3; ++p) hand_over(acc[p][1], p);
-    }
-    __syncthreads();
-    f32x16 got[3];
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const f32x4 v = *(const f32x4*)(lds + (((wv ^ 2) * 3 + p) * 4 + i) * 256 + lane * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) got[p][4 * i + e] = v[e];
-      }
-    // waves 0/1: even = (A0 + A1) + A2; waves 2/3 (holding A2, A3): odd = (A1 - A2) - A3
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      acc[p][0] = qh ? (got[p] - acc[p][0]) - acc[p][1] : (acc[p][0] + acc[p][1]) + got[p];
-      asm volatile("" : "+v"(acc[p][0]));
-    }
-#pragma unroll
-    for (int z = 0; z < 2; ++z) {
-      f32x16 o[1][1];
-      o[0][0] = acc[0][0] + acc[1 + z][0];
-      asm volatile("" : "+v"(o[0][0]));
-      const int ooff[1] = {ooff0 >= 0 ? ooff0 + (z * S * S + qh) * 8 : -1};
-      __builtin_amdgcn_sched_barrier(0);
-      conv_epilogue<1, 1>(a, o, nte, h, on, ooff, 2 * S);
-    }
-  } else {
-#pragma unroll
-    for (int p = 0; p < 3; ++p) {
-      const f32x16 ev = (acc[p][0] + acc[p][1]) + acc[p][2];
-      acc[p][1] = (acc[p][1] - acc[p][2]) - acc[p][3];
-      acc[p][0] = ev;
-      asm volatile("" : "+v"(acc[p][0]), "+v"(acc[p][1]));       // formed HERE, not sunk into the guarded stores below
-    }
-#pragma unroll
-    for (int z = 0; z < 2; ++z)
-#pragma unroll
-      for (int par = 0; par < 2; ++par) {
-        f32x16 o[1][1];
-        o[0][0] = acc[0][par] + acc[1 + z][par];
-        asm volatile("" : "+v"(o[0][0]));
-        const int ooff[1] = {ooff0 >= 0 ? ooff0 + (z * S * S + par) * 8 : -1};
-        __builtin_amdgcn_sched_barrier(0);
-        conv_epilogue<1, 1>(a, o, nte, h, on, ooff, 2 * S);
-      }
-  }
-}
-
 // ---- x-quad form of the 3x3x3 pad-1 conv at Z == 2 (fp32): the pair form in z composed with Winograd F(4,3) along x ----
 // F(4,3) gives four neighbouring outputs of a 3-tap filter g with six products instead of twelve: with d0..d5 the inputs at
 // columns 4j - 1 .. 4j + 4 (zero outside the plane),
@@ -815,10 +553,11 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
 //   T5 = (4 d1 - 5 d3) + d5           U5 = g2
 //   A_q = sum over cin, ky of U_q[ky] T_q[y + ky - 1][j];  s = A1 + A2, d = A1 - A2, s' = A3 + A4, d' = A3 - A4
 //   out[4j] = (A0 + s) + s'   out[4j + 1] = d + 2 d'   out[4j + 2] = s + 4 s'   out[4j + 3] = (d + 8 d') + A5.
-// As in conv3d_xpair it applies to each of the three z products (V = W1, W2 - W1, W0 - W1 on X0 + X1, X1, X0): 54 tap-products
-// per eight outputs, 6.75 per output against the x-pair's 9.  ORDER OF SUMS of every output, in both tiles: cin block, product,
-// ky, k inside an accumulator A_q(p); then the output transform exactly as written above; then Y(z0) = P(1) + P(2), Y(z1) =
-// P(1) + P(3); then the common epilogue.  So HALF = 0 and 1 give identical bits.
+// The identity is linear in the weights, so it applies to each of the three z products of the pair form (V = W1, W2 - W1, W0 - W1
+// on X0 + X1, X1, X0): per (product, ky) six transform positions per group replace three taps per voxel, 54 tap-products per
+// eight outputs, 6.75 per output against the pair form's 13.5.  A_q(p) is accumulated on the MFMA exactly as a tap is.  ORDER OF
+// SUMS of every output, in both tiles: cin block, product, ky, k inside an accumulator A_q(p); then the output transform exactly
+// as written above; then Y(z0) = P(1) + P(2), Y(z1) = P(1) + P(3); then the epilogue.  So HALF = 0 and 1 give identical bits.
 // A workgroup owns MG four-column groups, both output planes and 32 couts (a 64-cout ring of two product slots would pass the
 // 64 KiB an LDS-DMA destination must stay below).  A wave owns 32 groups x 32 couts and three of the six q (3 products x 3 q = 9
 // accumulators); wave & 1 is the q half, wave >> 1 the group tile.  HALF = 0: 8 waves, 128 groups (1024 output voxels), one
@@ -829,8 +568,17 @@ __global__ __launch_bounds__(256, 2) void conv3d_xpair(ConvArgs a) {
 // past 64 KiB, so a lane keeps one hidden base per product (16-byte slots: every fragment read is one ds_read_b128 with a
 // 16-bit offset).  At TW = 8 a wave's 32 groups span two patches 20 rows apart: the lanes of the first ds_read_b128 group take
 // the first patch, the others the second (conv_lane_voxel's TW = 16 table), so each group reads sixteen consecutive rows.
-// Ring schedule and barriers are conv3d_xpair's: product n = 3 cb + p reads slot n & 1, the pieces of product n + 1 go out behind
-// its first taps, a wave retires its own with the vmcnt(0) in front of the next product's barrier.
+//
+// PIPE = 0, the four-barrier schedule.  The weights are a ring of two PRODUCT slots (the 18 taps (ky, q) of one product of a cin
+// block) filled by LDS-DMA, one tap per piece, the pieces dealt round the waves: product n = 3 cb + p reads slot n & 1, the pieces
+// of product n + 1 go out behind its first taps into the slot every wave left at the barrier in front of product n, and a wave
+// retires its own with the vmcnt(0) in front of the next product's barrier.  The X planes are three sets of six q-planes, one
+// set per product of the block, all transformed and stored in one phase.  A cin block costs four barriers:
+//   vmcnt(0) | B0 | T(cb) -> LDS | B1 | P1, X(cb + 1) -> registers | vmcnt(0) | B2 | P2 | vmcnt(0) | B3 | P3
+// B0: X(cb) is in registers, this wave's pieces of product 3 cb landed, and every wave is through block cb - 1, so the planes and
+// the other slot are free.  B1 (lgkmcnt(0) in front): the planes are visible; the loads of X(cb + 1) go out behind it, under P1.
+// B2, B3: everybody's pieces of the product are visible and the slot of the product before is free.  The last cin block is its
+// own instantiation of the block body: no branch round a piece or a load.
 //
 // PIPE = 1, the pipelined schedule (same pack, tiles, lane maps, accumulators and epilogue): the X planes are a ring of TWO SETS
 // of six q-planes, and no phase is left in which the matrix pipe must idle.  The products of a block run in the order X0, X1,
@@ -1529,9 +1277,8 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
     case CF_ZSKIP: case CF_PAIR:   // 3x3x3 pad 1 over two planes
       if (L.zmode != ZM_PAD1 || !z2) return hipErrorInvalidValue;
       break;
-    case CF_XPAIR: case CF_XQUAD:  // ... with Winograd along x: planes of at least 8 x 8, plain epilogue
-      if (L.zmode != ZM_PAD1 || !z2 || L.x.H < 8 || up2) return hipErrorInvalidValue;
-      if (form == CF_XQUAD && L.gate) return hipErrorInvalidValue;   // its own epilogue: bias, GELU flag and residual, no gate
+    case CF_XQUAD:                 // ... with Winograd along x: planes of at least 8 x 8; its own epilogue (bias, GELU flag
+      if (L.zmode != ZM_PAD1 || !z2 || L.x.H < 8 || up2 || L.gate) return hipErrorInvalidValue;   // and residual): no gate
       break;
     case CF_ZSKIP_UPS: case CF_PAIR_UPS:   // 3x3x3 pad 1 of the nearest-x2 upsampled x, on the low-resolution x
       if (L.zmode != ZM_UPS || !z2 || up2 || L.res || L.gate) return hipErrorInvalidValue;
@@ -1569,7 +1316,7 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
         return large ? launch_tiled<conv3d_zpair_ups<0, TW>, ZPUGeo<0, TW>>(a, 4, s)
                      : launch_tiled<conv3d_zpair_ups<1, TW>, ZPUGeo<1, TW>>(a, 4, s);
       });
-    case CF_XQUAD:
+    default:   // CF_XQUAD
       a.ntile = (L.w.Cout + 31) / 32;                          // the kernel's cout tiles are of 32 (the pack holds 2 * ntile of them)
       if (L.xquad_sched < -1 || L.xquad_sched > 1) return hipErrorInvalidValue;
       return with_tile_width<16>(S, [&](auto tw) {
@@ -1580,21 +1327,15 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
         return large ? launch_tiled<conv3d_xquad<0, TW, 0>, XQGeo<0, TW, 0>, 64 * XQGeo<0, TW, 0>::NW>(a, 1, s)
                      : launch_tiled<conv3d_xquad<1, TW, 0>, XQGeo<1, TW, 0>, 64 * XQGeo<1, TW, 0>::NW>(a, 1, s);
       });
-    default:   // CF_XPAIR
-      return with_tile_width<16>(S, [&](auto tw) {
-        constexpr int TW = decltype(tw)::value;
-        return large ? launch_tiled<conv3d_xpair<0, TW>, XPGeo<0, TW>, 64 * XPGeo<0, TW>::NW>(a, 1, s)
-                     : launch_tiled<conv3d_xpair<1, TW>, XPGeo<1, TW>, 64 * XPGeo<1, TW>::NW>(a, 1, s);
-      });
   }
 }
 
 // ---- the lane -> LDS address maps of the three LDS-DMA conv kernels, evaluated on the host (no device call) ----
-// The same functions the kernels address with (tm_conv_frag.h, conv_lane_of, zp_wtap / zp_xtap / xp_xtap), composed as the
+// The same functions the kernels address with (tm_conv_frag.h, conv_lane_of, zp_wtap / zp_xtap / xq_xtap), composed as the
 // kernels compose them: out[lane] = byte address inside the workgroup's dynamic LDS of what lane `lane` of wave wv reads or
 // stores, -1 for a lane that stores nothing.  what 0: the weight fragment of tap (p, ky, kx) and 32-cout sub-tile `sub` (slot 0
 // of a ring); 1: the X fragment of (p, ky, kx), `sub` = the output phase 2 py + px of the upsampled form; 2: the staging store
-// into plane p of the thread's item ky (its k-th of PX).  conv3d_xpair: kx is the wave's q (0 .. NQ - 1), in what 2 the q-plane.
+// into plane p of the thread's item ky (its k-th of PX).
 template <class G, int HALF, int TW, bool UPS>
 static int zpair_frag_addrs(int what, int wv, int p, int ky, int kx, int sub, int* out) {
   constexpr int NC = HALF ? 1 : 2, KW = UPS ? 2 : 3;
@@ -1617,23 +1358,7 @@ static int zpair_frag_addrs(int what, int wv, int p, int ky, int kx, int sub, in
   }
   return 0;
 }
-template <int HALF, int TW>
-static int xpair_frag_addrs(int what, int wv, int p, int ky, int q, int* out) {
-  using G = XPGeo<HALF, TW>;
-  if (p < 0 || p > 2 || q < 0 || q >= (what == 2 ? 4 : G::NQ) || ky < 0 || ky > (what == 2 ? 0 : 2)) return -1;
-  const int pt = HALF ? 0 : (wv >> 1), ch = wv & 1, q0 = HALF ? (wv >> 1) * 2 : 0;
-  for (int lane = 0; lane < 64; ++lane) {
-    const int i32 = lane & 31, h = lane >> 5, tid = wv * 64 + lane;
-    int a = -1;
-    if (what == 0) a = q0 * 512 + conv_w_off(ch * 32 + i32, 4 * h) + (ky * 4 + q) * 512;
-    else if (what == 1)
-      a = 2 * G::WSLOT + q0 * G::XP * 8 + conv_lane_of<G::TR, G::PWD, G::HR * G::PWD, G::PWD, G::XP>(pt * 32 + i32, h, 0, 0).xb + xp_xtap<G>(p, q, ky);
-    else if (tid < G::XITEMS)
-      a = 2 * G::WSLOT + conv_frag_off(conv_stage_row(tid), conv_stage_half(tid), G::XP) + (p * 4 + q) * G::XP * 8;
-    out[lane] = a < 0 ? -1 : a * 4;
-  }
-  return 0;
-}
+// conv3d_xquad: kx is the wave's q (0 .. 2), in what 2 the q-plane (0 .. 5), ky 0.
 // set: the plane set of an X fragment or a staging store: the product's own in the four-barrier schedule, the ring's set (0 | 1)
 // in the pipelined one
 template <int HALF, int TW, int PIPE>
@@ -1662,7 +1387,7 @@ int conv_xquad_lds_bytes(int half, int tw, int sched) {
 }
 int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int ky, int kx, int sub, int* out) {
   const bool xq = kernel == 4 || kernel == 5;
-  if (!out || kernel < 0 || kernel > 5 || kernel == 3 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > (xq ? 7 : 3)) return -1;
+  if (!out || kernel < 0 || kernel > 5 || kernel == 2 || kernel == 3 || half < 0 || half > 1 || what < 0 || what > 2 || wv < 0 || wv > (xq ? 7 : 3)) return -1;
   if (kernel == 4 && tw == 8) return half ? xquad_frag_addrs<1, 8, 0>(what, wv, p, ky, kx, p, out) : xquad_frag_addrs<0, 8, 0>(what, wv, p, ky, kx, p, out);
   if (kernel == 4 && tw == 16) return half ? xquad_frag_addrs<1, 16, 0>(what, wv, p, ky, kx, p, out) : xquad_frag_addrs<0, 16, 0>(what, wv, p, ky, kx, p, out);
   // the pipelined schedule: sub = the plane set (0 for a weight fragment: slot 0 of the ring)
@@ -1677,8 +1402,6 @@ int conv_frag_addrs(int kernel, int half, int tw, int what, int wv, int p, int k
   }
   TM_FRAG(1, 4) TM_FRAG(0, 8) TM_FRAG(1, 8) TM_FRAG(0, 16) TM_FRAG(1, 16) TM_FRAG(0, 32) TM_FRAG(1, 32)
 #undef TM_FRAG
-  if (kernel == 2 && tw == 8) return half ? xpair_frag_addrs<1, 8>(what, wv, p, ky, kx, out) : xpair_frag_addrs<0, 8>(what, wv, p, ky, kx, out);
-  if (kernel == 2 && tw == 16) return half ? xpair_frag_addrs<1, 16>(what, wv, p, ky, kx, out) : xpair_frag_addrs<0, 16>(what, wv, p, ky, kx, out);
   return -1;                                                     // no such instantiation
 }
 

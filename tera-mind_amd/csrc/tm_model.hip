@@ -114,8 +114,7 @@ struct tm_model {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   size_t prof_used = 0;
   double prof_nominal = 0, prof_bytes = 0;
-  double prof_xp_flops = 0;              // the part of prof_nominal launched in the x-pair form (18 of the nominal 54 tap-products)
-  double prof_xq_flops = 0;              // ... and in the x-quad form (13.5 of the nominal 54)
+  double prof_xq_flops = 0;              // the part of prof_nominal launched in the x-quad form (13.5 of the nominal 54 taps)
   struct ProfTag { int cin, cout, S, N; double nominal; };
   std::vector<ProfTag> prof_tag;     // per counted launch (TM_PROF_LAYERS)
 };
@@ -640,14 +639,14 @@ extern "C" int tm_profile_collect(tm_model* m, tm_prof_stats* out) {
   // Z == 2: the pair form issues 27 taps per plane PAIR (27 of the nominal 54), the z-skip form 18 of 27 per plane; Z == 1: the
   // centre slice only (9); Z >= 3: all 27 (zero planes staged)
   // (the 16-bit conv never stages z-padding planes: (3Z - 2) / 3Z of the taps for any Z)
-  // per layer: a launch in the x-pair form issues 36 tap-products per FOUR outputs, 18 of the nominal 54
-  out->executed_flops = (m->prof_nominal - m->prof_xp_flops - m->prof_xq_flops) *
+  // per layer: a launch in the x-quad form issues 54 tap-products per EIGHT outputs, 13.5 of the nominal 54
+  out->executed_flops = (m->prof_nominal - m->prof_xq_flops) *
                             (is_h16(m->cfg.dtype) ? (3.0 * m->z - 2.0) / (3.0 * m->z)
                                                   : (m->z == 2 ? (conv_pick_form(3, ZM_PAD1, 2, false, ROLE_RES) == CF_PAIR ? 27.0 / 54.0 : 18.0 / 27.0)
                                                                : (m->z == 1 ? 9.0 / 27.0 : 1.0))) +
-                        m->prof_xp_flops * (18.0 / 54.0) + m->prof_xq_flops * (13.5 / 54.0);
+                        m->prof_xq_flops * (13.5 / 54.0);
   out->alg_bytes = m->prof_bytes;
-  m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0; m->prof_xp_flops = 0; m->prof_xq_flops = 0;
+  m->prof_used = 0; m->prof_nominal = 0; m->prof_bytes = 0; m->prof_xq_flops = 0;
   return TM_OK;
 }
 
@@ -779,7 +778,7 @@ static void fuse_mid_section(Launch& L, const Ctx& cx, const ResW& w, int per_im
 }
 
 // What one counted 3x3x3 launch adds to the books of tm_profile_collect
-struct ConvBook { int cin, cout, S, N; double vox, bytes; bool xpair; bool xquad = false; };
+struct ConvBook { int cin, cout, S, N; double vox, bytes; bool xquad; };
 // The profiling bracket of the 3x3x3 launchers: ensure an event pair, record, launch, record, book.  book == nullptr or
 // profiling off: the launch alone.
 template <class LaunchFn>
@@ -802,7 +801,6 @@ static void launch_booked(Ctx& cx, const ConvBook* book, LaunchFn launch) {
   m->prof_used++;
   const double nominal = 2.0 * book->cin * book->cout * 27.0 * book->vox;
   m->prof_nominal += nominal;
-  if (book->xpair) m->prof_xp_flops += nominal;
   if (book->xquad) m->prof_xq_flops += nominal;
   m->prof_tag.push_back({book->cin, book->cout, book->S, book->N, nominal});
   m->prof_bytes += book->bytes;
@@ -814,7 +812,7 @@ static void run_conv(Ctx& cx, const ConvLaunch& L, int count_cin = 0) {
   if (cx.dry) return;
   const double vox = (double)L.x.N * L.x.Z * L.x.H * L.x.W;
   const ConvBook book = {count_cin, L.w.Cout, L.x.H, L.x.N, vox,
-                         4.0 * (vox * L.x.Cb * 8 + (double)L.w.ntile * L.w.Cbi * L.w.taps * 512 + vox * L.y.Cb * 8), L.w.form == CF_XPAIR, L.w.form == CF_XQUAD};
+                         4.0 * (vox * L.x.Cb * 8 + (double)L.w.ntile * L.w.Cbi * L.w.taps * 512 + vox * L.y.Cb * 8), L.w.form == CF_XQUAD};
   launch_booked(cx, count_cin ? &book : nullptr, [&] { return launch_conv_mfma(L, cx.s); });
 }
 // 16-bit 3x3x3 conv; cw: the ConvW behind L.w (pack size).  count_cin as above (0: the in-plane pyramid convs, 9 real taps, and

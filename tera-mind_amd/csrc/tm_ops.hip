@@ -268,47 +268,26 @@ extern "C" int tm_op_conv_ups_pair_f32(const void* x_cb8, const void* w_host, co
   return finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_ups_pair (fp32)");
 }
 
-// The x-pair form of the fp32 3x3x3 pad-1 conv at Z == 2 (conv3d_xpair), alone.  Returns the tile it launched (1 = the 64-voxel
-// tile, 2 = the 128-voxel one) or a negative error; what the kernel does not take is refused here, before any device call.
-static int xpair_args(const void* x, const void* w, const void* b, const void* y, int N, int Cin, int Cout, int Z, int S,
-                      int tile_variant) {
+// What the two forms of the fp32 3x3x3 pad-1 conv at Z == 2 with a hook of their own take (form: CF_PAIR | CF_XQUAD); what the
+// kernels do not take is refused here, before any device call.
+static int pad1_z2_args(int form, const void* x, const void* w, const void* b, const void* y, int N, int Cin, int Cout, int Z, int S,
+                        int tile_variant) {
+  const bool xq = form == CF_XQUAD;
   if (!x || !w || !b || !y) return fail(TM_ERR_ARG, "null argument");
   if (N < 1 || Cin < 1 || Cout < 1) return fail(TM_ERR_ARG, "N, Cin, Cout must be positive");
-  if (Z != 2) return fail(TM_ERR_ARG, "the x-pair form exists at Z == 2 only (got Z = %d)", Z);
+  if (Z != 2) return fail(TM_ERR_ARG, "the %s form exists at Z == 2 only (got Z = %d)", xq ? "x-quad" : "pair", Z);
   if (S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return fail(TM_ERR_ARG, "S must be 8, 16, 32, 64 or 128 (got %d)", S);
   if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
-  if (conv_pick_form(3, ZM_PAD1, 2, true, ROLE_OP_XPAIR) != CF_XPAIR)
-    return fail(TM_ERR_ARG, "the x-pair form is switched off (TM_CONV_XPAIR=0)");
+  if (conv_pick_form(3, ZM_PAD1, 2, true, xq ? ROLE_OP_XQUAD : ROLE_OP) != form)
+    return fail(TM_ERR_ARG, "the %s form is switched off (%s=0)", xq ? "x-quad" : "pair", xq ? "TM_CONV_XQUAD" : "TM_CONV_ZPAIR");
   return TM_OK;
-}
-extern "C" int tm_op_conv_xpair_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
-                                    int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream) {
-  if (const int rc = xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
-  if (res_half && !res_cb8) return fail(TM_ERR_ARG, "res_half needs a residual");
-  ConvOp op;
-  if (const int rc = conv_op(op, CF_XPAIR, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, Z, S, Z, S, ZM_PAD1, tile_variant, res_cb8,
-                             res_half))
-    return rc;
-  const int rc = finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_xpair (fp32)");
-  return rc ? rc : conv_tile(CF_XPAIR, (long)N * Z * S * S, op.L.w.ntile, S, tile_variant);
 }
 
-// The x-quad form (conv3d_xquad, Winograd F(4,3) along x), alone, with the arguments of tm_op_conv_xpair_f32.  Returns the tile it
-// launched (1 = 64 four-column groups per workgroup, 2 = 128) or a negative error; refusals come before any device call.
-static int xquad_args(const void* x, const void* w, const void* b, const void* y, int N, int Cin, int Cout, int Z, int S,
-                      int tile_variant) {
-  if (!x || !w || !b || !y) return fail(TM_ERR_ARG, "null argument");
-  if (N < 1 || Cin < 1 || Cout < 1) return fail(TM_ERR_ARG, "N, Cin, Cout must be positive");
-  if (Z != 2) return fail(TM_ERR_ARG, "the x-quad form exists at Z == 2 only (got Z = %d)", Z);
-  if (S != 8 && S != 16 && S != 32 && S != 64 && S != 128) return fail(TM_ERR_ARG, "S must be 8, 16, 32, 64 or 128 (got %d)", S);
-  if (tile_variant < 0 || tile_variant > 2) return fail(TM_ERR_ARG, "tile_variant must be 0 (auto), 1 or 2 (got %d)", tile_variant);
-  if (conv_pick_form(3, ZM_PAD1, 2, true, ROLE_OP_XQUAD) != CF_XQUAD)
-    return fail(TM_ERR_ARG, "the x-quad form is switched off (TM_CONV_XQUAD=0)");
-  return TM_OK;
-}
+// The x-quad form (conv3d_xquad, Winograd F(4,3) along x), alone.  Returns the tile it launched (1 = 64 four-column groups per
+// workgroup, 2 = 128) or a negative error.
 static int xquad_op(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8, int res_half, int N,
                     int Cin, int Cout, int Z, int S, int tile_variant, int sched, void* stream) {
-  if (const int rc = xquad_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
+  if (const int rc = pad1_z2_args(CF_XQUAD, x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
   if (res_half && !res_cb8) return fail(TM_ERR_ARG, "res_half needs a residual");
   ConvOp op;
   if (const int rc = conv_op(op, CF_XQUAD, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, Z, S, Z, S, ZM_PAD1, tile_variant, res_cb8,
@@ -329,18 +308,16 @@ extern "C" int tm_op_conv_xquad_sched_f32(const void* x_cb8, const void* w_host,
   return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, sched, stream);
 }
 
-// Timing hook (tools/bench_conv_xpair.py): the 3x3x3 pad-1 conv at Z == 2 packed once for `form` (0 = the pair form, 1 = the
-// x-pair form, 2 = the x-quad form), then `iters` launches, each between two events of its own; ms_out[i] (host) = the time of
+// Timing hook (tools/bench_conv_xquad.py): the 3x3x3 pad-1 conv at Z == 2 packed once for `form` (0 = the pair form, 2 = the
+// x-quad form; 1 is no form any more), then `iters` launches, each between two events of its own; ms_out[i] (host) = the time of
 // launch i.  sched: the schedule of conv3d_xquad (form 2 only): -1 = the launcher's choice, 0 | 1 forced.
-static int pad1_time(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin, int Cout, int S, int form,
-                     int tile_variant, int sched, int iters, float* ms_out, void* stream) {
-  if (const int rc = form == 2 ? xquad_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant)
-                               : xpair_args(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant))
-    return rc;
-  if (form < 0 || form > 2 || iters < 1 || !ms_out) return fail(TM_ERR_ARG, "form must be 0, 1 or 2, iters >= 1, ms_out non-null");
+extern "C" int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                              int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out,
+                                              void* stream) {
+  const int cf = form == 2 ? CF_XQUAD : CF_PAIR;
+  if (const int rc = pad1_z2_args(cf, x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant)) return rc;
+  if ((form != 0 && form != 2) || iters < 1 || !ms_out) return fail(TM_ERR_ARG, "form must be 0 or 2, iters >= 1, ms_out non-null");
   if (sched < -1 || sched > 1 || (sched >= 0 && form != 2)) return fail(TM_ERR_ARG, "sched must be -1, or 0 | 1 with form 2 (got %d)", sched);
-  const int cf = conv_pick_form(3, ZM_PAD1, 2, true, form == 2 ? ROLE_OP_XQUAD : form ? ROLE_OP_XPAIR : ROLE_OP);
-  if (!form && cf != CF_PAIR) return fail(TM_ERR_ARG, "the pair form is switched off (TM_CONV_ZPAIR=0)");
   ConvOp op;
   if (const int rc = conv_op(op, cf, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, 2, S, 2, S, ZM_PAD1, tile_variant)) return rc;
   op.L.xquad_sched = sched;
@@ -355,15 +332,6 @@ static int pad1_time(const void* x_cb8, const void* w_host, const void* bias_hos
     HIP_TRY(hipEventElapsedTime(ms_out + i, e0, e1));
   }
   return finish(st, hipSuccess, "conv_pad1_time (fp32)");
-}
-extern "C" int tm_op_conv_pad1_time_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                                        int Cout, int S, int form, int tile_variant, int iters, float* ms_out, void* stream) {
-  return pad1_time(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, form, tile_variant, -1, iters, ms_out, stream);
-}
-extern "C" int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                                              int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out,
-                                              void* stream) {
-  return pad1_time(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, form, tile_variant, sched, iters, ms_out, stream);
 }
 
 // power of two >= 2: what a half-resolution gate needs of S (read at (z, y >> 1, x >> 1))

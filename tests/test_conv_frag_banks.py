@@ -1,6 +1,6 @@
-"""No GPU: the LDS bank rule applied to every fragment read and staging store of the three fp32 LDS-DMA conv kernels
-(conv3d_zpair, conv3d_zpair_ups, conv3d_xpair), on the byte addresses the library computes with the kernels' own address functions
-(tm_conv_frag_addrs, tm_conv_frag.h).
+"""No GPU: the LDS bank rule applied to every fragment read and staging store of the two fp32 z-pair LDS-DMA conv kernels
+(conv3d_zpair, conv3d_zpair_ups; conv3d_xquad has tests/test_xquad_host.py), on the byte addresses the library computes with the
+kernels' own address functions (tm_conv_frag_addrs, tm_conv_frag.h).
 
 The rule (MI355X LDS): `ds_read_b128` is served in four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the
 same of lanes 32-63, bank = (a / 4) mod 64; a group takes one LDS cycle plus one for every further distinct address on a busy
@@ -20,10 +20,9 @@ from teramind_amd import _lib
 READ_GROUPS = [[*range(0, 4), *range(12, 16), *range(20, 28)], [*range(4, 12), *range(16, 20), *range(28, 32)]]
 READ_GROUPS += [[l + 32 for l in g] for g in READ_GROUPS[:2]]
 WRITE_GROUPS = [list(range(8 * g, 8 * g + 8)) for g in range(8)]
-ZPAIR, UPS, XPAIR = 0, 1, 2
+ZPAIR, UPS = 0, 1
 # (kernel, half, tw): every instantiation the launcher takes
 INST = [(k, h, tw) for k in (ZPAIR, UPS) for h, tw in ((1, 4), (0, 8), (1, 8), (0, 16), (1, 16), (0, 32), (1, 32))]
-INST += [(XPAIR, h, tw) for h in (0, 1) for tw in (8, 16)]
 
 
 def cycles(addrs, groups, banks):
@@ -58,29 +57,16 @@ def zp_geo(half, tw, new=False):
     return dict(tr=tr, npb=npb, hr=hr, hc=hc, xv=npb * (40 if (new and tw == 4) else hr * hc))
 
 
-def xp_geo(half, tw):
-    mp = 32 if half else 64
-    pwd = tw // 2
-    tr = min(mp // pwd, tw)
-    npb = mp // (tr * pwd)
-    return dict(tr=tr, npb=npb, hr=tr + 2, pwd=pwd, xp=npb * (tr + 2) * pwd, nq=2 if half else 4)
-
-
 def fragments(kernel, half):
     """every (what, p, ky, kx, sub) of the K loop"""
     kw = 2 if kernel == UPS else 3
     for p in range(3):
         for ky in range(kw):
-            if kernel == XPAIR:
-                for q in range(2 if half else 4):
-                    yield 0, p, ky, q, 0
-                    yield 1, p, ky, q, 0
-            else:
-                for kx in range(kw):
-                    for ct in range(1 if half else 2):
-                        yield 0, p, ky, kx, ct
-                    for ph in range(4 if kernel == UPS else 1):
-                        yield 1, p, ky, kx, ph
+            for kx in range(kw):
+                for ct in range(1 if half else 2):
+                    yield 0, p, ky, kx, ct
+                for ph in range(4 if kernel == UPS else 1):
+                    yield 1, p, ky, kx, ph
 
 
 # ---- the previous maps: operand images of [row][8 floats], a lane reads float row * 8 + 4 h ----
@@ -88,27 +74,16 @@ def old_addrs(kernel, half, tw, what, wave, p, ky, kx, sub):
     out = []
     for lane in range(64):
         i32, h = lane & 31, lane >> 5
-        if kernel == XPAIR:
-            g = xp_geo(half, tw)
-            pt, ch, q0 = (0 if half else wave >> 1), wave & 1, ((wave >> 1) * 2 if half else 0)
-            if what == 0:
-                a = q0 * 512 + ch * 256 + i32 * 8 + 4 * h + (ky * 4 + kx) * 512
-            else:
-                v = pt * 32 + i32
-                ps, rem = divmod(v, g["tr"] * g["pwd"])
-                r, c = divmod(rem, g["pwd"])
-                a = 2 * 12 * 512 + q0 * g["xp"] * 8 + ((ps * g["hr"] + r) * g["pwd"] + c) * 8 + 4 * h + ((p * 4 + kx) * g["xp"] + ky * g["pwd"]) * 8
+        g = zp_geo(half, tw)
+        vt, ct0 = (wave & 1, wave >> 1) if half else (wave, 0)
+        if what == 0:
+            tap = p * 4 + ky * 2 + kx if kernel == UPS else p * 9 + ky * 3 + kx
+            a = tap * 512 + sub * 256 + ct0 * 256 + i32 * 8 + 4 * h
         else:
-            g = zp_geo(half, tw)
-            vt, ct0 = (wave & 1, wave >> 1) if half else (wave, 0)
-            if what == 0:
-                tap = p * 4 + ky * 2 + kx if kernel == UPS else p * 9 + ky * 3 + kx
-                a = tap * 512 + sub * 256 + ct0 * 256 + i32 * 8 + 4 * h
-            else:
-                v = vt * 32 + i32
-                ps, rem = divmod(v, g["tr"] * tw)
-                r, c = divmod(rem, tw)
-                a = p * g["xv"] * 8 + (ky * g["hc"] + kx) * 8 + ((ps * g["hr"] + r + (sub >> 1)) * g["hc"] + c + (sub & 1)) * 8 + 4 * h
+            v = vt * 32 + i32
+            ps, rem = divmod(v, g["tr"] * tw)
+            r, c = divmod(rem, tw)
+            a = p * g["xv"] * 8 + (ky * g["hc"] + kx) * 8 + ((ps * g["hr"] + r + (sub >> 1)) * g["hc"] + c + (sub & 1)) * 8 + 4 * h
         out.append(a * 4)
     return out
 
@@ -123,20 +98,16 @@ def test_fragment_reads_are_conflict_free(kernel, half, tw):
             cyc = cycles(a, READ_GROUPS, 64)
             assert cyc == 4, (wave, what, p, ky, kx, sub, cyc)
             n += 1
-    per_wave = {ZPAIR: 27 * (1 if half else 2) + 27, UPS: 12 * (1 if half else 2) + 48, XPAIR: 2 * 9 * (2 if half else 4)}[kernel]
+    per_wave = {ZPAIR: 27 * (1 if half else 2) + 27, UPS: 12 * (1 if half else 2) + 48}[kernel]
     assert n == 4 * per_wave
 
 
 @pytest.mark.parametrize("kernel,half,tw", INST)
 def test_fragments_stay_inside_their_areas(kernel, half, tw):
     """weights inside the ring (LDS-DMA destinations below 64 KiB), activations inside the X planes, both 16-byte aligned"""
-    if kernel == XPAIR:
-        g = xp_geo(half, tw)
-        w_end, x_end = 2 * 12 * 512 * 4, (2 * 12 * 512 + 12 * g["xp"] * 8) * 4
-    else:
-        g = zp_geo(half, tw, new=True)
-        w_end = (2 * 12 * 512 if kernel == UPS else 27 * 512) * 4
-        x_end = w_end + 3 * g["xv"] * 8 * 4
+    g = zp_geo(half, tw, new=True)
+    w_end = (2 * 12 * 512 if kernel == UPS else 27 * 512) * 4
+    x_end = w_end + 3 * g["xv"] * 8 * 4
     assert w_end <= 65536 and x_end <= 81920                     # two workgroups per CU
     for wave in range(4):
         for what, p, ky, kx, sub in fragments(kernel, half):
@@ -149,15 +120,12 @@ def test_fragments_stay_inside_their_areas(kernel, half, tw):
 def test_staging_stores(kernel, half, tw):
     """conflict-free (eight cycles per full wave instruction, as the interleaved image's stores were), every slot a fragment
     read touches written exactly once per plane, and no more store instructions per thread than before"""
-    if kernel == XPAIR:
-        planes, items_old = [(p, q) for p in range(3) for q in range(4)], 1
-    else:
-        planes, items_old = [(p, 0) for p in range(3)], (2 * zp_geo(half, tw)["xv"] + 255) // 256
-    for p, q in planes:
+    items_old = (2 * zp_geo(half, tw)["xv"] + 255) // 256
+    for p in range(3):
         written = []
         k = 0
         while True:
-            per_wave = [addrs_of(kernel, half, tw, 2, wave, p, k, q, 0) for wave in range(4)]
+            per_wave = [addrs_of(kernel, half, tw, 2, wave, p, k, 0, 0) for wave in range(4)]
             if per_wave[0] is None:
                 break
             for a in per_wave:
@@ -167,28 +135,26 @@ def test_staging_stores(kernel, half, tw):
             k += 1
         assert k == items_old
         assert len(written) == len(set(written))
-        if p == 0 and q == 0:
+        if p == 0:
             first = written
-    # the reads of plane (0, 0) fall on written slots (pad columns of the pitch and rows nobody reads excepted: never read)
+    # the reads of plane 0 fall on written slots (pad columns of the pitch and rows nobody reads excepted: never read)
     ws = set(first)
     for wave in range(4):
         for what, p, ky, kx, sub in fragments(kernel, half):
-            if what == 1 and p == 0 and (kernel != XPAIR or kx == 0):
+            if what == 1 and p == 0:
                 a = addrs_of(kernel, half, tw, 1, wave, p, ky, kx, sub)
-                q0 = (wave >> 1) * 2 if (kernel == XPAIR and half) else 0
-                if q0 == 0:
-                    assert set(a) <= ws, (wave, ky, kx, sub)
+                assert set(a) <= ws, (wave, ky, kx, sub)
 
 
 def test_previous_maps_show_their_conflicts():
-    """[row][8] images: every weight read is 2-way conflicted in all four groups (8 cycles); the x-pair's consecutive rows
-    likewise; the halo rows of the z-pair kernels collide wherever a group's rows repeat mod 8: 2-way or worse."""
+    """[row][8] images: every weight read is 2-way conflicted in all four groups (8 cycles); the halo rows of the z-pair kernels
+    collide wherever a group's rows repeat mod 8: 2-way or worse."""
     seen_x = {}
     for kernel, half, tw in INST:
         for wave in range(4):
             for what, p, ky, kx, sub in fragments(kernel, half):
                 cyc = cycles(old_addrs(kernel, half, tw, what, wave, p, ky, kx, sub), READ_GROUPS, 64)
-                if what == 0 or kernel == XPAIR:
+                if what == 0:
                     assert cyc == 8, (kernel, half, tw, wave, what, cyc)
                 else:
                     seen_x.setdefault((kernel, tw), set()).add(cyc)
@@ -214,7 +180,8 @@ def test_refusals():
     f = _lib.lib().tm_conv_frag_addrs
     assert f(3, 0, 8, 0, 0, 0, 0, 0, 0, out) == -1               # kernel
     assert f(0, 0, 4, 0, 0, 0, 0, 0, 0, out) == -1               # the 4-wide tile has no 128-voxel form
-    assert f(2, 0, 32, 0, 0, 0, 0, 0, 0, out) == -1              # the x-pair stops at 16-wide tiles
+    assert f(2, 0, 8, 0, 0, 0, 0, 0, 0, out) == -1               # kernel 2 is no kernel any more
+    assert f(2, 0, 16, 0, 0, 0, 0, 0, 0, out) == -1
     assert f(0, 1, 8, 0, 0, 0, 0, 0, 1, out) == -1               # the small tile has one cout sub-tile per wave
     assert f(0, 0, 8, 1, 0, 3, 0, 0, 0, out) == -1               # product
     assert f(1, 0, 8, 1, 0, 0, 2, 0, 0, out) == -1               # 2 x 2 window

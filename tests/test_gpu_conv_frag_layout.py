@@ -1,8 +1,8 @@
-"""-m gpu: the three fp32 LDS-DMA conv kernels on their k-half operand images (tm_conv_frag.h) -- conv3d_zpair (plain and with the
-fused mid-section), conv3d_zpair_ups and conv3d_xpair through their single-op hooks, at the smallest shapes that reach every
-lane -> address map: S = 8, 16, 32 (one per tile width; the x-pair's widest tile is 16), N = 1 and 3 (3 leaves a partial
-workgroup at S = 8), Cin 5 and 37 (one block and five, pad channels in the last), Cout 37 and 128 (pad slots, two cout tiles), both
-tiles.  Integer operands: bit-equal to float64 F.conv3d.  Random operands: inside the bounds of the kernels' own case modules
+"""-m gpu: the two fp32 z-pair LDS-DMA conv kernels on their k-half operand images (tm_conv_frag.h) -- conv3d_zpair (plain and
+with the fused mid-section) and conv3d_zpair_ups through their single-op hooks (conv3d_xquad, the third kernel on these images,
+has tests/test_gpu_xquad*.py), at the smallest shapes that reach every lane -> address map: S = 8, 16, 32 (one per tile width),
+N = 1 and 3 (3 leaves a partial workgroup at S = 8), Cin 5 and 37 (one block and five, pad channels in the last), Cout 37 and
+128 (pad slots, two cout tiles), both tiles.  Integer operands: bit-equal to float64 F.conv3d.  Random operands: inside the bounds of the kernels' own case modules
 (imported, not restated).  Both tiles give identical bits.  Every output lies between NaN fences that must stay NaN, is prefilled
 with NaN and must come back without one.  A wrong weight image, activation image, staging store or lane map changes which
 operands meet in the MFMA: the integer cases then differ from F.conv3d."""
@@ -56,11 +56,8 @@ def _launch(kernel, c, variant):
     args = (_lib.ptr(xc), C.c_void_p(wh.data_ptr()), C.c_void_p(bh.data_ptr()), _lib.ptr(yc))
     if kernel == "zpair":
         _lib.check(L.tm_op_conv_mfma(*args, N, Cin, Cout, 2, S, 3, 0, 0, variant, st), "tm_op_conv_mfma")
-    elif kernel == "ups":
-        _lib.check(L.tm_op_conv_ups_pair_f32(*args, N, Cin, Cout, 2, S, variant, st), "tm_op_conv_ups_pair_f32")
     else:
-        tile = L.tm_op_conv_xpair_f32(*args, C.c_void_p(0), 0, N, Cin, Cout, 2, S, variant, st)
-        assert tile == variant, f"asked for tile {variant}, the hook reports {tile}"
+        _lib.check(L.tm_op_conv_ups_pair_f32(*args, N, Cin, Cout, 2, S, variant, st), "tm_op_conv_ups_pair_f32")
     torch.cuda.synchronize()
     assert bool(torch.isnan(buf[:FENCE]).all()) and bool(torch.isnan(buf[FENCE + n:]).all()), "a fence around y was written"
     assert not bool(torch.isnan(yc).any()), "the kernel left output elements unwritten"
@@ -69,7 +66,7 @@ def _launch(kernel, c, variant):
     return util.from_cb8(yc, Cout).cpu(), yc.clone()
 
 
-@pytest.mark.parametrize("kernel", ["zpair", "ups", "xpair"])
+@pytest.mark.parametrize("kernel", ["zpair", "ups"])
 @pytest.mark.parametrize("case", CASES, ids=_id)
 def test_integers_equal_float64_conv3d(case, kernel):
     c = _data(case, "int")
@@ -82,16 +79,14 @@ def test_integers_equal_float64_conv3d(case, kernel):
     assert torch.equal(raws[0], raws[1]), "the two tiles differ in bits"
 
 
-@pytest.mark.parametrize("kernel", ["zpair", "ups", "xpair"])
+@pytest.mark.parametrize("kernel", ["zpair", "ups"])
 @pytest.mark.parametrize("case", CASES, ids=_id)
 def test_random_inside_the_case_modules_bounds(case, kernel):
     c = _data(case, "float")
     if kernel == "zpair":
         ref, bnd = c["ref"], ZT._bound(c["x"], c["w"], c["b"], None)
-    elif kernel == "ups":
-        ref, bnd = c["ref_ups"], UC.bound(c)
     else:
-        ref, bnd = c["ref"], XC.bound(c)
+        ref, bnd = c["ref_ups"], UC.bound(c)
     raws = []
     for variant in (1, 2):
         got, raw = _launch(kernel, c, variant)

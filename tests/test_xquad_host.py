@@ -78,4 +78,5 @@ def test_hook_refusals_need_no_device():
     assert f(p, p, p, p, n, 0, 0, 8, 64, 2, 8, 0, None) == -1      # N < 1
     assert L.tm_last_error()
     ms = (C.c_float * 2)()
-    assert L.tm_op_conv_pad1_time_f32(p, p, p, p, 1, 8, 64, 8, 3, 0, 2, ms, None) == -1    # form outside 0 .. 2
+    assert L.tm_op_conv_pad1_time_sched_f32(p, p, p, p, 1, 8, 64, 8, 3, 0, -1, 2, ms, None) == -1    # no such form
+    assert L.tm_op_conv_pad1_time_sched_f32(p, p, p, p, 1, 8, 64, 8, 1, 0, -1, 2, ms, None) == -1    # form 1 is no form any more

@@ -1,6 +1,6 @@
-"""Cases, float64 model and error bound of the x-pair form of the fp32 3x3x3 pad-1 conv at Z = 2 (conv3d_xpair, hook
-tm_op_conv_xpair_f32): the pair form in z composed with the 1-D Winograd identity F(2,3) along x.  Shared by
-tests/test_xpair_host.py (no GPU) and tests/test_gpu_xpair.py.
+"""Cases, float64 model and error bound of the x-pair form of the fp32 3x3x3 pad-1 conv at Z = 2: the pair form in z composed
+with the 1-D Winograd identity F(2,3) along x.  The kernel that ran it (conv3d_xpair) is retired (profiles/conv_xpair_retired.txt);
+tests/test_xpair_host.py (no GPU, no library) checks the model, and tests/test_gpu_conv_frag_layout.py takes its operands from make.
 
 THE IDENTITY.  W0, W1, W2 the kz slices, X0, X1 the two input planes.  Products p = 1, 2, 3 use the filters V(1) = W1,
 V(2) = W2 - W1, V(3) = W0 - W1 on the planes Xs(1) = X0 + X1, Xs(2) = X1, Xs(3) = X0.  For a filter row ky with taps g0, g1, g2

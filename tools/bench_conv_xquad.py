@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Op-level timing of the fp32 3x3x3 pad-1 conv at Z = 2 in its three forms, the pair form (conv3d_zpair), the x-pair form
-(conv3d_xpair, F(2,3) along x) and the x-quad form (conv3d_xquad, F(4,3) along x), at the governing geometries of the fp32
-step.  Per geometry ROUNDS rounds of CHUNK launches of each form, interleaved (pair, x-pair, x-quad s0, x-quad s1, pair, ..), every launch
-between two events of its own (tm_op_conv_pad1_time_sched_f32); the first launch of a chunk is dropped.  Prints one JSON line per
-geometry: median, 10th and 90th percentile in microseconds of each form -- the x-quad form once per schedule of conv3d_xquad
-(s0 = four barriers per cin block, s1 = pipelined) -- and for each Winograd form whether its median is below the other forms' by
-more than the largest of the p90 - p10 spreads; pipe_wins: schedule 1 against schedule 0 by the same rule on their two widths.
+"""Op-level timing of the fp32 3x3x3 pad-1 conv at Z = 2 in its two forms, the pair form (conv3d_zpair) and the x-quad form
+(conv3d_xquad, F(4,3) along x), at the governing geometries of the fp32 step.  Per geometry ROUNDS rounds of CHUNK launches of
+each form, interleaved (pair, x-quad s0, x-quad s1, pair, ..), every launch between two events of its own
+(tm_op_conv_pad1_time_sched_f32); the first launch of a chunk is dropped.  Prints one JSON line per geometry: median, 10th and
+90th percentile in microseconds of each form -- the x-quad form once per schedule of conv3d_xquad (s0 = four barriers per cin
+block, s1 = pipelined) -- xquad_ratio, the better x-quad median over the pair form's, and xquad_wins, whether it is below the pair
+form's by more than the largest of the p90 - p10 spreads; pipe_wins: schedule 1 against schedule 0 by the same rule on their two
+widths.
 
-    python3 tools/bench_conv_xpair.py [--rounds 5] [--chunk 21] [--tile 0]
+    python3 tools/bench_conv_xquad.py [--rounds 5] [--chunk 21] [--tile 0]
 """
 import argparse
 import ctypes as C
@@ -26,7 +27,7 @@ from teramind_amd import _lib  # noqa: E402
 # decoder's second conv and the shallowest decoder's
 GEOMETRIES = [(128, 96, 64, 64), (128, 128, 128, 32), (128, 256, 256, 16), (128, 512, 512, 8), (32, 1253, 512, 8),
               (32, 512, 256, 16), (32, 160, 64, 64), (32, 512, 512, 8)]
-NAMES = {0: "pair", 1: "xpair", 3: "xquad_s0", 4: "xquad_s1"}   # 3 | 4: the timing hook's form 2 with schedule 0 | 1 forced
+NAMES = {0: "pair", 3: "xquad_s0", 4: "xquad_s1"}   # 3 | 4: the timing hook's form 2 with schedule 0 | 1 forced
 
 
 def main():
@@ -58,13 +59,11 @@ def main():
         out = {"N": N, "Cin": Cin, "Cout": Cout, "S": S, "tile": a.tile, "launches": len(t[0])}
         for f, name in NAMES.items():
             out[name + "_us"] = [round(v, 1) for v in q[f]]
-        out["xpair_ratio"] = round(q[1][0] / q[0][0], 4)
         xq = min(q[3][0], q[4][0])
-        out["xquad_ratio"] = round(xq / min(q[0][0], q[1][0]), 4)
+        out["xquad_ratio"] = round(xq / q[0][0], 4)
         out["pipe_ratio"] = round(q[4][0] / q[3][0], 4)
         out["spread_us"] = round(spread, 1)
-        out["wins"] = bool(q[0][0] - q[1][0] > spread)
-        out["xquad_wins"] = bool(min(q[0][0], q[1][0]) - xq > spread)
+        out["xquad_wins"] = bool(q[0][0] - xq > spread)
         out["pipe_wins"] = bool(q[3][0] - q[4][0] > max(q[3][2] - q[3][1], q[4][2] - q[4][1]))
         print(json.dumps(out), flush=True)
 

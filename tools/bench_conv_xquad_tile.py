@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Op-level timing of the two tiles of the x-quad form (conv3d_xquad: 1 = 64 four-column groups on four waves, two workgroups per
 CU; 2 = 128 groups on eight waves, one per CU) in both schedules (s0 = four barriers per cin block, s1 = pipelined), at the
-geometries of tools/bench_conv_xpair.py and at (128, 64, 64, 64).  Per geometry ROUNDS rounds of CHUNK launches of each of the
+geometries of tools/bench_conv_xquad.py and at (128, 64, 64, 64).  Per geometry ROUNDS rounds of CHUNK launches of each of the
 four (tile, schedule) combinations, interleaved, every launch between two events of its own (tm_op_conv_pad1_time_sched_f32); the
 first launch of a chunk is dropped.  Prints one JSON line per geometry: median, 10th and 90th percentile in microseconds of each
 combination, the combination the launcher takes on its own (`incumbent`), the fastest one (`best`) and whether it wins by the

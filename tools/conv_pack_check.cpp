@@ -1,12 +1,22 @@
 // Stand-alone host check of the conv weight packers (no GPU): every form is packed for the segment lists (5, 16, 3) and (8) at
 // Cout 37 and 128 into buffers of exactly conv_pack_floats() floats -- built with -fsanitize=address,undefined a write past the
-// end aborts.  The forms that reach LDS by LDS-DMA (CF_PAIR, CF_PAIR_UPS, CF_XPAIR) must hold, tap for tap, the [64 cout][8 cin]
+// end aborts.  The forms that reach LDS by LDS-DMA (CF_PAIR, CF_PAIR_UPS) must hold, tap for tap, the [64 cout][8 cin]
 // image permuted into [2 k-halves][64 cout][4 cin] (tm_conv_frag.h); CF_XQUAD holds tiles of 32 couts, a tap being
-// [2 k-halves][32 cout][4 cin], and is checked against the F(4,3) filter transform evaluated here (the parent has no such form).  With -DTM_PARENT_PACK and a second copy of the packer,
-// from the parent commit and compiled with -Dtmk=tmk_parent, every form the parent has must be byte-identical to ITS pack;
-// without it the run checks sizes, pad slots and the sanitizers' silence.  Pad slots (couts past Cout, channels past a segment) must be zero.
-//   hipcc -O1 -g -std=c++17 -x hip --cuda-host-only -fsanitize=address,undefined -Itera-mind_amd/csrc -Iinclude \
-//         tools/conv_pack_check.cpp tera-mind_amd/csrc/tm_conv_pack.cpp -o conv_pack_check && ./conv_pack_check
+// [2 k-halves][32 cout][4 cin], and is checked against the F(4,3) filter transform evaluated here.  Pad slots (couts past Cout,
+// channels past a segment) must be zero.
+//   F="-O1 -g -std=c++17 -x hip --cuda-host-only -fsanitize=address,undefined"
+//   hipcc $F -Itera-mind_amd/csrc -Iinclude tools/conv_pack_check.cpp tera-mind_amd/csrc/tm_conv_pack.cpp -o conv_pack_check \
+//     && ./conv_pack_check
+// With -DTM_PARENT_PACK and a second copy of the packer, from the parent commit and compiled with -Dtmk=tmk_parent against its own
+// headers, every form must also be byte-identical to ITS pack.  The forms are passed by this commit's numbers, so the parent's
+// ConvForm must number them alike (the sed line: the parent of the commit that removed CF_XPAIR had it in front of CF_XQUAD):
+//   mkdir -p P/a/b P/include && git show HEAD~1:include/teramind_hip.h > P/include/teramind_hip.h
+//   for f in tm_conv_pack.cpp tm_kernels.h tm_conv_frag.h; do git show HEAD~1:tera-mind_amd/csrc/$f > P/a/b/$f; done
+//   sed -i '/^  CF_XPAIR,/{h;d};/^  CF_XQUAD,/G' P/a/b/tm_kernels.h
+//   hipcc $F -Dtmk=tmk_parent -c P/a/b/tm_conv_pack.cpp -o P/parent_pack.o
+//   hipcc $F -Itera-mind_amd/csrc -Iinclude -DTM_PARENT_PACK -c tools/conv_pack_check.cpp -o P/check.o
+//   hipcc $F -Itera-mind_amd/csrc -Iinclude -c tera-mind_amd/csrc/tm_conv_pack.cpp -o P/pack.o
+//   hipcc -fsanitize=address,undefined P/check.o P/pack.o P/parent_pack.o -o P/check_parent && P/check_parent
 #include <stdio.h>
 #include <string.h>
 
@@ -30,12 +40,12 @@ static int fails = 0;
 
 int main() {
   const int segs[2][3] = {{5, 16, 3}, {8, 0, 0}}, nsegs[2] = {3, 1}, couts[2] = {37, 128};
-  const int forms[] = {CF_1X1, CF_INPLANE, CF_PLANES3, CF_ZSKIP, CF_ZSKIP_UPS, CF_PAIR, CF_PAIR_UPS, CF_XPAIR, CF_XQUAD};
-  const char* names[] = {"CF_1X1", "CF_INPLANE", "CF_PLANES3", "CF_ZSKIP", "CF_ZSKIP_UPS", "CF_PAIR", "CF_PAIR_UPS", "CF_XPAIR", "CF_XQUAD"};
+  const int forms[] = {CF_1X1, CF_INPLANE, CF_PLANES3, CF_ZSKIP, CF_ZSKIP_UPS, CF_PAIR, CF_PAIR_UPS, CF_XQUAD};
+  const char* names[] = {"CF_1X1", "CF_INPLANE", "CF_PLANES3", "CF_ZSKIP", "CF_ZSKIP_UPS", "CF_PAIR", "CF_PAIR_UPS", "CF_XQUAD"};
   unsigned long long lcg = 88172645463325252ull;
   for (int si = 0; si < 2; ++si)
     for (int ci = 0; ci < 2; ++ci)
-      for (int fi = 0; fi < 9; ++fi) {
+      for (int fi = 0; fi < 8; ++fi) {
         const int form = forms[fi], Cout = couts[ci], nseg = nsegs[si];
         int Cin = 0, Cbi = 0;
         for (int s = 0; s < nseg; ++s) { Cin += segs[si][s]; Cbi += (segs[si][s] + 7) / 8; }
@@ -45,7 +55,15 @@ int main() {
         const size_t n = conv_pack_floats(form, Cout, Cbi);
         std::vector<float> pk(n, -7.f);
         conv_pack_host(form, w.data(), Cout, segs[si], nseg, pk.data());
-        const bool halves = form == CF_PAIR || form == CF_PAIR_UPS || form == CF_XPAIR;
+        auto same_as_parent = [&] {
+#ifdef TM_PARENT_PACK
+          CHECK(tmk_parent::conv_pack_floats(form, Cout, Cbi) == n, "%s pack size changed", names[fi]);
+          std::vector<float> old(n, -9.f);
+          tmk_parent::conv_pack_host(form, w.data(), Cout, segs[si], nseg, old.data());
+          CHECK(memcmp(old.data(), pk.data(), n * sizeof(float)) == 0, "%s bytes changed", names[fi]);
+#endif
+        };
+        const bool halves = form == CF_PAIR || form == CF_PAIR_UPS;
         if (form == CF_XQUAD) {                                    // every slot: the transformed tap of its (cout, cin), or a zero pad
           size_t pads = 0, nonzero = 0, wrong = 0;
           const int n32 = (Cout + 63) / 64 * 2;
@@ -80,6 +98,7 @@ int main() {
                   }
           }
           CHECK(wrong == 0, "CF_XQUAD: %zu slots are not the F(4,3) transform of their filter row", wrong);
+          same_as_parent();
           printf("%-12s segs %-8s Cout %3d: %8zu floats, %7zu pad slots zero, %7zu real non-zero\n", names[fi], si ? "(8)" : "(5,16,3)",
                  Cout, n, pads, nonzero);
           continue;
@@ -100,12 +119,7 @@ int main() {
                       else nonzero += v != 0.f;
                     }
           }
-#ifdef TM_PARENT_PACK
-        CHECK(tmk_parent::conv_pack_floats(form, Cout, Cbi) == n, "%s pack size changed", names[fi]);
-        std::vector<float> old(n, -9.f);
-        tmk_parent::conv_pack_host(form, w.data(), Cout, segs[si], nseg, old.data());
-        CHECK(memcmp(old.data(), pk.data(), n * sizeof(float)) == 0, "%s bytes changed", names[fi]);
-#endif
+        same_as_parent();
         printf("%-12s segs %-8s Cout %3d: %8zu floats, %7zu pad slots zero, %7zu real non-zero\n", names[fi],
                si ? "(8)" : "(5,16,3)", Cout, n, pads, nonzero);
       }
