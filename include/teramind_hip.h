@@ -547,6 +547,26 @@ int tm_conv_xquad_lds_bytes(int half, int tw, int sched);
  * choice. */
 int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
                                    int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out, void* stream);
+/* tm_op_conv_xquad_sched_f32 with the K loop split over workgroups: ksplit workgroups per (voxel tile, cout tile) run disjoint
+ * ranges of the cin blocks and write raw partial sums, and a second pass (xquad_split_reduce) forms ((p0 + p1) + p2) + p3, adds
+ * the bias and then the residual, one float4 per lane, so res_cb8 == y_cb8 is legal.  ksplit 0 =
+ * the rule (tm_conv_xquad_ksplit), 1 | 2 | 4 force the factor; 1 is the unsplit launch, bit for bit.  Returns the factor taken.
+ * TM_ERR_ARG before any device call, besides the refusals of tm_op_conv_xquad_sched_f32: a factor outside 0 | 1 | 2 | 4, a
+ * factor above the count of cin blocks ceil(Cin / 8) (a split would be empty), a forced split with res_half. */
+int tm_op_conv_xquad_split_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                               int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, int sched, int ksplit,
+                               void* stream);
+/* The rule of the split: the factor (1 | 2) of an x-quad launch of N patches of 2 x S x S voxels.  1 wherever the launch has
+ * 256 large workgroups or more, or 256 small ones, with res_half, with fewer than 8 cin blocks, and everywhere with
+ * TM_CONV_XQUAD_SPLIT=0 (read once); 2 otherwise, however few the workgroups, so that one image sums in the order of its batch.
+ * The rule of one launch on its own: the executor fixes the factor per layer (2 for the decoder blocks of the deepest level at
+ * every patch count, 1 for every other layer), so that results do not depend on how many patches a call holds.  No device call. */
+int tm_conv_xquad_ksplit(int N, int Cin, int Cout, int S, int res_half);
+/* tm_op_conv_pad1_time_sched_f32 with ksplit (form 2 only; 0 = the rule, 1 | 2 | 4 forced): a launch is the conv and, when
+ * split, its reduction, both between the two events. */
+int tm_op_conv_pad1_time_split_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                   int Cout, int S, int form, int tile_variant, int sched, int ksplit, int iters, float* ms_out,
+                                   void* stream);
 
 /* The fp32 1x1x1 conv / Linear (conv1_mfma) in every form the model launches: y = res + gate_up * act(W x + b).
  * x_cb8: DEVICE [N][x_cbtot][Z][S][S][8]; the conv reads the channel-block slice [x_cb0, x_cb0 + ceil(Cin/8)) of it in place

@@ -116,6 +116,9 @@ SIGNATURES = {
     "tm_op_conv_xquad_sched_f32": (c_int, [c_void_p] * 5 + [c_int] * 8 + [c_void_p]),
     "tm_conv_xquad_lds_bytes": (c_int, [c_int] * 3),
     "tm_op_conv_pad1_time_sched_f32": (c_int, [c_void_p] * 4 + [c_int] * 8 + [C.POINTER(c_float), c_void_p]),
+    "tm_op_conv_xquad_split_f32": (c_int, [c_void_p] * 5 + [c_int] * 9 + [c_void_p]),
+    "tm_conv_xquad_ksplit": (c_int, [c_int] * 5),
+    "tm_op_conv_pad1_time_split_f32": (c_int, [c_void_p] * 4 + [c_int] * 9 + [C.POINTER(c_float), c_void_p]),
     "tm_op_conv27_time":(c_int, [c_int] * 10 + [c_void_p, c_void_p]),
     "tm_op_conv1_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 4),
     "tm_op_conv1_h16_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p] * 3 + [c_int] * 3 + [c_void_p]),

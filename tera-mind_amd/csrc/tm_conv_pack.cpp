@@ -32,6 +32,10 @@ static bool switch_on(const char* name) {        // an A/B switch: on unless the
   const char* v = getenv(name);
   return !(v && atoi(v) == 0);
 }
+bool xquad_split_on() {
+  static const bool on = switch_on("TM_CONV_XQUAD_SPLIT");
+  return on;
+}
 int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse_mid) {
   static const bool zpair_on = switch_on("TM_CONV_ZPAIR"), fuse_on = switch_on("TM_CONV_FUSE_MID"),
                     xquad_on = switch_on("TM_CONV_XQUAD");
@@ -44,10 +48,12 @@ int conv_pick_form(int ksize, int zmode, int Z, bool deep8, int role, bool* fuse
   if (Z != 2) return (Z == 1 && (role & ROLE_RES)) ? CF_INPLANE : CF_PLANES3;
   if ((role & ROLE_OP_XQUAD) && xquad_on) return CF_XQUAD;
   if (!pair) return CF_ZSKIP;
-  // a ResBlock conv above the deepest decoder level, on planes of at least 8 x 8, runs in the x-quad form (F(4,3) along x, half
-  // the pair form's MFMAs); TM_CONV_XQUAD=0 leaves it on the pair form.  c1 of a 64-channel block: the pair form fuses the mid
-  // norm into its epilogue; an x-quad workgroup holds 32 of the 64 channels and leaves the norm to the separate pass
-  const bool xq = (role & ROLE_RES) && !(role & ROLE_DEEP) && deep8 && xquad_on;
+  // a ResBlock conv on planes of at least 8 x 8 runs in the x-quad form (F(4,3) along x, half the pair form's MFMAs);
+  // TM_CONV_XQUAD=0 leaves it on the pair form.  The decoder blocks of the deepest level have too few workgroups for the chip
+  // unless their K loop is split (xquad_ksplit): with TM_CONV_XQUAD_SPLIT=0 they stay on the pair form.  c1 of a 64-channel
+  // block: the pair form fuses the mid norm into its epilogue; an x-quad workgroup holds 32 of the 64 channels and leaves the
+  // norm to the separate pass
+  const bool xq = (role & ROLE_RES) && !((role & ROLE_DEEP) && !xquad_split_on()) && deep8 && xquad_on;
   if (fuse_mid) *fuse_mid = (role & ROLE_C1_64) && fuse_on && !xq;
   return xq ? CF_XQUAD : CF_PAIR;
 }

@@ -133,6 +133,11 @@ struct ConvArgs {
   long mod_stride = 0;
   int per_image = 1;                // patches per image (n -> modulation row)
   float inv_c = 0.f;                // 1 / 64
+  // conv3d_xquad only: split K.  The grid is ksplit (1 | 2 | 4) times the unsplit one; split ks of a (voxel tile, cout tile)
+  // runs cin blocks [ks Cbi / ksplit, (ks + 1) Cbi / ksplit) and writes its raw sums at y + ks * part_stride floats
+  // (xquad_split_reduce adds them)
+  int ksplit = 1;
+  long part_stride = 0;
 };
 
 // in-plane element offset of voxel (z, y, x) -> (z, y >> 1, x >> 1) of the half-resolution plane; ls = log2(S)

@@ -66,7 +66,8 @@ ConvW conv_w(int form, int Cout, int Cbi);               // the weight geometry 
 enum { ROLE_OP = 0,             // single-operator hooks and the training tape: pair form at Z == 2, never x-quad
        ROLE_RES = 1,            // a ResBlock 3x3x3 conv of the executor: centre slice at Z == 1; at Z == 2 x-quad, or pair
                                 //   (TM_CONV_XQUAD=0)
-       ROLE_DEEP = 2,           // + a decoder block of the deepest level: stays on the pair form (profiles/fp32_xpair.txt)
+       ROLE_DEEP = 2,           // + a decoder block of the deepest level: x-quad only with its K loop split over workgroups
+                                //   (xquad_ksplit); TM_CONV_XQUAD_SPLIT=0 keeps it on the pair form
        ROLE_C1_64 = 4,          // + the first conv of a 64-channel block: on the pair form it runs the fused mid-section
        ROLE_OP_PAIR_UPS = 16,   // the hook of the upsampled pair form: under no switch
        ROLE_OP_XQUAD = 32 };    // the hooks of the x-quad form: under TM_CONV_XQUAD alone
@@ -96,6 +97,11 @@ struct ConvLaunch {
   int zmode = ZM_PAD1;   // the caller's statement of the z semantics; must agree with w.form (ignored for CF_1X1)
   int xquad_sched = -1;  // CF_XQUAD only: 0 = the four-barrier schedule of conv3d_xquad, 1 = the pipelined one, -1 = the launcher's
                          // choice per instantiation and launch size (TM_CONV_XQUAD_PIPE=0: the four-barrier schedule everywhere)
+  // CF_XQUAD only: split K.  1 = one workgroup runs the whole K loop; 2 | 4 = that many workgroups per (voxel tile, cout tile),
+  // each over its own range of cin blocks, their raw sums in `part` (xquad_part_floats(...) floats), then xquad_split_reduce adds
+  // them, the bias, the GELU flag and the residual into y.  The caller decides (xquad_ksplit is the rule); no res_half
+  int xquad_ksplit = 1;
+  float* part = nullptr;
   // CF_PAIR, Cout == 64, the 128-voxel tile, no residual / gate / flags: fuse RMSNorm(C) * norm_w -> x (1 + scale) +
   // shift -> SiLU into the epilogue and write `a2` (the next conv's input) instead of y; y carries the geometry only
   int fuse_norm = 0;
@@ -112,6 +118,17 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s);
 // workgroups on, except at S >= 64 from 2048 on.  The one statement of the rule, for the launcher and for whoever must know the
 // tile beforehand (the fused mid-section exists in the large tile only).  No device call.
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant);
+// The split-K factor of an x-quad launch of ovox = N * 2 * S * S output voxels, Cout couts and Cbi cin blocks: 1 where the
+// launch has 256 large workgroups or more, with res_half and with TM_CONV_XQUAD_SPLIT=0 (xquad_split_on, read once); otherwise 2
+// where the launch has fewer than XQUAD_SPLIT_WGS small-tile workgroups and both splits keep XQUAD_SPLIT_FLOOR cin blocks (4
+// is a factor of the kernel and the hooks; the rule never takes it).  A pure function of the shapes: the dry pass and the real
+// pass agree.  It is the rule of a launch on its own (the hooks, the op table).  The executor gives the factor to the layer, not
+// to the launch: the decoder blocks of the deepest level take 2 at every patch count (split_k, tm_model.hip).  No device call.
+constexpr int XQUAD_SPLIT_WGS = 256, XQUAD_SPLIT_FLOOR = 4;
+int xquad_ksplit(long ovox, int Cout, int Cbi, int S, bool res_half);
+bool xquad_split_on();
+// floats of the partial sums of a split launch into y: ksplit slices of y's own geometry
+inline size_t xquad_part_floats(int ksplit, const TV& y) { return ksplit > 1 ? (size_t)ksplit * y.N * y.nstride : 0; }
 // byte addresses in LDS of the 64 lanes of wave wv for one fragment read or staging store of conv3d_zpair (kernel 0),
 // conv3d_zpair_ups (1), conv3d_xquad (4; 2 and 3 are no kernels: waves 0 .. 7 in the large tile, kx = the wave's q 0 .. 2, in a
 // staging store the q-plane 0 .. 5), its pipelined schedule (5: as 4, `sub` = the plane set 0 | 1 of an X fragment or a staging store),

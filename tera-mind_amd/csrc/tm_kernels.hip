@@ -670,7 +670,16 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
 
   const int S = a.S;
   const ConvTile t = conv_tile_of<TW, G::TR, false, false>(a);   // a.ntile counts 32-cout tiles here
-  const int nt = t.nt, pg = t.pg, tr = t.tr, tc = t.tc;
+  // split K (a.ksplit 1 | 2 | 4): the split index is the slowest term of the swizzled block index, so it arrives on top of the
+  // patch group.  Split ks owns cin blocks [cb0, cb0 + nkb) of this (voxel tile, cout tile): x and the weight resource start at
+  // cb0, the K loop runs nkb blocks and the raw sums go to partial ks.  All of it is wave-uniform: scalar registers only
+  const int pgs = (a.N + G::NPB - 1) / G::NPB;
+  const int ks = __builtin_amdgcn_readfirstlane(a.ksplit > 1 ? (t.pg >= pgs) + (t.pg >= 2 * pgs) + (t.pg >= 3 * pgs) : 0);
+  const int cb0 = __builtin_amdgcn_readfirstlane((ks * a.Cbi) >> (a.ksplit >> 1));
+  const int nkb = __builtin_amdgcn_readfirstlane((((ks + 1) * a.Cbi) >> (a.ksplit >> 1)) - cb0);
+  a.x += (long)cb0 * a.x_plane;
+  a.y += ks * a.part_stride;
+  const int nt = t.nt, pg = t.pg - ks * pgs, tr = t.tr, tc = t.tc;
 
   // ---- staging descriptor: this thread's (row, group, half block); xoff addresses column 4j of plane 0 ----
   long xoff = -1;
@@ -715,7 +724,7 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
   clear_acc(acc);
 
   const unsigned lw_lds = (unsigned)(size_t)(__attribute__((address_space(3))) float*)lw;
-  const rsrc_words wrs = weight_rsrc<true>(a.w + (long)nt * a.Cbi * 3 * G::WSLOT, a.Cbi * 3 * G::WSLOT * 4);
+  const rsrc_words wrs = weight_rsrc<true>(a.w + ((long)nt * a.Cbi + cb0) * 3 * G::WSLOT, nkb * 3 * G::WSLOT * 4);
   const int wvo = lane * 16;
   const int wvu = __builtin_amdgcn_readfirstlane(wv);
   // piece k of this wave of product n: tap j = NW k + wave of the product's 18
@@ -839,8 +848,8 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  for (int cb = 0; cb + 1 < a.Cbi; ++cb) block(cb, std::true_type{});
-  block(a.Cbi - 1, std::false_type{});
+  for (int cb = 0; cb + 1 < nkb; ++cb) block(cb, std::true_type{});
+  block(nkb - 1, std::false_type{});
   } else {
   load_x(0);
 #pragma unroll
@@ -891,8 +900,8 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  for (int cb = 0; cb + 1 < a.Cbi; ++cb) stage(cb, std::true_type{});
-  stage(a.Cbi - 1, std::false_type{});
+  for (int cb = 0; cb + 1 < nkb; ++cb) stage(cb, std::true_type{});
+  stage(nkb - 1, std::false_type{});
   }
 
   // ---- the q halves exchange through LDS (free behind the barrier: nothing of the K loop is read or in flight any more):
@@ -1018,6 +1027,31 @@ __global__ __launch_bounds__(HALF ? 256 : 512, 2) void conv3d_xquad(ConvArgs a) 
         const long uni = (long)cob * a.y_plane + z * (S * S * 8) + par * 16;
         if (cob < a.Cob && okv) *(f32x4*)(a.y + yl + uni) = rv[z][par][g];
       }
+}
+
+// The second pass of a split x-quad launch: y = res + gelu?(((p0 + p1) + p2) + p3 + bias), conv_epilogue's arithmetic in its
+// order over the raw sums of the ksplit partials (slices of y's own geometry, part_stride floats apart).  One float4 per lane,
+// read and written by that lane alone, so res == y (the skip conv's output updated in place) is legal; it touches what the
+// unsplit kernel's guarded stores touch: every lane of blocks [0, Cob) of patches [0, N).  No atomics: the sum has one order.
+// The zero vector is the bias a split launch hands the conv kernel's tail.
+constexpr int XQ_ZERO_FLOATS = 4096;
+__device__ float xq_zero_bias[XQ_ZERO_FLOATS];
+__global__ __launch_bounds__(256) void xquad_split_reduce(const float* part, long part_stride, int ksplit, const float* bias, const float* res,
+                                                          long res_nstride, float* y, long y_nstride, long per_n4, int plane4, long total4,
+                                                          int flags) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total4) return;
+  const long n = i / per_n4, rem = i - n * per_n4;               // rem: float4 index inside the patch's Cob blocks
+  const long off = n * y_nstride + rem * 4;
+  f32x4 v = *(const f32x4*)(part + off);
+  for (int k = 1; k < ksplit; ++k) v = v + *(const f32x4*)(part + k * part_stride + off);
+  v = v + *(const f32x4*)(bias + (rem / plane4) * 8 + (rem & 1) * 4);
+  if (flags & EPI_GELU) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = gelu_tanh_hw(v[j]);
+  }
+  if (res) v = *(const f32x4*)(res + n * res_nstride + rem * 4) + v;
+  *(f32x4*)(y + off) = v;
 }
 
 // ---- 1x1x1 conv / Linear over voxels (flat voxel tiles, KC channel blocks per stage) ----
@@ -1154,6 +1188,16 @@ int conv1_form(long vox, int ntile, int tile_variant) {
 // more (what was measured: the S = 64 levels at 128 patches, whose K loops of 8 and 12 cin blocks are the shortest of the step)
 static long xquad_large_wgs(long ovox, int ntile) { return (ovox / 1024) * 2 * ntile; }
 static bool xquad_many_wgs(long ovox, int ntile, int S) { return S >= 64 && xquad_large_wgs(ovox, ntile) >= 2048; }
+
+// Split K of the x-quad form (tm_kernels.h has the statement).  A launch below 256 large workgroups takes the small tile, of
+// ceil(ovox / 512) * ceil(Cout / 32) workgroups; where those are fewer than XQUAD_SPLIT_WGS, K-ranges of a tile go to
+// different workgroups (profiles/fp32_xquad_splitk.txt: the factors measured at the launches of the step).  The factor is 2
+// however few the workgroups are: 4 never beat 2
+int xquad_ksplit(long ovox, int Cout, int Cbi, int S, bool res_half) {
+  if (!xquad_split_on() || res_half || S < 8 || xquad_large_wgs(ovox, (Cout + 63) / 64) >= 256) return 1;
+  const long small = (ovox + 511) / 512 * ((Cout + 31) / 32);
+  return small < XQUAD_SPLIT_WGS && Cbi / 2 >= XQUAD_SPLIT_FLOOR ? 2 : 1;
+}
 
 int conv_tile(int form, long ovox, int ntile, int S, int tile_variant) {
   if (S == 4) return 1;                        // 4 x 4 planes: several patches per workgroup of the small tile
@@ -1316,17 +1360,33 @@ hipError_t launch_conv_mfma(const ConvLaunch& L, hipStream_t s) {
         return large ? launch_tiled<conv3d_zpair_ups<0, TW>, ZPUGeo<0, TW>>(a, 4, s)
                      : launch_tiled<conv3d_zpair_ups<1, TW>, ZPUGeo<1, TW>>(a, 4, s);
       });
-    default:   // CF_XQUAD
+    default: {   // CF_XQUAD
       a.ntile = (L.w.Cout + 31) / 32;                          // the kernel's cout tiles are of 32 (the pack holds 2 * ntile of them)
       if (L.xquad_sched < -1 || L.xquad_sched > 1) return hipErrorInvalidValue;
-      return with_tile_width<16>(S, [&](auto tw) {
+      // split K: the conv writes raw sums (a bias of zeros, no residual, no flags) into the partials, the reduction finishes y
+      const int ksp = L.xquad_ksplit;
+      if (ksp != 1) {
+        if ((ksp != 2 && ksp != 4) || ksp > a.Cbi || !L.part || L.res_half || L.y.Cb * 8 > XQ_ZERO_FLOATS) return hipErrorInvalidValue;
+        float* zeros = nullptr;
+        if (hipError_t e = hipGetSymbolAddress((void**)&zeros, HIP_SYMBOL(xq_zero_bias)); e != hipSuccess) return e;
+        a.ksplit = ksp; a.part_stride = (long)L.y.N * L.y.nstride;
+        a.y = L.part; a.bias = zeros; a.res = nullptr; a.res_nstride = 0; a.flags = 0;
+      }
+      const hipError_t e = with_tile_width<16>(S, [&](auto tw) {
         constexpr int TW = decltype(tw)::value;
         if (L.xquad_sched < 0 ? xquad_pipe_default(!large, TW, xquad_many_wgs((long)a.N * a.Z * a.S * a.S, L.w.ntile, S)) : L.xquad_sched == 1)
-          return large ? launch_tiled<conv3d_xquad<0, TW, 1>, XQGeo<0, TW, 1>, 64 * XQGeo<0, TW, 1>::NW>(a, 1, s)
-                       : launch_tiled<conv3d_xquad<1, TW, 1>, XQGeo<1, TW, 1>, 64 * XQGeo<1, TW, 1>::NW>(a, 1, s);
-        return large ? launch_tiled<conv3d_xquad<0, TW, 0>, XQGeo<0, TW, 0>, 64 * XQGeo<0, TW, 0>::NW>(a, 1, s)
-                     : launch_tiled<conv3d_xquad<1, TW, 0>, XQGeo<1, TW, 0>, 64 * XQGeo<1, TW, 0>::NW>(a, 1, s);
+          return large ? launch_tiled<conv3d_xquad<0, TW, 1>, XQGeo<0, TW, 1>, 64 * XQGeo<0, TW, 1>::NW>(a, ksp, s)
+                       : launch_tiled<conv3d_xquad<1, TW, 1>, XQGeo<1, TW, 1>, 64 * XQGeo<1, TW, 1>::NW>(a, ksp, s);
+        return large ? launch_tiled<conv3d_xquad<0, TW, 0>, XQGeo<0, TW, 0>, 64 * XQGeo<0, TW, 0>::NW>(a, ksp, s)
+                     : launch_tiled<conv3d_xquad<1, TW, 0>, XQGeo<1, TW, 0>, 64 * XQGeo<1, TW, 0>::NW>(a, ksp, s);
       });
+      if (e != hipSuccess || ksp == 1) return e;
+      const int plane4 = (int)(L.y.plane() / 4);
+      const long per_n4 = (long)L.y.Cb * plane4, total4 = per_n4 * L.y.N;
+      hipLaunchKernelGGL(xquad_split_reduce, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, L.part, a.part_stride, ksp, L.w.bias,
+                         L.res ? L.res->p : nullptr, L.res ? L.res->nstride : 0, L.y.p, L.y.nstride, per_n4, plane4, total4, L.flags);
+      return hipGetLastError();
+    }
   }
 }
 

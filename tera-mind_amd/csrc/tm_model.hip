@@ -806,7 +806,21 @@ static void launch_booked(Ctx& cx, const ConvBook* book, LaunchFn launch) {
   m->prof_bytes += book->bytes;
 }
 
-// fp32 conv (launch_conv_mfma: every form).  count_cin: the real input channels of a ResBlock 3x3x3 conv, which is counted; 0:
+// Split K of an x-quad conv (xquad_ksplit, a function of the shapes alone: the dry pass carves what the real pass carves): the
+// partial sums come from the context and live until the block's mark.  The factor belongs to the layer, as its form does, and
+// never follows the patch count: another factor is another order of the sum, and one image alone, a tile alone and the same
+// image or tile inside a larger call must agree bit for bit (tests/test_gpu_fullsize.py, tests/test_gpu_sweep.py).  So the
+// decoder blocks of the deepest level (`deep`), whose launches at the benchmark's 32 patches are the ones xquad_ksplit splits,
+// take its factor for that launch, 2, at every patch count -- also where the launch would fill the chip unsplit and the rule
+// itself says 1 (the 400 patches of a tile) -- and every other layer stays unsplit
+static void split_k(Ctx& cx, ConvLaunch& L, bool deep) {
+  if (!deep || L.w.form != CF_XQUAD || L.res_half) return;
+  L.xquad_ksplit = xquad_split_on() && L.w.Cbi / 2 >= XQUAD_SPLIT_FLOOR ? 2 : 1;
+  if (L.xquad_ksplit > 1) L.part = cx.alloc_f(xquad_part_floats(L.xquad_ksplit, L.y));
+}
+
+// fp32 conv (launch_conv_mfma: every form; a split x-quad launch is the conv and its reduction, both inside the profiling
+// bracket).  count_cin: the real input channels of a ResBlock 3x3x3 conv, which is counted; 0:
 // not counted (1x1 convs and Linears, the pyramid convs, down_z, the upsampled-input form)
 static void run_conv(Ctx& cx, const ConvLaunch& L, int count_cin = 0) {
   if (cx.dry) return;
@@ -1004,6 +1018,7 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
   } else {
     TV H1 = cx.tensor(N, w.cout, Z, S_out);
     L1.y = H1;
+    split_k(cx, L1, w.dec_deep);
     run_conv(cx, L1, w.cin);
     PrepLaunch Q = mid_section(cx, w, H1, per_image);
     prep_out(Q, A2);
@@ -1012,6 +1027,7 @@ static TV res_block(Ctx& cx, const ResW& w, const std::vector<Src>& src, int N, 
   if (w.has_skip) run_conv(cx, conv(raw, w.skip, out));
   ConvLaunch L2 = conv(A2, w.c2, out);
   L2.res = w.has_skip ? &out : (need_raw ? &raw : &src[0].t);
+  split_k(cx, L2, w.dec_deep);
   run_conv(cx, L2, w.cout);
   cx.top = mark;
   return out;

@@ -285,8 +285,25 @@ static int pad1_z2_args(int form, const void* x, const void* w, const void* b, c
 
 // The x-quad form (conv3d_xquad, Winograd F(4,3) along x), alone.  Returns the tile it launched (1 = 64 four-column groups per
 // workgroup, 2 = 128) or a negative error.
+// The split-K factor of a hook's x-quad launch from its argument (0 = the rule, 1 | 2 | 4 forced) into *ksplit, or TM_ERR_ARG
+// with the text, before any device call
+static int xquad_split_arg(int arg, int N, int Cin, int Cout, int S, int res_half, int* ksplit) {
+  const int Cbi = (Cin + 7) / 8;
+  if (arg != 0 && arg != 1 && arg != 2 && arg != 4) return fail(TM_ERR_ARG, "ksplit must be 0 (the rule), 1, 2 or 4 (got %d)", arg);
+  if (arg > Cbi) return fail(TM_ERR_ARG, "ksplit %d is above the %d cin blocks: a split would be empty", arg, Cbi);
+  if (arg > 1 && res_half) return fail(TM_ERR_ARG, "a split launch takes no half-resolution residual (res_half)");
+  *ksplit = arg ? arg : xquad_ksplit((long)N * 2 * S * S, Cout, Cbi, S, res_half != 0);
+  return TM_OK;
+}
+// the partial sums of a split launch, from the op's scratch
+static int xquad_split_scratch(ConvOp& op, int ksplit) {
+  op.L.xquad_ksplit = ksplit;
+  if (ksplit > 1) op.L.part = op.tmp.alloc<float>(xquad_part_floats(ksplit, op.L.y));
+  return op.tmp.err ? op.tmp.report() : TM_OK;
+}
+// ksplit: 1 | 2 | 4 (xquad_split_arg)
 static int xquad_op(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8, int res_half, int N,
-                    int Cin, int Cout, int Z, int S, int tile_variant, int sched, void* stream) {
+                    int Cin, int Cout, int Z, int S, int tile_variant, int sched, int ksplit, void* stream) {
   if (const int rc = pad1_z2_args(CF_XQUAD, x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
   if (res_half && !res_cb8) return fail(TM_ERR_ARG, "res_half needs a residual");
   ConvOp op;
@@ -294,33 +311,52 @@ static int xquad_op(const void* x_cb8, const void* w_host, const void* bias_host
                              res_half))
     return rc;
   op.L.xquad_sched = sched;
+  if (const int rc = xquad_split_scratch(op, ksplit)) return rc;
   const int rc = finish((hipStream_t)stream, launch_conv_mfma(op.L, (hipStream_t)stream), "conv_xquad (fp32)");
   return rc ? rc : conv_tile(CF_XQUAD, (long)N * Z * S * S, op.L.w.ntile, S, tile_variant);
 }
 extern "C" int tm_op_conv_xquad_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                                     int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, void* stream) {
-  return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, -1, stream);
+  return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, -1, 1, stream);
 }
 // The same with the schedule of conv3d_xquad forced: 0 = the four-barrier schedule, 1 = the pipelined one (same pack, same bits).
 extern "C" int tm_op_conv_xquad_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
                                           int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, int sched, void* stream) {
   if (sched != 0 && sched != 1) return fail(TM_ERR_ARG, "sched must be 0 (four barriers) or 1 (pipelined) (got %d)", sched);
-  return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, sched, stream);
+  return xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, sched, 1, stream);
+}
+// ... and with the K loop split over ksplit workgroups per tile (0 = the rule): returns the factor taken
+extern "C" int tm_op_conv_xquad_split_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, const void* res_cb8,
+                                          int res_half, int N, int Cin, int Cout, int Z, int S, int tile_variant, int sched, int ksplit,
+                                          void* stream) {
+  if (const int rc = pad1_z2_args(CF_XQUAD, x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, Z, S, tile_variant)) return rc;
+  if (sched != 0 && sched != 1) return fail(TM_ERR_ARG, "sched must be 0 (four barriers) or 1 (pipelined) (got %d)", sched);
+  int k = 1;
+  if (const int rc = xquad_split_arg(ksplit, N, Cin, Cout, S, res_half, &k)) return rc;
+  const int rc = xquad_op(x_cb8, w_host, bias_host, y_cb8, res_cb8, res_half, N, Cin, Cout, Z, S, tile_variant, sched, k, stream);
+  return rc < 0 ? rc : k;
+}
+extern "C" int tm_conv_xquad_ksplit(int N, int Cin, int Cout, int S, int res_half) {
+  return xquad_ksplit((long)N * 2 * S * S, Cout, (Cin + 7) / 8, S, res_half != 0);
 }
 
 // Timing hook (tools/bench_conv_xquad.py): the 3x3x3 pad-1 conv at Z == 2 packed once for `form` (0 = the pair form, 2 = the
 // x-quad form; 1 is no form any more), then `iters` launches, each between two events of its own; ms_out[i] (host) = the time of
 // launch i.  sched: the schedule of conv3d_xquad (form 2 only): -1 = the launcher's choice, 0 | 1 forced.
-extern "C" int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
-                                              int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out,
-                                              void* stream) {
+// ksplit: the split-K factor of the x-quad form as in tm_op_conv_xquad_split_f32 (a launch is then the conv and its reduction)
+static int conv_pad1_time(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin, int Cout, int S,
+                          int form, int tile_variant, int sched, int ksplit, int iters, float* ms_out, void* stream) {
   const int cf = form == 2 ? CF_XQUAD : CF_PAIR;
   if (const int rc = pad1_z2_args(cf, x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, 2, S, tile_variant)) return rc;
   if ((form != 0 && form != 2) || iters < 1 || !ms_out) return fail(TM_ERR_ARG, "form must be 0 or 2, iters >= 1, ms_out non-null");
   if (sched < -1 || sched > 1 || (sched >= 0 && form != 2)) return fail(TM_ERR_ARG, "sched must be -1, or 0 | 1 with form 2 (got %d)", sched);
+  if (ksplit != 1 && form != 2) return fail(TM_ERR_ARG, "ksplit other than 1 needs form 2 (got %d)", ksplit);
+  int k = 1;
+  if (const int rc = xquad_split_arg(ksplit, N, Cin, Cout, S, 0, &k)) return rc;
   ConvOp op;
   if (const int rc = conv_op(op, cf, w_host, bias_host, x_cb8, y_cb8, N, Cin, Cout, 2, S, 2, S, ZM_PAD1, tile_variant)) return rc;
   op.L.xquad_sched = sched;
+  if (const int rc = xquad_split_scratch(op, k)) return rc;
   hipEvent_t e0 = op.tmp.event(), e1 = op.tmp.event();
   if (op.tmp.err) return op.tmp.report();
   hipStream_t st = (hipStream_t)stream;
@@ -332,6 +368,16 @@ extern "C" int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_h
     HIP_TRY(hipEventElapsedTime(ms_out + i, e0, e1));
   }
   return finish(st, hipSuccess, "conv_pad1_time (fp32)");
+}
+extern "C" int tm_op_conv_pad1_time_sched_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                              int Cout, int S, int form, int tile_variant, int sched, int iters, float* ms_out,
+                                              void* stream) {
+  return conv_pad1_time(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, form, tile_variant, sched, 1, iters, ms_out, stream);
+}
+extern "C" int tm_op_conv_pad1_time_split_f32(const void* x_cb8, const void* w_host, const void* bias_host, void* y_cb8, int N, int Cin,
+                                              int Cout, int S, int form, int tile_variant, int sched, int ksplit, int iters,
+                                              float* ms_out, void* stream) {
+  return conv_pad1_time(x_cb8, w_host, bias_host, y_cb8, N, Cin, Cout, S, form, tile_variant, sched, ksplit, iters, ms_out, stream);
 }
 
 // power of two >= 2: what a half-resolution gate needs of S (read at (z, y >> 1, x >> 1))
