@@ -388,6 +388,46 @@ int tm_jpeg_encode_tiles_rgb(const void* const* planes, const int64_t* pitches, 
  * *out_bytes is set.  Host only. */
 int tm_jpeg_tables_rgb(int quality, void* buf, size_t cap, size_t* out_bytes);
 
+/* ---- attention heat maps: the figures test_attn.py:145-250 (`gen_img`) draws from a slice of the read-out mosaic --------
+ * tm_heat_field: the smoothed scalar field of one slice.  src float16 device [C][H][W], row y of channel c at
+ *   src + c * src_chan + y * src_pitch (both in ELEMENTS, so a slice of the [50, 4K, H, W] mosaic or a window of it is read in
+ *   place); dst float32 device [H][W], dst_pitch in elements; cells of dst outside [H][W] are not written.  Per cell
+ *     v = sum over c in [sum0, sum0 + nsum) of max(float(src[c]), 0), added in index order in float32 (1 <= nsum <= 8)
+ *     f = log2(v * wei + 1)
+ *     p = f where every src[mask0 + k] != 0, k < nmask (0 <= nmask <= 8; nmask = 0: everywhere), else 0
+ *     dst[y][x] = sum_i sum_j t[i] t[j] p[R(y + i - r, H)][R(x + j - r, W)], along axis 0 first, then along axis 1, each
+ *       a float32 sum of 2 r + 1 multiply-adds in tap order from zero; t = taps_host, 2 r + 1 float32 on the HOST, 0 <= r <= 16
+ *       (r = 0 with t = {1}: the identity); R the half-sample reflection of scipy's mode='reflect', R(-j) = j - 1,
+ *       R(n - 1 + j) = n - j
+ *   = scipy.ndimage.gaussian_filter(np.log2(s * wei + 1) * msk, sigma) (test_attn.py:204-206) when the taps are scipy's.
+ *   Held to a derived float32 bound against a float64 model (tests/heatmap_cases.py), not to bits; no atomics, two calls give
+ *   the same bits.  Non-finite inputs give non-finite outputs inside their window.  One kernel, no global scratch.
+ *   Asynchronous on `stream`.  TM_ERR_ARG with a text before any device call: a null pointer, r outside 0 .. 16, H or W below
+ *   max(r, 1) (one reflection must suffice), nsum outside 1 .. 8, nmask outside 0 .. 8, a channel range outside [0, C), a
+ *   pitch below the row, a channel stride below the extent of one channel, a misaligned pointer. */
+int tm_heat_field(const void* src, int C, int H, int W, int64_t src_pitch, int64_t src_chan, int sum0, int nsum, float wei,
+                  int mask0, int nmask, const float* taps_host, int r, void* dst, int64_t dst_pitch, void* stream);
+
+/* tm_heat_render: field float32 device [H][W] (field_pitch in elements) -> colour bytes [H scale][W scale], scale in
+ *   {1, 2, 4, 8, 16}, through the table lut_host uint8 [N][3] on the HOST, 2 <= N <= 256.  Exact float32, every operation
+ *   rounded once, nothing fused.  Pixel (y, x):
+ *     sx = (x + 0.5f) * (1.0f / scale) - 0.5f, clamped to [0, W - 1]; x0 = (int)sx, x1 = min(x0 + 1, W - 1), wx = sx - x0;
+ *     the same for y (bilinear, half-pixel centres: F.interpolate(align_corners=False))
+ *     top = f00 + (f01 - f00) * wx; bot = f10 + (f11 - f10) * wx; g = top + (bot - top) * wy  (scale 1: g = the cell, when
+ *     its right / lower neighbours are finite)
+ *     i = ((g - vmin) * inv_range) * N, inv_range = float32(1 / (vmax - vmin)) formed by the caller
+ *     idx = !(i >= 0) ? 0 : min(N - 1, (int)i)  (NaN -> 0): matplotlib's Colormap.__call__(bytes=True) after Normalize
+ *     pixel = (0, 0, 0) when idx < floor_idx (>= 0), else lut[idx]  (the colour encoder's overlay blend treats black as
+ *     transparent; inferno[0] is (0, 0, 3))
+ *   Destination: either planes[0 .. 2] = R, G, B planar uint8 device with pitches[] in bytes (what tm_rgb_compose /
+ *   tm_jpeg_encode_tiles_rgb take as planes), or `interleaved` uint8 device [h][w][3] with inter_pitch >= 3 w bytes (what they
+ *   take as overlay); exactly one of the two is non-null.  Bytes outside the image are not written.  Asynchronous on `stream`.
+ *   TM_ERR_ARG with a text before any device call: a null pointer, both or neither destination, another scale, N outside
+ *   2 .. 256, floor_idx < 0, a pitch below the row, 3 W scale or H scale beyond 2^31 - 1. */
+int tm_heat_render(const void* field, int H, int W, int64_t field_pitch, int scale, float vmin, float inv_range,
+                   const uint8_t* lut_host, int N, int floor_idx, void* const* planes, const int64_t* pitches, void* interleaved,
+                   int64_t inter_pitch, void* stream);
+
 /* ---- ROI evaluation ("evaluation"): the measures of utils/metrics.py:201-541 for a generated / real plane pair ----
  * Pixels are uint8 or float32, chosen by `dtype`; pitches and plane strides are in bytes.  uint8 pointers need no alignment;
  * float32 pointers, pitches and strides are multiples of 4. */

@@ -93,6 +93,10 @@ SIGNATURES = {
     "tm_jpeg_encode_tiles_rgb": (c_int, [C.POINTER(c_void_p), c_i64_p, c_int, c_int, c_float, c_void_p] + [c_int] * 6 +
                                  [c_void_p, C.c_int64] + [c_void_p] * 4),
     "tm_jpeg_tables_rgb": (c_int, [c_int, c_void_p, c_size_t, C.POINTER(c_size_t)]),
+    "tm_heat_field": (c_int, [c_void_p] + [c_int] * 3 + [C.c_int64] * 2 + [c_int, c_int, c_float, c_int, c_int, C.POINTER(c_float),
+                              c_int, c_void_p, C.c_int64, c_void_p]),
+    "tm_heat_render": (c_int, [c_void_p, c_int, c_int, C.c_int64, c_int, c_float, c_float, c_void_p, c_int, c_int,
+                               C.POINTER(c_void_p), c_i64_p, c_void_p, C.c_int64, c_void_p]),
     "tm_ssim_planes": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [C.c_int64] * 4 + [C.POINTER(c_float), c_int, c_float, c_float, c_void_p, c_void_p]),
     "tm_avgpool2_pad": (c_int, [c_void_p] + [c_int] * 4 + [C.c_int64] * 2 + [c_void_p] + [C.c_int64] * 2 + [c_void_p]),
     "tm_ssim_volumes": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [C.c_int64] * 6 + [C.POINTER(c_float), c_int, c_float, c_float, c_void_p, c_void_p]),

@@ -9,7 +9,9 @@ reductions and the JPEG tile scans computed on the GPU (ometiff.py).  Pinned the
 libjpeg's and Pillow / libtiff reads the container back; not pinned: byte equality with a libvips-written file,
 libvips' level sizes at odd dimensions, QuPath / Bio-Formats (never run).  `save_composites_pyramid` writes the two stains
 of a slice as one colour pyramid (PolyT green, DAPI blue, utils/vis_mba.py:193-195), optionally brightened and with an
-ontology overlay as onto_overlay does; the composite is formed inside the colour JPEG kernel.  Output index `sl = s * n_stain + c` (slice-major, stain-minor), as the reference's
+ontology overlay as onto_overlay does; the composite is formed inside the colour JPEG kernel.  `save_attn_heatmaps_pyramid`
+writes a slice of the attention read-out mosaic as a colour-mapped pyramid of its smoothed field (heatmap.py), on its own or
+blended over that composite.  Output index `sl = s * n_stain + c` (slice-major, stain-minor), as the reference's
 per-slice directories are numbered.
 """
 import os
@@ -18,7 +20,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from . import formats, ometiff, tiles
+from . import formats, heatmap, ometiff, tiles
 
 
 def to_uint8(g: torch.Tensor) -> torch.Tensor:
@@ -258,3 +260,76 @@ def save_attn_slices(mosaic, odir, names: Optional[Sequence[int]] = None):
     for k in range(arr.shape[0]):
         sl = k if names is None else names[k]
         formats.write_zarr_zip(os.path.join(str(odir), f"all_{sl}.zip"), arr[k])
+
+
+def save_attn_heatmaps_pyramid(mosaic, odir, K: int, mode: str = "att_all", gene: Optional[int] = None,
+                               slices: Optional[Sequence[int]] = None, lut=None, vmax: Optional[float] = None, sigma: float = 2.0,
+                               scale: int = 4, quality: int = 90, under=None, slc: int = 50, alpha: int = 160, floor: int = 1,
+                               page: Optional[int] = None, wei: float = 229, path: Optional[str] = None, device=None):
+    """Heat maps of the attention read-out mosaic float16 [S, 4K, H, W] (stitch_attn_dir's array or a device tensor; a host
+    mosaic is uploaded one slice at a time) as tiled pyramidal OME-TIFFs of colour JPEG pages, what test_attn.gen_img draws with
+    matplotlib (test_attn.py:145-250).  Per chosen slice sl (indices into S, default all): heatmap.field (mode, gene, wei,
+    sigma) -> heatmap.render (lut, 0 .. vmax, scale, floor) -> the colour pyramid writer.
+      under=None    '{odir}/heat_{mode}_{sl}.tif': the three rendered planes through ometiff.write_pyramid_rgb
+      under=state   '{odir}/heat_over_{mode}_{sl}.tif': the PolyT-green / DAPI-blue composite of slice sl of the resident
+                    [(c s), H, W] two-stain state (or uint8 '(s c)' mosaic; `slc` slices, as save_composites_pyramid takes)
+                    with the interleaved heat map as the encoder's overlay at `alpha`; the encoder samples the overlay by
+                    each level's own size, so the map is rendered once, at `scale`
+    lut, vmax: the table and the value painted with its last entry.  With path = 'GLUT' | 'DOPA' | 'BLOD' they default to the
+    reference's (test_attn.py:173-180): INFERNO and PATHWAY_VMAX[path]['att_all'] for att_all, the gene's two-colour palette
+    and PATHWAY_VMAX[path]['expr'][gene] for expr; lut alone defaults to INFERNO; without them vmax is required.
+    floor: table entries below it stay black (= transparent in the blend).  page: also write that level as '.jpg' through Pillow."""
+    os.makedirs(str(odir), exist_ok=True)
+    if path is not None and path not in heatmap.PATHWAY_VMAX:
+        raise ValueError(f"path must be one of {', '.join(heatmap.PATHWAY_VMAX)}, got {path!r}")
+    heatmap.mode_ranges(K, mode, gene)                             # refuses an unknown mode / a missing gene before any work
+    if path is not None and mode == "expr":
+        if lut is None:
+            lut = heatmap.two_colour(heatmap.PATHWAY_COLOURS[path][gene])
+        if vmax is None:
+            vmax = heatmap.PATHWAY_VMAX[path]["expr"][gene]
+    elif path is not None and mode == "att_all" and vmax is None:
+        vmax = heatmap.PATHWAY_VMAX[path]["att_all"]
+    if lut is None:
+        lut = heatmap.INFERNO
+    if vmax is None:
+        raise ValueError(f"vmax is required for mode {mode!r} without a pathway that states it")
+    if isinstance(mosaic, np.ndarray):
+        mosaic = torch.from_numpy(mosaic)
+    if mosaic.dim() != 4 or mosaic.dtype != torch.float16 or mosaic.shape[1] != 4 * K:
+        raise ValueError(f"the mosaic is float16 [S, 4K = {4 * K}, H, W], got {mosaic.dtype} {tuple(mosaic.shape)}")
+    dev = torch.device(device) if device is not None else (mosaic.device if mosaic.is_cuda else torch.device("cuda"))
+    picks = list(range(mosaic.shape[0])) if slices is None else list(slices)
+    if any(not 0 <= s < mosaic.shape[0] for s in picks):
+        raise ValueError(f"slices are indices 0 .. {mosaic.shape[0] - 1}, got {picks}")
+    n_stain, is_u8 = 0, False
+    if under is not None:
+        if isinstance(under, np.ndarray):
+            under = torch.from_numpy(under)
+        is_u8 = under.dtype == torch.uint8
+        if under.shape[0] % slc or under.shape[0] // slc < 2:
+            raise ValueError(f"the state under a heat map has two stains per slice; got {under.shape[0]} planes, slc = {slc}")
+        n_stain = under.shape[0] // slc
+        if any(s >= slc for s in picks):
+            raise ValueError(f"slices are indices 0 .. {slc - 1} of the state, got {picks}")
+    bufs = ometiff.JpegBatches(dev, ometiff.BATCH_TILES, 3 * ometiff.SLOT_BYTES)
+    for sl in picks:
+        fld = heatmap.field(mosaic[sl].to(dev), K, mode, wei, sigma, gene)
+        if under is None:
+            name = f"heat_{mode}_{sl}"
+            planes = heatmap.render(fld, lut, 0.0, vmax, scale, floor)
+            levels = ometiff.write_pyramid_rgb(os.path.join(str(odir), name + ".tif"), planes, quality, buffers=bufs)
+        else:
+            name = f"heat_over_{mode}_{sl}"
+            ov = heatmap.render(fld, lut, 0.0, vmax, scale, floor, interleaved=True)
+            pair = []
+            for c in (1, 0):                                       # green = PolyT, blue = DAPI
+                if is_u8:
+                    pair.append(under[sl * n_stain + c].to(dev).contiguous())
+                else:
+                    pair.append(to_uint8(under[c * slc + sl].to(dev)).contiguous())
+            levels = ometiff.write_pyramid_rgb(os.path.join(str(odir), name + ".tif"), (None, pair[0], pair[1]), quality, 1.0, ov,
+                                               alpha, buffers=bufs)
+        if page is not None:
+            from PIL import Image
+            Image.fromarray(levels[page].compose().cpu().numpy(), mode="RGB").save(os.path.join(str(odir), name + ".jpg"))

@@ -4,7 +4,9 @@ reference's COO '.npz' gene tiles through brain.GeneTileDir, or --synthetic devi
 (fused read-out kernel, one float16 '{r0}_{r1}_{c0}_{c1}.zip' per tile) -> stitch.stitch_attn_dir -> 'all_{sl}.zip' per
 slice (test_attn.py:433-497, infer_attn.py:9-39).  Hashed weights unless the caller loads a checkpoint into the model.
 `--gpus N` starts N rank processes through launch.spawn_ranks (one per GPU; tile rows are split over them, no exchange);
-the calling process never opens a GPU itself in that case.  Prints one JSON line (measured at the stated ROI size)."""
+the calling process never opens a GPU itself in that case.  `--heatmap MODE` also writes every slice of the mosaic as a
+colour-mapped pyramid (stitch.save_attn_heatmaps_pyramid) into 'heat_{path}_{mode}' next to 'attn_{path}_all' ('expr': one
+directory per gene, 'heat_{path}_expr_g{k}').  Prints one JSON line (measured at the stated ROI size)."""
 import argparse
 import json
 import os
@@ -19,7 +21,7 @@ sys.path.insert(0, ROOT)
 def worker(args):
     import torch
     import teramind_amd  # noqa: F401
-    from teramind_amd import attn_maps, launch, stitch
+    from teramind_amd import attn_maps, heatmap, launch, stitch
     from teramind_amd.brain import GeneTileDir, device_gene_provider
     from teramind_amd.config import PathConfig
     from teramind_amd.unet import GeneAttnModel
@@ -60,6 +62,23 @@ def worker(args):
             mosaic = stitch.stitch_attn_dir(tdir, args.hst, args.wst, args.hnm, args.wnm)
             stitch.save_attn_slices(mosaic, os.path.join(out_dir, f"attn_{args.path}_all"))
             stitch_s, shape = round(time.perf_counter() - t1, 3), list(mosaic.shape)
+        heat = {}
+        if args.heatmap:
+            t2 = time.perf_counter()
+            path = None if args.glst else args.path              # the reference's palettes and scales belong to its gene pairs
+            kw = dict(K=len(glst), mode=args.heatmap, vmax=args.heat_vmax, sigma=args.heat_sigma, scale=args.heat_scale,
+                      wei=heatmap.gene_weight(cfg.rna_num), path=path, device=dev)
+            dirs = []
+            if args.heatmap == "expr":
+                for k in range(len(glst)):
+                    dirs.append(os.path.join(out_dir, f"heat_{args.path}_expr_g{k}"))
+                    stitch.save_attn_heatmaps_pyramid(mosaic, dirs[-1], gene=k, **kw)
+            else:
+                dirs.append(os.path.join(out_dir, f"heat_{args.path}_{args.heatmap}"))
+                stitch.save_attn_heatmaps_pyramid(mosaic, dirs[-1], **kw)
+            torch.cuda.synchronize(dev)
+            heat = {"heatmap": args.heatmap, "heatmap_s": round(time.perf_counter() - t2, 3),
+                    "heatmap_files": sum(len(os.listdir(d)) for d in dirs)}
         tiles = args.hnm * args.wnm
         print(json.dumps({"what": "attention read-out sweep, measured", "tiles": tiles, "rank0_tiles": res["tiles"], "n_gpus": world,
                           "glst": glst, "fused": not args.unfused, "batch_tiles": args.batch_tiles,
@@ -67,7 +86,7 @@ def worker(args):
                           "prefetched": bool(args.prefetch), "tile_files_written": not args.no_tile_files,
                           "seconds": round(total, 4), "rank0_sweep_s": round(dt, 4), "tiles_per_s": round(tiles / total, 2),
                           "bytes_written_rank0": res["bytes_written"], "stitch_s": stitch_s, "mosaic_shape": shape,
-                          "out_dir": out_dir}), flush=True)
+                          "out_dir": out_dir, **heat}), flush=True)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
@@ -91,7 +110,15 @@ def main():
     ap.add_argument("--unfused", action="store_true", help="the four-map path (tm_gene_attn + torch gather), for comparison")
     ap.add_argument("--no_tile_files", action="store_true", help="compute every tile, write nothing")
     ap.add_argument("--out_dir", default=None)
+    ap.add_argument("--heatmap", choices=["att_all", "att_up", "att_dn", "expr"], default=None,
+                    help="also write the slices as colour-mapped pyramids of this field (test_attn.gen_img)")
+    ap.add_argument("--heat_scale", type=int, default=4, choices=[1, 2, 4, 8, 16], help="pixels per mosaic cell")
+    ap.add_argument("--heat_sigma", type=float, default=2.0)
+    ap.add_argument("--heat_vmax", type=float, default=None,
+                    help="upper end of the colour scale (default: the reference's for --path; required for att_up / att_dn and with --glst)")
     args = ap.parse_args()
+    if args.heatmap and args.no_tile_files:
+        ap.error("--heatmap draws the stitched mosaic: it needs the tile files (drop --no_tile_files)")
     from teramind_amd import launch
     if args.gpus > 1 and not launch.launched_as_rank():
         sys.exit(launch.spawn_ranks(args.gpus, [os.path.abspath(__file__)] + sys.argv[1:]))
